@@ -2,7 +2,7 @@
 """Benchmark of the MI355X training path: audio frames/sec for a full training step (forward + fused loss + backward +
 Adam) on synthetic 1024-sample frames.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 6000 --warmup 20
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,7 +10,10 @@ Workload (BASELINE.json configs[1] / configs[2]): S=1024, H=2048, L=64, per-GPU 
 accumulation, fp32 master weights and Adam state.  A step is one pass of the hot path over one resident batch (a pool of
 8 distinct device-resident batches is cycled); eps is drawn on-device.  One host call per step (`rv_plan_step`) enqueues
 its 9 kernels back to back on one stream, eagerly (`--graph` replays them from a hipGraph instead: the kernels run as
-fast, consecutive replays are a few us apart).
+fast, consecutive replays are a few us apart).  The headline is ONE timed pass of exactly K = --steps steps, after the
+engine's eager first step and W = --warmup untimed ones (settle_clocks runs before those, on a scratch engine); the
+default K = 6000 is about one second of steps at C2.  `--dump-outputs DIR` then writes what the K-th step computed
+(dump_outputs).
 
 N > 1: one process per GPU; each step is one `rv_plan_step_ddp` call that also issues the RCCL collectives (all-reduce
 schedule, two buckets; the bf16 gradient payload by explicit choice of this bench -- named in `config.ddp_payload`, with
@@ -40,6 +43,7 @@ sys.path.insert(0, REPO)
 S, H, L, B = 1024, 2048, 64, 4096
 KL_BETA, LR = 1e-4, 1e-4
 POOL = 8
+SETTLE_STEPS = 3000     # settle_clocks: ~0.5 s at C2
 PEAK_BF16_TFLOPS = 2500.0  # dense, /opt/skills/guides/MI355X_MICROARCH.md "Peak BF16/FP16 MFMA"
 PEAK_HBM_GBS = 8000.0      # same guide, "HBM3E peak BW" (6.29 TB/s measured for a float4 copy)
 
@@ -47,7 +51,9 @@ PEAK_HBM_GBS = 8000.0      # same guide, "HBM3E peak BW" (6.29 TB/s measured for
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=6000,
+                    help="K: the headline is ONE timed pass of exactly K steps (default: about one second at C2; a window "
+                         "shorter than --min-seconds is reported on stderr)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--graph", action="store_true",
                     help="replay each step from a hipGraph (N=1); a few us/step slower than back-to-back eager launches "
@@ -73,8 +79,13 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--repeats", type=int, default=0,
-                    help="timed passes of K steps each (0 = at least 5 and enough for --min-seconds of timed work)")
-    ap.add_argument("--min-seconds", type=float, default=1.0, help="minimum total timed work (all repeats)")
+                    help="timed passes of K steps each of the side lines (0 = at least 5 and enough for --min-seconds of "
+                         "timed work); the headline is one pass of exactly --steps steps")
+    ap.add_argument("--min-seconds", type=float, default=1.0,
+                    help="minimum total timed work of a side line (all repeats); a shorter headline window is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step left for its caller as DIR/<name>.npy "
+                         "(dump_outputs)")
     return ap.parse_args()
 
 
@@ -319,6 +330,43 @@ def time_deep_c4(dev, comp, steps, warmup):
                          "launch: dX=relu'(dY W) 4096x2048x2048 + dW=dY^T X split-K %d)" % eng.splits[wname],
                          "achieved": ach, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s", "frac": ach / PEAK_BF16_TFLOPS,
                          "us_per_launch": kern_us}}
+
+
+def settle_clocks(dev, comp, pool):
+    """SETTLE_STEPS untimed steps of a scratch engine, just before the headline's warm-up.  The headline is a single pass
+    of exactly --steps steps; entered from an idle GPU a short one measures the clocks coming up (13 % slow at --steps 20
+    --warmup 5, 3.4 % at 200 / 20: profiles/r07_headline_spread.txt).  A scratch engine, so that the headline's own
+    engine takes exactly 1 + warmup + steps; a fixed count, so that every run launches the same kernels."""
+    import torch
+    from rawaudiovae_kelsey_amd import engine as E
+    from rawaudiovae_kelsey_amd.synth import make_params
+    es = E.TrainEngine(S, H, L, B, device=dev, kl_beta=KL_BETA, lr=LR, seed=1, ring=16)
+    es.load_params(make_params(S, H, L, 0))
+    for i in range(SETTLE_STEPS):
+        es.step(pool[i % POOL], stream=comp)
+    torch.cuda.synchronize()
+    del es
+
+
+def dump_outputs(eng, out_dir):
+    """--dump-outputs: what the timed path's last step left for its caller, as out_dir/<name>.npy, all float32 and
+    complete (57 MB at the headline's shape): `loss` = (total, mse, kld); `mu`, `logvar` [B, L]; every parameter under
+    its state_dict key with the reference's nn.Linear shape, and its Adam moments as `exp_avg.<key>` / `exp_avg_sq.<key>`.
+    The inputs are seeded and the engine has taken exactly 1 + --warmup + --steps steps, so two runs with the same
+    arguments -- of the same build or of two builds -- are comparable file for file."""
+    import numpy as np
+    from rawaudiovae_kelsey_amd.engine import PARAM_NAMES
+    arrays = {"loss": np.asarray(eng.last_loss(), dtype=np.float32)}
+    arrays["mu"], arrays["logvar"] = (t.cpu().numpy() for t in eng.outputs())
+    for prefix, arena in (("", eng.param), ("exp_avg.", eng.exp_avg), ("exp_avg_sq.", eng.exp_avg_sq)):
+        for k in PARAM_NAMES:
+            arrays[prefix + k] = eng.view(arena, k).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > 64 << 20:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the 64 MB budget" % total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def host_cpu_quota():
@@ -573,17 +621,9 @@ def main():
                 el = float(t.item())
             return el, host
 
-        def timed_passes(step_fn, n_rep=None, cap=2000):
-            """Median of >= 5 passes and >= --min-seconds of timed work in total; every rank runs the same
-            number of passes (the count comes from rank 0's first pass)."""
+        def timed_passes(step_fn, n_rep):
+            """n_rep passes of K steps each, sorted (the side lines' median)."""
             first_dt, host_dt = timed_pass(step_fn, args.warmup)
-            if n_rep is None:
-                n_rep = args.repeats if args.repeats > 0 else max(5, int(args.min_seconds / max(first_dt, 1e-6)) + 1)
-                n_rep = min(n_rep, cap)
-                if multi:
-                    t = torch.tensor([n_rep], dtype=torch.int64, device=dev if backend == "nccl" else "cpu")
-                    dist.broadcast(t, 0)
-                    n_rep = int(t.item())
             passes = [first_dt]
             for r in range(1, n_rep):
                 passes.append(timed_pass(step_fn, args.warmup + r * args.steps)[0])
@@ -608,17 +648,30 @@ def main():
             return same
 
         try:
+            if not args.step_kernels_only:     # profiling runs launch nothing but the headline's steps
+                settle_clocks(dev, comp, pool)
             for i in range(args.warmup):
                 one_step(i)
             torch.cuda.synchronize()
-            passes, host_dt = timed_passes(one_step)
+            # the headline: ONE pass of exactly --steps steps, so the engine has taken 1 + warmup + steps steps when it
+            # ends (what --dump-outputs writes); a steadier figure takes a larger --steps
+            dt, host_dt = timed_pass(one_step, args.warmup)
         except Exception as exc:
             if use_ddp and multi:
                 die_together("a timed data-parallel step raised", "%s: %s" % (type(exc).__name__, str(exc)[:300]))
             raise
-        dt, dt_min, dt_max = passes[len(passes) // 2], passes[0], passes[-1]
+        passes = [dt]
+        if rank == 0 and dt < args.min_seconds:
+            print("bench.py: the headline's window is %.3f s (%d steps), under --min-seconds %.1f: it measures the clock and "
+                  "the scheduler as much as the step; a larger --steps gives a steadier figure" % (dt, args.steps, args.min_seconds),
+                  file=sys.stderr)
         last = eng.losses(min(8, args.steps))
         replicas_consistent = replicas_identical(eng)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(eng, args.dump_outputs)
+        # passes of each side line: >= 5 and >= --min-seconds of timed work, from the headline's pass (all-reduced: the
+        # same count on every rank)
+        side_reps = args.repeats if args.repeats > 0 else min(2000, max(5, int(args.min_seconds / max(dt, 1e-6)) + 1))
 
         # ---- side lines at N > 1 (never the headline; each is entered by every rank or by none) ----
         ddp_alts = {}
@@ -632,7 +685,7 @@ def main():
                 for i in range(5):
                     one_step(i)
                 torch.cuda.synchronize()
-                ap, _ = timed_passes(one_step, n_rep=min(len(passes), 7))
+                ap, _ = timed_passes(one_step, n_rep=min(side_reps, 7))
                 ddp_alts["alt_%s_payload" % other] = {
                     "grad_allreduce": "%s payload, same schedule" % other, "ms_per_step": ap[len(ap) // 2] / args.steps * 1e3,
                     "value": float(B) * world * args.steps / ap[len(ap) // 2], "repeats": len(ap)}
@@ -653,7 +706,7 @@ def main():
                 for i in range(args.warmup + 1):
                     run2.step(pool[i % POOL])
                 torch.cuda.synchronize()
-                sp_, _ = timed_passes(lambda i: run2.step(pool[i % POOL]), n_rep=min(len(passes), 7))
+                sp_, _ = timed_passes(lambda i: run2.step(pool[i % POOL]), n_rep=min(side_reps, 7))
                 ddp_alts["alt_no_defer"] = {"grad_allreduce": "%s payload, every step completing itself" % run2.payload,
                                             "ms_per_step": sp_[len(sp_) // 2] / args.steps * 1e3,
                                             "value": float(B) * world * args.steps / sp_[len(sp_) // 2], "repeats": len(sp_)}
@@ -680,7 +733,7 @@ def main():
                         e2.step(pool[i % POOL], stream=comp)
                     torch.cuda.synchronize()
                     reps = []
-                    for r in range(max(5, min(len(passes), 50))):
+                    for r in range(max(5, min(side_reps, 50))):
                         t0 = time.perf_counter()
                         for i in range(args.steps):
                             e2.step(pool[(r * args.steps + i) % POOL], stream=comp)
@@ -816,7 +869,7 @@ def main():
                                                       "rounded once" if not rehearsal else "fp32, rounded once (stand-in collectives)")}
                           if runner is not None else {}),
                        "grad_allreduce": ddp_mode},
-            # `value` / `ms_per_step` are the MEDIAN over `repeats` passes of exactly `steps` steps each
+            # `value` / `ms_per_step` are over one pass of exactly `steps` steps (`repeats` = 1)
             "timing": {"repeats": len(passes), "ms_per_step_min": min(ms), "ms_per_step_max": max(ms),
                        "timed_seconds_total": sum(passes)},
             "host_us_per_step": host_dt / args.steps * 1e6,

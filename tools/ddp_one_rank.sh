@@ -18,7 +18,7 @@ except Exception as e:
 PY
 }
 export MASTER_ADDR=127.0.0.1 MASTER_PORT=29517 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0
-B="python bench.py --steps 200 --warmup 20 --repeats 5 --no-cpu-baseline --no-alts --step-kernels-only"
+B="python bench.py --steps 1000 --warmup 20 --no-cpu-baseline --no-alts --step-kernels-only"
 {
 for i in 1 2; do
   $B > $O/tmp_b.json 2>$O/tmp_b.err; line "local step" $O/tmp_b.json

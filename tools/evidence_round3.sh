@@ -11,7 +11,7 @@ d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print("%-40s %7.1f us/step  %6.2f M frames/s  pair %5.1f us (frac %.3f)  loss %.6f" % (sys.argv[1], d["ms_per_step"] * 1e3, d["value"] / 1e6, d["roofline"]["us_per_launch"], d["roofline"]["frac"], d["final_loss"]))
 PY
 }
-B="python bench.py --steps 200 --warmup 20 --repeats 7 --no-cpu-baseline --no-alts"
+B="python bench.py --steps 1400 --warmup 20 --no-cpu-baseline --no-alts"
 {
 echo "== same box, interleaved twice; default = fp16 block-floating-point slabs, row-local latent forward and backward, eager launches"
 for i in 1 2; do
