@@ -297,6 +297,30 @@ int rv_scale_by3(const float* a0, float* out0, long n0, const float* a1, float* 
 int rv_gather_frames(const float* audio, long n_samples, const long long* frame_index,
                      long first_frame, long n_frames, long S, long hop, float* out, void* stream);
 
+/* Audio ingest on the device: the file loading of IterableAudioDataset (rawvae/dataset.py:47-58,
+ * `torchaudio.load` + channel 0 + `torchaudio.functional.resample`), for the streaming loader's
+ * device ingest (data.StreamingFrames(ingest="device")).
+ *
+ * rv_pcm_to_f32: a WAV `data` payload (nbytes raw bytes on the device, 16-byte aligned; interleaved
+ * `channels` channels of `bytes_per_sample` bytes) -> channel 0 as fp32, out[0 : n) with
+ * n = nbytes / (channels * bytes_per_sample), zeros up to n_out, which must be n rounded up to a
+ * multiple of `hop` (hop = 1: no padding).  RV_WAV_PCM: 1-byte unsigned ((x - 128) / 128), 2-, 3-
+ * (scipy's left-justified int32) and 4-byte signed (x / 2^(bits - 1)); RV_WAV_FLOAT: 4- and 8-byte
+ * IEEE (8-byte rounded to nearest).  Bit-identical to data._to_float32(scipy's read)[:, 0]. */
+#define RV_WAV_PCM 1
+#define RV_WAV_FLOAT 3
+int rv_pcm_to_f32(const void* src, long nbytes, int format, int channels, int bytes_per_sample, long hop, float* out,
+                  long n_out, void* stream);
+
+/* rv_resample_sinc_hann: `torchaudio.functional.resample(x, sr_in, sr_out)` (dataset.py:50-51; defaults
+ * sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) in its polyphase form.  orig / new_ = the rates
+ * over their gcd (orig != new_: at equal rates the caller keeps its input), bank = [new_][2 * width + orig]
+ * fp32 filters as data._sinc_hann_bank builds them; out[j * new_ + i] = filter i at offset j * orig of the
+ * input padded by `width` zeros in front and zeros behind.  The ceil(new_ * n / orig) kept outputs are
+ * written to out[0 : ...), zeros up to n_out (>= that count).  fp32 operands and accumulation. */
+int rv_resample_sinc_hann(const float* src, long n, const float* bank, long orig, long new_, long width, float* out,
+                          long n_out, void* stream);
+
 /* Standard normal draws (replaces torch.randn_like, model.py:25). */
 int rv_randn(float* out, long n, unsigned long long seed, unsigned long long offset,
              void* stream);

@@ -43,6 +43,7 @@ OPT_DDP_DEFER_TAIL = 9
 PLAN_GEMM, PLAN_TILE, PLAN_PAIR = 0, 1, 2
 TILE_AUTO, SLAB_F32, SLAB_F16 = -1, 0, 1
 TILE_256x256 = 7     # RV_TILE_256x256 (include/rawvae_hip.h)
+WAV_PCM, WAV_FLOAT = 1, 3   # RV_WAV_PCM, RV_WAV_FLOAT (rv_pcm_to_f32)
 PHASE_FWD, PHASE_BWD_A, PHASE_BWD_B = 1, 2, 4
 PHASE_FINALIZE_A, PHASE_ADAM, PHASE_FINALIZE_B = 8, 16, 32
 PHASE_ADAM_A, PHASE_ADAM_B = 64, 128
@@ -107,6 +108,8 @@ _SIGS = {
                                   c_void_p, c_void_p]),
     "rv_randn": (c_int, [c_void_p, c_long, c_u64, c_u64, c_void_p]),
     "rv_gather_frames": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_long, c_void_p, c_void_p]),
+    "rv_pcm_to_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_long, c_void_p, c_long, c_void_p]),
+    "rv_resample_sinc_hann": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]),
     "rv_plan_create": (c_int, [C.POINTER(c_void_p), c_long, c_long, c_long, c_long]),
     "rv_plan_destroy": (None, [c_void_p]),
     "rv_plan_workspace_bytes": (c_long, [c_void_p]),

@@ -11,7 +11,9 @@ train_iterable.py:70-74,195; rawvae/dataset.py:38-84), checkpoints are indexed b
 Differences from the reference: the step is `TrainEngine.step`; frames are gathered on the
 device from per-file waveforms cached in HBM; batch losses are printed when the device loss
 ring is drained (every `loss_ring` batches) rather than with a sync per batch; the frame length
-follows `[audio] segment_length` (the reference hard-codes 1024, dataset.py:66).
+follows `[audio] segment_length` (the reference hard-codes 1024, dataset.py:66).  `[mi355x] ingest = device`
+reads the wav payloads in a background thread and converts / resamples them on the GPU, prefetched behind the step
+(default `host`: decoded and resampled on the CPU).
 """
 import argparse
 import os
@@ -87,6 +89,9 @@ def main(argv=None):
     seed = int(hw.get('seed', 0))
     ring = int(hw.get('loss_ring', 64))
     use_tb = str(hw.get('tensorboard', 'True')).lower() in ('1', 'true', 'yes')
+    ingest = str(hw.get('ingest', 'host')).strip().lower()
+    if ingest not in ('host', 'device'):
+        raise ValueError("[mi355x] ingest = {} (expected host or device)".format(ingest))
 
     device = T.require_gpu()
     device_name = torch.cuda.get_device_name()
@@ -101,7 +106,8 @@ def main(argv=None):
         print("Workspace: {}".format(workdir))
         print('creating the dataset...')
         files = sorted(my_audio.glob('*.wav'))
-        stream = D.StreamingFrames(files, sampling_rate, hop_length, segment_length, device, shuffle=True, seed=seed)
+        stream = D.StreamingFrames(files, sampling_rate, hop_length, segment_length, device, shuffle=True, seed=seed,
+                                   ingest=ingest)
         print('Total number of batches: {}'.format(total_num_batches))
 
         config_path = workdir / 'config.ini'
