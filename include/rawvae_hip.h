@@ -84,7 +84,8 @@ int rv_linear_fwd_f32(const void* x_bf16, long ldx, const void* w_bf16, long ldw
  * (tutorial.ipynb:461,505-506,922-923).  F.linear + F.relu / F.tanh, model.py:20-21,29-30, in the
  * reference's own precision: f32-input MFMA (a k-ordered fmaf chain), so outputs match the
  * reference to f32 summation order.  Exact shapes (no padding), x [M,K], w [N,K] ([out,in]),
- * bias [N] or NULL, y [M,N]; act: 0 none, 1 relu, 2 tanh. */
+ * bias [N] or NULL, y [M,N]; act: 0 none, 1 relu, 2 tanh.  ldx may be smaller than K: rows of x
+ * may overlap (hop-strided frames read straight from a waveform, rv_match_pad). */
 int rv_linear_fp32(const float* x, long ldx, const float* w, long ldw, const float* bias, long M,
                    long N, long K, int act, float* y, long ldy, void* stream);
 
@@ -320,6 +321,39 @@ int rv_pcm_to_f32(const void* src, long nbytes, int format, int channels, int by
  * written to out[0 : ...), zeros up to n_out (>= that count).  fp32 operands and accumulation. */
 int rv_resample_sinc_hann(const float* src, long n, const float* bank, long orig, long new_, long width, float* out,
                           long n_out, void* stream);
+
+/* Latent interpolation and resynthesis of whole waveforms (the reference's tutorial.ipynb: stepwise mix
+ * 456-530, meso-scale curve 834-925, the same at hop_length 128 "with extensions" 1200-1279), between the exact-fp32
+ * encoder and decoder GEMMs (rv_linear_fp32).
+ *
+ * rv_match_pad: dst[i] = src[i % n_src] for i < n_valid, 0 for n_valid <= i < n_out.  n_valid > n_src repeats
+ * the shorter source (the notebook's doubling-then-crop, tutorial.ipynb:429-437), n_valid <= n_src crops it
+ * (423-427); n_out is the framing's padded length (AudioDataset: a multiple of hop, dataset.py:99-104;
+ * TestDataset: a multiple of S, dataset.py:141-146).  fc1 reads the frames from dst through rv_linear_fp32
+ * with ldx = hop: frame f is dst[f * hop, f * hop + S). */
+int rv_match_pad(const float* src, long n_src, long n_valid, float* dst, long n_out, void* stream);
+
+/* rv_latent_mix: output rows [row0, row0 + rows) of z = mu + eps * exp(logvar / 2) with mu = mu_a (1 - a) + mu_b a
+ * and logvar likewise (tutorial.ipynb:501-505, 916-923); mu_a .. lv_b are
+ * [N, L] fp32; z, eps_in / eps_out, mu_out, lv_out are [rows, L] fp32 (this chunk), alpha_out [rows] fp64 (the a
+ * of each row).  eps_in NULL: eps = the Philox draw of rv_reparameterize at flat index (row0 + i) * L + l.
+ *   RV_ALPHA_LIST : alpha = n_alpha fp64 scalars, n_alpha * N output rows in alpha-major order (row = k N + n).
+ *                   fp32 arithmetic: (1 - a) formed in fp64 and rounded, a rounded; each product and sum rounded
+ *                   (no contraction); z by rv_reparameterize's expression (bit-equal on the mixed mu / logvar).
+ *   RV_ALPHA_F32  : alpha = [N] fp32 per frame; (1 - a) in fp32, otherwise as RV_ALPHA_LIST.
+ *   RV_ALPHA_F64  : alpha = [N] fp64 per frame; mix and reparameterisation in fp64 (torch's promotion), z, mu_out
+ *                   and lv_out rounded once to fp32.
+ *   RV_ALPHA_CURVE: alpha = [n_alpha] fp64 curve stretched to N frames as scipy.interpolate.interp1d(arange(C),
+ *                   curve) evaluated at numpy.linspace(0, C - 1, N) (tutorial.ipynb:907-908; scipy evaluates a
+ *                   1-D linear interp1d through numpy.interp, whose rule is restated), then RV_ALPHA_F64. */
+#define RV_ALPHA_LIST 0
+#define RV_ALPHA_F32 1
+#define RV_ALPHA_F64 2
+#define RV_ALPHA_CURVE 3
+int rv_latent_mix(const float* mu_a, const float* lv_a, const float* mu_b, const float* lv_b, long N, long L,
+                  int alpha_mode, const void* alpha, long n_alpha, long row0, long rows, const float* eps_in,
+                  float* eps_out, unsigned long long seed, unsigned long long offset, float* z, float* mu_out,
+                  float* lv_out, double* alpha_out, void* stream);
 
 /* Standard normal draws (replaces torch.randn_like, model.py:25). */
 int rv_randn(float* out, long n, unsigned long long seed, unsigned long long offset,

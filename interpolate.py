@@ -1,0 +1,151 @@
+"""`python interpolate.py --config default.ini --checkpoint ckpt_00500 --a a.wav --b b.wav --out out.wav`
+
+Latent interpolation between two sounds with a trained model: the workflow of the reference's tutorial.ipynb
+(stepwise 456-530, meso-scale curve 834-925, with extensions 1200-1279) as one command, computed on the GPU by
+rawaudiovae_kelsey_amd.interpolate.LatentInterpolator.
+
+  --mode stepwise --alphas 0:1.1:0.2       numpy.arange(start, stop, step), or a comma list 0,0.5,1
+  --mode curve --curve sin:-500:500:20000  sin(linspace(-500 pi, 500 pi, 20000)), stretched to the frame count
+  --mode curve --curve file.npy            a float64 curve from a .npy file
+  --hop N                                  frame like AudioDataset at hop N (default: TestDataset framing)
+  --match repeat|crop                      repeat the shorter source (default) or crop the longer one
+  --seed S                                 seed of the on-device eps draw
+
+The model shape (segment_length, n_units, latent_dim) and sampling_rate come from the .ini as in train.py.  The
+checkpoint is a training checkpoint dict (its 'state_dict', as tutorial.ipynb:292-298 loads it) or a whole-module
+pickle (best_model.pt / last_model.pt).  Bad flag values raise ValueError naming the flag.
+"""
+import argparse
+import configparser
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+
+def parse_alphas(spec):
+    """'start:stop:step' -> numpy.arange(start, stop, step); 'a,b,c' -> [a, b, c] (float64)."""
+    try:
+        if ":" in spec:
+            parts = [float(p) for p in spec.split(":")]
+            if len(parts) != 3 or parts[2] == 0:
+                raise ValueError
+            out = np.arange(parts[0], parts[1], parts[2])
+        else:
+            out = np.array([float(p) for p in spec.split(",")], dtype=np.float64)
+    except ValueError:
+        raise ValueError("--alphas %r: expected start:stop:step (nonzero step) or a comma list of numbers" % spec)
+    if out.size == 0:
+        raise ValueError("--alphas %r gives no values" % spec)
+    return out.astype(np.float64)
+
+
+def parse_curve(spec):
+    """'sin:lo:hi:n' -> sin(linspace(lo pi, hi pi, n)); a path ending in .npy -> its 1-D float64 array."""
+    if spec.endswith(".npy"):
+        if not os.path.exists(spec):
+            raise ValueError("--curve %r: no such file" % spec)
+        c = np.load(spec)
+        if c.ndim != 1 or c.size < 2 or not np.issubdtype(c.dtype, np.floating):
+            raise ValueError("--curve %r: expected a 1-D float array of at least 2 points, got %s %s"
+                             % (spec, c.dtype, c.shape))
+        return c.astype(np.float64)
+    parts = spec.split(":")
+    try:
+        if len(parts) != 4 or parts[0] != "sin":
+            raise ValueError
+        lo, hi, n = float(parts[1]), float(parts[2]), int(parts[3])
+    except ValueError:
+        raise ValueError("--curve %r: expected sin:lo:hi:n (multiples of pi, n points) or a .npy file" % spec)
+    if n < 2:
+        raise ValueError("--curve %r: a curve needs at least 2 points" % spec)
+    return np.sin(np.linspace(lo * np.pi, hi * np.pi, n))
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Latent interpolation between two sounds (tutorial.ipynb on the GPU)")
+    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
+    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    p.add_argument("--a", required=True, help="first sound (wav)")
+    p.add_argument("--b", required=True, help="second sound (wav)")
+    p.add_argument("--out", required=True, help="output wav")
+    p.add_argument("--mode", default="stepwise", help="stepwise | curve")
+    p.add_argument("--alphas", default="0:1.1:0.2", help="stepwise: start:stop:step or a comma list")
+    p.add_argument("--curve", default="sin:-500:500:20000", help="curve: sin:lo:hi:n or file.npy")
+    p.add_argument("--hop", default=None, help="AudioDataset hop (default: TestDataset framing)")
+    p.add_argument("--match", default="repeat", help="repeat | crop")
+    p.add_argument("--seed", default="0", help="seed of the eps draw")
+    p.add_argument("--max-rows", default="16384", help="frames per chunk")
+    args = p.parse_args(argv)
+    if args.mode not in ("stepwise", "curve"):
+        raise ValueError("--mode %r: expected stepwise or curve" % args.mode)
+    if args.match not in ("repeat", "crop"):
+        raise ValueError("--match %r: expected repeat or crop" % args.match)
+    for flag in ("hop", "seed", "max_rows"):
+        v = getattr(args, flag)
+        if v is None:
+            continue
+        try:
+            iv = int(v)
+        except ValueError:
+            iv = -1
+        if iv < 0 or (flag != "seed" and iv == 0):
+            raise ValueError("--%s %r: expected a %s integer" % (flag.replace("_", "-"), v,
+                                                                  "non-negative" if flag == "seed" else "positive"))
+        setattr(args, flag, iv)
+    args.alpha_values = parse_alphas(args.alphas) if args.mode == "stepwise" else None
+    args.curve_values = parse_curve(args.curve) if args.mode == "curve" else None
+    return args
+
+
+def read_model_config(path):
+    config = configparser.ConfigParser(allow_no_value=True)
+    if not config.read(path):
+        raise ValueError("--config %r: file not found" % path)
+    return dict(sampling_rate=config["audio"].getint("sampling_rate"),
+                segment_length=config["audio"].getint("segment_length"),
+                n_units=config["VAE"].getint("n_units"), latent_dim=config["VAE"].getint("latent_dim"))
+
+
+def load_model(path, cfg, device="cuda"):
+    """VAE of the .ini's shape with the checkpoint's parameters."""
+    import torch
+    from rawvae.model import VAE
+    state = torch.load(path, map_location=device, weights_only=False)
+    model = VAE(cfg["segment_length"], cfg["n_units"], cfg["latent_dim"]).to(device)
+    if isinstance(state, dict):
+        sd = state.get("state_dict", state)
+    elif isinstance(state, torch.nn.Module):
+        sd = state.state_dict()
+    else:
+        raise ValueError("--checkpoint %r: neither a checkpoint dict nor a module pickle" % path)
+    model.load_state_dict(sd)
+    return model.eval()
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cfg = read_model_config(args.config)
+    from rawaudiovae_kelsey_amd import data as D
+    from rawaudiovae_kelsey_amd.interpolate import LatentInterpolator
+    model = load_model(args.checkpoint, cfg)
+    a = D.load_audio_mono(args.a, cfg["sampling_rate"])
+    b = D.load_audio_mono(args.b, cfg["sampling_rate"])
+    it = LatentInterpolator(model, max_rows=args.max_rows)
+    if args.mode == "stepwise":
+        out = it.stepwise(a, b, args.alpha_values, hop=args.hop, seed=args.seed, match=args.match)
+    else:
+        out = it.curve(a, b, args.curve_values, hop=args.hop, seed=args.seed, match=args.match)
+    y = out.cpu().numpy()
+    D.write_wav(args.out, y, cfg["sampling_rate"])
+    print("wrote %s: %d samples (%.2f s at %d Hz)" % (args.out, y.size, y.size / cfg["sampling_rate"],
+                                                      cfg["sampling_rate"]))
+    return y
+
+
+if __name__ == "__main__":
+    main()

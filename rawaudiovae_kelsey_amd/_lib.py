@@ -44,6 +44,7 @@ PLAN_GEMM, PLAN_TILE, PLAN_PAIR = 0, 1, 2
 TILE_AUTO, SLAB_F32, SLAB_F16 = -1, 0, 1
 TILE_256x256 = 7     # RV_TILE_256x256 (include/rawvae_hip.h)
 WAV_PCM, WAV_FLOAT = 1, 3   # RV_WAV_PCM, RV_WAV_FLOAT (rv_pcm_to_f32)
+ALPHA_LIST, ALPHA_F32, ALPHA_F64, ALPHA_CURVE = 0, 1, 2, 3   # RV_ALPHA_* (rv_latent_mix)
 PHASE_FWD, PHASE_BWD_A, PHASE_BWD_B = 1, 2, 4
 PHASE_FINALIZE_A, PHASE_ADAM, PHASE_FINALIZE_B = 8, 16, 32
 PHASE_ADAM_A, PHASE_ADAM_B = 64, 128
@@ -107,6 +108,9 @@ _SIGS = {
     "rv_reparameterize": (c_int, [c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_u64, c_u64,
                                   c_void_p, c_void_p]),
     "rv_randn": (c_int, [c_void_p, c_long, c_u64, c_u64, c_void_p]),
+    "rv_match_pad": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p]),
+    "rv_latent_mix": (c_int, [c_void_p] * 4 + [c_long, c_long, c_int, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p,
+                              c_u64, c_u64] + [c_void_p] * 5),
     "rv_gather_frames": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_long, c_void_p, c_void_p]),
     "rv_pcm_to_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_long, c_void_p, c_long, c_void_p]),
     "rv_resample_sinc_hann": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]),

@@ -83,7 +83,8 @@ __global__ void __launch_bounds__(256) k_linear_fp32(const float* __restrict__ x
 extern "C" int rv_linear_fp32(const float* x, long ldx, const float* w, long ldw, const float* bias, long M, long N,
                               long K, int act, float* y, long ldy, void* stream) {
   RV_REQUIRE(x && w && y, RV_ERR_NULL, "rv_linear_fp32: null operand");
-  RV_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= K && ldw >= K && ldy >= N, RV_ERR_SHAPE,
+  // ldx < K is allowed: x is only read, so its rows may overlap (hop-strided frames of one waveform)
+  RV_REQUIRE(M > 0 && N > 0 && K > 0 && ldx >= 1 && ldw >= K && ldy >= N, RV_ERR_SHAPE,
              "rv_linear_fp32: bad extents M=%ld N=%ld K=%ld ldx=%ld ldw=%ld ldy=%ld", M, N, K, ldx, ldw, ldy);
   RV_REQUIRE(act >= 0 && act <= 2, RV_ERR_UNSUPPORTED, "rv_linear_fp32: act %d (0 none, 1 relu, 2 tanh)", act);
   RV_REQUIRE((N + BT - 1) / BT <= 0x7fffffffL && (M + BT - 1) / BT <= 65535, RV_ERR_SHAPE,
