@@ -355,6 +355,36 @@ int rv_latent_mix(const float* mu_a, const float* lv_a, const float* mu_b, const
                   float* eps_out, unsigned long long seed, unsigned long long offset, float* z, float* mu_out,
                   float* lv_out, double* alpha_out, void* stream);
 
+/* Self-organising map of latent vectors (the SOM whose clusters.json / data-concatenated.json pick the sources of
+ * tutorial.ipynb:725-805 and 1078-1146; rawaudiovae_kelsey_amd/som.py).
+ *
+ * rv_segment_mean: out[f] = mean(x[offsets[f] : offsets[f+1]]) for f < F; x [R, L] fp32, out [F, L] fp32.  offsets is
+ * [F+1] int64 in device memory, offsets_host the same values in host memory: they are checked before the launch
+ * (0 <= offsets[0], offsets[F] <= R) and an empty segment is RV_ERR_SHAPE.  Each mean is an fp64 sum in ascending row
+ * order divided by the count and rounded once. */
+int rv_segment_mean(const float* x, long R, long L, const long long* offsets, const long long* offsets_host, long F,
+                    float* out, void* stream);
+
+/* rv_som_bmu: for each row n of x [N, L] fp32 the best and second-best node of w [M, L] fp32 under the squared
+ * distance sum_l (x[n,l] - w[m,l])^2: best / second [N] int32, d_best / d_second [N] fp32.  Any N >= 1, M >= 2,
+ * L >= 1.  Ties go to the lower node index; a row whose distances are all NaN gets index -1.  Direct form in fp32:
+ * each term one fma, summed in ascending l within tiles of 32, the tile sums added in order (relative error at most
+ * about (34 + L / 32) * 2^-24 of the distance). */
+int rv_som_bmu(const float* x, long N, const float* w, long M, long L, int* best, int* second, float* d_best,
+               float* d_second, void* stream);
+
+/* rv_som_node_sums: for bmu [N] int32 (indices into M nodes) sums[m] = sum of the rows x[n] with bmu[n] == m, [M, L]
+ * fp64 in ascending n, and counts[m] = their number [M] int64.  No atomics: bit-identical from run to run. */
+int rv_som_node_sums(const float* x, long N, long L, const int* bmu, long M, double* sums, long long* counts,
+                     void* stream);
+
+/* rv_som_update: the batch-SOM step on a rows x cols grid (node m at (m / cols, m % cols)):
+ * w_new[m] = sum_b h(m,b) sums[b] / sum_b h(m,b) counts[b], h = exp(-((dr)^2 + (dc)^2) / (2 sigma^2)), in fp64
+ * ascending b, rounded once to fp32; w_new[m] = w_old[m] where the denominator is 0.  sums [M, L] fp64, counts [M]
+ * int64, w_old / w_new [M, L] fp32 (distinct buffers), sigma > 0. */
+int rv_som_update(const double* sums, const long long* counts, const float* w_old, long rows, long cols, long L,
+                  double sigma, float* w_new, void* stream);
+
 /* Standard normal draws (replaces torch.randn_like, model.py:25). */
 int rv_randn(float* out, long n, unsigned long long seed, unsigned long long offset,
              void* stream);

@@ -10,6 +10,8 @@ rawaudiovae_kelsey_amd.interpolate.LatentInterpolator.
   --hop N                                  frame like AudioDataset at hop N (default: TestDataset framing)
   --match repeat|crop                      repeat the shorter source (default) or crop the longer one
   --seed S                                 seed of the on-device eps draw
+  --som DIR --audio DIR --a-cluster K      source a is node K of a SOM (som.py): its files concatenated in list
+                                           order, as the notebook's concat_audio_som (743-756); likewise --b-cluster
 
 The model shape (segment_length, n_units, latent_dim) and sampling_rate come from the .ini as in train.py.  The
 checkpoint is a training checkpoint dict (its 'state_dict', as tutorial.ipynb:292-298 loads it) or a whole-module
@@ -70,8 +72,12 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Latent interpolation between two sounds (tutorial.ipynb on the GPU)")
     p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
     p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
-    p.add_argument("--a", required=True, help="first sound (wav)")
-    p.add_argument("--b", required=True, help="second sound (wav)")
+    p.add_argument("--a", default=None, help="first sound (wav); or --a-cluster")
+    p.add_argument("--b", default=None, help="second sound (wav); or --b-cluster")
+    p.add_argument("--som", default=None, help="folder with clusters.json and data-concatenated.json (som.py)")
+    p.add_argument("--audio", default=None, help="the folder the SOM's relative paths start from")
+    p.add_argument("--a-cluster", default=None, help="first sound: the files of this SOM node, concatenated")
+    p.add_argument("--b-cluster", default=None, help="second sound: the files of this SOM node, concatenated")
     p.add_argument("--out", required=True, help="output wav")
     p.add_argument("--mode", default="stepwise", help="stepwise | curve")
     p.add_argument("--alphas", default="0:1.1:0.2", help="stepwise: start:stop:step or a comma list")
@@ -97,6 +103,20 @@ def parse_args(argv=None):
             raise ValueError("--%s %r: expected a %s integer" % (flag.replace("_", "-"), v,
                                                                   "non-negative" if flag == "seed" else "positive"))
         setattr(args, flag, iv)
+    for s in ("a", "b"):
+        wav, node = getattr(args, s), getattr(args, s + "_cluster")
+        if (wav is None) == (node is None):
+            raise ValueError("--%s / --%s-cluster: give exactly one of them" % (s, s))
+        if node is not None:
+            try:
+                k = int(node)
+            except ValueError:
+                k = -1
+            if k < 0:
+                raise ValueError("--%s-cluster %r: expected a non-negative node index" % (s, node))
+            if args.som is None or args.audio is None:
+                raise ValueError("--%s-cluster needs --som and --audio" % s)
+            setattr(args, s + "_cluster", k)
     args.alpha_values = parse_alphas(args.alphas) if args.mode == "stepwise" else None
     args.curve_values = parse_curve(args.curve) if args.mode == "curve" else None
     return args
@@ -127,14 +147,32 @@ def load_model(path, cfg, device="cuda"):
     return model.eval()
 
 
+def cluster_audio(som_dir, audio_dir, node, sampling_rate, flag):
+    """concat_audio_som (tutorial.ipynb:743-756): the node's files in list order, each loaded at sampling_rate, joined
+    into one waveform.  A missing or empty node raises ValueError naming `flag`."""
+    from rawaudiovae_kelsey_amd import data as D
+    from rawaudiovae_kelsey_amd.som import cluster_paths, read_som
+    clusters, data = read_som(som_dir)
+    try:
+        paths = cluster_paths(clusters, data, audio_dir, node)
+    except KeyError:
+        raise ValueError("%s %d: no such node in %s" % (flag, node, os.path.join(som_dir, "clusters.json")))
+    if not paths:
+        raise ValueError("%s %d: the node has no files" % (flag, node))
+    return np.concatenate([D.load_audio_mono(p, sampling_rate) for p in paths], 0)
+
+
 def main(argv=None):
     args = parse_args(argv)
     cfg = read_model_config(args.config)
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd.interpolate import LatentInterpolator
     model = load_model(args.checkpoint, cfg)
-    a = D.load_audio_mono(args.a, cfg["sampling_rate"])
-    b = D.load_audio_mono(args.b, cfg["sampling_rate"])
+    sr = cfg["sampling_rate"]
+    a = (D.load_audio_mono(args.a, sr) if args.a is not None
+         else cluster_audio(args.som, args.audio, args.a_cluster, sr, "--a-cluster"))
+    b = (D.load_audio_mono(args.b, sr) if args.b is not None
+         else cluster_audio(args.som, args.audio, args.b_cluster, sr, "--b-cluster"))
     it = LatentInterpolator(model, max_rows=args.max_rows)
     if args.mode == "stepwise":
         out = it.stepwise(a, b, args.alpha_values, hop=args.hop, seed=args.seed, match=args.match)

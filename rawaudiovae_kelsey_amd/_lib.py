@@ -111,6 +111,10 @@ _SIGS = {
     "rv_match_pad": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p]),
     "rv_latent_mix": (c_int, [c_void_p] * 4 + [c_long, c_long, c_int, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p,
                               c_u64, c_u64] + [c_void_p] * 5),
+    "rv_segment_mean": (c_int, [c_void_p, c_long, c_long, c_void_p, C.POINTER(c_i64), c_long, c_void_p, c_void_p]),
+    "rv_som_bmu": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long] + [c_void_p] * 5),
+    "rv_som_node_sums": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
+    "rv_som_update": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, C.c_double, c_void_p, c_void_p]),
     "rv_gather_frames": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_long, c_void_p, c_void_p]),
     "rv_pcm_to_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_long, c_void_p, c_long, c_void_p]),
     "rv_resample_sinc_hann": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]),
