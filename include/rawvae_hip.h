@@ -483,8 +483,8 @@ typedef struct rv_plan_buffers {
 #define RV_PHASE_ADAM_B 128    /* ... only fc1, fc21, fc22                             */
 /* finer split, in gradient-availability order (data-parallel buckets: fc4 | fc1 | the rest):  */
 #define RV_PHASE_BWD_FC4 0x0100   /* fc4 backward: fc4.w, fc4.b, fc3.b gradients ready         */
-#define RV_PHASE_BWD_CHAIN 0x0200 /* dz, reparam bwd, heads dgrad, fc1 wgrad: fc1.*, head biases */
-#define RV_PHASE_BWD_REST 0x0400  /* fc3 wgrad, heads wgrad                                    */
+#define RV_PHASE_BWD_CHAIN 0x0200 /* dz, reparam bwd, heads dgrad+wgrad, fc1 wgrad: fc1.*, heads  */
+#define RV_PHASE_BWD_REST 0x0400  /* fc3 wgrad                                                 */
 #define RV_PHASE_FIN_FC4 0x0800
 #define RV_PHASE_FIN_FC1 0x1000
 #define RV_PHASE_FIN_MID 0x2000   /* fc21, fc22, fc3                                           */
@@ -592,7 +592,7 @@ int rv_plan_ddp_flush(rv_plan*, void* stream);
  * dlogvar [B,L], all exact-shape fp32, each NULL = zero; the reparameterisation backward then takes kl_beta from
  * the rv_plan_step call (pass 0 when dmu / dlogvar already hold the KL gradient).  grad_out (or NULL = the bound
  * grad arena) receives the FINALIZE phases' flat fp32 gradients.  All NULL restores the fused loss of the forward
- * phase.  Not honoured by the full-step schedules (phases == RV_PHASE_ALL_LOCAL). */
+ * phase.  A full local step (BWD_A | BWD_B | ADAM without FINALIZE) with them set is RV_ERR_STATE. */
 int rv_plan_set_external_grads(rv_plan*, const float* d_recon, const float* recon, const float* dmu,
                                const float* dlogvar, float* grad_out);
 /* The plan's OWN loss across the autograd boundary (loss_function of rawvae/model.py:38-47 called on the untouched

@@ -73,6 +73,20 @@ struct Range {   // scope guard
 };
 }  // namespace
 
+// What a forward decided (fwd_decide).  Split-phase callers run its backward in a later call, which reads these.
+struct rv_fwd_decisions {
+  bool f8_w1 = false;   // fc1's weight gradient on fp8 operands follows (fp8_w1): the frames' bf16 copy is not written
+  bool no_h3 = false;   // the bf16 h3 is not written either (fc4's dgrad then masks with the fp8 image)
+  int n_amax_h3 = 0;    // how many of h3's maxima the forward writes (dP1's go right behind them)
+};
+
+// Frames read from a resident waveform (rv_plan_step_frames): the forward's `x` is then that waveform
+struct rv_frame_src {
+  const long long* idx;
+  long first, hop, n_samples;
+  const void* bf16;   // the waveform as bf16 (fc1's operand is gathered from it), or null
+};
+
 struct rv_plan {
   long B, S, H, L, Bp, Sp, Hp, Lp, L2p;
   int s_heads, s_dz, s_w4, s_w3, s_wh, s_w1;  // split-K factors
@@ -112,11 +126,8 @@ struct rv_plan {
   int fp8 = 0;                 // fc1 / fc4 forward on fp8 operands (RV_OPT_FP8)
   int n_amax_cap = 4096;       // entries of the workspace buffer "h3_amax" for h3's maxima
   int n_amax_dp1 = 0;          // ... and for dP1's behind them (fp8 weight gradient of fc1)
-  int n_amax_h3 = 0;           // how many of h3's the forward in use writes (set by the forward phase)
   bool heads_half = false;     // the streaming heads' backward writes fp16 dWh slabs (heads_mode_apply)
-  bool fwd_for_fp8_w1 = false; // set by rv_plan_step_ddp around its forward call (fp8_w1)
-  bool last_fwd_f8_w1 = false; // what the most recent forward phase decided (fp8_w1): the backward follows IT, not its own phase mask
-  bool last_fwd_no_h3 = false; // ... and whether it left the bf16 h3 unwritten (fc4's dgrad then masks with the fp8 image)
+  rv_fwd_decisions fwd;        // what the most recent forward decided: the backward follows IT, not its own phase mask
   int ddp_seq = 0;             // data-parallel steps enqueued with device-side flags (their sequence number)
   int ddp_signal = 1;          // RV_OPT_DDP_SIGNAL: 1 device-side flags between the two streams (default), 0 HIP events
   long ddp_wait_ms = 30000;    // RV_OPT_DDP_WAIT_MS: bound of a flag wait whose setter sits behind a collective (peers)
@@ -134,10 +145,6 @@ struct rv_plan {
   int slab_dtype = RV_SLAB_F16;   // element type of the dW1 / dW4 split-K slabs (RV_OPT_SLAB_DTYPE)
   float* us_w1 = nullptr;         // per-granule scale tables of the fp16 slabs (workspace "dW1_us" / "dW4_us")
   float* us_w4 = nullptr;
-  // frame source of the step in flight (rv_plan_step_frames): `x` is then the resident waveform
-  const long long* fr_idx = nullptr;
-  long fr_first = 0, fr_hop = 0, fr_nsamples = 0;
-  const void* fr_bf16 = nullptr;   // the waveform as bf16 (fc1's operand is gathered from it), or null
   int payload_bf16 = 0;
   void* grad_bf16 = nullptr;   // caller's flat bf16 payload arena (rv_comm_desc.grad_bf16)
 
@@ -168,7 +175,12 @@ static bool heads_streaming(const rv_plan* p) {
   // GEMM forms take over with the other latent-sized launches)
   return p->latent_fused && p->hb_groups > 0 && rv_latent_rowlocal(p->Bp, p->Hp, p->Lp);
 }
-static bool latent_bwd_fused(const rv_plan* p);
+// The latent backward's fused form (rv_latent_bwd: dz + reparameterisation backward, dW3 on extra workgroups of the same
+// launch; RV_OPT_LATENT_FUSED) and with it the fused latent forward: row-local kernels at a padded latent width of 64 and
+// batches up to 8192 (hidden width a multiple of 512 up to 2048), GEMM forms with the reparameterisation in their
+// epilogues for 128 / 256 -- the reference's own latent_dim = 256 --, large batches and every other hidden width
+// (rv_latent_rowlocal, csrc/latent.hip).
+static bool latent_bwd_fused(const rv_plan* p) { return p->latent_fused && p->Hp % 128 == 0; }
 static void heads_mode_apply(rv_plan* p) {
   const bool st = heads_streaming(p);
   {
@@ -621,23 +633,29 @@ static bool fp8_bwd_possible(const rv_plan* p) {   // (at forward time: which im
   return p->fp8 == 1 && rv_dgrad_wgrad_fp8_fits(p->Bp, p->Hp, p->Sp, p->s_w4);
 }
 // fc1's weight gradient on fp8 operands (RV_OPT_FP8 = 1), in the schedules whose dW1 launch has an fp8 form -- the one
-// with rider blocks: the full local step (riders = optimizer) and the data-parallel all-reduce step (riders = slab sums;
-// it announces itself to its forward call through `fwd_for_fp8_w1`): the heads' streaming backward writes dP1 as fp8 (its
-// scale follows the maximum it measured in the previous step), the frames' fp8 image is the one fc1's forward read, and
-// neither bf16 copy is written.
-static bool latent_bwd_fused(const rv_plan* p);
-static bool fp8_w1(const rv_plan* p, bool full_local) {
-  return p->fp8 == 1 && (full_local || p->fwd_for_fp8_w1) && latent_bwd_fused(p) && heads_streaming(p) && p->n_amax_dp1 > 0 &&
+// with rider blocks: the full local step (riders = optimizer) and the data-parallel all-reduce step (riders = slab sums).
+// `for_w1`: the forward is one of theirs.  The heads' streaming backward writes dP1 as fp8 (its scale follows the maximum
+// it measured in the previous step), the frames' fp8 image is the one fc1's forward read, and neither bf16 copy is written.
+static bool fp8_w1(const rv_plan* p, bool for_w1) {
+  return p->fp8 == 1 && for_w1 && latent_bwd_fused(p) && heads_streaming(p) && p->n_amax_dp1 > 0 &&
          rv_wgrad_adam_fits(p->Hp, p->Sp, p->Bp, p->s_w1) && (p->Hp / 256) * (p->Sp / 256) * p->s_w1 <= 192 &&
          p->Bp % (128L * p->s_w1) == 0 && (p->Bp / 128 / p->s_w1) % 2 == 0 && p->Hp % 16 == 0 && p->Sp % 16 == 0;
 }
+// fc4's backward masks with ReLU'(h3): the bf16 h3, or -- behind a forward that did not write it (no_h3) -- the fp8 image
+// of h3 that its fp8 form reads anyway.  Gradients from outside set since such a forward send it down the bf16 form.
+static int h3_check(const rv_plan* p, const rv_fwd_decisions& d) {
+  RV_REQUIRE(!d.no_h3 || fp8_bwd(p), RV_ERR_STATE,
+             "fc4 backward: the last forward (an fp8 full step) left the bf16 h3 unwritten, and with gradients from outside "
+             "this backward reads it; run a forward of its own (RV_PHASE_FWD) first");
+  return RV_OK;
+}
 static int fc4_backward(rv_plan* p, void* stream) {
   const long Bp = p->Bp, Sp = p->Sp, Hp = p->Hp;
+  const int rc = h3_check(p, p->fwd);
+  if (rc) return rc;
   if (fp8_bwd(p)) {
     float* f8 = (float*)p->ws("fp8_state");
-    // the ReLU mask: the bf16 h3, or -- where the forward of this step did not write it (last_fwd_no_h3) -- the fp8 image
-    // of h3 that is this launch's weight-gradient operand anyway
-    const bool m8 = p->last_fwd_no_h3;
+    const bool m8 = p->fwd.no_h3;
     return rv_linear_dgrad_wgrad_fp8(p->ws("dP4q"), Sp, p->ws("W4q"), Hp, p->ws("h3q"), Hp, m8 ? p->ws("h3q") : p->ws("h3"), Hp,
                                      m8 ? 1 : 0, f8 + 10, f8 + 11, Bp, Hp, Sp, p->ws("dP3"), Hp, (float*)p->ws("db3p"), p->ws("dW4"),
                                      Hp, p->s_w4, p->slab_dtype, p->us_w4, stream);
@@ -646,63 +664,245 @@ static int fc4_backward(rv_plan* p, void* stream) {
                                (float*)p->ws("db3p"), p->ws("dW4"), Hp, p->s_w4, p->slab_dtype, p->us_w4, stream);
 }
 
-// The latent-sized backward between the fc4 pair and fc1's weight gradient: dz, the reparameterisation backward (which
-// also finishes the loss), fc3's weight gradient, and the heads' dgrad + wgrad.  Row-local form (RV_OPT_LATENT_FUSED,
-// padded latent width 64; its GEMM form above that): rv_latent_bwd (dz + reparam backward with dW3 on extra workgroups of
-// the same launch) and the heads' backward -- two launches.  Otherwise three: dz + dW3 as split-K slabs, rv_reparam_bwd,
-// the heads' backward.
-// (padded latent width 64 at batches up to 8192: the row-local kernels, hidden width a multiple of 512 up to 2048; 128 / 256
-// -- the reference's own latent_dim = 256 --, large batches and every other hidden width: the GEMM forms with the
-// reparameterisation in their epilogues; rv_latent_rowlocal, csrc/latent.hip)
-static bool latent_bwd_fused(const rv_plan* p) { return p->latent_fused && p->Hp % 128 == 0; }
+#define RV_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
 
-static int latent_heads_bwd(rv_plan* p, const float* eps_used, float kl_beta, const float* dmu_ext, const float* dlv_ext,
-                            void* stream, bool f8_w1 = false) {
-  const long Bp = p->Bp, Hp = p->Hp, Lp = p->Lp, L2p = 2 * p->Lp, B = p->B, L = p->L, S = p->S;
-  void* dP3 = p->ws("dP3"); void* z = p->ws("z"); void* h1 = p->ws("h1"); void* dP1 = p->ws("dP1"); void* dmulv = p->ws("dmulv");
-  float* mulv = (float*)p->ws("mulv"); float* dz_slabs = (float*)p->ws("dz_slabs");
-  float* mse_part = (float*)p->ws("mse_part"); float* kl_part = (float*)p->ws("kl_part");
-  const bool do_latent = !(p->skip >> 5 & 1), do_heads = !(p->skip >> 6 & 1);   // rv_plan_diag_skip
-  int rc;
-  if (latent_bwd_fused(p)) {
-    if (do_latent) {
-      rc = rv_latent_bwd(dP3, Hp, p->ws("W3b"), Lp, Bp, Hp, Lp, B, L, S, mulv, eps_used, kl_beta, dmu_ext, dlv_ext, dmulv,
-                         (float*)p->ws("dbhp"), mse_part, p->n_mse, kl_part, p->n_kl, p->b.loss_ring, p->b.step_counter,
-                         p->b.ring, z, Lp, (float*)p->ws("dW3"), Lp, p->s_w3, stream);
-      if (rc) return rc;
-    }
-    if (!do_heads) return RV_OK;
-    if (f8_w1) {   // dP1 as fp8 only, its maxima behind h3's (fp8_w1)
-      float* f8 = (float*)p->ws("fp8_state");
-      return rv_heads_bwd_ex(dmulv, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, Lp, nullptr, 0, (float*)p->ws("db1p"), (float*)p->ws("dWh"), Hp,
-                             p->ws("dP1q"), Hp, f8 + 13, (float*)p->ws("h3_amax") + p->n_amax_h3,
-                             p->heads_half ? (float*)p->ws("dWh_us") : nullptr, stream);
-    }
-    if (heads_streaming(p))
-      return rv_heads_bwd_ex(dmulv, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, Lp, dP1, Hp, (float*)p->ws("db1p"), (float*)p->ws("dWh"), Hp,
-                             nullptr, 0, nullptr, nullptr, p->heads_half ? (float*)p->ws("dWh_us") : nullptr, stream);
-    return rv_linear_dgrad_wgrad(dmulv, L2p, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, L2p, dP1, Hp, (float*)p->ws("db1p"),
-                                 p->ws("dWh"), Hp, p->s_wh, p->heads_half ? RV_SLAB_F16 : RV_SLAB_F32,
-                                 p->heads_half ? (float*)p->ws("dWh_us") : nullptr, stream);
+// Launch slot k of a step (rv_plan_diag_skip): 0 cast, 1 fc1, 2 latent forward, 3 fc4 + loss, 4 fc4 backward, 5 latent
+// backward, 6 heads backward, 7 fc1's weight gradient, 8 Adam.  A set bit leaves the slot out.
+static bool slot_on(const rv_plan* p, int k) { return !(p->skip >> k & 1); }
+
+// ---- forward
+// The forward's decisions, taken -- and checked -- ahead of the first launch of the call that runs it.  `for_w1`: the
+// forward feeds an fp8 form of fc1's weight gradient (fp8_w1).
+static int fwd_decide(const rv_plan* p, bool for_w1, rv_fwd_decisions* d) {
+  const long Bp = p->Bp, Hp = p->Hp, Lp = p->Lp;
+  d->f8_w1 = fp8_w1(p, for_w1);
+  // ... then nothing but fc4's dgrad reads the bf16 h3 (its ReLU mask): the fp8 image serves (round 6: 16 MB less written
+  // by the latent forward, 8 MB less read by the pair)
+  d->no_h3 = d->f8_w1 && fp8_bwd_possible(p) && rv_latent_rowlocal(Bp, Hp, Lp);
+  d->n_amax_h3 = 0;
+  if (p->fp8 && latent_bwd_fused(p) && rv_latent_rowlocal(Bp, Hp, Lp)) {
+    d->n_amax_h3 = (int)(Bp / 16) * 8;   // one maximum per wave of rv_latent_fwd_ex
+    RV_REQUIRE(d->n_amax_h3 <= p->n_amax_cap, RV_ERR_STATE, "rv_plan_step: h3_amax holds %d entries, the fused latent forward writes %d",
+               p->n_amax_cap, d->n_amax_h3);
+  } else if (p->fp8) {
+    int bm3 = 128, bn3 = 128;
+    rv_gemm_tile(Bp, Hp, 1, &bm3, &bn3);
+    d->n_amax_h3 = (int)((Bp / bm3) * (Hp / bn3));
+    RV_REQUIRE(d->n_amax_h3 <= p->n_amax_cap, RV_ERR_SHAPE, "rv_plan_step: fp8 path supports up to %d fc3 output tiles (got %d)",
+               p->n_amax_cap, d->n_amax_h3);
   }
-  if (do_latent) {
-    rc = rv_linear_dgrad_wgrad_f32(dP3, Hp, p->ws("W3b"), Lp, z, Lp, Bp, Lp, Hp, dz_slabs, Lp, p->s_dz, (float*)p->ws("dW3"), Lp,
-                                   p->s_w3, stream);
-    if (rc) return rc;
-    rc = rv_reparam_bwd(dz_slabs, p->s_dz, Bp, Lp, B, L, S, mulv, eps_used, kl_beta, dmu_ext, dlv_ext, dmulv, (float*)p->ws("dbhp"),
-                        mse_part, p->n_mse, kl_part, p->n_kl, p->b.loss_ring, p->b.step_counter, p->b.ring, stream);
-    if (rc) return rc;
-  }
-  if (!do_heads) return RV_OK;
-  return rv_linear_dgrad_wgrad(dmulv, L2p, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, L2p, dP1, Hp, (float*)p->ws("db1p"), p->ws("dWh"), Hp,
-                               p->s_wh, p->heads_half ? RV_SLAB_F16 : RV_SLAB_F32, p->heads_half ? (float*)p->ws("dWh_us") : nullptr,
-                               stream);
+  return RV_OK;
 }
 
-int rv_plan_step(rv_plan* p, int phases, const float* x, const float* eps, float* recon_out,
-                 float kl_beta, float lr, float grad_scale, int adam_from_flat,
-                 unsigned long long seed, void* stream) {
-  RV_REQUIRE(p && p->bound, RV_ERR_STATE, "rv_plan_step: plan not bound");
+// The forward's four launch slots: 0 the frames -> fc1's bf16 (and fp8) operand, 1 fc1, 2 heads -> reparameterisation ->
+// fc3 (one launch where the fused kernel exists, else three), 3 fc4 + tanh + loss.  `fr`: frames from the resident
+// waveform `x`, or null for the B frames at `x`.
+static int plan_forward(rv_plan* p, const rv_fwd_decisions& d, const float* x, const rv_frame_src* fr, const float* eps,
+                        float* recon_out, unsigned long long seed, void* stream) {
+  Range range(p->roctx, "rv:fwd");
+  p->fwd = d;
+  const long B = p->B, S = p->S, L = p->L, Bp = p->Bp, Sp = p->Sp, Hp = p->Hp, Lp = p->Lp;
+  void* xb = p->ws("xb"); void* xq = p->ws("xq"); void* h1 = p->ws("h1"); void* z = p->ws("z");
+  void* h3 = p->ws("h3"); void* h3q = p->ws("h3q"); void* W3b = p->ws("W3b"); void* W4b = p->ws("W4b"); void* W4q = p->ws("W4q");
+  float* f8 = (float*)p->ws("fp8_state"); float* amax = (float*)p->ws("h3_amax");
+  float* b1p = (float*)p->ws("b1p"); float* b3p = (float*)p->ws("b3p"); float* b4p = (float*)p->ws("b4p");
+  float* mulv = (float*)p->ws("mulv"); float* eps_buf = (float*)p->ws("eps");
+  float* kl_part = (float*)p->ws("kl_part"); float* mse_part = (float*)p->ws("mse_part"); float* db4p = (float*)p->ws("db4p");
+  long long* counter = p->b.step_counter;
+  const bool q8 = p->fp8 != 0;
+  // fp8 backward of fc4: the forward writes dP4 as fp8 (dP4q) INSTEAD of bf16 (a caller that then supplies its own
+  // gradients gets its bf16 dP4 from rv_tanh_bwd_pack)
+  const bool f8_bwd = fp8_bwd_possible(p);
+  void* dP4 = f8_bwd ? nullptr : p->ws("dP4");
+  void* dP4q = f8_bwd ? p->ws("dP4q") : nullptr;
+  void* xb_out = d.f8_w1 ? nullptr : xb;   // (fp8 dW1: nothing reads the frames' bf16 copy)
+  const int n_amax2 = d.f8_w1 ? p->n_amax_dp1 : 0;
+  // In place (N1 as SURVEY 8f words it): fc1's A-tile loader reads frame i at i * hop of the resident bf16 waveform, and
+  // the framed bf16 matrix dW1 needs later is a by-product of that launch -- no cast / gather kernel.  Only when the
+  // padded frame length IS the frame length: with S < Sp the loader's columns S..Sp would be the samples that follow the
+  // frame instead of zeros (harmless to fc1, whose weight columns there are zero, but they would reach the framed copy and
+  // with it fc1's weight gradient and the exponents of its fp16 slabs).
+  const bool in_place = fr && fr->bf16 && !q8 && fr->hop % 8 == 0 && ((uintptr_t)fr->bf16 & 15) == 0 && S == Sp;
+  if (fr && !in_place) {
+    // frames come straight from the resident waveform: waveform -> bf16 (and fp8) operand in one kernel
+    if (slot_on(p, 0))
+      RV_TRY(rv_gather_cast_frames(x, fr->n_samples, fr->idx, fr->first, B, S, fr->hop, xb_out, Bp, Sp, Sp, q8 ? xq : nullptr, Sp,
+                                   q8 ? f8 : nullptr, amax, d.n_amax_h3, n_amax2, counter, stream));
+  } else if (!fr && q8) {
+    if (slot_on(p, 0))
+      RV_TRY(rv_cast_pad_bf16_q8(x, B, S, S, xb_out, Bp, Sp, Sp, xq, Sp, f8, amax, d.n_amax_h3, n_amax2, counter, stream));
+  } else if (!fr) {
+    if (p->cast_done) p->cast_done = 0;   // went out ahead of the previous step's deferred update (rv_plan_step_ddp)
+    else if (slot_on(p, 0)) RV_TRY(rv_cast_pad_bf16(x, B, S, S, xb, Bp, Sp, Sp, counter, stream));
+  }
+  if (slot_on(p, 1)) {
+    if (in_place)
+      RV_TRY(rv_linear_fwd_frames(fr->bf16, fr->idx, fr->first, fr->hop, B, p->ws("W1b"), Sp, b1p, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp,
+                                  xb, Sp, counter, stream));
+    else if (q8)
+      RV_TRY(rv_linear_fwd_fp8(xq, Sp, p->ws("W1q"), Sp, b1p, f8 + 5, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, stream));
+    else
+      RV_TRY(rv_linear_fwd_ex(xb, Sp, p->ws("W1b"), Sp, b1p, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, nullptr, 0, nullptr, nullptr, stream));
+  }
+  if (slot_on(p, 2)) {
+    if (latent_bwd_fused(p)) {   // (the fused forward exists for the same shapes)
+      RV_TRY(rv_latent_fwd_ex(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), W3b, Lp, b3p, Bp, Hp, Lp, B, L, eps, eps_buf, seed,
+                              counter, mulv, z, kl_part, d.no_h3 ? nullptr : h3, Hp, q8 ? h3q : nullptr, Hp, q8 ? f8 + 3 : nullptr,
+                              q8 ? amax : nullptr, stream));
+    } else {
+      RV_TRY(rv_heads_reparam_fwd(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), Bp, Lp, Hp, B, L, p->s_heads,
+                                  (float*)p->ws("mulv_slabs"), eps, eps_buf, seed, counter, mulv, z, kl_part, stream));
+      RV_TRY(rv_linear_fwd_ex(z, Lp, W3b, Lp, b3p, Bp, Hp, Lp, RV_ACT_RELU, h3, Hp, q8 ? h3q : nullptr, q8 ? Hp : 0,
+                              q8 ? f8 + 3 : nullptr, q8 ? amax : nullptr, stream));
+    }
+  }
+  if (slot_on(p, 3)) {
+    if (fr)
+      RV_TRY(rv_decode_out_loss_fwd_frames(q8 ? h3q : h3, Hp, q8 ? W4q : W4b, Hp, b4p, q8 ? f8 + 6 : nullptr, Bp, Sp, Hp, B, S, x,
+                                           fr->n_samples, fr->idx, fr->first, fr->hop, recon_out, S, dP4, Sp, dP4q, Sp, f8 + 12,
+                                           mse_part, db4p, stream));
+    else if (q8)
+      RV_TRY(rv_decode_out_loss_fwd_fp8(h3q, Hp, W4q, Hp, b4p, f8 + 6, Bp, Sp, Hp, B, S, x, S, recon_out, S, dP4, Sp, dP4q, Sp,
+                                        f8 + 12, mse_part, db4p, stream));
+    else
+      RV_TRY(rv_decode_out_loss_fwd(h3, Hp, W4b, Hp, b4p, Bp, Sp, Hp, B, S, x, S, recon_out, S, dP4, Sp, mse_part, db4p, stream));
+  }
+  return RV_OK;
+}
+
+// ---- backward stages between the fc4 pair and fc1's weight gradient
+// Latent part (slot 5): dz and the reparameterisation backward (which also finishes the loss), with fc3's weight gradient
+// when `w3`.  Fused: rv_latent_bwd, dW3 on extra workgroups of the same launch.  Otherwise dz (with dW3 as split-K slabs
+// beside it) and then rv_reparam_bwd.
+static int latent_bwd(rv_plan* p, bool w3, const float* eps_used, float kl_beta, const float* dmu, const float* dlv,
+                      void* stream) {
+  if (!slot_on(p, 5)) return RV_OK;
+  const long B = p->B, S = p->S, L = p->L, Bp = p->Bp, Hp = p->Hp, Lp = p->Lp;
+  void* dP3 = p->ws("dP3"); void* W3b = p->ws("W3b"); void* z = p->ws("z"); void* dmulv = p->ws("dmulv");
+  float* mulv = (float*)p->ws("mulv"); float* dW3 = (float*)p->ws("dW3"); float* dz_slabs = (float*)p->ws("dz_slabs");
+  float* dbhp = (float*)p->ws("dbhp"); float* mse_part = (float*)p->ws("mse_part"); float* kl_part = (float*)p->ws("kl_part");
+  if (latent_bwd_fused(p))
+    return rv_latent_bwd(dP3, Hp, W3b, Lp, Bp, Hp, Lp, B, L, S, mulv, eps_used, kl_beta, dmu, dlv, dmulv, dbhp, mse_part, p->n_mse,
+                         kl_part, p->n_kl, p->b.loss_ring, p->b.step_counter, p->b.ring, w3 ? z : nullptr, Lp, dW3, Lp, p->s_w3,
+                         stream);
+  if (w3) RV_TRY(rv_linear_dgrad_wgrad_f32(dP3, Hp, W3b, Lp, z, Lp, Bp, Lp, Hp, dz_slabs, Lp, p->s_dz, dW3, Lp, p->s_w3, stream));
+  else RV_TRY(rv_linear_dgrad(dP3, Hp, W3b, Lp, Bp, Lp, Hp, nullptr, 0, nullptr, 0, nullptr, dz_slabs, Lp, p->s_dz, stream));
+  return rv_reparam_bwd(dz_slabs, p->s_dz, Bp, Lp, B, L, S, mulv, eps_used, kl_beta, dmu, dlv, dmulv, dbhp, mse_part, p->n_mse,
+                        kl_part, p->n_kl, p->b.loss_ring, p->b.step_counter, p->b.ring, stream);
+}
+
+// Heads part (slot 6): dgrad (ReLU mask of h1) + wgrad from dmulv, one launch.  The streaming kernel where it applies
+// (heads_streaming) -- writing dP1 only as fp8, its maxima behind h3's, when fc1's weight gradient runs on fp8 operands
+// (`f8_w1`) -- else the generic pair.
+static int heads_bwd(rv_plan* p, bool f8_w1, void* stream) {
+  if (!slot_on(p, 6)) return RV_OK;
+  const long Bp = p->Bp, Hp = p->Hp, Lp = p->Lp;
+  void* dmulv = p->ws("dmulv"); void* Whb = p->ws("Whb"); void* h1 = p->ws("h1");
+  float* db1p = (float*)p->ws("db1p"); float* dWh = (float*)p->ws("dWh");
+  float* us = p->heads_half ? (float*)p->ws("dWh_us") : nullptr;
+  if (f8_w1)
+    return rv_heads_bwd_ex(dmulv, Whb, Hp, h1, Hp, Bp, Hp, Lp, nullptr, 0, db1p, dWh, Hp, p->ws("dP1q"), Hp,
+                           (float*)p->ws("fp8_state") + 13, (float*)p->ws("h3_amax") + p->fwd.n_amax_h3, us, stream);
+  if (heads_streaming(p))
+    return rv_heads_bwd_ex(dmulv, Whb, Hp, h1, Hp, Bp, Hp, Lp, p->ws("dP1"), Hp, db1p, dWh, Hp, nullptr, 0, nullptr, nullptr, us,
+                           stream);
+  return rv_linear_dgrad_wgrad(dmulv, 2 * Lp, Whb, Hp, h1, Hp, Bp, Hp, 2 * Lp, p->ws("dP1"), Hp, db1p, dWh, Hp, p->s_wh,
+                               p->heads_half ? RV_SLAB_F16 : RV_SLAB_F32, us, stream);
+}
+
+// ---- the step
+// What a phase mask selects: the one place the RV_PHASE_* bits are read (coarse and fine bits alike)
+namespace {
+struct Stages {
+  bool fwd;
+  bool full_local;   // the whole local step: BWD_A | BWD_B | ADAM, no FINALIZE, Adam from the slabs
+  bool pair;         // fc4's paired backward
+  bool chain_a;      // dz + reparameterisation backward
+  bool chain_b;      // heads dgrad + wgrad, fc1's weight gradient
+  bool w3;           // fc3's weight gradient
+  unsigned fin, adam;   // tensors to finalize / update (bit i = parameter i in state_dict order)
+};
+}  // namespace
+static Stages decode_phases(int phases, int adam_from_flat) {
+  const bool a = phases & RV_PHASE_BWD_A, b = phases & RV_PHASE_BWD_B, chain = phases & RV_PHASE_BWD_CHAIN;
+  Stages s;
+  s.fwd = phases & RV_PHASE_FWD;
+  s.full_local = a && b && (phases & RV_PHASE_ADAM) && !(phases & (RV_PHASE_FINALIZE_A | RV_PHASE_FINALIZE_B)) && !adam_from_flat;
+  s.pair = a || (phases & RV_PHASE_BWD_FC4);
+  s.chain_a = a || chain;
+  s.chain_b = b || chain;
+  s.w3 = a || (phases & RV_PHASE_BWD_REST);
+  s.fin = 0; s.adam = 0;
+  if (phases & RV_PHASE_FINALIZE_A) s.fin |= 0x3C0;  // fc3, fc4
+  if (phases & RV_PHASE_FINALIZE_B) s.fin |= 0x03F;  // fc1, fc21, fc22
+  if (phases & RV_PHASE_FIN_FC4) s.fin |= 0x300;
+  if (phases & RV_PHASE_FIN_FC1) s.fin |= 0x003;
+  if (phases & RV_PHASE_FIN_MID) s.fin |= 0x0FC;
+  if (phases & RV_PHASE_ADAM) s.adam |= 0x3FF;
+  if (phases & RV_PHASE_ADAM_A) s.adam |= 0x3C0;
+  if (phases & RV_PHASE_ADAM_B) s.adam |= 0x03F;
+  if (phases & RV_PHASE_ADAM_FC4) s.adam |= 0x300;
+  if (phases & RV_PHASE_ADAM_FC1) s.adam |= 0x003;
+  if (phases & RV_PHASE_ADAM_MID) s.adam |= 0x0FC;
+  return s;
+}
+
+// The next run of consecutive tensors in `mask` from tensor *i on: [*i, *j), false when there is none.  FINALIZE and Adam
+// go out as one launch per run.
+static bool next_run(unsigned mask, int* i, int* j) {
+  while (*i < 10 && !(mask >> *i & 1)) ++*i;
+  for (*j = *i; *j < 10 && (mask >> *j & 1); ++*j) {}
+  return *i < 10;
+}
+
+// Backward and update of the full local step, one stream.  dW1 is the last GEMM of the backward: 32 tiles x 4 K splits of
+// 256x256 fill half the chip, so its launch also carries the optimizer step of every tensor whose gradient is already
+// complete on the other CUs (fc21, fc22, fc3, fc4); fc1's update is the step's last launch.  An optimizer block streams
+// ~25 GB/s from its CU, so half the chip moves ~3 TB/s -- about what the GEMM blocks take to finish.
+static int local_bwd_adam(rv_plan* p, const float* eps_used, float kl_beta, float lr, float grad_scale, void* stream) {
+  const long Bp = p->Bp, Sp = p->Sp, Hp = p->Hp;
+  const int n_gemm = (int)((Hp / 256) * (Sp / 256) * p->s_w1);
+  int rf = 2, rl = 10;   // tensors [rf, rl) of the table: their updates ride beside fc1's weight gradient (rider_range)
+  {
+    Range r(p->roctx, "rv:fc4-bwd");
+    if (slot_on(p, 4)) RV_TRY(fc4_backward(p, stream));
+  }
+  {
+    Range r(p->roctx, "rv:rest-bwd");
+    // fc1's weight gradient on fp8 operands only when the FORWARD of this step prepared it (no bf16 copy of the frames,
+    // dP1's delayed scale latched from the previous step's maxima): a forward enqueued by a call of its own
+    // (RV_PHASE_FWD alone is not a full local step) wrote the bf16 copies, and this backward reads those
+    const bool f8_w1 = p->fwd.f8_w1 && fp8_w1(p, true);
+    RV_TRY(latent_bwd(p, true, eps_used, kl_beta, nullptr, nullptr, stream));
+    RV_TRY(heads_bwd(p, f8_w1, stream));
+    // (round 3, with 16-byte slab loads in the optimizer blocks: the heads' tensors ride as well -- 192.0 against
+    // 194.8 us per step with only fc3 / fc4 riding, 196.3 with only fc4: profiles/r03_ab_step.txt)
+    // (fp8 operands: only fc4's update riding here and the rest in the last launch was tried in round 5 -- 166.2-167.1 us
+    // per step against 164.0-164.2 with the whole table riding and the GEMM blocks taking 15 % of it: profiles/r05_fp8_riders.txt)
+    rider_range(p, &rf, &rl);
+    if (slot_on(p, 7) && f8_w1)
+      RV_TRY(rv_linear_wgrad_adam_fp8(p->ws("dP1q"), Hp, p->ws("xq"), Sp, (float*)p->ws("fp8_state") + 15, Hp, Sp, Bp, p->s_w1,
+                                      p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, p->d_slab + rf, rl - rf, p->b.param, p->b.exp_avg,
+                                      p->b.exp_avg_sq, lr, grad_scale, p->b.step_counter, 256 - n_gemm, stream));
+    else if (slot_on(p, 7))
+      RV_TRY(rv_linear_wgrad_adam(p->ws("dP1"), Hp, p->ws("xb"), Sp, Hp, Sp, Bp, p->s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1,
+                                  p->d_slab + rf, rl - rf, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, lr, grad_scale,
+                                  p->b.step_counter, 256 - n_gemm, stream));
+  }
+  Range r(p->roctx, "rv:adam");
+  // the last launch: everything that did not ride ([0, rf) and [rl, 10), one table)
+  rv_param_desc rest[10];
+  int n_rest = 0;
+  for (int i = 0; i < 10; ++i)
+    if (i < rf || i >= rl) rest[n_rest++] = p->d_slab[i];
+  if (slot_on(p, 8))
+    RV_TRY(rv_adam_multi(rest, n_rest, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, nullptr, nullptr, lr, grad_scale,
+                         p->b.step_counter, stream));
+  return fp8_after_update(p, stream);
+}
+
+static int plan_step(rv_plan* p, int phases, const float* x, const rv_frame_src* fr, const float* eps, float* recon_out,
+                     float kl_beta, float lr, float grad_scale, int adam_from_flat, unsigned long long seed, void* stream) {
   if (p->tail_pending) {   // a data-parallel step left its last update to "the next call": this is it
     void* ts = p->tail_stream;
     const int frc = rv_plan_ddp_flush(p, nullptr);   // (on the stream that step was enqueued on)
@@ -715,255 +915,60 @@ int rv_plan_step(rv_plan* p, int phases, const float* x, const float* eps, float
       RV_HIP(hipStreamWaitEvent((hipStream_t)stream, p->ev_flush, 0));
     }
   }
-  WtScope wt_scope(p);
-  const long B = p->B, S = p->S, L = p->L, Bp = p->Bp, Sp = p->Sp, Hp = p->Hp, Lp = p->Lp, L2p = p->L2p;
-  void* xb = p->ws("xb"); void* h1 = p->ws("h1"); void* z = p->ws("z"); void* h3 = p->ws("h3");
-  void* dP4 = p->ws("dP4"); void* dP3 = p->ws("dP3"); void* dmulv = p->ws("dmulv"); void* dP1 = p->ws("dP1");
-  float* mulv_slabs = (float*)p->ws("mulv_slabs"); float* mulv = (float*)p->ws("mulv");
-  float* eps_buf = (float*)p->ws("eps"); float* dz_slabs = (float*)p->ws("dz_slabs");
-  float* mse_part = (float*)p->ws("mse_part"); float* kl_part = (float*)p->ws("kl_part");
-  const float* eps_used = eps ? eps : eps_buf;
-  int rc;
-#define RV_TRY(call) do { rc = (call); if (rc) return rc; } while (0)
-#define RV_K(k, call) do { if (!(p->skip >> (k) & 1)) RV_TRY(call); } while (0)   /* launch k of the step (rv_plan_diag_skip) */
-  const bool full_local = (phases & (RV_PHASE_BWD_A | RV_PHASE_BWD_B | RV_PHASE_ADAM)) ==
-                              (RV_PHASE_BWD_A | RV_PHASE_BWD_B | RV_PHASE_ADAM) &&
-                          !(phases & (RV_PHASE_FINALIZE_A | RV_PHASE_FINALIZE_B)) && !adam_from_flat;
-  if (phases & RV_PHASE_FWD) {
+  // every check that can fail the call, ahead of its first launch
+  const Stages st = decode_phases(phases, adam_from_flat);
+  rv_fwd_decisions fd;
+  if (st.fwd) {
     RV_REQUIRE(x, RV_ERR_NULL, "rv_plan_step: x is null");
-    Range range_fwd(p->roctx, "rv:fwd");
-    float* f8 = (float*)p->ws("fp8_state");
-    // fp8 backward of fc4: the forward writes dP4 as fp8 (dP4q) INSTEAD of bf16 (a caller that then supplies its own
-    // gradients gets its bf16 dP4 from rv_tanh_bwd_pack)
-    const bool f8_bwd = fp8_bwd_possible(p);
-    const bool f8_w1 = fp8_w1(p, full_local);     // then nothing reads the frames' bf16 copy: it is not written
-    p->last_fwd_f8_w1 = f8_w1;
-    // ... and nothing but fc4's dgrad reads the bf16 h3 then (its ReLU mask): the fp8 image serves (round 6: 16 MB less
-    // written by the latent forward, 8 MB less read by the pair)
-    const bool no_h3 = f8_w1 && f8_bwd && rv_latent_rowlocal(Bp, Hp, Lp);
-    p->last_fwd_no_h3 = no_h3;
-    void* xb_out = f8_w1 ? nullptr : xb;
-    const int n_amax2 = f8_w1 ? p->n_amax_dp1 : 0;
-    int n_amax = 0;
-    // heads -> reparam -> fc3: one launch where the fused kernel exists (padded latent width 64), else three
-    const bool latent_fused = latent_bwd_fused(p);   // (same shapes both ways)
-    if (p->fp8 && latent_fused && rv_latent_rowlocal(Bp, Hp, Lp)) {
-      n_amax = (int)(Bp / 16) * 8;   // one maximum per wave of rv_latent_fwd_ex
-      RV_REQUIRE(n_amax <= p->n_amax_cap, RV_ERR_STATE, "rv_plan_step: h3_amax holds %d entries, the fused latent forward writes %d", p->n_amax_cap, n_amax);
-    } else if (p->fp8) {
-      int bm3 = 128, bn3 = 128;
-      rv_gemm_tile(Bp, Hp, 1, &bm3, &bn3);
-      n_amax = (int)((Bp / bm3) * (Hp / bn3));
-      RV_REQUIRE(n_amax <= p->n_amax_cap, RV_ERR_SHAPE, "rv_plan_step: fp8 path supports up to %d fc3 output tiles (got %d)", p->n_amax_cap, n_amax);
-    }
-    p->n_amax_h3 = n_amax;
-    // in place only when the padded frame length IS the frame length: with S < Sp the loader's columns S..Sp would be
-    // the samples that follow the frame instead of zeros (harmless to fc1, whose weight columns there are zero, but
-    // they would reach the framed copy and with it fc1's weight gradient and the exponents of its fp16 slabs)
-    if (p->fr_hop && p->fr_bf16 && !p->fp8 && p->fr_hop % 8 == 0 && ((uintptr_t)p->fr_bf16 & 15) == 0 && S == Sp) {
-      // N1 as SURVEY 8f words it: fc1's A-tile loader reads frame i at i * hop of the resident bf16 waveform; the
-      // framed bf16 matrix dW1 needs later is a by-product of that launch; no cast / gather kernel
-      RV_K(1, rv_linear_fwd_frames(p->fr_bf16, p->fr_idx, p->fr_first, p->fr_hop, B, p->ws("W1b"), Sp, (float*)p->ws("b1p"),
-                                  Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, xb, Sp, p->b.step_counter, stream));
-    } else if (p->fr_hop) {
-      // frames come straight from the resident waveform: waveform -> bf16 (and fp8) operand in one kernel
-      RV_K(0, rv_gather_cast_frames(x, p->fr_nsamples, p->fr_idx, p->fr_first, B, S, p->fr_hop, xb_out, Bp, Sp, Sp,
-                                   p->fp8 ? p->ws("xq") : nullptr, Sp, p->fp8 ? f8 : nullptr, (float*)p->ws("h3_amax"), n_amax,
-                                   n_amax2, p->b.step_counter, stream));
-      if (p->fp8)
-        RV_K(1, rv_linear_fwd_fp8(p->ws("xq"), Sp, p->ws("W1q"), Sp, (float*)p->ws("b1p"), f8 + 5, Bp, Hp, Sp, RV_ACT_RELU,
-                                 h1, Hp, stream));
-      else
-        RV_K(1, rv_linear_fwd_ex(xb, Sp, p->ws("W1b"), Sp, (float*)p->ws("b1p"), Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, nullptr, 0,
-                                nullptr, nullptr, stream));
-    } else if (p->fp8) {
-      RV_K(0, rv_cast_pad_bf16_q8(x, B, S, S, xb_out, Bp, Sp, Sp, p->ws("xq"), Sp, f8, (float*)p->ws("h3_amax"), n_amax,
-                                 n_amax2, p->b.step_counter, stream));
-      RV_K(1, rv_linear_fwd_fp8(p->ws("xq"), Sp, p->ws("W1q"), Sp, (float*)p->ws("b1p"), f8 + 5, Bp, Hp, Sp, RV_ACT_RELU,
-                               h1, Hp, stream));
-    } else {
-      if (p->cast_done) p->cast_done = 0;   // went out ahead of the previous step's deferred update (rv_plan_step_ddp)
-      else RV_K(0, rv_cast_pad_bf16(x, B, S, S, xb, Bp, Sp, Sp, p->b.step_counter, stream));
-      RV_K(1, rv_linear_fwd_ex(xb, Sp, p->ws("W1b"), Sp, (float*)p->ws("b1p"), Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, nullptr, 0,
-                                nullptr, nullptr, stream));
-    }
-    {
-      if (latent_fused)
-        RV_K(2, rv_latent_fwd_ex(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), p->ws("W3b"), Lp, (float*)p->ws("b3p"), Bp, Hp, Lp,
-                                B, L, eps, eps_buf, seed, p->b.step_counter, mulv, z, kl_part, no_h3 ? nullptr : h3, Hp,
-                                p->fp8 ? p->ws("h3q") : nullptr, Hp, p->fp8 ? f8 + 3 : nullptr,
-                                p->fp8 ? (float*)p->ws("h3_amax") : nullptr, stream));
-      else
-        RV_K(2, rv_heads_reparam_fwd(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), Bp, Lp, Hp, B, L, p->s_heads, mulv_slabs,
-                                    eps, eps_buf, seed, p->b.step_counter, mulv, z, kl_part, stream));
-      if (p->fr_hop) {
-        if (p->fp8 && !latent_fused)
-          RV_K(2, rv_linear_fwd_ex(z, Lp, p->ws("W3b"), Lp, (float*)p->ws("b3p"), Bp, Hp, Lp, RV_ACT_RELU, h3, Hp,
-                                  p->ws("h3q"), Hp, f8 + 3, (float*)p->ws("h3_amax"), stream));
-        else if (!latent_fused)
-          RV_K(2, rv_linear_fwd_ex(z, Lp, p->ws("W3b"), Lp, (float*)p->ws("b3p"), Bp, Hp, Lp, RV_ACT_RELU, h3, Hp, nullptr, 0,
-                                  nullptr, nullptr, stream));
-        RV_K(3, rv_decode_out_loss_fwd_frames(p->fp8 ? p->ws("h3q") : h3, Hp, p->fp8 ? p->ws("W4q") : p->ws("W4b"), Hp,
-                                             (float*)p->ws("b4p"), p->fp8 ? f8 + 6 : nullptr, Bp, Sp, Hp, B, S, x,
-                                             p->fr_nsamples, p->fr_idx, p->fr_first, p->fr_hop, recon_out, S,
-                                             f8_bwd ? nullptr : dP4, Sp, f8_bwd ? p->ws("dP4q") : nullptr, Sp, f8 + 12,
-                                             mse_part, (float*)p->ws("db4p"), stream));
-      } else if (p->fp8) {
-        if (!latent_fused)
-          RV_K(2, rv_linear_fwd_ex(z, Lp, p->ws("W3b"), Lp, (float*)p->ws("b3p"), Bp, Hp, Lp, RV_ACT_RELU, h3, Hp,
-                                  p->ws("h3q"), Hp, f8 + 3, (float*)p->ws("h3_amax"), stream));
-        RV_K(3, rv_decode_out_loss_fwd_fp8(p->ws("h3q"), Hp, p->ws("W4q"), Hp, (float*)p->ws("b4p"), f8 + 6, Bp, Sp, Hp, B, S,
-                                          x, S, recon_out, S, f8_bwd ? nullptr : dP4, Sp, f8_bwd ? p->ws("dP4q") : nullptr, Sp,
-                                          f8 + 12, mse_part, (float*)p->ws("db4p"), stream));
-      } else {
-        if (!latent_fused)
-          RV_K(2, rv_linear_fwd_ex(z, Lp, p->ws("W3b"), Lp, (float*)p->ws("b3p"), Bp, Hp, Lp, RV_ACT_RELU, h3, Hp, nullptr, 0,
-                                  nullptr, nullptr, stream));
-        RV_K(3, rv_decode_out_loss_fwd(h3, Hp, p->ws("W4b"), Hp, (float*)p->ws("b4p"), Bp, Sp, Hp, B, S, x, S,
-                                      recon_out, S, dP4, Sp, mse_part, (float*)p->ws("db4p"), stream));
-      }
-    }
+    RV_TRY(fwd_decide(p, st.full_local, &fd));
   }
-  // The latent layer's backward (dz + dW3, both read dP3) and the heads' backward (dP1 + dWh, both read
-  // dmulv and h1) each go out as ONE launch (rv_linear_dgrad_wgrad_f32 / rv_linear_dgrad_wgrad).
-  auto latent_bwd = [&](void* st) {
-    return rv_linear_dgrad_wgrad_f32(dP3, Hp, p->ws("W3b"), Lp, z, Lp, Bp, Lp, Hp, dz_slabs, Lp, p->s_dz,
-                                     (float*)p->ws("dW3"), Lp, p->s_w3, st);
-  };
-  auto heads_bwd = [&](void* st) {
-    if (heads_streaming(p))
-      return rv_heads_bwd_ex(dmulv, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, Lp, dP1, Hp, (float*)p->ws("db1p"), (float*)p->ws("dWh"), Hp,
-                             nullptr, 0, nullptr, nullptr, p->heads_half ? (float*)p->ws("dWh_us") : nullptr, st);
-    return rv_linear_dgrad_wgrad(dmulv, L2p, p->ws("Whb"), Hp, h1, Hp, Bp, Hp, L2p, dP1, Hp, (float*)p->ws("db1p"),
-                                 (float*)p->ws("dWh"), Hp, p->s_wh, p->heads_half ? RV_SLAB_F16 : RV_SLAB_F32,
-                                 p->heads_half ? (float*)p->ws("dWh_us") : nullptr, st);
-  };
-  RV_REQUIRE(!(full_local && (p->ext_d_recon || p->ext_dmu || p->ext_dlv)), RV_ERR_STATE,
+  RV_REQUIRE(!(st.full_local && (p->ext_d_recon || p->ext_dmu || p->ext_dlv)), RV_ERR_STATE,
              "rv_plan_step: external gradients are set (rv_plan_set_external_grads); run the backward phases without ADAM");
-  auto reparam_bwd = [&](void* st) {
-    return rv_reparam_bwd(dz_slabs, p->s_dz, Bp, Lp, B, L, S, mulv, eps_used, kl_beta, p->ext_dmu, p->ext_dlv, dmulv,
-                              (float*)p->ws("dbhp"), mse_part, p->n_mse, kl_part, p->n_kl, p->b.loss_ring,
-                              p->b.step_counter, p->b.ring, st);
-  };
-  if (full_local && rv_wgrad_adam_fits(Hp, Sp, Bp, p->s_w1) && (Hp / 256) * (Sp / 256) * p->s_w1 <= 192) {
-    // Default schedule, one stream.  dW1 is the last GEMM of the backward: 32 tiles x 4 K splits of 256x256 fill
-    // half the chip, so its launch also carries the optimizer step of every tensor whose gradient is already
-    // complete on the other CUs (fc21, fc22, fc3, fc4); fc1's update is the step's last launch.  An optimizer block
-    // streams ~25 GB/s from its CU, so half the chip moves ~3 TB/s -- about what the GEMM blocks take to finish.
-    const int n_gemm = (int)((Hp / 256) * (Sp / 256) * p->s_w1);
-    int rf = 2, rl = 10;   // tensors [rf, rl) of the table: their updates ride beside fc1's weight gradient (rider_range)
-    {
-      Range r(p->roctx, "rv:fc4-bwd");
-      RV_K(4, fc4_backward(p, stream));
-    }
-    {
-      Range r(p->roctx, "rv:rest-bwd");
-      // fc1's weight gradient on fp8 operands only when the FORWARD of this step prepared it (no bf16 copy of the frames,
-      // dP1's delayed scale latched from the previous step's maxima): a forward enqueued by a call of its own
-      // (RV_PHASE_FWD alone is not a full local step) wrote the bf16 copies, and this backward reads those
-      const bool f8_w1 = p->last_fwd_f8_w1 && fp8_w1(p, true);
-      RV_TRY(latent_heads_bwd(p, eps_used, kl_beta, nullptr, nullptr, stream, f8_w1));
-      // (round 3, with 16-byte slab loads in the optimizer blocks: the heads' tensors ride as well -- 192.0 against
-      // 194.8 us per step with only fc3 / fc4 riding, 196.3 with only fc4: profiles/r03_ab_step.txt)
-      // (fp8 operands: only fc4's update riding here and the rest in the last launch was tried in round 5 -- 166.2-167.1 us
-      // per step against 164.0-164.2 with the whole table riding and the GEMM blocks taking 15 % of it: profiles/r05_fp8_riders.txt)
-      rider_range(p, &rf, &rl);
-      if (f8_w1)
-        RV_K(7, rv_linear_wgrad_adam_fp8(p->ws("dP1q"), Hp, p->ws("xq"), Sp, (float*)p->ws("fp8_state") + 15, Hp, Sp, Bp, p->s_w1,
-                                         p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, p->d_slab + rf, rl - rf, p->b.param, p->b.exp_avg,
-                                         p->b.exp_avg_sq, lr, grad_scale, p->b.step_counter, 256 - n_gemm, stream));
-      else
-        RV_K(7, rv_linear_wgrad_adam(dP1, Hp, xb, Sp, Hp, Sp, Bp, p->s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, p->d_slab + rf,
-                                     rl - rf, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, lr, grad_scale,
-                                     p->b.step_counter, 256 - n_gemm, stream));
-    }
-    Range r(p->roctx, "rv:adam");
-    // the last launch: everything that did not ride ([0, rf) and [rl, 10), one table)
-    rv_param_desc rest[10];
-    int n_rest = 0;
-    for (int i = 0; i < 10; ++i)
-      if (i < rf || i >= rl) rest[n_rest++] = p->d_slab[i];
-    RV_K(8, rv_adam_multi(rest, n_rest, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, nullptr, nullptr, lr, grad_scale,
-                          p->b.step_counter, stream));
-    return fp8_after_update(p, stream);
-  }
-  // ---- backward / finalize / Adam as an ordered list of steps, each enabled by the phase mask ----
-  const bool old_a = phases & RV_PHASE_BWD_A, old_b = phases & RV_PHASE_BWD_B;
-  const bool do_pair = old_a || (phases & RV_PHASE_BWD_FC4);
-  const bool do_chain_a = old_a || (phases & RV_PHASE_BWD_CHAIN);   // dz, reparam_bwd
-  const bool do_chain_b = old_b || (phases & RV_PHASE_BWD_CHAIN);   // heads dgrad + wgrad (one launch), fc1 wgrad
-  const bool do_w3 = old_a || (phases & RV_PHASE_BWD_REST);         // fc3 wgrad
-  if (do_pair && p->ext_d_recon) {
+  if (st.pair) RV_TRY(h3_check(p, st.fwd ? fd : p->fwd));
+  float* fin_out = p->ext_grad_out ? p->ext_grad_out : p->b.grad;
+  RV_REQUIRE(!st.fin || fin_out, RV_ERR_STATE, "rv_plan_step: FINALIZE needs a grad arena");
+  RV_REQUIRE(!st.adam || !adam_from_flat || p->b.grad, RV_ERR_STATE, "rv_plan_step: adam_from_flat needs a grad arena");
+
+  WtScope wt_scope(p);
+  if (st.fwd) RV_TRY(plan_forward(p, fd, x, fr, eps, recon_out, seed, stream));
+  const float* eps_used = eps ? eps : (float*)p->ws("eps");
+  if (st.full_local && w1_tile(p) == RV_TILE_256x256) return local_bwd_adam(p, eps_used, kl_beta, lr, grad_scale, stream);
+  // ---- otherwise: backward / finalize / Adam as an ordered list of stages, each run when the phase mask selects it
+  const long B = p->B, S = p->S, Bp = p->Bp, Sp = p->Sp, Hp = p->Hp, Lp = p->Lp;
+  if (st.pair && p->ext_d_recon) {
     // dP4 = d_recon * (1 - recon^2) and its column sums (fc4.bias) from the caller's gradient instead of the
     // forward's fused MSE gradient; the partial-sum rows this does not write are zero
     RV_HIP(hipMemsetAsync(p->ws("db4p"), 0, (size_t)p->n_mt4 * Sp * sizeof(float), (hipStream_t)stream));
-    RV_TRY(rv_tanh_bwd_pack(p->ext_d_recon, p->ext_recon, B, S, dP4, Bp, Sp, stream));
-    RV_TRY(rv_colsum_partial(dP4, 1, Bp, Sp, Sp, (float*)p->ws("db4p"), Sp, stream));
+    RV_TRY(rv_tanh_bwd_pack(p->ext_d_recon, p->ext_recon, B, S, p->ws("dP4"), Bp, Sp, stream));
+    RV_TRY(rv_colsum_partial(p->ws("dP4"), 1, Bp, Sp, Sp, (float*)p->ws("db4p"), Sp, stream));
   }
-  if (do_pair) RV_K(4, fc4_backward(p, stream));
-  bool w3_done = false;
-  if (do_chain_a && do_chain_b && do_w3) {
-    RV_TRY(latent_heads_bwd(p, eps_used, kl_beta, p->ext_dmu, p->ext_dlv, stream));
-    w3_done = true;
-  } else {
-    if (do_chain_a && latent_bwd_fused(p)) {
-      RV_TRY(rv_latent_bwd(dP3, Hp, p->ws("W3b"), Lp, Bp, Hp, Lp, B, L, S, mulv, eps_used, kl_beta, p->ext_dmu, p->ext_dlv, dmulv,
-                           (float*)p->ws("dbhp"), mse_part, p->n_mse, kl_part, p->n_kl, p->b.loss_ring, p->b.step_counter,
-                           p->b.ring, do_w3 ? z : nullptr, Lp, (float*)p->ws("dW3"), Lp, p->s_w3, stream));
-      w3_done = do_w3;
-    } else if (do_chain_a) {
-      if (do_w3) {
-        RV_TRY(latent_bwd(stream));
-        w3_done = true;
-      } else {
-        RV_TRY(rv_linear_dgrad(dP3, Hp, p->ws("W3b"), Lp, Bp, Lp, Hp, nullptr, 0, nullptr, 0, nullptr, dz_slabs, Lp,
-                               p->s_dz, stream));
-      }
-      RV_TRY(reparam_bwd(stream));
-    }
-    if (do_chain_b) RV_TRY(heads_bwd(stream));
+  if (st.pair && slot_on(p, 4)) RV_TRY(fc4_backward(p, stream));
+  if (st.chain_a) RV_TRY(latent_bwd(p, st.w3, eps_used, kl_beta, p->ext_dmu, p->ext_dlv, stream));
+  if (st.chain_b) {
+    RV_TRY(heads_bwd(p, false, stream));
+    if (slot_on(p, 7))
+      RV_TRY(rv_linear_wgrad(p->ws("dP1"), Hp, p->ws("xb"), Sp, Hp, Sp, Bp, p->s_w1, w1_tile(p), p->ws("dW1"), Sp, p->slab_dtype,
+                             p->us_w1, stream));
   }
-  if (do_chain_b) {
-    RV_K(7, rv_linear_wgrad(dP1, Hp, xb, Sp, Hp, Sp, Bp, p->s_w1, w1_tile(p), p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, stream));
-  }
-  if (do_w3 && !w3_done) RV_TRY(rv_linear_wgrad(dP3, Hp, z, Lp, Hp, Lp, Bp, p->s_w3, RV_TILE_AUTO, p->ws("dW3"), Lp, RV_SLAB_F32, nullptr, stream));
-
-  // tensor masks (bit i = parameter i in state_dict order)
-  unsigned fin = 0, adam = 0;
-  if (phases & RV_PHASE_FINALIZE_A) fin |= 0x3C0;  // fc3, fc4
-  if (phases & RV_PHASE_FINALIZE_B) fin |= 0x03F;  // fc1, fc21, fc22
-  if (phases & RV_PHASE_FIN_FC4) fin |= 0x300;
-  if (phases & RV_PHASE_FIN_FC1) fin |= 0x003;
-  if (phases & RV_PHASE_FIN_MID) fin |= 0x0FC;
-  if (phases & RV_PHASE_ADAM) adam |= 0x3FF;
-  if (phases & RV_PHASE_ADAM_A) adam |= 0x3C0;
-  if (phases & RV_PHASE_ADAM_B) adam |= 0x03F;
-  if (phases & RV_PHASE_ADAM_FC4) adam |= 0x300;
-  if (phases & RV_PHASE_ADAM_FC1) adam |= 0x003;
-  if (phases & RV_PHASE_ADAM_MID) adam |= 0x0FC;
-  float* fin_out = p->ext_grad_out ? p->ext_grad_out : p->b.grad;
-  if (fin) RV_REQUIRE(fin_out, RV_ERR_STATE, "rv_plan_step: FINALIZE needs a grad arena");
-  if (adam) RV_REQUIRE(!adam_from_flat || p->b.grad, RV_ERR_STATE, "rv_plan_step: adam_from_flat needs a grad arena");
-  const rv_param_desc* ad = adam_from_flat ? p->d_flat : p->d_slab;
-  for (int i = 0; i < 10;) {   // contiguous runs of selected tensors -> one launch each
-    if (!((fin >> i) & 1)) { ++i; continue; }
-    int j = i;
-    while (j < 10 && ((fin >> j) & 1)) ++j;
+  if (st.w3 && !st.chain_a && slot_on(p, 5))   // fc3's weight gradient on its own
+    RV_TRY(rv_linear_wgrad(p->ws("dP3"), Hp, p->ws("z"), Lp, Hp, Lp, Bp, p->s_w3, RV_TILE_AUTO, p->ws("dW3"), Lp, RV_SLAB_F32,
+                           nullptr, stream));
+  for (int i = 0, j; next_run(st.fin, &i, &j); i = j)
     RV_TRY(rv_grad_finalize_scaled(p->d_slab + i, j - i, fin_out, 0, p->loss_grad_dev, stream));
-    i = j;
-  }
-  for (int i = 0; i < 10;) {
-    if (!((adam >> i) & 1)) { ++i; continue; }
-    int j = i;
-    while (j < 10 && ((adam >> j) & 1)) ++j;
-    RV_K(8, rv_adam_multi(ad + i, j - i, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, nullptr, nullptr, lr, grad_scale,
-                          p->b.step_counter, stream));
-    i = j;
-  }
-  if (adam & 0x101) RV_TRY(fp8_after_update(p, stream));   // fc1.weight or fc4.weight were updated
-#undef RV_K
-#undef RV_TRY
+  const rv_param_desc* ad = adam_from_flat ? p->d_flat : p->d_slab;
+  for (int i = 0, j; next_run(st.adam, &i, &j); i = j)
+    if (slot_on(p, 8))
+      RV_TRY(rv_adam_multi(ad + i, j - i, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, nullptr, nullptr, lr, grad_scale,
+                           p->b.step_counter, stream));
+  if (st.adam & 0x101) RV_TRY(fp8_after_update(p, stream));   // fc1.weight or fc4.weight were updated
   return RV_OK;
+}
+
+int rv_plan_step(rv_plan* p, int phases, const float* x, const float* eps, float* recon_out,
+                 float kl_beta, float lr, float grad_scale, int adam_from_flat,
+                 unsigned long long seed, void* stream) {
+  RV_REQUIRE(p && p->bound, RV_ERR_STATE, "rv_plan_step: plan not bound");
+  return plan_step(p, phases, x, nullptr, eps, recon_out, kl_beta, lr, grad_scale, adam_from_flat, seed, stream);
 }
 
 int rv_plan_step_frames(rv_plan* p, int phases, const float* audio, const void* audio_bf16, long n_samples,
@@ -971,10 +976,8 @@ int rv_plan_step_frames(rv_plan* p, int phases, const float* audio, const void* 
                         float kl_beta, float lr, float grad_scale, int adam_from_flat, unsigned long long seed, void* stream) {
   RV_REQUIRE(p && p->bound, RV_ERR_STATE, "rv_plan_step_frames: plan not bound");
   RV_REQUIRE(audio && n_samples > 0 && hop > 0, RV_ERR_SHAPE, "rv_plan_step_frames: bad waveform / hop");
-  p->fr_idx = frame_index; p->fr_first = first_frame; p->fr_hop = hop; p->fr_nsamples = n_samples; p->fr_bf16 = audio_bf16;
-  const int rc = rv_plan_step(p, phases, audio, eps, recon_out, kl_beta, lr, grad_scale, adam_from_flat, seed, stream);
-  p->fr_idx = nullptr; p->fr_first = 0; p->fr_hop = 0; p->fr_nsamples = 0; p->fr_bf16 = nullptr;
-  return rc;
+  const rv_frame_src fr = {frame_index, first_frame, hop, n_samples, audio_bf16};
+  return plan_step(p, phases, audio, &fr, eps, recon_out, kl_beta, lr, grad_scale, adam_from_flat, seed, stream);
 }
 
 // ------------------------------------------------------------ data-parallel step
@@ -1053,40 +1056,37 @@ int rv_plan_step_ddp(rv_plan* p, const float* x, const float* eps, float* recon_
   RV_REQUIRE(p->b.grad, RV_ERR_STATE, "rv_plan_step_ddp: needs a grad arena (the all-reduce payload)");
   WtScope wt_scope(p);
   RV_REQUIRE(stream, RV_ERR_NULL, "rv_plan_step_ddp: needs a non-default stream");
-  if (p->tail_pending) {
-    // the previous step's deferred half: this step's cast first (it reads x and writes the bf16 frames, nothing else --
-    // fc1's weight gradient, the frames' last reader, is long done), then the wait for the exchange and the update
-    RV_REQUIRE(x, RV_ERR_NULL, "rv_plan_step_ddp: x is null");
-    RV_REQUIRE(stream == p->tail_stream, RV_ERR_STATE,
-               "rv_plan_step_ddp: the previous step deferred its last update on another stream (rv_plan_ddp_flush it first)");
-    {
-      // a captured graph would re-apply the previous step's update on every replay
-      hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
-      RV_HIP(hipStreamIsCapturing((hipStream_t)stream, &cap0));
-      RV_REQUIRE(cap0 == hipStreamCaptureStatusNone, RV_ERR_STATE,
-                 "rv_plan_step_ddp: a deferred update is pending and the stream is capturing (rv_plan_ddp_flush before the capture)");
-    }
-    if (!p->fp8 && !(p->skip & 1)) {
-      const int crc = rv_cast_pad_bf16(x, p->B, p->S, p->S, p->ws("xb"), p->Bp, p->Sp, p->Sp, p->b.step_counter, stream);
-      if (crc) return crc;
-      p->cast_done = 1;
-    }
-    // (a failure here leaves cast_done set: the cast HAS run and bumped the device step counter, so a retried call must not
-    // run it -- and count the step -- again; round-5 advisor)
-    const int frc = ddp_finish_tail(p);
-    if (frc) return frc;
-  }
+  RV_REQUIRE(x, RV_ERR_NULL, "rv_plan_step_ddp: x is null");
   const long Bp = p->Bp, Sp = p->Sp, Hp = p->Hp;
-  void* xb = p->ws("xb"); void* dP1 = p->ws("dP1");
-  const float* eps_used = eps ? eps : (float*)p->ws("eps");
-  hipStream_t s0 = (hipStream_t)stream, sc = p->comm_stream;
-  const float scale = 1.0f / (float)p->world;
-  int rc;
-#define RV_TRY(call) do { rc = (call); if (rc) return rc; } while (0)
   // fc1's weight gradient with its finalize riders has an fp8 form (the wide form and the other tiles have none)
   const int s_w1 = (p->ddp_w1_wide && w1_tile(p) == RV_TILE_256x256) ? p->s_w1_ddp : p->s_w1;
   const int n_gemm = (int)((Hp / 256) * (Sp / 256) * s_w1);
   const bool riders = w1_tile(p) == RV_TILE_256x256 && n_gemm <= 192;
+  rv_fwd_decisions fd;
+  RV_TRY(fwd_decide(p, riders && s_w1 == p->s_w1, &fd));
+  RV_TRY(h3_check(p, fd));
+  hipStream_t s0 = (hipStream_t)stream, sc = p->comm_stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  RV_HIP(hipStreamIsCapturing(s0, &cap));
+  if (p->tail_pending) {
+    // the previous step's deferred half: this step's cast first (it reads x and writes the bf16 frames, nothing else --
+    // fc1's weight gradient, the frames' last reader, is long done), then the wait for the exchange and the update
+    RV_REQUIRE(stream == p->tail_stream, RV_ERR_STATE,
+               "rv_plan_step_ddp: the previous step deferred its last update on another stream (rv_plan_ddp_flush it first)");
+    // a captured graph would re-apply the previous step's update on every replay
+    RV_REQUIRE(cap == hipStreamCaptureStatusNone, RV_ERR_STATE,
+               "rv_plan_step_ddp: a deferred update is pending and the stream is capturing (rv_plan_ddp_flush before the capture)");
+    if (!p->fp8 && slot_on(p, 0)) {
+      RV_TRY(rv_cast_pad_bf16(x, p->B, p->S, p->S, p->ws("xb"), p->Bp, p->Sp, p->Sp, p->b.step_counter, stream));
+      p->cast_done = 1;
+    }
+    // (a failure here leaves cast_done set: the cast HAS run and bumped the device step counter, so a retried call must not
+    // run it -- and count the step -- again; round-5 advisor)
+    RV_TRY(ddp_finish_tail(p));
+  }
+  void* xb = p->ws("xb"); void* dP1 = p->ws("dP1");
+  const float* eps_used = eps ? eps : (float*)p->ws("eps");
+  const float scale = 1.0f / (float)p->world;
   // Bucket = tensors [t0, t1) of the flat arena: slabs -> flat payload (caller's stream), then the SUM over ranks
   // on stream `on`
   // fc1's weight gradient on all CUs (see rv_plan_create): its descriptor for the payload kernel carries the split count
@@ -1119,18 +1119,12 @@ int rv_plan_step_ddp(rv_plan* p, const float* x, const float* eps, float* recon_
                                  p->payload_bf16 ? p->grad_bf16 : nullptr, lr, scale, p->b.step_counter, poison, stream);
   };
   // forward + loss and the paired fc4 backward (as rv_plan_step)
-  p->fwd_for_fp8_w1 = riders && s_w1 == p->s_w1;
-  const bool f8_w1 = fp8_w1(p, false);
-  rc = rv_plan_step(p, RV_PHASE_FWD, x, eps, recon_out, kl_beta, lr, 1.f, 0, seed, stream);
-  p->fwd_for_fp8_w1 = false;
-  if (rc) return rc;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  RV_HIP(hipStreamIsCapturing(s0, &cap));
+  RV_TRY(plan_forward(p, fd, x, nullptr, eps, recon_out, seed, stream));
   bool edge0_armed = false;   // the paired launch itself signals ev_ready[0] (see `signal`, edge 0)
   {
     Range r(p->roctx, "rv:fc4-bwd");
     if (cap == hipStreamCaptureStatusNone) rv_pair_stop_event(p->ev_ready[0]);
-    rc = fc4_backward(p, stream);
+    const int rc = fc4_backward(p, stream);
     edge0_armed = cap == hipStreamCaptureStatusNone && !rv_pair_stop_event(nullptr);   // taken by a paired launch
     if (rc) return rc;
   }
@@ -1180,7 +1174,8 @@ int rv_plan_step_ddp(rv_plan* p, const float* x, const float* eps, float* recon_
   RV_TRY(payload(8, 10, sc));                              // slabs and travels behind ALL the rest of the backward
   RV_TRY(reduce(0, 8, 10, sc));
   RV_TRY(post(2, sc));
-  RV_TRY(latent_heads_bwd(p, eps_used, kl_beta, nullptr, nullptr, stream, f8_w1));
+  RV_TRY(latent_bwd(p, true, eps_used, kl_beta, nullptr, nullptr, stream));
+  RV_TRY(heads_bwd(p, fd.f8_w1, stream));
   // dW1 runs WITHOUT optimizer riders here: at several ranks fc4's sum has not arrived when this launch starts (an 8.4 MB
   // bucket needs 40-65 us on the links; the latent-sized backward in front of this launch lasts 25).  It keeps the local
   // step's 128 workgroups by default: this launch runs beside fc4's exchange, whose workgroups hold CUs, and a GEMM that
@@ -1189,7 +1184,7 @@ int rv_plan_step_ddp(rv_plan* p, const float* x, const float* eps, float* recon_
     // the GEMM leaves CUs idle: rider blocks sum the slabs of everything else in the second bucket (fc1.bias, heads, fc3:
     // complete since the heads' backward) into the payload meanwhile, and only fc1.weight's own slabs are left to sum
     void* pay = p->payload_bf16 ? p->grad_bf16 : (void*)p->b.grad;
-    if (f8_w1)
+    if (fd.f8_w1)
       RV_TRY(rv_linear_wgrad_finalize_fp8(p->ws("dP1q"), Hp, p->ws("xq"), Sp, (float*)p->ws("fp8_state") + 15, Hp, Sp, Bp, s_w1,
                                           p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, dd + 1, 7, pay, p->payload_bf16, 256 - n_gemm,
                                           stream));

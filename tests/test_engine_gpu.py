@@ -391,3 +391,27 @@ def test_fp16_split_k_slabs_vs_fp32_slabs(shape):
         r.step(xi, ei)
     la, lb = np.array(e.losses(6)), np.array(r.losses(6))
     assert np.abs(la - lb).max() <= 1e-4 * lb.max(), (la, lb)
+
+
+def test_full_local_step_with_external_grads_is_refused_before_any_launch():
+    """A full local step (backward + ADAM in one call) cannot take gradients from outside.  The call is refused before its
+    forward goes out: the device step counter and recon_out are as they were."""
+    from rawaudiovae_kelsey_amd._lib import RvError, lib, ptr
+    S, H, L, B = 64, 96, 8, 16
+    e = _engine(S, H, L, B)
+    x = torch.from_numpy(make_frames(B, S, 1234)).cuda()
+    eps = torch.from_numpy(make_eps(B, L, 4321)).cuda()
+    e.step(x, eps)
+    recon = torch.full((B, S), 7.0, device="cuda")
+    d_recon = torch.ones(B, S, device="cuda")
+    torch.cuda.synchronize()
+    steps = e.step_counter.clone()
+    lib().rv_plan_set_external_grads(e._plan, ptr(d_recon), ptr(recon), None, None, None)
+    try:
+        with pytest.raises(RvError, match="external gradients"):
+            e.step(x, eps, recon)
+    finally:
+        lib().rv_plan_set_external_grads(e._plan, None, None, None, None, None)
+    torch.cuda.synchronize()
+    assert torch.equal(e.step_counter, steps)
+    assert (recon == 7.0).all()

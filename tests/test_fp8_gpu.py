@@ -248,3 +248,29 @@ def test_fp8_split_phase_calls_follow_the_forwards_decision():
         a = two.view(two.exp_avg, k).cpu().numpy().astype(np.float64)
         b = one.view(one.exp_avg, k).cpu().numpy().astype(np.float64)
         assert _rel_l2(a, b) < (6e-2 if k == "fc1.weight" else 1e-3), (k, _rel_l2(a, b))
+
+
+def test_fp8_backward_after_full_step_refuses_the_h3_it_left_unwritten():
+    """A full fp8 step at C2 leaves the bf16 h3 unwritten (fc4's dgrad masks with its fp8 image).  Gradients from outside
+    set after it send fc4's backward down the bf16 form, which reads that h3: a backward-only call must refuse, not run on
+    a stale mask.  A call with a forward of its own then runs."""
+    from rawaudiovae_kelsey_amd import engine as E
+    from rawaudiovae_kelsey_amd._lib import RvError, lib, ptr
+    S, H, L, B = 1024, 2048, 64, 4096
+    x = torch.from_numpy(make_frames(B, S, 1234)).cuda()
+    eps = torch.from_numpy(make_eps(B, L, 4321)).cuda()
+    e = _engine(S, H, L, B, fp8="full")
+    e.step(x, eps)
+    recon = torch.zeros(B, S, device="cuda")
+    d_recon = torch.ones(B, S, device="cuda")
+    grad = torch.zeros(e.n_params, device="cuda")
+    bwd = E.PHASE_BWD_A | E.PHASE_BWD_B | E.PHASE_FINALIZE_A | E.PHASE_FINALIZE_B
+    lib().rv_plan_set_external_grads(e._plan, ptr(d_recon), ptr(recon), None, None, ptr(grad))
+    try:
+        with pytest.raises(RvError, match="forward of its own"):
+            e.step(x, eps, phases=bwd)
+        e.step(x, eps, recon, phases=E.PHASE_FWD | bwd)
+    finally:
+        lib().rv_plan_set_external_grads(e._plan, None, None, None, None, None)
+    torch.cuda.synchronize()
+    assert torch.isfinite(grad).all() and grad.abs().sum() > 0
