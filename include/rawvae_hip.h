@@ -385,6 +385,42 @@ int rv_som_node_sums(const float* x, long N, long L, const int* bmu, long M, dou
 int rv_som_update(const double* sums, const long long* counts, const float* w_old, long rows, long cols, long L,
                   double sigma, float* w_new, void* stream);
 
+/* ---- Streaming resynthesis (csrc/stream.hip) ----
+ * rv_small_linear_f32: y = act(x W^T + b) for few rows, one lane per output column: acc = +0, then
+ * acc = fmaf(x[k], W[n,k], acc) in ascending k, + b, then fmaxf / tanhf (act 0 none, 1 relu, 2 tanh) -- the arithmetic of
+ * rv_linear_fp32, and a row's value does not depend on M.  x [M, K] with row stride ldx (rows may overlap), W [N, K]
+ * with row stride ldw >= K, b [N] or NULL, y [M, N] with row stride ldy >= N. */
+int rv_small_linear_f32(const float* x, long ldx, const float* w, long ldw, const float* bias, long M, long N, long K,
+                        int act, float* y, long ldy, void* stream);
+
+/* One call of the streaming engine: n_streams streams, `block` new samples each, frames of S samples every `hop`
+ * (P = S - hop samples of history), F = block / hop frames decoded per stream.  Weights are the model's fp32 tensors
+ * in place ([out, in], contiguous).  Rows of mu / logvar / eps are stream-major: row s * F + j.  The controls give
+ * mu' = mu * scale + offset and z = mu' + (temperature * eps) * exp(logvar / 2); eps is eps_in [n_streams * F, L] or,
+ * when eps_in is NULL, Philox(seed) keyed by (stream, absolute frame, latent index).  window [S] (ones for a
+ * rectangular window) and norm [P + hop] (the window sums of output position t, t < P, and of P + t % hop beyond) are
+ * the caller's.  State (history, overlap-add tail, frame counters) lives in the workspace of
+ * rv_stream_workspace_bytes, zeroed before the first call. */
+typedef struct rv_stream_desc {
+  long S, H, L, n_streams, block, hop;
+  const float *w1, *b1, *w21, *b21, *w22, *b22, *w3, *b3, *w4, *b4;
+  const float* x;      /* [n_streams, ld_x]: the block of every stream             */
+  long ld_x;
+  float* y;            /* [n_streams, ld_y]: the block of output of every stream   */
+  long ld_y;
+  float *mu, *logvar;  /* [n_streams * F, L]                                       */
+  const float* eps_in; /* [n_streams * F, L] or NULL                               */
+  unsigned long long seed;
+  const float *scale, *offset; /* [n_streams, L]                                   */
+  const float* temperature;    /* [n_streams]                                      */
+  const float *window, *norm;
+  void* workspace;
+} rv_stream_desc;
+long rv_stream_workspace_bytes(long S, long H, long L, long n_streams, long block, long hop);
+int rv_stream_process(const rv_stream_desc* d, void* stream);
+/* Zero the state of stream `which` (-1: every stream) of the workspace laid out for d's extents. */
+int rv_stream_reset(const rv_stream_desc* d, long which, void* stream);
+
 /* Standard normal draws (replaces torch.randn_like, model.py:25). */
 int rv_randn(float* out, long n, unsigned long long seed, unsigned long long offset,
              void* stream);

@@ -32,6 +32,16 @@ class PlanBuffers(C.Structure):
                 ("loss_ring", c_void_p), ("ring", c_int)]
 
 
+class StreamDesc(C.Structure):
+    """rv_stream_desc: one call of the streaming resynthesis engine (stream.py)."""
+    _fields_ = ([(n, c_long) for n in ("S", "H", "L", "n_streams", "block", "hop")]
+                + [(n, c_void_p) for n in ("w1", "b1", "w21", "b21", "w22", "b22", "w3", "b3", "w4", "b4")]
+                + [("x", c_void_p), ("ld_x", c_long), ("y", c_void_p), ("ld_y", c_long), ("mu", c_void_p),
+                   ("logvar", c_void_p), ("eps_in", c_void_p), ("seed", c_u64), ("scale", c_void_p),
+                   ("offset", c_void_p), ("temperature", c_void_p), ("window", c_void_p), ("norm", c_void_p),
+                   ("workspace", c_void_p)])
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),
@@ -111,6 +121,11 @@ _SIGS = {
     "rv_match_pad": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p]),
     "rv_latent_mix": (c_int, [c_void_p] * 4 + [c_long, c_long, c_int, c_void_p, c_long, c_long, c_long, c_void_p, c_void_p,
                               c_u64, c_u64] + [c_void_p] * 5),
+    "rv_small_linear_f32": (c_int, [c_void_p, c_long, c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_int,
+                                    c_void_p, c_long, c_void_p]),
+    "rv_stream_workspace_bytes": (c_long, [c_long] * 6),
+    "rv_stream_process": (c_int, [C.POINTER(StreamDesc), c_void_p]),
+    "rv_stream_reset": (c_int, [C.POINTER(StreamDesc), c_long, c_void_p]),
     "rv_segment_mean": (c_int, [c_void_p, c_long, c_long, c_void_p, C.POINTER(c_i64), c_long, c_void_p, c_void_p]),
     "rv_som_bmu": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long] + [c_void_p] * 5),
     "rv_som_node_sums": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),

@@ -1,0 +1,120 @@
+"""`python resynth.py --config default.ini --checkpoint ckpt_00500 --in in.wav --out out.wav --hop 256 --window hann`
+
+Streaming resynthesis of one wav through a trained model, block by block, as a live host would run it
+(rawaudiovae_kelsey_amd.stream.StreamingVAE with one stream):
+
+  --hop N            frame hop (default: segment_length, the reference's non-overlapping reconstruction)
+  --window hann|none weighted overlap-add window (default none: rectangular)
+  --block N          samples per call (a multiple of hop; default segment_length); the output does not depend on it
+  --temperature T    scale of eps (0: decode mu' itself)
+  --offset file.npy  latent_dim values added to mu
+  --seed S           seed of the on-device eps draw
+
+The input is fed in blocks, followed by zeros to flush the latency (segment_length - hop samples); the output is
+trimmed by that latency so that it lines up with the input and has its length.  Bad flag values raise ValueError
+naming the flag.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Block-by-block streaming resynthesis of a wav on the GPU")
+    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
+    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    p.add_argument("--in", dest="inp", required=True, help="input wav")
+    p.add_argument("--out", required=True, help="output wav")
+    p.add_argument("--hop", default=None, help="frame hop (default: segment_length)")
+    p.add_argument("--window", default="none", help="none | hann")
+    p.add_argument("--block", default=None, help="samples per call (default: segment_length)")
+    p.add_argument("--temperature", default="1", help="scale of eps")
+    p.add_argument("--offset", default=None, help=".npy of latent_dim values added to mu")
+    p.add_argument("--seed", default="0", help="seed of the eps draw")
+    args = p.parse_args(argv)
+    for flag in ("hop", "block", "seed"):
+        v = getattr(args, flag)
+        if v is None:
+            continue
+        try:
+            iv = int(v)
+        except ValueError:
+            iv = -1
+        if iv < 0 or (flag != "seed" and iv == 0):
+            raise ValueError("--%s %r: expected a %s integer" % (flag, v, "non-negative" if flag == "seed" else "positive"))
+        setattr(args, flag, iv)
+    try:
+        args.temperature = float(args.temperature)
+    except ValueError:
+        raise ValueError("--temperature %r: expected a number" % args.temperature)
+    if args.window not in ("none", "hann"):
+        raise ValueError("--window %r: expected none or hann" % args.window)
+    args.window = None if args.window == "none" else args.window
+    return args
+
+
+def check_stream(args, cfg):
+    """(hop, block, latency) of the flags against the model's segment_length; ValueError naming the flag."""
+    from rawaudiovae_kelsey_amd.stream import check_args
+    S = cfg["segment_length"]
+    hop = S if args.hop is None else args.hop
+    block = S if args.block is None else args.block
+    try:
+        _, latency, _ = check_args(S, block, hop, args.window)
+    except ValueError as e:
+        raise ValueError("--hop %d / --block %d / --window %s: %s" % (hop, block, args.window or "none", e))
+    return hop, block, latency
+
+
+def resynthesize(model, audio, hop, block, window=None, temperature=1.0, offset=None, seed=0):
+    """The whole waveform through one stream: [audio | zeros] in blocks, output trimmed by the latency -> fp32 numpy
+    array of len(audio) samples."""
+    import torch
+    from rawaudiovae_kelsey_amd.stream import StreamingVAE
+    eng = StreamingVAE(model, 1, block, hop=hop, window=window, seed=seed)
+    eng.temperature.fill_(float(temperature))
+    if offset is not None:
+        eng.offset.copy_(torch.as_tensor(np.asarray(offset, dtype=np.float32).reshape(1, -1)))
+    n = audio.size
+    total = -(-(n + eng.latency) // block) * block
+    x = np.zeros(total, dtype=np.float32)
+    x[:n] = audio
+    xd = torch.from_numpy(x).to(eng.device)
+    out = torch.empty(total, dtype=torch.float32, device=eng.device)
+    for k in range(total // block):
+        out[k * block:(k + 1) * block] = eng.process(xd[k * block:(k + 1) * block].view(1, block))[0]
+    return out[eng.latency:eng.latency + n].cpu().numpy()
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    from interpolate import load_model, read_model_config
+    cfg = read_model_config(args.config)
+    hop, block, _ = check_stream(args, cfg)
+    offset = None
+    if args.offset is not None:
+        if not os.path.exists(args.offset):
+            raise ValueError("--offset %r: no such file" % args.offset)
+        offset = np.load(args.offset)
+        if offset.ndim != 1 or offset.size != cfg["latent_dim"]:
+            raise ValueError("--offset %r: expected %d values, got shape %s" % (args.offset, cfg["latent_dim"],
+                                                                                offset.shape))
+    from rawaudiovae_kelsey_amd import data as D
+    model = load_model(args.checkpoint, cfg)
+    sr = cfg["sampling_rate"]
+    a = D.load_audio_mono(args.inp, sr)
+    y = resynthesize(model, a, hop, block, args.window, args.temperature, offset, args.seed)
+    D.write_wav(args.out, y, sr)
+    print("wrote %s: %d samples (%.2f s at %d Hz), hop %d, block %d, window %s"
+          % (args.out, y.size, y.size / sr, sr, hop, block, args.window or "none"))
+    return y
+
+
+if __name__ == "__main__":
+    main()
