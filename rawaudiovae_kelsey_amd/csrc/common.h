@@ -97,6 +97,22 @@ __device__ __forceinline__ float fast_tanh(float y) {
 
 }  // namespace rv
 
+// Slots of the fp8 state block (workspace buffer "fp8_state"; the layout is documented under RV_OPT_FP8 in the public
+// header): scales, the dequantisation factors the first kernel of a step rewrites, the maxima they follow.
+enum Fp8Slot {
+  FP8_X_SCALE = 0, FP8_W1_SCALE = 1, FP8_W4_SCALE = 2, FP8_H3_SCALE = 3,
+  FP8_H3_MAX = 4,                     // max|h3| of the previous step
+  FP8_DQ_X_W1 = 5, FP8_DQ_H3_W4 = 6,  // fc1's and fc4's forward
+  FP8_FREEZE = 7,                     // non-zero: keep the h3 / dP1 / weight scales fixed
+  FP8_W1_MAX = 8, FP8_W4_MAX = 9,
+  FP8_DQ_DP4_W4 = 10, FP8_DQ_DP4_H3 = 11,  // fc4's backward: dgrad / wgrad
+  FP8_DP4_SCALE = 12, FP8_DP1_SCALE = 13,
+  FP8_DP1_MAX = 14,                   // max|dP1| of the previous step
+  FP8_DQ_DP1_X = 15,                  // fc1's weight gradient
+  FP8_STATE_FLOATS = 16,              // the state proper (then 16 reserved floats)
+  FP8_WMAX = 32,                      // first of the 2 x 1024 max|W| slots behind them
+};
+
 // ---- host-side error plumbing (C-ABI functions return int, never throw) ----
 enum {
   RV_OK = 0,

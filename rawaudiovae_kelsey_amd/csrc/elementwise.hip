@@ -60,7 +60,7 @@ constexpr int FP8_WSLOTS = 1024;
 __device__ __forceinline__ void fp8_latch_block(float* st, const float* amax_part, int n_amax, int n_amax2) {
   __shared__ float red[4][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  float* w_amax = st + 32;
+  float* w_amax = st + FP8_WMAX;
   float a[FP8_WSLOTS / 256], b[FP8_WSLOTS / 256];
 #pragma unroll
   for (int k = 0; k < FP8_WSLOTS / 256; ++k) {
@@ -93,38 +93,38 @@ __device__ __forceinline__ void fp8_latch_block(float* st, const float* amax_par
     g1 = fmaxf(fmaxf(red[3][0], red[3][1]), fmaxf(red[3][2], red[3][3]));
     // the whole block in registers first: read entry by entry between the writes below, every access would be a round
     // trip of its own (the compiler cannot move a load of st[] over a store to st[]) -- ~4 us at the head of the step
-    float s[16];
+    float s[FP8_STATE_FLOATS];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < FP8_STATE_FLOATS / 4; ++k) {
       const float4 v = reinterpret_cast<const float4*>(st)[k];
       s[4 * k] = v.x; s[4 * k + 1] = v.y; s[4 * k + 2] = v.z; s[4 * k + 3] = v.w;
     }
-    const bool live = s[7] == 0.f;
-    s[4] = m;
-    if (live && m > 0.f) s[3] = 224.f / m;
-    s[5] = 1.f / (s[0] * s[1]);
-    s[6] = 1.f / (s[3] * s[2]);
+    const bool live = s[FP8_FREEZE] == 0.f;
+    s[FP8_H3_MAX] = m;
+    if (live && m > 0.f) s[FP8_H3_SCALE] = 224.f / m;
+    s[FP8_DQ_X_W1] = 1.f / (s[FP8_X_SCALE] * s[FP8_W1_SCALE]);
+    s[FP8_DQ_H3_W4] = 1.f / (s[FP8_H3_SCALE] * s[FP8_W4_SCALE]);
     // fp8 backward of fc4: dP4's image is written with the fixed scale [12] (set by the caller: 112 / (2 / (B S)), so
     // that |dP4| <= 2 * 2 / (B S) lands within +-224); the dgrad multiplies it with W4's shadow, the wgrad with h3's image
-    s[10] = 1.f / (s[12] * s[2]);
-    s[11] = 1.f / (s[12] * s[3]);
+    s[FP8_DQ_DP4_W4] = 1.f / (s[FP8_DP4_SCALE] * s[FP8_W4_SCALE]);
+    s[FP8_DQ_DP4_H3] = 1.f / (s[FP8_DP4_SCALE] * s[FP8_H3_SCALE]);
     // fp8 weight gradient of fc1: the heads' backward writes dP1's image with [13], which follows the maximum it
     // measured in the previous step (delayed scaling, as h3's); the GEMM multiplies it with x's image
     if (n_amax2 > 0) {
-      s[14] = g1;
-      if (live && g1 > 0.f) s[13] = 224.f / g1;
+      s[FP8_DP1_MAX] = g1;
+      if (live && g1 > 0.f) s[FP8_DP1_SCALE] = 224.f / g1;
     }
-    s[15] = 1.f / (s[13] * s[0]);
+    s[FP8_DQ_DP1_X] = 1.f / (s[FP8_DP1_SCALE] * s[FP8_X_SCALE]);
     // the weight shadows read by this step were written with [1] / [2] (now inside [5] / [6]); the coming optimizer
     // update quantises with scales that follow the weights it last saw
-    s[8] = w1;
-    s[9] = w4;
+    s[FP8_W1_MAX] = w1;
+    s[FP8_W4_MAX] = w4;
     if (live) {
-      if (w1 > 0.f) s[1] = 224.f / w1;
-      if (w4 > 0.f) s[2] = 224.f / w4;
+      if (w1 > 0.f) s[FP8_W1_SCALE] = 224.f / w1;
+      if (w4 > 0.f) s[FP8_W4_SCALE] = 224.f / w4;
     }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) reinterpret_cast<float4*>(st)[k] = make_float4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
+    for (int k = 0; k < FP8_STATE_FLOATS / 4; ++k) reinterpret_cast<float4*>(st)[k] = make_float4(s[4 * k], s[4 * k + 1], s[4 * k + 2], s[4 * k + 3]);
   }
 }
 
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) k_fp8_wmax(const unsigned char* __restric
   const unsigned char* q = second ? w4q : w1q;
   const long n = second ? n4 : n1;
   const int b = (int)blockIdx.x - (second ? WMAX_BLOCKS : 0);
-  const float inv_scale = 1.f / st[second ? 2 : 1];   // (requested with the data, not behind the reduction)
+  const float inv_scale = 1.f / st[second ? FP8_W4_SCALE : FP8_W1_SCALE];   // (requested with the data, not behind the reduction)
   float m = 0.f;
   constexpr long STRIDE = (long)WMAX_BLOCKS * 256 * 16;
   for (long i = ((long)b * 256 + threadIdx.x) * 16; i + 16 <= n; i += 4 * STRIDE) {
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(256) k_fp8_wmax(const unsigned char* __restric
   if (threadIdx.x == 0) {
     m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     // block b of a tensor owns slot b of that tensor's 1024 (the rest stay zero)
-    st[32 + (second ? FP8_WSLOTS : 0) + b] = m * inv_scale;
+    st[FP8_WMAX + (second ? FP8_WSLOTS : 0) + b] = m * inv_scale;
   }
 }
 
@@ -695,7 +695,7 @@ int rv_cast_pad_bf16_q8(const float* src, long rows, long cols, long ld_src, voi
   RV_REQUIRE(total < 0x7fffffffL, RV_ERR_SHAPE, "cast: %ld x %ld is too large for one launch", rows_p, cols_p);
   hipLaunchKernelGGL(k_cast_pad_bf16, dim3(grid_for(total, 8192) + (fp8_state ? 1 : 0)), dim3(256), 0, (hipStream_t)stream,
                      src, rows, cols, ld_src, (bf16_t*)dst, rows_p, cols_p, ld_dst, step_counter,
-                     (unsigned char*)dst_fp8, ld_fp8, fp8_state, (const float*)fp8_state /* [0] = scale of x */,
+                     (unsigned char*)dst_fp8, ld_fp8, fp8_state, fp8_state + FP8_X_SCALE,
                      amax_part, amax_part ? n_amax : 0, amax_part ? n_amax2 : 0, (const long long*)nullptr, 0L, 0L, 0L, cast_wt());
   RV_CHECK_LAUNCH();
   return RV_OK;
@@ -715,7 +715,7 @@ int rv_gather_cast_frames(const float* audio, long n_samples, const long long* f
   RV_REQUIRE(total < 0x7fffffffL, RV_ERR_SHAPE, "cast: %ld x %ld is too large for one launch", rows_p, cols_p);
   hipLaunchKernelGGL(k_cast_pad_bf16, dim3(grid_for(total, 8192) + (fp8_state ? 1 : 0)), dim3(256), 0, (hipStream_t)stream,
                      audio, n_frames, S, 0L, (bf16_t*)dst_bf16, rows_p, cols_p, ld_dst, step_counter,
-                     (unsigned char*)dst_fp8, ld_fp8, fp8_state, (const float*)fp8_state, amax_part,
+                     (unsigned char*)dst_fp8, ld_fp8, fp8_state, fp8_state + FP8_X_SCALE, amax_part,
                      amax_part ? n_amax : 0, amax_part ? n_amax2 : 0, frame_index, first_frame, hop, n_samples, cast_wt());
   RV_CHECK_LAUNCH();
   return RV_OK;

@@ -98,8 +98,6 @@ int launch_tile(int tile, const GemmArgs& a, long Mp, long Np, long Kp, int spli
   RV_REQUIRE(tile_fits(tile, Mp, Np), RV_ERR_SHAPE, "gemm: tile %d does not divide %ld x %ld", tile, Mp, Np);
   RV_REQUIRE(splits >= 1 && (Kp / 64) % splits == 0, RV_ERR_SHAPE,
              "gemm: K tiles %ld not divisible by splits %d", Kp / 64, splits);
-  RV_REQUIRE(a.lda % 8 == 0 && a.ldb % 8 == 0, RV_ERR_SHAPE, "gemm: leading dims must be multiples of 8");
-  RV_REQUIRE((((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0, RV_ERR_SHAPE, "gemm: operands must be 16-byte aligned");
   switch (tile) {
     case 0: return launch<64, 64, 2, 2, 4, AK, BK, EPI>(a, Mp, Np, splits, st);
     case 1: return launch<128, 128, 2, 2, 4, AK, BK, EPI>(a, Mp, Np, splits, st);
@@ -149,7 +147,7 @@ gemm_wgrad_adam_kernel(const GemmArgs wgrad, const int n_gemm, const DescTable t
   } else {
     if (fin_f32 || fin_bf16) {
       // riders that only SUM the slabs of the table's tensors into a flat gradient payload (rv_grad_finalize's work;
-      // rv_linear_wgrad_finalize): the data-parallel step's second bucket minus the gradient this GEMM produces
+      // a payload target of rv_linear_wgrad_riders): the data-parallel step's second bucket minus the gradient this GEMM produces
       const long total = tab.blk_start[tab.n];
       const int half = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 8));
       for (long vb = 2L * ((long)blockIdx.x - n_gemm) + half; vb < total; vb += 2L * ((long)gridDim.x - n_gemm))
@@ -173,14 +171,11 @@ gemm_wgrad_adam_kernel(const GemmArgs wgrad, const int n_gemm, const DescTable t
   }
 }
 
-// fp8 (e4m3) forward GEMMs: operands are fp8 bytes viewed as bf16 pairs, `Kp2` = K / 2 in such pairs (so a staged
-// 64-pair tile holds 128 fp8 values per row and every tile / swizzle / ring rule of the bf16 kernels carries over).
+// fp8 (e4m3) forward GEMMs (operands as set_operands leaves them; `Kp` in fp8 values)
 template <int EPI>
-int launch_tile_fp8(int tile, const GemmArgs& a, long Mp, long Np, long Kp2, hipStream_t st) {
-  RV_REQUIRE(Mp > 0 && Np > 0 && Kp2 > 0 && Kp2 % 64 == 0, RV_ERR_SHAPE, "fp8 gemm: K must be a multiple of 128 (got %ld)", 2 * Kp2);
+int launch_tile_fp8(int tile, const GemmArgs& a, long Mp, long Np, long Kp, hipStream_t st) {
+  RV_REQUIRE(Mp > 0 && Np > 0 && Kp > 0 && Kp % 128 == 0, RV_ERR_SHAPE, "fp8 gemm: K must be a multiple of 128 (got %ld)", Kp);
   RV_REQUIRE(tile_fits(tile, Mp, Np), RV_ERR_SHAPE, "fp8 gemm: tile %d does not divide %ld x %ld", tile, Mp, Np);
-  RV_REQUIRE(a.lda % 8 == 0 && a.ldb % 8 == 0, RV_ERR_SHAPE, "fp8 gemm: leading dims must be multiples of 16 bytes");
-  RV_REQUIRE((((uintptr_t)a.A | (uintptr_t)a.B) & 15) == 0, RV_ERR_SHAPE, "fp8 gemm: operands must be 16-byte aligned");
   switch (tile) {
     case 0: return launch<64, 64, 2, 2, 4, true, true, EPI, true>(a, Mp, Np, 1, st);
     case 2: return launch<256, 128, 4, 2, 3, true, true, EPI, true>(a, Mp, Np, 1, st);
@@ -201,6 +196,23 @@ int set_slabs(GemmArgs& g, void* dw, long lddw, long split_stride, int dtype, fl
     g.out_f16 = dw; g.f16_unscale = unscale;
     g.us_ld = Np / 32; g.us_split_stride = (Mp / 32) * (Np / 32);
   }
+  return RV_OK;
+}
+
+// A / B operands and K tiling of `g` (rv_gemm_operands).  fp8 (e4m3) operands are bytes viewed as bf16 pairs: leading
+// dims and K halve, so a staged 64-pair K tile holds 128 fp8 values per row and every tile / swizzle / ring rule of the
+// bf16 kernels carries over.  `K`: the contraction one block walks (one split's share).  Rows of 16 bytes, whole K tiles
+// and 16-byte aligned operands (the LDS-DMA pieces) are checked here for every launcher.
+int set_operands(const char* who, GemmArgs& g, const rv_gemm_operands& op, long K) {
+  const bool fp8 = op.dq != nullptr;
+  const long kt = fp8 ? 128 : 64, ld = fp8 ? 16 : 8;
+  RV_REQUIRE(K % kt == 0 && op.lda % ld == 0 && op.ldb % ld == 0, RV_ERR_SHAPE,
+             "%s: K and leading dims must be multiples of %ld / %ld%s elements", who, kt, ld, fp8 ? " fp8" : "");
+  RV_REQUIRE((((uintptr_t)op.a | (uintptr_t)op.b) & 15) == 0, RV_ERR_SHAPE, "%s: operands must be 16-byte aligned", who);
+  const int per = fp8 ? 2 : 1;   // elements per bf16 slot
+  g.A = (const bf16_t*)op.a; g.lda = op.lda / per;
+  g.B = (const bf16_t*)op.b; g.ldb = op.ldb / per;
+  g.k_tiles = (int)(K / kt); g.dq = op.dq;
   return RV_OK;
 }
 
@@ -371,92 +383,61 @@ extern "C" {
 
 int rv_linear_fwd(const void* x, long ldx, const void* w, long ldw, const float* bias, long Mp,
                   long Np, long Kp, int act, void* y, long ldy, void* stream) {
-  RV_REQUIRE(x && w && y, RV_ERR_NULL, "rv_linear_fwd: null operand");
-  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_RELU, RV_ERR_UNSUPPORTED, "rv_linear_fwd: act %d", act);
-  GemmArgs a{};
-  a.A = (const bf16_t*)x; a.lda = ldx; a.B = (const bf16_t*)w; a.ldb = ldw;
-  a.k_tiles = (int)(Kp / 64); a.M_valid = (int)Mp; a.N_valid = (int)Np;
-  a.relu = act == RV_ACT_RELU; a.bias = bias; a.out_bf16 = (bf16_t*)y; a.ld_bf16 = ldy;
-  return launch_auto<true, true, EPI_BIAS_ACT_BF16>(a, Mp, Np, Kp, 1, (hipStream_t)stream);
+  return rv_linear_fwd_ex({x, ldx, w, ldw, nullptr}, bias, Mp, Np, Kp, act, y, ldy, nullptr, 0, nullptr, nullptr, nullptr, 0,
+                          nullptr, stream);
 }
 
-int rv_linear_fwd_ex(const void* x, long ldx, const void* w, long ldw, const float* bias, long Mp, long Np, long Kp,
-                     int act, void* y, long ldy, void* y_fp8, long ldy_fp8, const float* q_scale, float* amax_part,
-                     void* stream) {
-  RV_REQUIRE(x && w && y, RV_ERR_NULL, "rv_linear_fwd_ex: null operand");
-  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_RELU, RV_ERR_UNSUPPORTED, "rv_linear_fwd_ex: act %d", act);
-  RV_REQUIRE(!y_fp8 || (q_scale && ldy_fp8 % 8 == 0 && ((uintptr_t)y_fp8 & 7) == 0), RV_ERR_SHAPE,
-             "rv_linear_fwd_ex: fp8 output needs a scale and 8-byte aligned rows");
-  GemmArgs a{};
-  a.A = (const bf16_t*)x; a.lda = ldx; a.B = (const bf16_t*)w; a.ldb = ldw;
-  a.k_tiles = (int)(Kp / 64); a.M_valid = (int)Mp; a.N_valid = (int)Np;
-  a.relu = act == RV_ACT_RELU; a.bias = bias; a.out_bf16 = (bf16_t*)y; a.ld_bf16 = ldy;
-  a.out_fp8 = (unsigned char*)y_fp8; a.ld_fp8 = ldy_fp8; a.q_scale = q_scale; a.amax_part = amax_part;
-  return launch_auto<true, true, EPI_BIAS_ACT_BF16>(a, Mp, Np, Kp, 1, (hipStream_t)stream);
-}
-
-// fc1 forward on the real-data path: the A operand's rows are hop-strided frames of the resident bf16 waveform
-// (GemmArgs::a_hop), the framed bf16 matrix is written as a by-product, block 0 bumps the step counter.
 int rv_linear_fwd_frames(const void* audio_bf16, const long long* frame_index, long first_frame, long hop, long B,
                          const void* w, long ldw, const float* bias, long Mp, long Np, long Kp, int act, void* y, long ldy,
                          void* frames_bf16, long ld_frames, long long* step_counter, void* stream) {
-  RV_REQUIRE(audio_bf16 && w && y, RV_ERR_NULL, "rv_linear_fwd_frames: null operand");
-  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_RELU, RV_ERR_UNSUPPORTED, "rv_linear_fwd_frames: act %d", act);
-  RV_REQUIRE(hop > 0 && hop % 8 == 0 && ((uintptr_t)audio_bf16 & 15) == 0, RV_ERR_SHAPE,
-             "rv_linear_fwd_frames: hop %ld must be a multiple of 8 and the waveform 16-byte aligned (16-byte LDS-DMA pieces)", hop);
-  RV_REQUIRE(B >= 1 && B <= Mp && first_frame >= 0, RV_ERR_SHAPE, "rv_linear_fwd_frames: %ld frames for %ld rows", B, Mp);
-  RV_REQUIRE(!frames_bf16 || (ld_frames >= Kp && ld_frames % 8 == 0 && ((uintptr_t)frames_bf16 & 15) == 0), RV_ERR_SHAPE,
-             "rv_linear_fwd_frames: the framed copy needs 16-byte aligned rows of at least Kp elements");
+  const rv_frame_src fr = {frame_index, first_frame, hop, 0, audio_bf16};
+  return rv_linear_fwd_ex({frames_bf16, ld_frames, w, ldw, nullptr}, bias, Mp, Np, Kp, act, y, ldy, nullptr, 0, nullptr, nullptr,
+                          &fr, B, step_counter, stream);
+}
+
+int rv_linear_fwd_ex(rv_gemm_operands op, const float* bias, long Mp, long Np, long Kp, int act, void* y, long ldy, void* y_fp8,
+                     long ldy_fp8, const float* q_scale, float* amax_part, const rv_frame_src* fr, long n_frames,
+                     long long* step_counter, void* stream) {
+  const char* who = fr ? "rv_linear_fwd_frames" : "rv_linear_fwd";
+  RV_REQUIRE((fr ? fr->bf16 : op.a) && op.b && y, RV_ERR_NULL, "%s: null operand", who);
+  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_RELU, RV_ERR_UNSUPPORTED, "%s: act %d", who, act);
+  RV_REQUIRE(!y_fp8 || (q_scale && ldy_fp8 % 8 == 0 && ((uintptr_t)y_fp8 & 7) == 0), RV_ERR_SHAPE,
+             "%s: fp8 output needs a scale and 8-byte aligned rows", who);
+  if (fr) {
+    // fc1 forward on the real-data path: the A operand's rows are hop-strided frames of the resident bf16 waveform
+    // (GemmArgs::a_hop), the framed bf16 matrix is written as a by-product (op.a), block 0 bumps the step counter.
+    RV_REQUIRE(!op.dq, RV_ERR_UNSUPPORTED, "rv_linear_fwd_frames: bf16 operands only");
+    RV_REQUIRE(fr->hop > 0 && fr->hop % 8 == 0 && ((uintptr_t)fr->bf16 & 15) == 0, RV_ERR_SHAPE,
+               "rv_linear_fwd_frames: hop %ld must be a multiple of 8 and the waveform 16-byte aligned (16-byte LDS-DMA pieces)", fr->hop);
+    RV_REQUIRE(n_frames >= 1 && n_frames <= Mp && fr->first >= 0, RV_ERR_SHAPE, "rv_linear_fwd_frames: %ld frames for %ld rows",
+               n_frames, Mp);
+    RV_REQUIRE(!op.a || (op.lda >= Kp && op.lda % 8 == 0 && ((uintptr_t)op.a & 15) == 0), RV_ERR_SHAPE,
+               "rv_linear_fwd_frames: the framed copy needs 16-byte aligned rows of at least Kp elements");
+  }
   GemmArgs a{};
-  a.A = (const bf16_t*)audio_bf16; a.lda = 8; a.B = (const bf16_t*)w; a.ldb = ldw;
-  a.k_tiles = (int)(Kp / 64); a.M_valid = (int)Mp; a.N_valid = (int)Np;
+  const int rc = set_operands(who, a, op, Kp);
+  if (rc) return rc;
+  a.M_valid = (int)Mp; a.N_valid = (int)Np;
   a.relu = act == RV_ACT_RELU; a.bias = bias; a.out_bf16 = (bf16_t*)y; a.ld_bf16 = ldy;
-  a.a_idx = frame_index; a.a_first = first_frame; a.a_hop = hop; a.a_rows = (int)B;
-  a.a_copy = (bf16_t*)frames_bf16; a.ld_copy = ld_frames; a.step_inc = step_counter;
+  a.out_fp8 = (unsigned char*)y_fp8; a.ld_fp8 = ldy_fp8; a.q_scale = q_scale; a.amax_part = amax_part;
+  if (op.dq) return launch_tile_fp8<EPI_BIAS_ACT_BF16>(choose_tile(Mp, Np, 1), a, Mp, Np, Kp, (hipStream_t)stream);
+  if (!fr) return launch_auto<true, true, EPI_BIAS_ACT_BF16>(a, Mp, Np, Kp, 1, (hipStream_t)stream);
+  a.A = (const bf16_t*)fr->bf16; a.lda = 8;
+  a.a_idx = fr->idx; a.a_first = fr->first; a.a_hop = fr->hop; a.a_rows = (int)n_frames;
+  a.a_copy = (bf16_t*)op.a; a.ld_copy = op.lda; a.step_inc = step_counter;
   const int tile = choose_tile(Mp, Np, 1);
   RV_REQUIRE(tile != 5 && tile != 7, RV_ERR_UNSUPPORTED,
              "rv_linear_fwd_frames: the gathered operand is implemented in the ring main loop only (tile %d)", tile);
   return launch_tile<true, true, EPI_BIAS_ACT_BF16>(tile, a, Mp, Np, Kp, 1, (hipStream_t)stream);
 }
 
-int rv_linear_fwd_fp8(const void* x_fp8, long ldx, const void* w_fp8, long ldw, const float* bias, const float* dq,
-                      long Mp, long Np, long Kp, int act, void* y, long ldy, void* stream) {
-  RV_REQUIRE(x_fp8 && w_fp8 && y && dq, RV_ERR_NULL, "rv_linear_fwd_fp8: null operand");
-  RV_REQUIRE(act == RV_ACT_NONE || act == RV_ACT_RELU, RV_ERR_UNSUPPORTED, "rv_linear_fwd_fp8: act %d", act);
-  RV_REQUIRE(Kp % 128 == 0 && ldx % 16 == 0 && ldw % 16 == 0, RV_ERR_SHAPE, "rv_linear_fwd_fp8: K and leading dims must be multiples of 128 / 16 fp8 elements");
-  GemmArgs a{};
-  a.A = (const bf16_t*)x_fp8; a.lda = ldx / 2; a.B = (const bf16_t*)w_fp8; a.ldb = ldw / 2;
-  a.k_tiles = (int)(Kp / 128); a.M_valid = (int)Mp; a.N_valid = (int)Np;
-  a.relu = act == RV_ACT_RELU; a.bias = bias; a.out_bf16 = (bf16_t*)y; a.ld_bf16 = ldy; a.dq = dq;
-  return launch_tile_fp8<EPI_BIAS_ACT_BF16>(choose_tile(Mp, Np, 1), a, Mp, Np, Kp / 2, (hipStream_t)stream);
-}
-
-int rv_decode_out_loss_fwd_fp8(const void* h3_fp8, long ldh, const void* w4_fp8, long ldw, const float* b4, const float* dq,
-                               long Bp, long Sp, long Hp, long B, long S, const float* x, long ldx, float* recon,
-                               long ld_recon, void* dP4, long ld_dp4, void* dP4_fp8, long ld_dp4q, const float* dp4_scale,
-                               float* mse_partial, float* db4_partial, void* stream) {
-  RV_REQUIRE(h3_fp8 && w4_fp8 && dq, RV_ERR_NULL, "rv_decode_out_loss_fwd_fp8: null operand");
-  RV_REQUIRE(B <= Bp && S <= Sp, RV_ERR_SHAPE, "rv_decode_out_loss_fwd_fp8: B,S exceed padded extents");
-  RV_REQUIRE(!x || dP4 || dP4_fp8, RV_ERR_NULL, "rv_decode_out_loss_fwd_fp8: x given without dP4 output");
-  RV_REQUIRE(!dP4_fp8 || (dp4_scale && ld_dp4q % 8 == 0 && ((uintptr_t)dP4_fp8 & 7) == 0), RV_ERR_SHAPE,
-             "rv_decode_out_loss_fwd_fp8: the fp8 image of dP4 needs its scale and 8-byte aligned rows");
-  RV_REQUIRE(Hp % 128 == 0 && ldh % 16 == 0 && ldw % 16 == 0, RV_ERR_SHAPE, "rv_decode_out_loss_fwd_fp8: K and leading dims must be multiples of 128 / 16 fp8 elements");
-  GemmArgs a{};
-  a.A = (const bf16_t*)h3_fp8; a.lda = ldh / 2; a.B = (const bf16_t*)w4_fp8; a.ldb = ldw / 2;
-  a.k_tiles = (int)(Hp / 128); a.M_valid = (int)B; a.N_valid = (int)S;
-  a.bias = b4; a.x = x; a.ld_x = ldx; a.recon = recon; a.ld_recon = ld_recon;
-  a.out_bf16 = (bf16_t*)dP4; a.ld_bf16 = ld_dp4; a.blocksum = mse_partial; a.colsum = db4_partial;
-  a.out_fp8 = (unsigned char*)dP4_fp8; a.ld_fp8 = ld_dp4q; a.q_scale = dp4_scale;
-  a.scale = 2.0f / ((float)B * (float)S); a.dq = dq;
-  return launch_tile_fp8<EPI_TANH_LOSS>(choose_tile(Bp, Sp, 1, 0, false), a, Bp, Sp, Hp / 2, (hipStream_t)stream);
-}
-
 int rv_linear_fwd_f32(const void* x, long ldx, const void* w, long ldw, const float* bias,
                       long Mp, long Np, long Kp, int splits, float* y, long ldy, void* stream) {
   RV_REQUIRE(x && w && y, RV_ERR_NULL, "rv_linear_fwd_f32: null operand");
   GemmArgs a{};
-  a.A = (const bf16_t*)x; a.lda = ldx; a.B = (const bf16_t*)w; a.ldb = ldw;
-  a.k_tiles = (int)(Kp / 64 / (splits > 0 ? splits : 1)); a.M_valid = (int)Mp; a.N_valid = (int)Np;
+  const int rc = set_operands("rv_linear_fwd_f32", a, {x, ldx, w, ldw, nullptr}, Kp / (splits > 0 ? splits : 1));
+  if (rc) return rc;
+  a.M_valid = (int)Mp; a.N_valid = (int)Np;
   a.bias = bias; a.out_f32 = y; a.ld_f32 = ldy; a.split_stride_f32 = Mp * ldy;
   return launch_auto<true, true, EPI_F32>(a, Mp, Np, Kp, splits, (hipStream_t)stream);
 }
@@ -465,42 +446,34 @@ int rv_decode_out_loss_fwd(const void* h3, long ldh, const void* w4, long ldw, c
                            long Bp, long Sp, long Hp, long B, long S, const float* x, long ldx,
                            float* recon, long ld_recon, void* dP4, long ld_dp4,
                            float* mse_partial, float* db4_partial, void* stream) {
-  RV_REQUIRE(h3 && w4, RV_ERR_NULL, "rv_decode_out_loss_fwd: null operand");
-  RV_REQUIRE(B <= Bp && S <= Sp, RV_ERR_SHAPE, "rv_decode_out_loss_fwd: B,S exceed padded extents");
-  RV_REQUIRE(!x || dP4, RV_ERR_NULL, "rv_decode_out_loss_fwd: x given without dP4 output");
-  GemmArgs a{};
-  a.A = (const bf16_t*)h3; a.lda = ldh; a.B = (const bf16_t*)w4; a.ldb = ldw;
-  a.k_tiles = (int)(Hp / 64); a.M_valid = (int)B; a.N_valid = (int)S;
-  a.bias = b4; a.x = x; a.ld_x = ldx; a.recon = recon; a.ld_recon = ld_recon;
-  a.out_bf16 = (bf16_t*)dP4; a.ld_bf16 = ld_dp4; a.blocksum = mse_partial; a.colsum = db4_partial;
-  a.scale = 2.0f / ((float)B * (float)S);
-  return launch_auto<true, true, EPI_TANH_LOSS>(a, Bp, Sp, Hp, 1, (hipStream_t)stream);
+  return rv_decode_out_loss_fwd_ex({h3, ldh, w4, ldw, nullptr}, b4, Bp, Sp, Hp, B, S, x, ldx, nullptr, recon, ld_recon, dP4, ld_dp4,
+                                   nullptr, 0, nullptr, mse_partial, db4_partial, stream);
 }
 
-// rv_decode_out_loss_fwd (bf16 or fp8 operands: h3/w4 fp8 when `dq` is given) with the target frames read from the
-// resident waveform: frame r = audio[f*hop : f*hop + S], f = frame_index ? frame_index[r] : first_frame + r.
-int rv_decode_out_loss_fwd_frames(const void* h3, long ldh, const void* w4, long ldw, const float* b4, const float* dq,
-                                  long Bp, long Sp, long Hp, long B, long S, const float* audio, long n_samples,
-                                  const long long* frame_index, long first_frame, long hop, float* recon, long ld_recon,
-                                  void* dP4, long ld_dp4, void* dP4_fp8, long ld_dp4q, const float* dp4_scale,
-                                  float* mse_partial, float* db4_partial, void* stream) {
-  RV_REQUIRE(h3 && w4 && audio && (dP4 || dP4_fp8), RV_ERR_NULL, "rv_decode_out_loss_fwd_frames: null operand");
-  RV_REQUIRE(!dP4_fp8 || (dq && dp4_scale && ld_dp4q % 8 == 0 && ((uintptr_t)dP4_fp8 & 7) == 0), RV_ERR_SHAPE,
-             "rv_decode_out_loss_fwd_frames: the fp8 image of dP4 belongs to the fp8 forward and needs its scale");
-  RV_REQUIRE(B <= Bp && S <= Sp && hop > 0 && n_samples > 0, RV_ERR_SHAPE, "rv_decode_out_loss_fwd_frames: bad extents");
+// With `fr` the target frames are read from the resident waveform x: frame r = x[f*hop : f*hop + S],
+// f = fr->idx ? fr->idx[r] : fr->first + r.
+int rv_decode_out_loss_fwd_ex(rv_gemm_operands op, const float* b4, long Bp, long Sp, long Hp, long B, long S, const float* x,
+                              long ldx, const rv_frame_src* fr, float* recon, long ld_recon, void* dP4, long ld_dp4,
+                              void* dP4_fp8, long ld_dp4q, const float* dp4_scale, float* mse_partial, float* db4_partial,
+                              void* stream) {
+  const char* who = "rv_decode_out_loss_fwd";
+  RV_REQUIRE(op.a && op.b && (!fr || x), RV_ERR_NULL, "%s: null operand", who);
+  RV_REQUIRE(B <= Bp && S <= Sp, RV_ERR_SHAPE, "%s: B,S exceed padded extents", who);
+  RV_REQUIRE(!fr || (fr->hop > 0 && fr->n_samples > 0), RV_ERR_SHAPE, "%s: frames of hop %ld from %ld samples", who, fr ? fr->hop : 0,
+             fr ? fr->n_samples : 0);
+  RV_REQUIRE(!x || dP4 || dP4_fp8, RV_ERR_NULL, "%s: x given without dP4 output", who);
+  RV_REQUIRE(!dP4_fp8 || (op.dq && dp4_scale && ld_dp4q % 8 == 0 && ((uintptr_t)dP4_fp8 & 7) == 0), RV_ERR_SHAPE,
+             "%s: the fp8 image of dP4 belongs to the fp8 forward and needs its scale and 8-byte aligned rows", who);
   GemmArgs a{};
+  const int rc = set_operands(who, a, op, Hp);
+  if (rc) return rc;
   a.M_valid = (int)B; a.N_valid = (int)S;
-  a.bias = b4; a.x = audio; a.ld_x = 0; a.x_idx = frame_index; a.x_first = first_frame; a.x_hop = hop; a.x_nsamples = n_samples;
-  a.recon = recon; a.ld_recon = ld_recon;
+  a.bias = b4; a.x = x; a.ld_x = ldx; a.recon = recon; a.ld_recon = ld_recon;
+  if (fr) { a.ld_x = 0; a.x_idx = fr->idx; a.x_first = fr->first; a.x_hop = fr->hop; a.x_nsamples = fr->n_samples; }
   a.out_bf16 = (bf16_t*)dP4; a.ld_bf16 = ld_dp4; a.blocksum = mse_partial; a.colsum = db4_partial;
   a.out_fp8 = (unsigned char*)dP4_fp8; a.ld_fp8 = ld_dp4q; a.q_scale = dp4_scale;
   a.scale = 2.0f / ((float)B * (float)S);
-  if (dq) {
-    RV_REQUIRE(Hp % 128 == 0 && ldh % 16 == 0 && ldw % 16 == 0, RV_ERR_SHAPE, "rv_decode_out_loss_fwd_frames: fp8 K and leading dims must be multiples of 128 / 16");
-    a.A = (const bf16_t*)h3; a.lda = ldh / 2; a.B = (const bf16_t*)w4; a.ldb = ldw / 2; a.k_tiles = (int)(Hp / 128); a.dq = dq;
-    return launch_tile_fp8<EPI_TANH_LOSS>(choose_tile(Bp, Sp, 1, 0, false), a, Bp, Sp, Hp / 2, (hipStream_t)stream);
-  }
-  a.A = (const bf16_t*)h3; a.lda = ldh; a.B = (const bf16_t*)w4; a.ldb = ldw; a.k_tiles = (int)(Hp / 64);
+  if (op.dq) return launch_tile_fp8<EPI_TANH_LOSS>(choose_tile(Bp, Sp, 1, 0, false), a, Bp, Sp, Hp, (hipStream_t)stream);
   return launch_auto<true, true, EPI_TANH_LOSS>(a, Bp, Sp, Hp, 1, (hipStream_t)stream);
 }
 
@@ -509,16 +482,16 @@ int rv_linear_dgrad(const void* dy, long lddy, const void* w, long ldw, long Mp,
                     float* dx32, long lddx32, int splits, void* stream) {
   RV_REQUIRE(dy && w, RV_ERR_NULL, "rv_linear_dgrad: null operand");
   GemmArgs a{};
-  a.A = (const bf16_t*)dy; a.lda = lddy; a.B = (const bf16_t*)w; a.ldb = ldw;
+  const int rc = set_operands("rv_linear_dgrad", a, {dy, lddy, w, ldw, nullptr}, mask ? Kp : Kp / (splits > 0 ? splits : 1));
+  if (rc) return rc;
   a.M_valid = (int)Mp; a.N_valid = (int)Np;
   if (mask) {
     RV_REQUIRE(dx, RV_ERR_NULL, "rv_linear_dgrad: mask given without bf16 output");
-    a.k_tiles = (int)(Kp / 64); a.mask = (const bf16_t*)mask; a.ld_mask = ldmask;
+    a.mask = (const bf16_t*)mask; a.ld_mask = ldmask;
     a.out_bf16 = (bf16_t*)dx; a.ld_bf16 = lddx; a.colsum = colsum;
     return launch_auto<true, false, EPI_MASK_BF16>(a, Mp, Np, Kp, 1, (hipStream_t)stream);
   }
   RV_REQUIRE(dx32, RV_ERR_NULL, "rv_linear_dgrad: no output given");
-  a.k_tiles = (int)(Kp / 64 / (splits > 0 ? splits : 1));
   a.out_f32 = dx32; a.ld_f32 = lddx32; a.split_stride_f32 = Mp * lddx32;
   return launch_auto<true, false, EPI_F32>(a, Mp, Np, Kp, splits, (hipStream_t)stream);
 }
@@ -531,9 +504,10 @@ int rv_linear_wgrad(const void* dy, long lddy, const void* x, long ldx, long Mp,
                  tile == RV_TILE_64x64, RV_ERR_UNSUPPORTED, "rv_linear_wgrad: unknown tile %d", tile);
   RV_REQUIRE(splits >= 1, RV_ERR_SHAPE, "rv_linear_wgrad: splits %d", splits);
   GemmArgs a{};
-  a.A = (const bf16_t*)dy; a.lda = lddy; a.B = (const bf16_t*)x; a.ldb = ldx;
-  a.k_tiles = (int)(Kp / 64 / splits); a.M_valid = (int)Mp; a.N_valid = (int)Np;
-  int rc = set_slabs(a, dw, lddw, Mp * lddw, slab_dtype, slab_unscale, Mp, Np);
+  int rc = set_operands("rv_linear_wgrad", a, {dy, lddy, x, ldx, nullptr}, Kp / splits);
+  if (rc) return rc;
+  a.M_valid = (int)Mp; a.N_valid = (int)Np;
+  rc = set_slabs(a, dw, lddw, Mp * lddw, slab_dtype, slab_unscale, Mp, Np);
   if (rc) return rc;
   if (tile == RV_TILE_AUTO) return launch_auto<false, false, EPI_F32>(a, Mp, Np, Kp, splits, (hipStream_t)stream);
   return launch_tile<false, false, EPI_F32>(tile, a, Mp, Np, Kp, splits, (hipStream_t)stream);
@@ -544,30 +518,30 @@ int rv_wgrad_adam_fits(long Mp, long Np, long Kp, int splits) {   // (plan.hip's
          (Kp / 64) % splits == 0 && g_force_tile < 0;
 }
 
-}  // extern "C" (the rider launchers below carry their own linkage)
+}  // extern "C" (the rider launcher below carries its own linkage)
 
 constexpr int TAIL_PCT_BF16 = 0, TAIL_PCT_FP8 = 15;   // C2 sweep: bf16 176 us per step at 0, 178-182 above; fp8 163 at 0, 158 from 12 to 22
-static int wgrad_riders(const char* who, const void* dy, long lddy, const void* x, long ldx, long Mp, long Np, long Kp, int splits,
-                        void* dw, long lddw, int slab_dtype, float* slab_unscale, const rv_param_desc* descs, int n_desc,
-                        float* param, float* exp_avg, float* exp_avg_sq, float lr, float grad_scale,
-                        const long long* step_counter, float* fin_f32, bf16_t* fin_bf16, int n_rider_blocks, void* stream,
-                        const float* fp8_dq = nullptr) {
-  const bool fp8 = fp8_dq != nullptr;   // operands are e4m3 bytes (leading dims in bytes), K tiles 128 deep, ping-pong loop only
+// fp8 operands (op.dq): e4m3 bytes, both read MN-major through ds_read_b64_tr_b8, K tiles 128 deep, ping-pong loop only.
+extern "C" int rv_linear_wgrad_riders(rv_gemm_operands op, long Mp, long Np, long Kp, int splits, void* dw, long lddw,
+                                      int slab_dtype, float* slab_unscale, const rv_param_desc* descs, int n_desc,
+                                      rv_rider_target t, int n_rider_blocks, void* stream) {
+  const char* who = t.grad_out ? "rv_linear_wgrad_riders" : "rv_linear_wgrad_adam";
+  const bool fp8 = op.dq != nullptr;
   const long kt = fp8 ? 128 : 64;
+  RV_REQUIRE(op.a && op.b && dw && (t.grad_out || (t.param && t.exp_avg && t.exp_avg_sq && t.step_counter)), RV_ERR_NULL,
+             "%s: null pointer", who);
   RV_REQUIRE(Mp > 0 && Np > 0 && Kp > 0 && Mp % 256 == 0 && Np % 256 == 0 && Kp % kt == 0 && splits >= 1 &&
                  (Kp / kt) % splits == 0, RV_ERR_SHAPE,
              "%s: %ld x %ld x %ld / %d splits does not tile by 256x256x%ld", who, Mp, Np, Kp, splits, kt);
-  RV_REQUIRE(!fp8 || ((Kp / kt / splits) % 2 == 0 && lddy % 16 == 0 && ldx % 16 == 0), RV_ERR_SHAPE,
-             "%s: fp8 operands need an even number of 128-deep K tiles per split and leading dims that are multiples of 16 bytes", who);
-  RV_REQUIRE(lddy % 8 == 0 && ldx % 8 == 0 && (((uintptr_t)dy | (uintptr_t)x) & 15) == 0, RV_ERR_SHAPE,
-             "%s: operands must be 16-byte aligned with leading dims multiples of 8", who);
+  RV_REQUIRE(!fp8 || (Kp / kt / splits) % 2 == 0, RV_ERR_SHAPE, "%s: fp8 operands need an even number of 128-deep K tiles per split", who);
   RV_REQUIRE(n_rider_blocks >= 1 && n_rider_blocks <= 4096, RV_ERR_SHAPE, "%s: %d rider blocks", who, n_rider_blocks);
-  DescTable tab;
-  int rc = adam_build_table(descs, n_desc, &tab);
-  if (rc) return rc;
   GemmArgs g{};
-  g.A = (const bf16_t*)dy; g.lda = fp8 ? lddy / 2 : lddy; g.B = (const bf16_t*)x; g.ldb = fp8 ? ldx / 2 : ldx;
-  g.k_tiles = (int)(Kp / kt / splits); g.M_valid = (int)Mp; g.N_valid = (int)Np; g.dq = fp8_dq;
+  int rc = set_operands(who, g, op, Kp / splits);
+  if (rc) return rc;
+  DescTable tab;
+  rc = adam_build_table(descs, n_desc, &tab);
+  if (rc) return rc;
+  g.M_valid = (int)Mp; g.N_valid = (int)Np;
   rc = set_slabs(g, dw, lddw, Mp * lddw, slab_dtype, slab_unscale, Mp, Np);
   if (rc) return rc;
   g.tiles_m = (int)(Mp / 256); g.tiles_n = (int)(Np / 256); g.splits = splits; g.wt = rv_store_wt;
@@ -582,39 +556,18 @@ static int wgrad_riders(const char* who, const void* dy, long lddy, const void* 
   // with plain-load riders only).  The riders stream at a per-CU rate whatever the GEMM does, so the share is what evens
   // the two halves out: measured per operand type at C2 (the sweep: profiles/r04_tail_sweep.txt).
   int tail_vb = 0;
-  if (!fin_f32 && !fin_bf16 && !stream_mode) tail_vb = (int)(tab.blk_start[n_desc] * (fp8 ? TAIL_PCT_FP8 : TAIL_PCT_BF16) / 100);
+  if (!t.grad_out && !stream_mode) tail_vb = (int)(tab.blk_start[n_desc] * (fp8 ? TAIL_PCT_FP8 : TAIL_PCT_BF16) / 100);
+  float* fin_f32 = t.out_bf16 ? nullptr : (float*)t.grad_out;
+  bf16_t* fin_bf16 = t.out_bf16 ? (bf16_t*)t.grad_out : nullptr;
   const bool pp = g.k_tiles % 2 == 0;
   const int which = fp8 ? 2 : (pp ? 1 : 0);
   auto kern = fp8 ? gemm_wgrad_adam_kernel<8, true> : (pp ? gemm_wgrad_adam_kernel<8, false> : gemm_wgrad_adam_kernel<2, false>);
   static std::atomic<unsigned long long> attr_done[3];
   lds_opt_in((const void*)kern, smem, attr_done[which]);
   hipLaunchKernelGGL(kern, dim3((unsigned)(n_gemm + n_rider_blocks)), dim3(512), smem, (hipStream_t)stream, g, n_gemm, tab,
-                     param, exp_avg, exp_avg_sq, lr, grad_scale, step_counter, stream_mode, fin_f32, fin_bf16, tail_vb);
+                     t.param, t.exp_avg, t.exp_avg_sq, t.lr, t.grad_scale, t.step_counter, stream_mode, fin_f32, fin_bf16, tail_vb);
   RV_CHECK_LAUNCH();
   return RV_OK;
-}
-
-// ... and on fp8 operands (as rv_linear_wgrad_adam_fp8 below: bytes, both MN-major, dq = 1 / (scale_dy * scale_x)).
-extern "C" int rv_linear_wgrad_finalize_fp8(const void* dy_fp8, long lddy, const void* x_fp8, long ldx, const float* dq, long Mp,
-                                 long Np, long Kp, int splits, void* dw, long lddw, int slab_dtype, float* slab_unscale,
-                                 const rv_param_desc* descs, int n_desc, void* grad_out, int out_bf16, int n_rider_blocks,
-                                 void* stream) {
-  RV_REQUIRE(dy_fp8 && x_fp8 && dq && dw && grad_out, RV_ERR_NULL, "rv_linear_wgrad_finalize_fp8: null pointer");
-  return wgrad_riders("rv_linear_wgrad_finalize_fp8", dy_fp8, lddy, x_fp8, ldx, Mp, Np, Kp, splits, dw, lddw, slab_dtype, slab_unscale,
-                      descs, n_desc, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, out_bf16 ? nullptr : (float*)grad_out,
-                      out_bf16 ? (bf16_t*)grad_out : nullptr, n_rider_blocks, stream, dq);
-}
-
-// rv_linear_wgrad_adam on fp8 (e4m3) operands (RV_OPT_FP8 = 1; plan.hip): dy_fp8 [Kp(batch), Mp] and x_fp8 [Kp, Np], one
-// byte per element, both read MN-major through ds_read_b64_tr_b8 (the contraction index is the row of both matrices);
-// dq: device scalar 1 / (scale_dy * scale_x).  Same slabs, riders and launch shape.  Not in the public header.
-extern "C" int rv_linear_wgrad_adam_fp8(const void* dy_fp8, long lddy, const void* x_fp8, long ldx, const float* dq, long Mp, long Np,
-                             long Kp, int splits, void* dw, long lddw, int slab_dtype, float* slab_unscale,
-                             const rv_param_desc* descs, int n_desc, float* param, float* exp_avg, float* exp_avg_sq, float lr,
-                             float grad_scale, const long long* step_counter, int n_adam_blocks, void* stream) {
-  RV_REQUIRE(dy_fp8 && x_fp8 && dq && dw && param && exp_avg && exp_avg_sq && step_counter, RV_ERR_NULL, "rv_linear_wgrad_adam_fp8: null pointer");
-  return wgrad_riders("rv_linear_wgrad_adam_fp8", dy_fp8, lddy, x_fp8, ldx, Mp, Np, Kp, splits, dw, lddw, slab_dtype, slab_unscale, descs,
-                      n_desc, param, exp_avg, exp_avg_sq, lr, grad_scale, step_counter, nullptr, nullptr, n_adam_blocks, stream, dq);
 }
 
 extern "C" int rv_pair_stop_event(void* ev) {   // returns whether an armed event was still pending (no paired launch took it)
@@ -628,21 +581,8 @@ extern "C" int rv_linear_wgrad_adam(const void* dy, long lddy, const void* x, lo
                          float* param, float* exp_avg,
                          float* exp_avg_sq, float lr, float grad_scale, const long long* step_counter,
                          int n_adam_blocks, void* stream) {
-  RV_REQUIRE(dy && x && dw && param && exp_avg && exp_avg_sq && step_counter, RV_ERR_NULL, "rv_linear_wgrad_adam: null pointer");
-  return wgrad_riders("rv_linear_wgrad_adam", dy, lddy, x, ldx, Mp, Np, Kp, splits, dw, lddw, slab_dtype, slab_unscale, descs,
-                      n_desc, param, exp_avg, exp_avg_sq, lr, grad_scale, step_counter, nullptr, nullptr, n_adam_blocks, stream);
-}
-
-// The same launch whose rider blocks only sum OTHER tensors' gradient slabs into a flat payload arena (fp32, or bf16
-// when out_bf16): rv_grad_finalize's work on the CUs the GEMM leaves idle (plan.hip: the data-parallel step's second
-// bucket, except the gradient this GEMM is producing).  Not in the public header.
-extern "C" int rv_linear_wgrad_finalize(const void* dy, long lddy, const void* x, long ldx, long Mp, long Np, long Kp, int splits,
-                             void* dw, long lddw, int slab_dtype, float* slab_unscale, const rv_param_desc* descs, int n_desc,
-                             void* grad_out, int out_bf16, int n_rider_blocks, void* stream) {
-  RV_REQUIRE(dy && x && dw && grad_out, RV_ERR_NULL, "rv_linear_wgrad_finalize: null pointer");
-  return wgrad_riders("rv_linear_wgrad_finalize", dy, lddy, x, ldx, Mp, Np, Kp, splits, dw, lddw, slab_dtype, slab_unscale, descs,
-                      n_desc, nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, out_bf16 ? nullptr : (float*)grad_out,
-                      out_bf16 ? (bf16_t*)grad_out : nullptr, n_rider_blocks, stream);
+  return rv_linear_wgrad_riders({dy, lddy, x, ldx, nullptr}, Mp, Np, Kp, splits, dw, lddw, slab_dtype, slab_unscale, descs, n_desc,
+                                {param, exp_avg, exp_avg_sq, lr, grad_scale, step_counter}, n_adam_blocks, stream);
 }
 
 
@@ -690,42 +630,61 @@ int rv_linear_dgrad_wgrad(const void* dy, long lddy, const void* w, long ldw, co
                              long Mp, long Np, long Kp, void* dx_bf16, long lddx,
                              float* colsum_partial, void* dw_slabs, long lddw, int splits, int slab_dtype, float* slab_unscale,
                              void* stream) {
-  RV_REQUIRE(dy && w && x && dx_bf16 && dw_slabs, RV_ERR_NULL, "rv_linear_dgrad_wgrad: null operand");
-  int paired, bm, sp;
-  int rc = rv_dgrad_wgrad_pick(Mp, Np, Kp, &paired, &bm, &sp);
+  return rv_linear_dgrad_wgrad_ex({dy, lddy, w, ldw, nullptr}, {dy, lddy, x, ldx, nullptr}, x, ldx, 0, Mp, Np, Kp, dx_bf16, lddx,
+                                  colsum_partial, dw_slabs, lddw, splits, slab_dtype, slab_unscale, stream);
+}
+
+// ... and the paired backward of fc4 on fp8 (e4m3) operands (RV_OPT_FP8; plan.hip), when the two dq are given: dX =
+// relu'(dYq Wq) and dW = dYq^T Xq in one 256 x 256 ping-pong launch, every operand one byte per element -- dy [Mp(batch),
+// Kp(out)] (the fp8 image of dP4 that the fc4 forward's epilogue wrote, K-major for the dgrad and MN-major for the wgrad),
+// w [Kp, Np] (the fp8 weight shadow, MN-major through ds_read_b64_tr_b8), x [Mp, Np] (the fp8 image of h3, the wgrad's
+// MN-major right operand); mask is the bf16 h3 (ReLU'), or -- mask_is_fp8 -- its fp8 image again (ldmask in bytes): the
+// bf16 copy of h3 then need not exist.  dq: device scalars 1 / (scale_dy * scale_w) and 1 / (scale_dy * scale_x).  Same
+// outputs, splits and slab formats.
+int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operands wgrad, const void* mask, long ldmask, int mask_is_fp8,
+                             long Mp, long Np, long Kp, void* dx_bf16, long lddx, float* colsum_partial, void* dw_slabs,
+                             long lddw, int splits, int slab_dtype, float* slab_unscale, void* stream) {
+  const char* who = "rv_linear_dgrad_wgrad";
+  const bool fp8 = dgrad.dq != nullptr;
+  RV_REQUIRE(dgrad.a && dgrad.b && wgrad.a && wgrad.b && mask && dx_bf16 && dw_slabs && !wgrad.dq == !fp8, RV_ERR_NULL,
+             "%s: null operand", who);
+  int paired = 1, bm, sp = splits, rc;
+  if (fp8) {
+    RV_REQUIRE(rv_dgrad_wgrad_fp8_fits(Mp, Np, Kp, splits), RV_ERR_SHAPE,
+               "%s: %ld x %ld x %ld / %d splits: fp8 extents must tile by 256 x 256 with an even number of 128-deep K tiles", who,
+               Mp, Np, Kp, splits);
+  } else {
+    rc = rv_dgrad_wgrad_pick(Mp, Np, Kp, &paired, &bm, &sp);
+    if (rc) return rc;
+    RV_REQUIRE(sp == splits, RV_ERR_STATE, "%s: caller passed %d splits, rv_dgrad_wgrad_pick says %d", who, splits, sp);
+  }
+  RV_REQUIRE(ldmask % (mask_is_fp8 ? 16 : 8) == 0 && ((uintptr_t)mask & 15) == 0, RV_ERR_SHAPE,
+             "%s: the mask needs 16-byte aligned rows of a multiple of 16 bytes", who);
+  GemmArgs d{}, g{};
+  rc = set_operands(who, d, dgrad, Kp);
   if (rc) return rc;
-  RV_REQUIRE(sp == splits, RV_ERR_STATE, "rv_linear_dgrad_wgrad: caller passed %d splits, rv_dgrad_wgrad_pick says %d",
-             splits, sp);
+  rc = set_operands(who, g, wgrad, Mp / splits);
+  if (rc) return rc;
+  d.M_valid = (int)Mp; d.N_valid = (int)Np;
+  d.mask = (const bf16_t*)mask; d.ld_mask = ldmask; d.mask_fp8 = mask_is_fp8 ? 1 : 0;
+  d.out_bf16 = (bf16_t*)dx_bf16; d.ld_bf16 = lddx; d.colsum = colsum_partial;
+  g.M_valid = (int)Kp; g.N_valid = (int)Np;
+  rc = set_slabs(g, dw_slabs, lddw, Kp * lddw, slab_dtype, slab_unscale, Kp, Np);
+  if (rc) return rc;
   if (!paired) {
     const int td = dgrad_tile_unpaired(Mp, Np, Kp, splits), tw = choose_tile(Kp, Np, splits, Mp);
-    GemmArgs d{}, g{};
-    d.A = (const bf16_t*)dy; d.lda = lddy; d.B = (const bf16_t*)w; d.ldb = ldw;
-    d.k_tiles = (int)(Kp / 64); d.M_valid = (int)Mp; d.N_valid = (int)Np;
-    d.mask = (const bf16_t*)x; d.ld_mask = ldx; d.out_bf16 = (bf16_t*)dx_bf16; d.ld_bf16 = lddx; d.colsum = colsum_partial;
-    g.A = (const bf16_t*)dy; g.lda = lddy; g.B = (const bf16_t*)x; g.ldb = ldx;
-    g.k_tiles = (int)(Mp / 64 / splits); g.M_valid = (int)Kp; g.N_valid = (int)Np;
-    rc = set_slabs(g, dw_slabs, lddw, Kp * lddw, slab_dtype, slab_unscale, Kp, Np);
-    if (rc) return rc;
     if (td == tw && (Mp / 64) % splits == 0 &&
         try_dual<false, false, EPI_F32, true, false, EPI_MASK_BF16>(td, g, Kp, Np, splits, d, Mp, Np, 1, (hipStream_t)stream, &rc))  // long (wgrad) blocks first
       return rc;
     rc = launch_tile<true, false, EPI_MASK_BF16>(td, d, Mp, Np, Kp, 1, (hipStream_t)stream);
     if (rc) return rc;
-    return rv_linear_wgrad(dy, lddy, x, ldx, Kp, Np, Mp, splits, RV_TILE_AUTO, dw_slabs, lddw, slab_dtype, slab_unscale, stream);
+    return rv_linear_wgrad(wgrad.a, wgrad.lda, wgrad.b, wgrad.ldb, Kp, Np, Mp, splits, RV_TILE_AUTO, dw_slabs, lddw, slab_dtype,
+                           slab_unscale, stream);
   }
-  RV_REQUIRE(lddy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0, RV_ERR_SHAPE, "rv_linear_dgrad_wgrad: leading dims must be multiples of 8");
-  RV_REQUIRE((((uintptr_t)dy | (uintptr_t)w | (uintptr_t)x) & 15) == 0, RV_ERR_SHAPE, "rv_linear_dgrad_wgrad: operands must be 16-byte aligned");
   constexpr int BM = 256, BN = 256;
-  GemmArgs d{}, g{};
-  d.A = (const bf16_t*)dy; d.lda = lddy; d.B = (const bf16_t*)w; d.ldb = ldw;
-  d.k_tiles = (int)(Kp / 64); d.M_valid = (int)Mp; d.N_valid = (int)Np;
-  d.mask = (const bf16_t*)x; d.ld_mask = ldx; d.out_bf16 = (bf16_t*)dx_bf16; d.ld_bf16 = lddx; d.colsum = colsum_partial;
   d.tiles_m = (int)(Mp / BM); d.tiles_n = (int)(Np / BN); d.splits = 1;
-  g.A = (const bf16_t*)dy; g.lda = lddy; g.B = (const bf16_t*)x; g.ldb = ldx;
-  g.k_tiles = (int)(Mp / 64 / splits); g.M_valid = (int)Kp; g.N_valid = (int)Np;
-  rc = set_slabs(g, dw_slabs, lddw, Kp * lddw, slab_dtype, slab_unscale, Kp, Np);
-  if (rc) return rc;
   g.tiles_m = (int)(Kp / BM); g.tiles_n = (int)(Np / BN); g.splits = splits;
+  if (fp8) return launch_pair<8, true>(d, g, (hipStream_t)stream);
   if (g_pair_loop == 8 && d.k_tiles % 2 == 0 && g.k_tiles % 2 == 0) return launch_pair<8>(d, g, (hipStream_t)stream);
   return launch_pair<2>(d, g, (hipStream_t)stream);
 }
@@ -743,14 +702,14 @@ int rv_linear_dgrad_wgrad_f32(const void* dy, long lddy, const void* w, long ldw
   int rc;
   if (td == tw) {
     GemmArgs d{}, g{};
-    d.A = (const bf16_t*)dy; d.lda = lddy; d.B = (const bf16_t*)w; d.ldb = ldw;
-    d.k_tiles = (int)(Kp / 64 / dgrad_splits); d.M_valid = (int)Mp; d.N_valid = (int)Np;
+    rc = set_operands("rv_linear_dgrad_wgrad_f32", d, {dy, lddy, w, ldw, nullptr}, Kp / dgrad_splits);
+    if (rc) return rc;
+    rc = set_operands("rv_linear_dgrad_wgrad_f32", g, {dy, lddy, x, ldx, nullptr}, Mp / wgrad_splits);
+    if (rc) return rc;
+    d.M_valid = (int)Mp; d.N_valid = (int)Np;
     d.out_f32 = dx_slabs; d.ld_f32 = lddx; d.split_stride_f32 = Mp * lddx;
-    g.A = (const bf16_t*)dy; g.lda = lddy; g.B = (const bf16_t*)x; g.ldb = ldx;
-    g.k_tiles = (int)(Mp / 64 / wgrad_splits); g.M_valid = (int)Kp; g.N_valid = (int)Np;
+    g.M_valid = (int)Kp; g.N_valid = (int)Np;
     g.out_f32 = dw_slabs; g.ld_f32 = lddw; g.split_stride_f32 = Kp * lddw;
-    RV_REQUIRE(lddy % 8 == 0 && ldw % 8 == 0 && ldx % 8 == 0, RV_ERR_SHAPE, "rv_linear_dgrad_wgrad_f32: leading dims must be multiples of 8");
-    RV_REQUIRE((((uintptr_t)dy | (uintptr_t)w | (uintptr_t)x) & 15) == 0, RV_ERR_SHAPE, "rv_linear_dgrad_wgrad_f32: operands must be 16-byte aligned");
     if (try_dual<true, false, EPI_F32, false, false, EPI_F32>(td, d, Mp, Np, dgrad_splits, g, Kp, Np, wgrad_splits,
                                                               (hipStream_t)stream, &rc))
       return rc;
@@ -758,41 +717,6 @@ int rv_linear_dgrad_wgrad_f32(const void* dy, long lddy, const void* w, long ldw
   rc = rv_linear_dgrad(dy, lddy, w, ldw, Mp, Np, Kp, nullptr, 0, nullptr, 0, nullptr, dx_slabs, lddx, dgrad_splits, stream);
   if (rc) return rc;
   return rv_linear_wgrad(dy, lddy, x, ldx, Kp, Np, Mp, wgrad_splits, RV_TILE_AUTO, dw_slabs, lddw, RV_SLAB_F32, nullptr, stream);
-}
-
-// The paired backward of fc4 on fp8 (e4m3) operands (RV_OPT_FP8; plan.hip): dX = relu'(dYq Wq) and dW = dYq^T Xq in
-// one 256 x 256 ping-pong launch, every operand one byte per element -- dy_fp8 [Mp(batch), Kp(out)] (the fp8 image of
-// dP4 that the fc4 forward's epilogue wrote, K-major for the dgrad and MN-major for the wgrad), w_fp8 [Kp, Np] (the
-// fp8 weight shadow, MN-major through ds_read_b64_tr_b8), x_fp8 [Mp, Np] (the fp8 image of h3, the wgrad's MN-major
-// right operand); mask is the bf16 h3 (ReLU'), or -- mask_is_fp8 -- its fp8 image again (ldmask in bytes): the bf16 copy of
-// h3 then need not exist.  dq_dgrad / dq_wgrad: device scalars 1 / (scale_dy * scale_w) and
-// 1 / (scale_dy * scale_x).  Same outputs, splits and slab formats as rv_linear_dgrad_wgrad.  Not in the public header.
-int rv_linear_dgrad_wgrad_fp8(const void* dy_fp8, long lddy, const void* w_fp8, long ldw, const void* x_fp8, long ldx,
-                              const void* mask, long ldmask, int mask_is_fp8, const float* dq_dgrad, const float* dq_wgrad,
-                              long Mp, long Np, long Kp, void* dx_bf16, long lddx, float* colsum_partial, void* dw_slabs,
-                              long lddw, int splits, int slab_dtype, float* slab_unscale, void* stream) {
-  const void* mask_bf16 = mask;
-  RV_REQUIRE(dy_fp8 && w_fp8 && x_fp8 && mask_bf16 && dx_bf16 && dw_slabs && dq_dgrad && dq_wgrad, RV_ERR_NULL,
-             "rv_linear_dgrad_wgrad_fp8: null operand");
-  RV_REQUIRE(rv_dgrad_wgrad_fp8_fits(Mp, Np, Kp, splits), RV_ERR_SHAPE,
-             "rv_linear_dgrad_wgrad_fp8: %ld x %ld x %ld / %d splits: extents must tile by 256 x 256 with an even number of 128-deep K tiles", Mp, Np, Kp, splits);
-  RV_REQUIRE(lddy % 16 == 0 && ldw % 16 == 0 && ldx % 16 == 0 && ldmask % (mask_is_fp8 ? 16 : 8) == 0, RV_ERR_SHAPE,
-             "rv_linear_dgrad_wgrad_fp8: leading dims must be multiples of 16 bytes");
-  RV_REQUIRE((((uintptr_t)dy_fp8 | (uintptr_t)w_fp8 | (uintptr_t)x_fp8 | (uintptr_t)mask_bf16) & 15) == 0, RV_ERR_SHAPE,
-             "rv_linear_dgrad_wgrad_fp8: operands must be 16-byte aligned");
-  constexpr int BM = 256, BN = 256;
-  GemmArgs d{}, g{};
-  d.A = (const bf16_t*)dy_fp8; d.lda = lddy / 2; d.B = (const bf16_t*)w_fp8; d.ldb = ldw / 2;
-  d.k_tiles = (int)(Kp / 128); d.M_valid = (int)Mp; d.N_valid = (int)Np;
-  d.mask = (const bf16_t*)mask_bf16; d.ld_mask = ldmask; d.mask_fp8 = mask_is_fp8 ? 1 : 0;
-  d.out_bf16 = (bf16_t*)dx_bf16; d.ld_bf16 = lddx; d.colsum = colsum_partial;
-  d.tiles_m = (int)(Mp / BM); d.tiles_n = (int)(Np / BN); d.splits = 1; d.dq = dq_dgrad;
-  g.A = (const bf16_t*)dy_fp8; g.lda = lddy / 2; g.B = (const bf16_t*)x_fp8; g.ldb = ldx / 2;
-  g.k_tiles = (int)(Mp / 128 / splits); g.M_valid = (int)Kp; g.N_valid = (int)Np; g.dq = dq_wgrad;
-  const int rc = set_slabs(g, dw_slabs, lddw, Kp * lddw, slab_dtype, slab_unscale, Kp, Np);
-  if (rc) return rc;
-  g.tiles_m = (int)(Kp / BM); g.tiles_n = (int)(Np / BN); g.splits = splits;
-  return launch_pair<8, true>(d, g, (hipStream_t)stream);
 }
 
 int rv_dgrad_wgrad_fp8_fits(long Mp, long Np, long Kp, int splits) {

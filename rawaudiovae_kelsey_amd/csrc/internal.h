@@ -29,29 +29,33 @@ RV_INTERNAL int rv_gather_cast_frames(const float* audio, long n_samples, const 
                                       long n_frames, long S, long hop, void* dst_bf16, long rows_p, long cols_p,
                                       long ld_dst, void* dst_fp8, long ld_fp8, float* fp8_state, const float* amax_part,
                                       int n_amax, int n_amax2, long long* step_counter, void* stream);
-// rv_linear_fwd with every optional output of a bias/ReLU forward GEMM (NULL = not wanted): the output also as
-// fp8(y * *q_scale) (the next layer's fp8 operand) and max|y| of every block in amax_part[block], from which the next
-// step derives its scale (delayed scaling).
-RV_INTERNAL int rv_linear_fwd_ex(const void* x_bf16, long ldx, const void* w_bf16, long ldw, const float* bias, long Mp,
-                                 long Np, long Kp, int act, void* y_bf16, long ldy, void* y_fp8, long ldy_fp8,
-                                 const float* q_scale, float* amax_part, void* stream);
-// rv_linear_fwd / rv_decode_out_loss_fwd on fp8 operands (K extents and leading dims in fp8 elements).
-RV_INTERNAL int rv_linear_fwd_fp8(const void* x_fp8, long ldx, const void* w_fp8, long ldw, const float* bias,
-                                  const float* dq, long Mp, long Np, long Kp, int act, void* y_bf16, long ldy,
-                                  void* stream);
-// (dP4_fp8 != NULL: the epilogue also writes fp8(dP4 * *dp4_scale), the fp8 fc4 backward's operand; dP4_bf16 may then be NULL)
-RV_INTERNAL int rv_decode_out_loss_fwd_fp8(const void* h3_fp8, long ldh, const void* w4_fp8, long ldw, const float* b4,
-                                           const float* dq, long Bp, long Sp, long Hp, long B, long S, const float* x,
-                                           long ldx, float* recon, long ld_recon, void* dP4_bf16, long ld_dp4,
-                                           void* dP4_fp8, long ld_dp4q, const float* dp4_scale,
-                                           float* mse_partial, float* db4_partial, void* stream);
-// rv_decode_out_loss_fwd whose fp32 target rows are read in place from the waveform (dq != NULL: fp8 operands).
-RV_INTERNAL int rv_decode_out_loss_fwd_frames(const void* h3, long ldh, const void* w4, long ldw, const float* b4,
-                                              const float* dq, long Bp, long Sp, long Hp, long B, long S,
-                                              const float* audio, long n_samples, const long long* frame_index,
-                                              long first_frame, long hop, float* recon, long ld_recon, void* dP4_bf16,
-                                              long ld_dp4, void* dP4_fp8, long ld_dp4q, const float* dp4_scale,
-                                              float* mse_partial, float* db4_partial, void* stream);
+// The two operands of a GEMM: bf16, or -- dq != NULL -- e4m3 bytes, dq then being the device scalar 1 / (scale_a * scale_b)
+// that undoes their scales.  Leading dims in elements either way.
+struct rv_gemm_operands {
+  const void* a; long lda;
+  const void* b; long ldb;
+  const float* dq;
+};
+// Frames read from a resident waveform (rv_plan_step_frames): frame r = waveform[f * hop ...], f = idx ? idx[r] : first + r
+struct rv_frame_src {
+  const long long* idx;
+  long first, hop, n_samples;
+  const void* bf16;   // the waveform as bf16 (fc1's operand is gathered from it), or null
+};
+// rv_linear_fwd with every option of a bias/ReLU forward GEMM (NULL = not wanted): fp8 operands (op.dq); the output also
+// as fp8(y * *q_scale) (the next layer's fp8 operand) and max|y| of every block in amax_part[block], from which the next
+// step derives its scale (delayed scaling); rv_linear_fwd_frames' form when `fr` is given: A's first n_frames rows are
+// gathered from fr->bf16, op.a (may be NULL) receives them as a by-product and block 0 bumps *step_counter.
+RV_INTERNAL int rv_linear_fwd_ex(rv_gemm_operands op, const float* bias, long Mp, long Np, long Kp, int act, void* y_bf16,
+                                 long ldy, void* y_fp8, long ldy_fp8, const float* q_scale, float* amax_part,
+                                 const rv_frame_src* fr, long n_frames, long long* step_counter, void* stream);
+// rv_decode_out_loss_fwd on bf16 or fp8 operands (op.dq); the fp32 target rows are x's, or -- `fr` -- frames of the
+// waveform x read in place.  dP4_fp8 != NULL (fp8 operands only): the epilogue also writes fp8(dP4 * *dp4_scale), the
+// fp8 fc4 backward's operand; dP4_bf16 may then be NULL.
+RV_INTERNAL int rv_decode_out_loss_fwd_ex(rv_gemm_operands op, const float* b4, long Bp, long Sp, long Hp, long B, long S,
+                                          const float* x, long ldx, const rv_frame_src* fr, float* recon, long ld_recon,
+                                          void* dP4_bf16, long ld_dp4, void* dP4_fp8, long ld_dp4q, const float* dp4_scale,
+                                          float* mse_partial, float* db4_partial, void* stream);
 // max|W1|, max|W4| of the fp8 weight shadows (n1 / n4 bytes) into the 2 x 1024 slots behind the fp8 state block
 // (RV_OPT_FP8): the plan runs it behind the optimizer, the next step's first kernel turns it into the weight scales.
 RV_INTERNAL int rv_fp8_wmax(const void* w1q, long n1, const void* w4q, long n4, float* fp8_state, void* stream);
@@ -79,23 +83,22 @@ RV_INTERNAL int rv_loss_from_partials(const float* mse_partial, int n_mse, const
                                       long L, float kl_beta, float* out3, void* stream);
 RV_INTERNAL int rv_grad_finalize_scaled(const rv_param_desc* descs, int n_desc, void* grad_out, int out_bf16,
                                         const float* scale_dev, void* stream);
-// rv_linear_wgrad_adam's launch shape (256 x 256 weight-gradient GEMM + rider blocks on the idle CUs) whose riders sum
-// the gradient slabs of `descs` into a flat payload arena instead of updating them (gemm_launch.hip).
-RV_INTERNAL int rv_linear_wgrad_finalize(const void* dy_bf16, long lddy, const void* x_bf16, long ldx, long Mp, long Np, long Kp,
-                                         int splits, void* dw_slabs, long lddw, int slab_dtype, float* slab_unscale,
-                                         const rv_param_desc* descs, int n_desc, void* grad_out, int out_bf16,
-                                         int n_rider_blocks, void* stream);
-// fc1's weight gradient + optimizer riders on fp8 operands (gemm_launch.hip), and the heads' backward that writes its
-// fp8 left operand (latent.hip).
-RV_INTERNAL int rv_linear_wgrad_adam_fp8(const void* dy_fp8, long lddy, const void* x_fp8, long ldx, const float* dq, long Mp,
-                                         long Np, long Kp, int splits, void* dw, long lddw, int slab_dtype, float* slab_unscale,
-                                         const rv_param_desc* descs, int n_desc, float* param, float* exp_avg,
-                                         float* exp_avg_sq, float lr, float grad_scale, const long long* step_counter,
-                                         int n_adam_blocks, void* stream);
-RV_INTERNAL int rv_linear_wgrad_finalize_fp8(const void* dy_fp8, long lddy, const void* x_fp8, long ldx, const float* dq, long Mp,
-                                             long Np, long Kp, int splits, void* dw, long lddw, int slab_dtype,
-                                             float* slab_unscale, const rv_param_desc* descs, int n_desc, void* grad_out,
-                                             int out_bf16, int n_rider_blocks, void* stream);
+// What the rider blocks of rv_linear_wgrad_riders do with the tensors of their table: the fused Adam update
+// (rv_linear_wgrad_adam), or -- grad_out != NULL -- only sum their slabs into a flat payload arena (fp32, or bf16 when
+// out_bf16): rv_grad_finalize's work.
+struct rv_rider_target {
+  float* param; float* exp_avg; float* exp_avg_sq;
+  float lr, grad_scale;
+  const long long* step_counter;
+  void* grad_out; int out_bf16;
+};
+// rv_linear_wgrad_adam's launch shape (256 x 256 weight-gradient GEMM + rider blocks on the idle CUs) on bf16 or fp8
+// operands (gemm_launch.hip).  fp8: dy [Kp(batch), Mp] and x [Kp, Np] both read MN-major (the contraction index is the
+// row of both matrices), dq = 1 / (scale_dy * scale_x).
+RV_INTERNAL int rv_linear_wgrad_riders(rv_gemm_operands op, long Mp, long Np, long Kp, int splits, void* dw_slabs, long lddw,
+                                       int slab_dtype, float* slab_unscale, const rv_param_desc* descs, int n_desc,
+                                       rv_rider_target riders, int n_rider_blocks, void* stream);
+// The heads' backward that writes its fp8 left operand (latent.hip).
 RV_INTERNAL int rv_heads_bwd_ex(const void* dmulv_bf16, const void* wh_bf16, long ldw, const void* h1_bf16, long ldh, long Bp,
                                 long Hp, long Lp, void* dp1_bf16, long ldp, float* db1_partial, float* dwh_slabs, long lddw,
                                 void* dp1_fp8, long ldq, const float* q_scale, float* amax_part, float* dwh_unscale,
@@ -105,10 +108,11 @@ RV_INTERNAL int rv_heads_bwd_ex(const void* dmulv_bf16, const void* wh_bf16, lon
 // Not under stream capture.  Returns 1 when an event armed earlier was still pending, i.e. no paired launch took it
 // (other tile forms): call with NULL behind the backward to disarm and to learn which.
 RV_INTERNAL int rv_pair_stop_event(void* hip_event);
-// The paired fc4 backward on fp8 operands (gemm_launch.hip) and whether the extents allow it.
+// Whether the paired fc4 backward on fp8 operands fits the extents (gemm_launch.hip), and rv_linear_dgrad_wgrad on
+// bf16 or fp8 operands: dgrad = {dy, w}, wgrad = {dy, x}; the dgrad's ReLU mask is the bf16 `mask` or -- mask_is_fp8 --
+// an fp8 image (ldmask in bytes).
 RV_INTERNAL int rv_dgrad_wgrad_fp8_fits(long Mp, long Np, long Kp, int splits);
-RV_INTERNAL int rv_linear_dgrad_wgrad_fp8(const void* dy_fp8, long lddy, const void* w_fp8, long ldw, const void* x_fp8, long ldx,
-                                          const void* mask, long ldmask, int mask_is_fp8, const float* dq_dgrad,
-                                          const float* dq_wgrad, long Mp, long Np, long Kp, void* dx_bf16, long lddx,
-                                          float* colsum_partial, void* dw_slabs, long lddw, int splits, int slab_dtype,
-                                          float* slab_unscale, void* stream);
+RV_INTERNAL int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operands wgrad, const void* mask, long ldmask,
+                                         int mask_is_fp8, long Mp, long Np, long Kp, void* dx_bf16, long lddx,
+                                         float* colsum_partial, void* dw_slabs, long lddw, int splits, int slab_dtype,
+                                         float* slab_unscale, void* stream);

@@ -926,8 +926,8 @@ int rv_latent_fwd_ex(const void* h_bf16, long ldh, const void* wh_bf16, long ldw
     const int rc = heads_reparam_gemm(h_bf16, ldh, wh_bf16, ldwh, bias_heads, Bp, Hp, Lp, B, L, eps_in, eps_out, seed, step_counter,
                                       mulv, z_bf16, kl_partial, (hipStream_t)stream);
     if (rc || heads_only) return rc;
-    return rv_linear_fwd_ex(z_bf16, Lp, w3_bf16, ldw3, bias3, Bp, Hp, Lp, RV_ACT_RELU, h3_bf16, ldh3, h3_fp8, ldq, q_scale, amax_part,
-                            stream);
+    return rv_linear_fwd_ex({z_bf16, Lp, w3_bf16, ldw3, nullptr}, bias3, Bp, Hp, Lp, RV_ACT_RELU, h3_bf16, ldh3, h3_fp8, ldq, q_scale,
+                            amax_part, nullptr, 0, nullptr, stream);
   }
   RV_REQUIRE(Bp > 0 && Bp % LAT_ROWS == 0 && Hp > 0 && B <= Bp && L <= Lp && ldh >= Hp && ldwh >= Hp &&
                  (heads_only || (ldw3 >= Lp && ldh3 >= Hp && ldw3 % 8 == 0 && ldh3 % 8 == 0)) && ldh % 8 == 0 && ldwh % 8 == 0,

@@ -80,13 +80,6 @@ struct rv_fwd_decisions {
   int n_amax_h3 = 0;    // how many of h3's maxima the forward writes (dP1's go right behind them)
 };
 
-// Frames read from a resident waveform (rv_plan_step_frames): the forward's `x` is then that waveform
-struct rv_frame_src {
-  const long long* idx;
-  long first, hop, n_samples;
-  const void* bf16;   // the waveform as bf16 (fc1's operand is gathered from it), or null
-};
-
 struct rv_plan {
   long B, S, H, L, Bp, Sp, Hp, Lp, L2p;
   int s_heads, s_dz, s_w4, s_w3, s_wh, s_w1;  // split-K factors
@@ -334,7 +327,7 @@ int rv_plan_create(rv_plan** out, long B, long S, long H, long L) {
   p->add("h3q", Bp * Hp);
   p->add("dP4q", Bp * Sp);        // fp8 image of dP4: the fp8 fc4 backward's operand (RV_OPT_FP8 = 1)
   p->add("dP1q", Bp * Hp);        // fp8 image of dP1: left operand of fc1's fp8 weight gradient (RV_OPT_FP8 = 1)
-  p->add("fp8_state", (32 + 2 * 1024) * 4);   // 16 state floats (+16 pad), then 2 x 1024 max|W| slots
+  p->add("fp8_state", (FP8_WMAX + 2 * 1024) * 4);   // 16 state floats (+16 pad), then 2 x 1024 max|W| slots
   // per-wave (fused latent forward: 8 per 16 batch rows) or per-tile max|h3| of the fc3 forward (zero until it has run)
   p->n_amax_cap = (int)(Bp / 2 > 4096 ? Bp / 2 : 4096);
   p->n_amax_dp1 = Bp % 512 == 0 ? (int)(8 * (Bp / 512) * (Hp / 64)) : 0;   // one maximum per wave of rv_heads_bwd_ex
@@ -428,8 +421,8 @@ static int plan_set_fp8(rv_plan* p, int enable) {
   float* st = (float*)p->ws("fp8_state");
   // Adam keeps the fp8 shadows of fc1.weight / fc4.weight current (descriptor 0 and 8)
   for (rv_param_desc* d : {p->d_slab, p->d_flat}) {
-    d[0].shadow_fp8 = enable ? p->ws("W1q") : nullptr; d[0].fp8_scale = st + 1;
-    d[8].shadow_fp8 = enable ? p->ws("W4q") : nullptr; d[8].fp8_scale = st + 2;
+    d[0].shadow_fp8 = enable ? p->ws("W1q") : nullptr; d[0].fp8_scale = st + FP8_W1_SCALE;
+    d[8].shadow_fp8 = enable ? p->ws("W4q") : nullptr; d[8].fp8_scale = st + FP8_W4_SCALE;
   }
   return RV_OK;
 }
@@ -653,15 +646,14 @@ static int fc4_backward(rv_plan* p, void* stream) {
   const long Bp = p->Bp, Sp = p->Sp, Hp = p->Hp;
   const int rc = h3_check(p, p->fwd);
   if (rc) return rc;
-  if (fp8_bwd(p)) {
-    float* f8 = (float*)p->ws("fp8_state");
-    const bool m8 = p->fwd.no_h3;
-    return rv_linear_dgrad_wgrad_fp8(p->ws("dP4q"), Sp, p->ws("W4q"), Hp, p->ws("h3q"), Hp, m8 ? p->ws("h3q") : p->ws("h3"), Hp,
-                                     m8 ? 1 : 0, f8 + 10, f8 + 11, Bp, Hp, Sp, p->ws("dP3"), Hp, (float*)p->ws("db3p"), p->ws("dW4"),
-                                     Hp, p->s_w4, p->slab_dtype, p->us_w4, stream);
-  }
-  return rv_linear_dgrad_wgrad(p->ws("dP4"), Sp, p->ws("W4b"), Hp, p->ws("h3"), Hp, Bp, Hp, Sp, p->ws("dP3"), Hp,
-                               (float*)p->ws("db3p"), p->ws("dW4"), Hp, p->s_w4, p->slab_dtype, p->us_w4, stream);
+  // fp8: dP4's image with the weight shadow and h3's image; the mask is h3's image where the bf16 h3 was not written
+  const bool q8 = fp8_bwd(p), m8 = p->fwd.no_h3;
+  float* f8 = (float*)p->ws("fp8_state");
+  void* dP4 = p->ws(q8 ? "dP4q" : "dP4");
+  return rv_linear_dgrad_wgrad_ex({dP4, Sp, p->ws(q8 ? "W4q" : "W4b"), Hp, q8 ? f8 + FP8_DQ_DP4_W4 : nullptr},
+                                  {dP4, Sp, p->ws(q8 ? "h3q" : "h3"), Hp, q8 ? f8 + FP8_DQ_DP4_H3 : nullptr},
+                                  p->ws(m8 ? "h3q" : "h3"), Hp, m8, Bp, Hp, Sp, p->ws("dP3"), Hp, (float*)p->ws("db3p"),
+                                  p->ws("dW4"), Hp, p->s_w4, p->slab_dtype, p->us_w4, stream);
 }
 
 #define RV_TRY(call) do { const int rc_ = (call); if (rc_) return rc_; } while (0)
@@ -735,38 +727,24 @@ static int plan_forward(rv_plan* p, const rv_fwd_decisions& d, const float* x, c
     if (p->cast_done) p->cast_done = 0;   // went out ahead of the previous step's deferred update (rv_plan_step_ddp)
     else if (slot_on(p, 0)) RV_TRY(rv_cast_pad_bf16(x, B, S, S, xb, Bp, Sp, Sp, counter, stream));
   }
-  if (slot_on(p, 1)) {
-    if (in_place)
-      RV_TRY(rv_linear_fwd_frames(fr->bf16, fr->idx, fr->first, fr->hop, B, p->ws("W1b"), Sp, b1p, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp,
-                                  xb, Sp, counter, stream));
-    else if (q8)
-      RV_TRY(rv_linear_fwd_fp8(xq, Sp, p->ws("W1q"), Sp, b1p, f8 + 5, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, stream));
-    else
-      RV_TRY(rv_linear_fwd_ex(xb, Sp, p->ws("W1b"), Sp, b1p, Bp, Hp, Sp, RV_ACT_RELU, h1, Hp, nullptr, 0, nullptr, nullptr, stream));
-  }
+  if (slot_on(p, 1))
+    RV_TRY(rv_linear_fwd_ex({q8 ? xq : xb, Sp, p->ws(q8 ? "W1q" : "W1b"), Sp, q8 ? f8 + FP8_DQ_X_W1 : nullptr}, b1p, Bp, Hp, Sp,
+                            RV_ACT_RELU, h1, Hp, nullptr, 0, nullptr, nullptr, in_place ? fr : nullptr, B, counter, stream));
   if (slot_on(p, 2)) {
     if (latent_bwd_fused(p)) {   // (the fused forward exists for the same shapes)
       RV_TRY(rv_latent_fwd_ex(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), W3b, Lp, b3p, Bp, Hp, Lp, B, L, eps, eps_buf, seed,
-                              counter, mulv, z, kl_part, d.no_h3 ? nullptr : h3, Hp, q8 ? h3q : nullptr, Hp, q8 ? f8 + 3 : nullptr,
-                              q8 ? amax : nullptr, stream));
+                              counter, mulv, z, kl_part, d.no_h3 ? nullptr : h3, Hp, q8 ? h3q : nullptr, Hp,
+                              q8 ? f8 + FP8_H3_SCALE : nullptr, q8 ? amax : nullptr, stream));
     } else {
       RV_TRY(rv_heads_reparam_fwd(h1, Hp, p->ws("Whb"), Hp, (float*)p->ws("bhp"), Bp, Lp, Hp, B, L, p->s_heads,
                                   (float*)p->ws("mulv_slabs"), eps, eps_buf, seed, counter, mulv, z, kl_part, stream));
-      RV_TRY(rv_linear_fwd_ex(z, Lp, W3b, Lp, b3p, Bp, Hp, Lp, RV_ACT_RELU, h3, Hp, q8 ? h3q : nullptr, q8 ? Hp : 0,
-                              q8 ? f8 + 3 : nullptr, q8 ? amax : nullptr, stream));
+      RV_TRY(rv_linear_fwd_ex({z, Lp, W3b, Lp, nullptr}, b3p, Bp, Hp, Lp, RV_ACT_RELU, h3, Hp, q8 ? h3q : nullptr, q8 ? Hp : 0,
+                              q8 ? f8 + FP8_H3_SCALE : nullptr, q8 ? amax : nullptr, nullptr, 0, nullptr, stream));
     }
   }
-  if (slot_on(p, 3)) {
-    if (fr)
-      RV_TRY(rv_decode_out_loss_fwd_frames(q8 ? h3q : h3, Hp, q8 ? W4q : W4b, Hp, b4p, q8 ? f8 + 6 : nullptr, Bp, Sp, Hp, B, S, x,
-                                           fr->n_samples, fr->idx, fr->first, fr->hop, recon_out, S, dP4, Sp, dP4q, Sp, f8 + 12,
-                                           mse_part, db4p, stream));
-    else if (q8)
-      RV_TRY(rv_decode_out_loss_fwd_fp8(h3q, Hp, W4q, Hp, b4p, f8 + 6, Bp, Sp, Hp, B, S, x, S, recon_out, S, dP4, Sp, dP4q, Sp,
-                                        f8 + 12, mse_part, db4p, stream));
-    else
-      RV_TRY(rv_decode_out_loss_fwd(h3, Hp, W4b, Hp, b4p, Bp, Sp, Hp, B, S, x, S, recon_out, S, dP4, Sp, mse_part, db4p, stream));
-  }
+  if (slot_on(p, 3))
+    RV_TRY(rv_decode_out_loss_fwd_ex({q8 ? h3q : h3, Hp, q8 ? W4q : W4b, Hp, q8 ? f8 + FP8_DQ_H3_W4 : nullptr}, b4p, Bp, Sp, Hp, B, S,
+                                     x, S, fr, recon_out, S, dP4, Sp, dP4q, Sp, f8 + FP8_DP4_SCALE, mse_part, db4p, stream));
   return RV_OK;
 }
 
@@ -802,7 +780,7 @@ static int heads_bwd(rv_plan* p, bool f8_w1, void* stream) {
   float* us = p->heads_half ? (float*)p->ws("dWh_us") : nullptr;
   if (f8_w1)
     return rv_heads_bwd_ex(dmulv, Whb, Hp, h1, Hp, Bp, Hp, Lp, nullptr, 0, db1p, dWh, Hp, p->ws("dP1q"), Hp,
-                           (float*)p->ws("fp8_state") + 13, (float*)p->ws("h3_amax") + p->fwd.n_amax_h3, us, stream);
+                           (float*)p->ws("fp8_state") + FP8_DP1_SCALE, (float*)p->ws("h3_amax") + p->fwd.n_amax_h3, us, stream);
   if (heads_streaming(p))
     return rv_heads_bwd_ex(dmulv, Whb, Hp, h1, Hp, Bp, Hp, Lp, p->ws("dP1"), Hp, db1p, dWh, Hp, nullptr, 0, nullptr, nullptr, us,
                            stream);
@@ -855,6 +833,12 @@ static bool next_run(unsigned mask, int* i, int* j) {
   return *i < 10;
 }
 
+// Operands of fc1's weight gradient dW1 = dP1^T x: bf16, or -- `f8` (fp8_w1) -- the fp8 images of both.
+static rv_gemm_operands w1_grad_operands(rv_plan* p, bool f8) {
+  if (f8) return {p->ws("dP1q"), p->Hp, p->ws("xq"), p->Sp, (float*)p->ws("fp8_state") + FP8_DQ_DP1_X};
+  return {p->ws("dP1"), p->Hp, p->ws("xb"), p->Sp, nullptr};
+}
+
 // Backward and update of the full local step, one stream.  dW1 is the last GEMM of the backward: 32 tiles x 4 K splits of
 // 256x256 fill half the chip, so its launch also carries the optimizer step of every tensor whose gradient is already
 // complete on the other CUs (fc21, fc22, fc3, fc4); fc1's update is the step's last launch.  An optimizer block streams
@@ -880,14 +864,11 @@ static int local_bwd_adam(rv_plan* p, const float* eps_used, float kl_beta, floa
     // (fp8 operands: only fc4's update riding here and the rest in the last launch was tried in round 5 -- 166.2-167.1 us
     // per step against 164.0-164.2 with the whole table riding and the GEMM blocks taking 15 % of it: profiles/r05_fp8_riders.txt)
     rider_range(p, &rf, &rl);
-    if (slot_on(p, 7) && f8_w1)
-      RV_TRY(rv_linear_wgrad_adam_fp8(p->ws("dP1q"), Hp, p->ws("xq"), Sp, (float*)p->ws("fp8_state") + 15, Hp, Sp, Bp, p->s_w1,
-                                      p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, p->d_slab + rf, rl - rf, p->b.param, p->b.exp_avg,
-                                      p->b.exp_avg_sq, lr, grad_scale, p->b.step_counter, 256 - n_gemm, stream));
-    else if (slot_on(p, 7))
-      RV_TRY(rv_linear_wgrad_adam(p->ws("dP1"), Hp, p->ws("xb"), Sp, Hp, Sp, Bp, p->s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1,
-                                  p->d_slab + rf, rl - rf, p->b.param, p->b.exp_avg, p->b.exp_avg_sq, lr, grad_scale,
-                                  p->b.step_counter, 256 - n_gemm, stream));
+    if (slot_on(p, 7))
+      RV_TRY(rv_linear_wgrad_riders(w1_grad_operands(p, f8_w1), Hp, Sp, Bp, p->s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1,
+                                    p->d_slab + rf, rl - rf,
+                                    {p->b.param, p->b.exp_avg, p->b.exp_avg_sq, lr, grad_scale, p->b.step_counter, nullptr, 0},
+                                    256 - n_gemm, stream));
   }
   Range r(p->roctx, "rv:adam");
   // the last launch: everything that did not ride ([0, rf) and [rl, 10), one table)
@@ -1184,13 +1165,8 @@ int rv_plan_step_ddp(rv_plan* p, const float* x, const float* eps, float* recon_
     // the GEMM leaves CUs idle: rider blocks sum the slabs of everything else in the second bucket (fc1.bias, heads, fc3:
     // complete since the heads' backward) into the payload meanwhile, and only fc1.weight's own slabs are left to sum
     void* pay = p->payload_bf16 ? p->grad_bf16 : (void*)p->b.grad;
-    if (fd.f8_w1)
-      RV_TRY(rv_linear_wgrad_finalize_fp8(p->ws("dP1q"), Hp, p->ws("xq"), Sp, (float*)p->ws("fp8_state") + 15, Hp, Sp, Bp, s_w1,
-                                          p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, dd + 1, 7, pay, p->payload_bf16, 256 - n_gemm,
-                                          stream));
-    else
-      RV_TRY(rv_linear_wgrad_finalize(dP1, Hp, xb, Sp, Hp, Sp, Bp, s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, dd + 1, 7,
-                                      pay, p->payload_bf16, 256 - n_gemm, stream));
+    RV_TRY(rv_linear_wgrad_riders(w1_grad_operands(p, fd.f8_w1), Hp, Sp, Bp, s_w1, p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, dd + 1,
+                                  7, {nullptr, nullptr, nullptr, 0.f, 1.f, nullptr, pay, p->payload_bf16}, 256 - n_gemm, stream));
     RV_TRY(payload(0, 1, s0));
   } else {
     RV_TRY(rv_linear_wgrad(dP1, Hp, xb, Sp, Hp, Sp, Bp, s_w1, w1_tile(p), p->ws("dW1"), Sp, p->slab_dtype, p->us_w1, stream));

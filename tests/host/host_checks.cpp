@@ -5,6 +5,89 @@
 #include <stdio.h>
 #include <string.h>
 #include "rawvae_hip.h"
+#include "../../rawaudiovae_kelsey_amd/csrc/internal.h"   // the step plan's launchers (hidden symbols of the objects linked here)
+
+// `rc` is the expected error code and the message starts with `prefix`
+static int expect(int rc, int code, const char* prefix, int line) {
+  if (rc == code && strncmp(rv_last_error(), prefix, strlen(prefix)) == 0) return 0;
+  printf("line %d: got %d \"%s\", expected %d \"%s...\"\n", line, rc, rv_last_error(), code, prefix);
+  return 1;
+}
+#define EXPECT(call, code, prefix) expect((call), (code), (prefix), __LINE__)
+
+// The rejections of the GEMM launchers that return before any HIP call.
+static int launcher_checks() {
+  alignas(16) static char buf[64];
+  const float* dq = (const float*)buf;   // non-NULL: fp8 operands
+  const char* fp8_ld = "K and leading dims must be multiples of 128 / 16 fp8 elements";
+  char msg[160];
+  int fails = 0;
+  // bias/ReLU forward (bf16, fp8, frames)
+  fails += EXPECT(rv_linear_fwd(NULL, 1024, buf, 1024, NULL, 256, 256, 1024, RV_ACT_RELU, buf, 256, NULL), RV_ERR_NULL,
+                  "rv_linear_fwd: null operand");
+  fails += EXPECT(rv_linear_fwd_ex({buf, 1024, NULL, 1024, dq}, NULL, 256, 256, 1024, RV_ACT_RELU, buf, 256, NULL, 0, NULL, NULL,
+                                   NULL, 0, NULL, NULL), RV_ERR_NULL, "rv_linear_fwd: null operand");
+  snprintf(msg, sizeof msg, "rv_linear_fwd: %s", fp8_ld);
+  fails += EXPECT(rv_linear_fwd_ex({buf, 1000, buf, 1024, dq}, NULL, 256, 256, 1024, RV_ACT_RELU, buf, 256, NULL, 0, NULL, NULL,
+                                   NULL, 0, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd_ex({buf, 1088, buf, 1088, dq}, NULL, 256, 256, 1088, RV_ACT_RELU, buf, 256, NULL, 0, NULL, NULL,
+                                   NULL, 0, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd_frames(NULL, NULL, 0, 256, 256, buf, 1024, NULL, 256, 256, 1024, RV_ACT_RELU, buf, 256, NULL, 0,
+                                       NULL, NULL), RV_ERR_NULL, "rv_linear_fwd_frames: null operand");
+  fails += EXPECT(rv_linear_fwd_frames(buf, NULL, 0, 260, 256, buf, 1024, NULL, 256, 256, 1024, RV_ACT_RELU, buf, 256, NULL, 0,
+                                       NULL, NULL), RV_ERR_SHAPE, "rv_linear_fwd_frames: hop 260 must be a multiple of 8");
+  // fc4 + tanh + loss forward
+  fails += EXPECT(rv_decode_out_loss_fwd(NULL, 2048, buf, 2048, NULL, 256, 256, 2048, 256, 256, NULL, 0, NULL, 0, NULL, 0, NULL,
+                                         NULL, NULL), RV_ERR_NULL, "rv_decode_out_loss_fwd: null operand");
+  snprintf(msg, sizeof msg, "rv_decode_out_loss_fwd: %s", fp8_ld);
+  fails += EXPECT(rv_decode_out_loss_fwd_ex({buf, 2008, buf, 2048, dq}, NULL, 256, 256, 2048, 256, 256, NULL, 0, NULL, NULL, 0, NULL,
+                                            0, NULL, 0, NULL, NULL, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_decode_out_loss_fwd_ex({buf, 2112, buf, 2112, dq}, NULL, 256, 256, 2112, 256, 256, NULL, 0, NULL, NULL, 0, NULL,
+                                            0, NULL, 0, NULL, NULL, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_decode_out_loss_fwd_ex({buf, 2048, buf, 2048, dq}, NULL, 256, 256, 2048, 256, 256, NULL, 0, NULL, NULL, 0, NULL,
+                                            0, buf, 256, NULL, NULL, NULL, NULL), RV_ERR_SHAPE,
+                  "rv_decode_out_loss_fwd: the fp8 image of dP4 belongs to the fp8 forward and needs its scale");
+  // paired dgrad + wgrad (fc4's extents at B = 4096: the fp8 pair fits)
+  int paired = 0, bm = 0, sp = 0;
+  fails += rv_gemm_plan(RV_PLAN_PAIR, 4096, 2048, 1024, 0, &bm, NULL, &sp, &paired) != 0;
+  fails += !rv_dgrad_wgrad_fp8_fits(4096, 2048, 1024, sp);
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, 1024, buf, 2048, NULL, 2048, 4096, 2048, 1024, buf, 2048, NULL, buf, 2048, sp,
+                                        RV_SLAB_F32, NULL, NULL), RV_ERR_NULL, "rv_linear_dgrad_wgrad: null operand");
+  fails += EXPECT(rv_linear_dgrad_wgrad_ex({buf, 1024, buf, 2048, dq}, {buf, 1024, buf, 2048, dq}, NULL, 2048, 0, 4096, 2048, 1024,
+                                           buf, 2048, NULL, buf, 2048, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_NULL, "rv_linear_dgrad_wgrad: null operand");
+  snprintf(msg, sizeof msg, "rv_linear_dgrad_wgrad: %s", fp8_ld);
+  fails += EXPECT(rv_linear_dgrad_wgrad_ex({buf, 1000, buf, 2048, dq}, {buf, 1000, buf, 2048, dq}, buf, 2048, 1, 4096, 2048, 1024,
+                                           buf, 2048, NULL, buf, 2048, sp, RV_SLAB_F32, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad_ex({buf, 1088, buf, 2048, dq}, {buf, 1088, buf, 2048, dq}, buf, 2048, 1, 4096, 2048, 1088,
+                                           buf, 2048, NULL, buf, 2048, sp, RV_SLAB_F32, NULL, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad_wgrad: 4096 x 2048 x 1088");
+  // weight gradient + rider blocks (fc1's extents at B = 4096, 4 K splits)
+  rv_param_desc d[1];
+  memset(d, 0, sizeof d);
+  const rv_rider_target adam = {(float*)buf, (float*)buf, (float*)buf, 1e-3f, 1.f, (const long long*)buf, NULL, 0};
+  const rv_rider_target fin = {NULL, NULL, NULL, 0.f, 1.f, NULL, buf, 0};
+  fails += EXPECT(rv_linear_wgrad_adam(buf, 2048, buf, 1024, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, NULL,
+                                       (float*)buf, (float*)buf, 1e-3f, 1.f, (const long long*)buf, 128, NULL),
+                  RV_ERR_NULL, "rv_linear_wgrad_adam: null pointer");
+  fails += EXPECT(rv_linear_wgrad_riders({NULL, 2048, buf, 1024, dq}, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, fin,
+                                         128, NULL), RV_ERR_NULL, "rv_linear_wgrad_riders: null pointer");
+  snprintf(msg, sizeof msg, "rv_linear_wgrad_adam: %s", fp8_ld);
+  fails += EXPECT(rv_linear_wgrad_riders({buf, 2008, buf, 1024, dq}, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, adam,
+                                         128, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_wgrad_riders({buf, 2048, buf, 1024, dq}, 2048, 1024, 4160, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, adam,
+                                         128, NULL), RV_ERR_SHAPE, "rv_linear_wgrad_adam: 2048 x 1024 x 4160 / 4 splits does not tile");
+  for (int n = 0; n <= 4097; n += 4097) {
+    snprintf(msg, sizeof msg, "rv_linear_wgrad_adam: %d rider blocks", n);
+    fails += EXPECT(rv_linear_wgrad_adam(buf, 2048, buf, 1024, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, (float*)buf,
+                                         (float*)buf, (float*)buf, 1e-3f, 1.f, (const long long*)buf, n, NULL), RV_ERR_SHAPE, msg);
+    snprintf(msg, sizeof msg, "rv_linear_wgrad_riders: %d rider blocks", n);
+    fails += EXPECT(rv_linear_wgrad_riders({buf, 2048, buf, 1024, dq}, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, fin,
+                                           n, NULL), RV_ERR_SHAPE, msg);
+  }
+  return fails;
+}
+
 int main() {
   long Bp, Sp, Hp, Lp; int bm, bn, sp, paired;
   int fails = 0;
@@ -40,6 +123,7 @@ int main() {
   fails += rv_plan_attach_comm(pl, &c) != 0;                           // comm == NULL: detach, always allowed
   fails += rv_gemm_plan(7, 256, 256, 256, 1, &bm, &bn, &sp, &paired) == 0;   // unknown query
   rv_plan_destroy(pl);
+  fails += launcher_checks();
   printf("host checks: %d failures; last error: %s\n", fails, rv_last_error());
   return fails != 0;
 }
