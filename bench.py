@@ -3,6 +3,7 @@
 Adam) on synthetic 1024-sample frames.
 
     python bench.py --gpus 1 --steps 6000 --warmup 20
+    python bench.py --gpus 1 --steps 6000 --warmup 20 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,22 +14,25 @@ its 9 kernels back to back on one stream, eagerly (`--graph` replays them from a
 fast, consecutive replays are a few us apart).  The headline is ONE timed pass of exactly K = --steps steps, after the
 engine's eager first step and W = --warmup untimed ones (settle_clocks runs before those, on a scratch engine); the
 default K = 6000 is about one second of steps at C2.  `--dump-outputs DIR` then writes what the K-th step computed
-(dump_outputs).
+(dump_outputs).  A plain run stops there and prints its line; everything else below is measured and checked only
+with `--full`.
 
 N > 1: one process per GPU; each step is one `rv_plan_step_ddp` call that also issues the RCCL collectives (all-reduce
 schedule, two buckets; the bf16 gradient payload by explicit choice of this bench -- named in `config.ddp_payload`, with
 the library's default, the exact fp32 mean, timed beside it as `alt_fp32_payload`: DESIGN.md section 5;
-`RV_DDP_PAYLOAD=fp32` selects the exact mean; `alt_fp32_payload` and `alt_no_defer` are timed beside the headline).  Weak scaling: per-GPU batch fixed.  Before it is
-timed the library-driven step is checked on scratch engines against the torch.distributed route; after every section
-that can fail on one rank alone the ranks AGREE on success (a MIN all-reduce) -- if any rank failed inside a step, every
-rank exits non-zero instead of going on to a collective its peers will never join.
+`RV_DDP_PAYLOAD=fp32` selects the exact mean; with `--full`, `alt_fp32_payload` and `alt_no_defer` are timed beside the
+headline).  Weak scaling: per-GPU batch fixed.  Before it is timed the library-driven step is checked on scratch engines
+against the torch.distributed route (in a plain run too: the check decides which route the headline times); after every
+section that can fail on one rank alone the ranks AGREE on success (a MIN all-reduce) -- if any rank failed inside a
+step, every rank exits non-zero instead of going on to a collective its peers will never join.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the LONGEST launch of the step, found in this run: every launch of the
-step is timed IN the step with HIP events (a hipGraph of steps minus the same graph without that launch; `kernels` holds
-all nine rows).  `cpu_baseline` is the stock-PyTorch CPU port of the same step (oracle/torch_port.py) timed on this node's
-host cores (N=1 only).  Side lines at N=1 (never the headline; `--no-alts` skips them): `alt_fp8` / `alt_fp8_forward_only`
-(the fp8 weight path), `alt_ref_ini` / `alt_default_ini` (the reference's own model, latent_dim 256, at batch 4096 and at
-default.ini's 131072, with every launch timed in the step), `alt_fp32_slabs`, `alt_deep_c4` (BASELINE configs[3]) and `alt_api_loop` (the reference's loop
+Rank 0 prints ONE JSON line.  With `--full` it also carries, at N=1: `roofline` for the LONGEST launch of the step, found
+in this run: every launch of the step is timed IN the step with HIP events (a hipGraph of steps minus the same graph
+without that launch; `kernels` holds all nine rows; a plain run's `roofline` is null).  `cpu_baseline` is the
+stock-PyTorch CPU port of the same step (oracle/torch_port.py) timed on this node's host cores.  Side lines (never the
+headline; `--no-alts` skips them): `alt_fp8` / `alt_fp8_forward_only` (the fp8 weight path), `alt_ref_ini` /
+`alt_default_ini` (the reference's own model, latent_dim 256, at batch 4096 and at default.ini's 131072, with every launch
+timed in the step), `alt_fp32_slabs`, `alt_deep_c4` (BASELINE configs[3]) and `alt_api_loop` (the reference's loop
 unchanged through `rawvae.model` + `torch.optim.Adam`; host-bound).
 """
 import argparse
@@ -66,17 +70,20 @@ def parse():
                     help="heads + reparam + fc3 of the forward as one row-local launch (1, default) or three launches (0)")
     ap.add_argument("--fp8", action="store_true",
                     help="ignored (kept for old command lines): the headline is bf16; the fp8 path is timed as the side line `alt_fp8`")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also time every launch in the step (`kernels`, `roofline`), the side lines "
+                         "and the CPU baseline; off by default, so that a plain run does only what its headline needs")
     ap.add_argument("--step-kernels-only", action="store_true",
                     help="profiling runs (tools/prof_round.sh, tools/pmc_round.sh): launch nothing but full training steps -- "
-                         "no per-kernel differential timing (its graphs leave launches out), no side lines; `roofline` is "
-                         "then null and the profile's own per-kernel durations are the figures")
+                         "even with --full, no per-kernel differential timing (its graphs leave launches out) and no side "
+                         "lines; `roofline` is then null and the profile's own per-kernel durations are the figures")
     ap.add_argument("--no-alts", action="store_true",
-                    help="skip the side lines `alt_fp8`, `alt_deep_c4`, `alt_fp32_slabs` and `alt_api_loop`; they are timed after the "
-                         "headline at N=1 and never replace it")
+                    help="with --full: skip the side lines `alt_fp8`, `alt_deep_c4`, `alt_fp32_slabs` and `alt_api_loop`; they "
+                         "are timed after the headline at N=1 and never replace it")
     ap.add_argument("--slab-dtype", default=None, choices=["fp32", "fp16"],
                     help="element type of the fc1 / fc4 weight-gradient split-K slabs (default: the engine's)")
     ap.add_argument("--roctx", action="store_true", help="roctx ranges around the step's phases (rocprofv3 --marker-trace)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--repeats", type=int, default=0,
                     help="timed passes of K steps each of the side lines (0 = at least 5 and enough for --min-seconds of "
@@ -673,9 +680,9 @@ def main():
         # same count on every rank)
         side_reps = args.repeats if args.repeats > 0 else min(2000, max(5, int(args.min_seconds / max(dt, 1e-6)) + 1))
 
-        # ---- side lines at N > 1 (never the headline; each is entered by every rank or by none) ----
+        # ---- side lines at N > 1 (--full; never the headline; each is entered by every rank or by none) ----
         ddp_alts = {}
-        if isinstance(runner, ddp.NativeDdpRunner) and os.environ.get("RV_DDP_ALT", "1") != "0" \
+        if args.full and isinstance(runner, ddp.NativeDdpRunner) and os.environ.get("RV_DDP_ALT", "1") != "0" \
                 and agree(replicas_consistent is not False, "headline replicas identical"):
             # the same schedule with the OTHER gradient payload (fp32 = the exact mean, twice the bytes on the links),
             # on the same engine: what the exchange costs at this GPU count
@@ -694,7 +701,7 @@ def main():
                 if multi:
                     die_together("side line (other payload) raised", "%s: %s" % (type(exc).__name__, str(exc)[:300]))
                 ddp_alts["alt_%s_payload" % other] = {"error": str(exc)[:200]}
-        if isinstance(runner, ddp.NativeDdpRunner) and runner.defer and os.environ.get("RV_DDP_ALT", "1") != "0" \
+        if args.full and isinstance(runner, ddp.NativeDdpRunner) and runner.defer and os.environ.get("RV_DDP_ALT", "1") != "0" \
                 and agree(replicas_consistent is not False, "headline replicas identical (before alt_no_defer)"):
             # the same schedule and payload with every step completing itself (RV_OPT_DDP_DEFER_TAIL off: the library's and
             # train.py's default) on a second engine -- round-5 advisor: the headline's deferred tail was sized on a one-GPU
@@ -719,12 +726,12 @@ def main():
                     die_together("side line (no deferred tail) raised", "%s: %s" % (type(exc).__name__, str(exc)[:300]))
                 ddp_alts["alt_no_defer"] = {"error": str(exc)[:200]}
 
-        # ---- per-launch timing and side lines at N = 1 ----
+        # ---- per-launch timing and side lines at N = 1 (--full) ----
         launches, noise_us = None, None
-        if rank == 0 and not use_ddp and not args.step_kernels_only:
+        if args.full and rank == 0 and not use_ddp and not args.step_kernels_only:
             launches, noise_us = time_launches_in_step(eng, pool[0])
         alts = {}
-        if not use_ddp and not args.no_alts and not args.step_kernels_only:
+        if args.full and not use_ddp and not args.no_alts and not args.step_kernels_only:
             def time_alt(what, **kw):
                 try:
                     e2 = E.TrainEngine(S, H, L, B, device=dev, kl_beta=KL_BETA, lr=LR, seed=1000 + rank, ring=256, **kw)
@@ -890,7 +897,7 @@ def main():
             **({"kernels": [{k: (round(v, 4) if isinstance(v, float) else v) for k, v in r.items()} for r in launches]}
                if launches else {}),
         }
-        if world == 1 and not use_ddp and not args.no_cpu_baseline:
+        if args.full and world == 1 and not use_ddp and not args.no_cpu_baseline:
             from oracle.torch_port import cpu_description, time_cpu_step
             usable, quota = host_cpu_quota()
             threads = max(1, min(usable, int(os.environ.get("RV_CPU_THREADS", "16"))))

@@ -27,9 +27,12 @@ def _bench(out_dir, steps, warmup, *flags):
 def test_dump_outputs_are_the_last_step_and_set_by_the_step_count(tmp_path):
     from rawaudiovae_kelsey_amd.engine import PARAM_NAMES
     out_a, a = _bench(tmp_path / "a", 3, 1, "--step-kernels-only")
-    # the same batches in the same order (1 + 2 + 2 = 1 + 1 + 3 steps), on the default path: settle_clocks' scratch engine
-    # and the per-launch timing (after the dump) leave the headline's outputs alone
-    _, b = _bench(tmp_path / "b", 2, 2)
+    # the same batches in the same order (1 + 2 + 2 = 1 + 1 + 3 steps), on the default path and with --full: settle_clocks'
+    # scratch engine and the per-launch timing (after the dump) leave the headline's outputs alone
+    out_b, b = _bench(tmp_path / "b", 2, 2)
+    out_f, f = _bench(tmp_path / "f", 2, 2, "--full")
+    assert out_b["roofline"] is None and "kernels" not in out_b          # a plain run times the headline alone
+    assert len(out_f["kernels"]) == 9 and out_f["roofline"]["us_per_launch"] > 0
     _, c = _bench(tmp_path / "c", 4, 1, "--step-kernels-only")       # one step more
     names = {"loss", "mu", "logvar"} | set(PARAM_NAMES) | {p + k for p in ("exp_avg.", "exp_avg_sq.") for k in PARAM_NAMES}
     assert set(a) == names
@@ -39,5 +42,5 @@ def test_dump_outputs_are_the_last_step_and_set_by_the_step_count(tmp_path):
     assert a["loss"][0] == np.float32(out_a["final_loss"])
     assert all(np.isfinite(v).all() for v in a.values())
     for k in names:
-        assert np.array_equal(a[k], b[k]), k
+        assert np.array_equal(a[k], b[k]) and np.array_equal(a[k], f[k]), k
     assert not np.array_equal(a["fc1.weight"], c["fc1.weight"]) and a["loss"][0] != c["loss"][0]

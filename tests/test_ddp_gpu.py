@@ -45,7 +45,7 @@ def test_two_rank_bench_flow_with_the_library_driven_step_through_standins():
     env = dict(os.environ, RV_DIST_BACKEND="gloo", RV_DDP_REHEARSAL="shm")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "6", "--warmup", "2", "--repeats", "3", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "6", "--warmup", "2", "--repeats", "3", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=REPO)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -11,7 +11,7 @@ d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
 print("%-40s %7.1f us/step  %6.2f M frames/s  pair %5.1f us (frac %.3f)  loss %.6f" % (sys.argv[1], d["ms_per_step"] * 1e3, d["value"] / 1e6, d["roofline"]["us_per_launch"], d["roofline"]["frac"], d["final_loss"]))
 PY
 }
-B="python bench.py --steps 1400 --warmup 20 --no-cpu-baseline --no-alts"
+B="python bench.py --steps 1400 --warmup 20 --full --no-cpu-baseline --no-alts"
 {
 echo "== same box, interleaved twice; default = fp16 block-floating-point slabs, row-local latent forward and backward, eager launches"
 for i in 1 2; do
@@ -29,5 +29,5 @@ cat $O/r03_ddp_one_rank.txt
 python tools/train_bench.py 2>&1 | grep -v amdgpu | tail -2 > $O/r03_train_bench.txt; cat $O/r03_train_bench.txt
 bash tools/prof_round3.sh r03_final > /dev/null
 cat $O/r03_final_timeline.txt
-python bench.py > $O/r03_bench.json 2> $O/r03_bench.err
+python bench.py --full > $O/r03_bench.json 2> $O/r03_bench.err
 tail -c 600 $O/r03_bench.json

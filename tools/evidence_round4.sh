@@ -5,7 +5,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
 python -m pytest tests -m gpu -q > $O/r04_gpu_tests.txt 2>&1; tail -2 $O/r04_gpu_tests.txt
-python bench.py > $O/r04_bench.json 2> $O/r04_bench.err; tail -c 400 $O/r04_bench.json; echo
+python bench.py --full > $O/r04_bench.json 2> $O/r04_bench.err; tail -c 400 $O/r04_bench.json; echo
 bash tools/prof_step.sh r04 > /dev/null 2>&1; cat $O/r04_kernel_summary.txt | head -10
 bash tools/pmc_round.sh r04 > /dev/null 2>&1; tail -11 $O/r04_traffic.txt
 { python tools/ddp_model.py; echo; echo "== the same reference point with stand-in workgroups that take their CUs whole (64 KB of LDS each)"; RV_MODEL_LDS=65536 python tools/ddp_model.py 8 300 15 bf16 | grep "^8\|^(stand"; RV_MODEL_LDS=65536 RV_DDP_W1_WIDE=1 python tools/ddp_model.py 8 300 15 bf16 | grep "^8" | sed 's/$/   <- RV_DDP_W1_WIDE=1/'; RV_DDP_W1_WIDE=1 python tools/ddp_model.py 8 300 15 bf16 | grep "^8" | sed 's/$/   <- RV_DDP_W1_WIDE=1, light stand-in/'; echo "== cross-stream edges as HIP events instead of device-side flags"; RV_DDP_SIGNAL=event python tools/ddp_model.py 8 300 15 bf16 | grep "^8"; } 2>/dev/null > $O/r04_ddp_model.txt; cat $O/r04_ddp_model.txt

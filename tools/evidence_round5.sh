@@ -6,7 +6,7 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 cd $R
 python -m pytest tests -m gpu -q > $O/r05_gpu_tests.txt 2>&1; tail -3 $O/r05_gpu_tests.txt
-python bench.py > $O/r05_bench.json 2> $O/r05_bench.err; tail -c 300 $O/r05_bench.json; echo
+python bench.py --full > $O/r05_bench.json 2> $O/r05_bench.err; tail -c 300 $O/r05_bench.json; echo
 bash tools/prof_step.sh r05 > /dev/null 2>&1; head -12 $O/r05_kernel_summary.txt
 bash tools/pmc_round.sh r05 > /dev/null 2>&1; tail -12 $O/r05_traffic.txt
 bash tools/pmc_sq_step.sh r05 > $O/r05_pmc_sq.log 2>&1; head -14 $O/r05_pmc_sq_summary.txt

@@ -9,7 +9,7 @@ mkdir -p $O
 cd $R
 # (.evidence_commit is written by the caller before the snapshot travels: the box has no .git)
 python -m pytest tests -m gpu -q -s > $O/r06_gpu_tests_full.txt 2>&1; grep -v "amdgpu.ids" $O/r06_gpu_tests_full.txt | grep "DDP_BF16\|passed\|failed" > $O/r06_gpu_tests.txt; cat $O/r06_gpu_tests.txt
-python bench.py > $O/r06_bench.json 2> $O/r06_bench.err; tail -c 400 $O/r06_bench.json; echo
+python bench.py --full > $O/r06_bench.json 2> $O/r06_bench.err; tail -c 400 $O/r06_bench.json; echo
 bash tools/prof_step.sh r06 > /dev/null 2>&1; head -14 $O/r06_kernel_summary.txt
 bash tools/r06_prof_shape.sh r06_refini 1024 2048 256 4096 > $O/r06_refini_timeline.txt 2>&1; head -12 $O/r06_refini_timeline.txt
 bash tools/r06_prof_shape.sh r06_default_ini 1024 2048 256 131072 > $O/r06_default_ini_timeline.txt 2>&1; head -16 $O/r06_default_ini_timeline.txt

@@ -3,7 +3,7 @@ O=$R/gpurun_out
 cd $R
 python -m pytest tests -m gpu -q > $O/r05_gpu_tests_final.txt 2>&1; tail -4 $O/r05_gpu_tests_final.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
-python bench.py --no-cpu-baseline > $O/r05_bench_final.json 2> $O/r05_bench_final.err; python - <<'PY'
+python bench.py --full --no-cpu-baseline > $O/r05_bench_final.json 2> $O/r05_bench_final.err; python - <<'PY'
 import json
 d = json.loads([l for l in open('gpurun_out/r05_bench_final.json') if l.startswith('{')][-1])
 print(d['ms_per_step'], [round(k['us'], 1) for k in d['kernels']])

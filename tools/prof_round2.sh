@@ -10,5 +10,5 @@ rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/r02_fetch -o
 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/r02_write -o w -- python3 $R/bench.py --no-cpu-baseline --no-alts --step-kernels-only --steps 20 --warmup 3 > $O/r02_write.log 2>&1
 cd $R
 python tools/timeline_csv.py $(find $O/r02_stats -name "*kernel_trace.csv" | head -1) 5 > $O/r02_timeline.txt
-python bench.py > $O/r02_bench.json 2>$O/r02_bench.err
+python bench.py --full > $O/r02_bench.json 2>$O/r02_bench.err
 tail -1 $O/r02_bench.json | cut -c1-300
