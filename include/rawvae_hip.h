@@ -385,6 +385,55 @@ int rv_som_node_sums(const float* x, long N, long L, const int* bmu, long M, dou
 int rv_som_update(const double* sums, const long long* counts, const float* w_old, long rows, long cols, long L,
                   double sigma, float* w_new, void* stream);
 
+/* ---- Latent audio mosaicing (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py) ----
+ * rv_mosaic(op, d, stream): one entry point for three operations, each reading the fields of *d its op names.
+ *
+ * RV_MOSAIC_KNN (rv_knn_topk): for each query row of q [T, L] fp32 the k nearest rows of c [N, L] fp32 under the
+ * squared distance: idx [T, k] int32 and dist [T, k] fp32 in ascending (distance, index) order.  1 <= k <= 16, k <= N.
+ * The arithmetic is rv_som_bmu's direct form (each term one fma in ascending l within tiles of 32, the tile sums added
+ * in order), so identical rows give exactly 0 and for k <= 2 the result is rv_som_bmu's best / second bit for bit.
+ * Ties go to the lower corpus index, NaN never wins, and a row with fewer than k candidates gets -1 / +inf in the
+ * remaining slots.  The corpus is split across workgroups (`splits` of them; 0 = the library's choice, which fills the
+ * chip for any T) and a second launch merges the per-split partials; the result does not depend on the split count.
+ * ws / ws_bytes: the workspace of the partials (device memory; unused with one split).
+ * RV_MOSAIC_KNN_WORKSPACE (rv_knn_workspace_bytes): stores the bytes RV_MOSAIC_KNN needs for (T, N, L, k, splits) in
+ * d->ws_bytes and launches nothing.
+ *
+ * RV_MOSAIC_GATHER_MEAN (rv_gather_mean): out[t, :width] = (1/k) sum_j src[start(idx[t, j]) : + width] for t < T with
+ * row stride ldo; the sum in fp32 in ascending j from +0, then multiplied by 1/k once.  start(i) = row_start[i] (int64)
+ * when row_start is not NULL, else i * stride.  Indices outside [0, n_rows) (-1: no neighbour) and rows that would
+ * leave src [src_len] add nothing.
+ *
+ * RV_MOSAIC_OLA (rv_ola): offline weighted overlap-add of F frames [F, S] at `hop` into out [n_out]:
+ * out[t] = sum_f w[t - f hop] D_f[t - f hop] / sum_f w[t - f hop] over the frames f that cover t, both sums in
+ * ascending f from +0 in fp32 (each product rounded before its add), 0 where the normaliser is 0.  window [S] fp32, or
+ * NULL for rectangular. */
+#define RV_MOSAIC_KNN 0
+#define RV_MOSAIC_KNN_WORKSPACE 1
+#define RV_MOSAIC_GATHER_MEAN 2
+#define RV_MOSAIC_OLA 3
+typedef struct rv_mosaic_desc {
+  long T, k;                     /* query / output rows, neighbours per row (KNN, GATHER_MEAN) */
+  int* idx;                      /* [T, k]: KNN output, GATHER_MEAN input */
+  const float* q;                /* KNN */
+  const float* c;
+  long N, L, splits;
+  float* dist;
+  void* ws;
+  long ws_bytes;
+  const float* src;              /* GATHER_MEAN */
+  long src_len;
+  const long long* row_start;
+  long stride, n_rows, width;
+  float* out;                    /* GATHER_MEAN [T, ldo], OLA [n_out] */
+  long ldo;
+  const float* frames;           /* OLA */
+  long F, S, hop;
+  const float* window;
+  long n_out;
+} rv_mosaic_desc;
+int rv_mosaic(int op, rv_mosaic_desc* d, void* stream);
+
 /* ---- Streaming resynthesis (csrc/stream.hip) ----
  * rv_small_linear_f32: y = act(x W^T + b) for few rows, one lane per output column: acc = +0, then
  * acc = fmaf(x[k], W[n,k], acc) in ascending k, + b, then fmaxf / tanhf (act 0 none, 1 relu, 2 tanh) -- the arithmetic of

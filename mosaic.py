@@ -1,0 +1,129 @@
+"""`python mosaic.py --config default.ini --checkpoint ckpt_00500 --corpus DIR --target in.wav --out out.wav`
+
+Latent audio mosaicing (rawaudiovae_kelsey_amd.mosaic.LatentIndex): every frame of the target is replaced by its
+nearest corpus frames in the model's latent space, and the result is overlap-added into a wav of the target's length.
+
+  --hop N            frame hop of the corpus and the target (default: segment_length, TestDataset framing)
+  --k N              neighbours per target frame, 1..16 (default 1)
+  --mode grains      the mean of the neighbours' audio; `decode`: the decoded mean of their mu
+  --window hann|none overlap-add window (default none: rectangular; hann needs hop <= segment_length / 2)
+  --matches FILE     one CSV line per target frame: the k (file, sample offset, distance) triples
+  --max-rows N       target frames per encoder / search / decoder chunk (the output does not depend on it)
+
+The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
+values, an empty corpus, unreadable wavs or a --k above the number of corpus frames raise ValueError naming the flag or
+the file.
+"""
+import argparse
+import csv
+import os
+import sys
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+import interpolate as _interp  # noqa: E402  (read_model_config, load_model)
+from som import _int_flag, load_wav  # noqa: E402
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Latent audio mosaicing: resynthesise a target from a corpus's frames")
+    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
+    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    p.add_argument("--corpus", required=True, help="folder of the corpus's .wav files")
+    p.add_argument("--target", required=True, help="the wav to resynthesise")
+    p.add_argument("--out", required=True, help="output wav")
+    p.add_argument("--hop", default=None, help="frame hop (default: segment_length)")
+    p.add_argument("--k", default="1", help="neighbours per target frame (1..16)")
+    p.add_argument("--mode", default="grains", help="grains | decode")
+    p.add_argument("--window", default="none", help="none | hann")
+    p.add_argument("--matches", default=None, help="CSV of the k (file, offset, distance) triples per target frame")
+    p.add_argument("--max-rows", default="16384", help="target frames per chunk")
+    args = p.parse_args(argv)
+    args.k = _int_flag("k", args.k, 1)
+    if args.k > 16:
+        raise ValueError("--k %d: at most 16" % args.k)
+    args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
+    args.max_rows = _int_flag("max-rows", args.max_rows, 1)
+    if args.mode not in ("grains", "decode"):
+        raise ValueError("--mode %r: expected grains or decode" % args.mode)
+    if args.window not in ("none", "hann"):
+        raise ValueError("--window %r: expected none or hann" % args.window)
+    args.window = None if args.window == "none" else args.window
+    if not os.path.isdir(args.corpus):
+        raise ValueError("--corpus %r: not a folder" % args.corpus)
+    return args
+
+
+def check_framing(args, S):
+    """--hop / --window against the model's segment_length; ValueError naming the flag."""
+    from rawaudiovae_kelsey_amd.mosaic import check_window
+    hop = S if args.hop is None else args.hop
+    if S % hop != 0:
+        raise ValueError("--hop %d: does not divide segment_length %d" % (hop, S))
+    try:
+        check_window(S, hop, args.window)
+    except ValueError as e:
+        raise ValueError("--window %s: %s" % (args.window, e))
+    return hop
+
+
+def corpus_files(corpus_dir):
+    """Sorted *.wav of corpus_dir (basenames); ValueError naming --corpus when there are none."""
+    import glob
+    files = sorted(os.path.basename(p) for p in glob.glob(os.path.join(corpus_dir, "*.wav")))
+    if not files:
+        raise ValueError("--corpus %r: no .wav files" % corpus_dir)
+    return files
+
+
+def write_matches(path, names_offsets, dist):
+    """One line per target frame: file_1, offset_1, distance_1, ..., file_k, offset_k, distance_k."""
+    with open(path, "w", newline="") as f:
+        wr = csv.writer(f)
+        for row, drow in zip(names_offsets, dist):
+            line = []
+            for (name, off), d in zip(row, drow):
+                line += [name if name is not None else "", off, repr(float(d))]
+            wr.writerow(line)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    cfg = _interp.read_model_config(args.config)
+    S, sr = cfg["segment_length"], cfg["sampling_rate"]
+    hop = check_framing(args, S)
+    files = corpus_files(args.corpus)
+    waves = [load_wav(os.path.join(args.corpus, f), sr) for f in files]
+    target = load_wav(args.target, sr)
+    from rawaudiovae_kelsey_amd import data as D
+    from rawaudiovae_kelsey_amd.interpolate import frame_layout
+    from rawaudiovae_kelsey_amd.mosaic import LatentIndex
+    framing = None if args.hop is None else hop
+    for f, w in zip(files, waves):
+        if frame_layout(w.size, S, framing)[0] < 1:
+            raise ValueError("%s: %d samples make no frame of %d samples at hop %d" % (
+                os.path.join(args.corpus, f), w.size, S, hop))
+    n_corpus = sum(frame_layout(w.size, S, framing)[0] for w in waves)
+    if args.k > n_corpus:
+        raise ValueError("--k %d: the corpus has only %d frames" % (args.k, n_corpus))
+    if frame_layout(target.size, S, framing)[0] < 1:
+        raise ValueError("--target %r: %d samples make no frame of %d samples at hop %d" % (args.target, target.size,
+                                                                                           S, hop))
+    model = _interp.load_model(args.checkpoint, cfg)
+    index = LatentIndex(model, hop=framing, max_rows=args.max_rows)
+    for f, w in zip(files, waves):
+        index.add(w, f)
+    y, idx, dist = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True)
+    y = y.cpu().numpy()
+    D.write_wav(args.out, y, sr)
+    if args.matches:
+        write_matches(args.matches, index.locate(idx), dist.cpu().numpy())
+    print("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s"
+          % (args.out, y.size, idx.shape[0], len(index), len(files), args.k, args.mode, args.window or "none"))
+    return y
+
+
+if __name__ == "__main__":
+    main()

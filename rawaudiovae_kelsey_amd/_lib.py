@@ -42,6 +42,15 @@ class StreamDesc(C.Structure):
                    ("workspace", c_void_p)])
 
 
+class MosaicDesc(C.Structure):
+    """rv_mosaic_desc: one rv_mosaic call (mosaic.py); each op reads the fields the header names for it."""
+    _fields_ = [("T", c_long), ("k", c_long), ("idx", c_void_p), ("q", c_void_p), ("c", c_void_p), ("N", c_long),
+                ("L", c_long), ("splits", c_long), ("dist", c_void_p), ("ws", c_void_p), ("ws_bytes", c_long),
+                ("src", c_void_p), ("src_len", c_long), ("row_start", c_void_p), ("stride", c_long), ("n_rows", c_long),
+                ("width", c_long), ("out", c_void_p), ("ldo", c_long), ("frames", c_void_p), ("F", c_long),
+                ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long)]
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),
@@ -64,6 +73,7 @@ PHASE_ADAM_FC4, PHASE_ADAM_FC1, PHASE_ADAM_MID = 0x4000, 0x8000, 0x10000
 PHASE_ANY_ADAM = PHASE_ADAM | PHASE_ADAM_A | PHASE_ADAM_B | PHASE_ADAM_FC4 | PHASE_ADAM_FC1 | PHASE_ADAM_MID
 PHASE_ALL_LOCAL = PHASE_FWD | PHASE_BWD_A | PHASE_BWD_B | PHASE_ADAM
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2   # ACT_TANH: rv_linear_fp32 only
+MOSAIC_KNN, MOSAIC_KNN_WORKSPACE, MOSAIC_GATHER_MEAN, MOSAIC_OLA = 0, 1, 2, 3   # RV_MOSAIC_* (rv_mosaic)
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {
@@ -130,6 +140,7 @@ _SIGS = {
     "rv_som_bmu": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long] + [c_void_p] * 5),
     "rv_som_node_sums": (c_int, [c_void_p, c_long, c_long, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "rv_som_update": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_long, c_long, C.c_double, c_void_p, c_void_p]),
+    "rv_mosaic": (c_int, [c_int, C.POINTER(MosaicDesc), c_void_p]),
     "rv_gather_frames": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_long, c_void_p, c_void_p]),
     "rv_pcm_to_f32": (c_int, [c_void_p, c_long, c_int, c_int, c_int, c_long, c_void_p, c_long, c_void_p]),
     "rv_resample_sinc_hann": (c_int, [c_void_p, c_long, c_void_p, c_long, c_long, c_long, c_void_p, c_long, c_void_p]),

@@ -1,0 +1,263 @@
+"""Latent audio mosaicing: resynthesise a target from the frames of a corpus that sound like it in the model's latent
+space (corpus-based concatenative synthesis with the VAE's encoder as the descriptor).
+
+  index = LatentIndex(model, hop=None)    frames each corpus file on its own (TestDataset at hop=None, AudioDataset at
+  index.add(wave, name)                   an int hop: interpolate.frame_layout) and encodes the frames with the
+                                          exact-fp32 encoder path; no frame straddles two files
+  index.search(mu, k)                     (idx [T, k] int32, dist [T, k] fp32): the k nearest corpus frames of every
+                                          row of mu, rv_mosaic(RV_MOSAIC_KNN)
+  index.locate(idx)                       (file name, sample offset) of corpus frames
+  index.mosaic(target, k, hop, mode, window)
+      the target is framed at `hop` and encoded; each frame is replaced by its k nearest corpus frames, either
+      "grains": the mean of their audio (S samples each, RV_MOSAIC_GATHER_MEAN over the corpus waveform), or
+      "decode": the mean of their mu decoded through fc3 and fc4 + tanh (rv_linear_fp32);
+      then an offline weighted overlap-add (RV_MOSAIC_OLA) with stream.py's window and normaliser rules.  The output
+      has the target's length.
+
+The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
+corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
+encoder, search, gather and decoder step), so the output is bit-identical for any chunking.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import ACT_RELU, ACT_TANH, MosaicDesc, lib, ptr, stream_ptr
+from .interpolate import LatentInterpolator, frame_layout
+from .stream import WINDOWS, window_values
+
+MODES = ("grains", "decode")
+K_MAX = 16
+
+
+def _call(op, **fields):
+    d = MosaicDesc(**fields)
+    lib().rv_mosaic(op, _lib.C.byref(d), None if op == _lib.MOSAIC_KNN_WORKSPACE else stream_ptr())
+    return d
+
+
+def _rows(x, what):
+    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
+        raise ValueError("%s must be a 2-D float32 device tensor, got %s" % (
+            what, "%s %s on %s" % (x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__))
+    return x.contiguous()
+
+
+def knn_workspace_bytes(T, N, L, k, splits=0):
+    """Bytes of device workspace knn_topk needs for these extents (0 when the corpus is not split)."""
+    return _call(_lib.MOSAIC_KNN_WORKSPACE, T=int(T), N=int(N), L=int(L), k=int(k), splits=int(splits)).ws_bytes
+
+
+def knn_topk(q, c, k, splits=0):
+    """(idx [T, k] int32, dist [T, k] fp32): the k nearest rows of c [N, L] to each row of q [T, L] under the squared
+    distance, in ascending (distance, index) order; -1 / +inf where a row has fewer than k candidates.  `splits` pins
+    the number of corpus splits (0: the library's choice); the result does not depend on it."""
+    q, c = _rows(q, "q"), _rows(c, "c")
+    if q.shape[1] != c.shape[1] or q.device != c.device:
+        raise ValueError("q %s and c %s must share L and device" % (tuple(q.shape), tuple(c.shape)))
+    T, N, L, k = q.shape[0], c.shape[0], q.shape[1], int(k)
+    if not 1 <= k <= min(K_MAX, N):
+        raise ValueError("k=%d must be in [1, %d] and at most the %d corpus rows" % (k, K_MAX, N))
+    idx = torch.empty((T, k), dtype=torch.int32, device=q.device)
+    dist = torch.empty((T, k), dtype=torch.float32, device=q.device)
+    nbytes = knn_workspace_bytes(T, N, L, k, splits)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
+    _call(_lib.MOSAIC_KNN, T=T, N=N, L=L, k=k, splits=int(splits), q=ptr(q), c=ptr(c), idx=ptr(idx), dist=ptr(dist),
+          ws=ptr(ws), ws_bytes=nbytes)
+    return idx, dist
+
+
+def gather_mean(src, idx, width, row_start=None, stride=None, n_rows=None, out=None, ldo=None):
+    """out [T, width] fp32: row t is (1/k) sum_j src[start(idx[t, j]) : + width], the sum in ascending j from +0.
+    start(i) = row_start[i] (int64 device tensor) or i * stride.  Indices outside [0, n_rows) add nothing."""
+    src = src.contiguous().view(-1)
+    idx = idx.to(torch.int32).contiguous()
+    T, k = idx.shape
+    width = int(width)
+    if row_start is None:
+        stride = int(stride)
+        n_rows = (src.numel() - width) // stride + 1 if n_rows is None else int(n_rows)
+    else:
+        row_start = row_start.to(torch.int64).contiguous()
+        n_rows = row_start.numel() if n_rows is None else int(n_rows)
+        stride = 0
+    ldo = width if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((T, ldo), dtype=torch.float32, device=src.device)
+    _call(_lib.MOSAIC_GATHER_MEAN, T=T, k=k, idx=ptr(idx), src=ptr(src), src_len=src.numel(), row_start=ptr(row_start),
+          stride=stride, n_rows=n_rows, width=width, out=ptr(out), ldo=ldo)
+    return out
+
+
+def ola(frames, hop, n_out, window=None, out=None):
+    """[n_out] fp32 weighted overlap-add of frames [F, S] at `hop` (window: [S] fp32 device tensor or None)."""
+    frames = frames.contiguous()
+    F, S = frames.shape
+    if out is None:
+        out = torch.empty(int(n_out), dtype=torch.float32, device=frames.device)
+    w = None if window is None else window.to(device=frames.device, dtype=torch.float32).contiguous()
+    if w is not None and w.numel() != S:
+        raise ValueError("window has %d values for frames of %d samples" % (w.numel(), S))
+    _call(_lib.MOSAIC_OLA, frames=ptr(frames), F=F, S=S, hop=int(hop), window=ptr(w), n_out=int(n_out), out=ptr(out))
+    return out
+
+
+def check_window(segment_length, hop, window):
+    """stream.py's window rules for a synthesis hop: ValueError for an unknown window or a Hann window whose sum is zero
+    at frame starts (hop > segment_length / 2)."""
+    if window not in WINDOWS:
+        raise ValueError("window %r: expected None (rectangular) or 'hann'" % (window,))
+    if window == "hann" and 2 * int(hop) > int(segment_length):
+        raise ValueError("a Hann window needs hop <= segment_length / 2 (got hop %d, segment_length %d)"
+                         % (hop, segment_length))
+
+
+def frame_tables(lengths, segment_length, hop=None):
+    """The corpus tables of files of `lengths` samples, each framed on its own (frame_layout) and stored padded, one
+    after the other -> (n_frames [F], padded [F], row_start [N] int64, file_of [N] int32, offset_of [N] int64):
+    frame i is samples [row_start[i], row_start[i] + segment_length) of the concatenation, which lie inside its file's
+    padded waveform at offset_of[i]."""
+    S = int(segment_length)
+    step = S if hop is None else int(hop)
+    lay = [frame_layout(n, S, hop) for n in lengths]
+    n_frames = np.array([max(f, 0) for f, _ in lay], dtype=np.int64)
+    padded = np.array([p for _, p in lay], dtype=np.int64)
+    base = np.concatenate([[0], np.cumsum(padded)[:-1]]).astype(np.int64)
+    file_of = np.repeat(np.arange(len(lay), dtype=np.int32), n_frames)
+    offset_of = np.concatenate([np.arange(n, dtype=np.int64) * step for n in n_frames] or [np.zeros(0, np.int64)])
+    return n_frames, padded, base[file_of] + offset_of, file_of, offset_of
+
+
+class LatentIndex:
+    """Frames of a corpus, their latents and their audio on the device (see the module doc).
+
+    Corpus frame i of file f at frame position p starts at sample p * hop of f's padded waveform; the padded waveforms
+    of all files are concatenated into one device buffer, and `row_start[i]` (int64) is frame i's sample offset in it.
+    `file_of[i]` and `offset_of[i]` (numpy) give the file and the sample offset within the file."""
+
+    def __init__(self, model, hop=None, max_rows=16384):
+        self._enc = LatentInterpolator(model, max_rows=max_rows)
+        self.model, self.max_rows, self.device = model, self._enc.max_rows, self._enc.device
+        self.S, self.H, self.L = self._enc.S, self._enc.H, self._enc.L
+        self.hop = None if hop is None else int(hop)
+        frame_layout(self.S, self.S, self.hop)   # ValueError for a hop that does not divide segment_length
+        self.names = []
+        self._lengths, self._waves, self._mus, self._n_frames = [], [], [], []
+        self._built = None
+
+    @property
+    def step(self):
+        return self.S if self.hop is None else self.hop
+
+    def __len__(self):
+        return int(sum(self._n_frames))
+
+    @torch.no_grad()
+    def add(self, wave, name):
+        """Frame, encode and append one corpus file.  ValueError naming `name` when it makes no frame."""
+        w = self._enc._wave(wave)
+        n_frames, _ = frame_layout(w.numel(), self.S, self.hop)
+        if n_frames < 1:
+            raise ValueError("%s: %d samples make no frame of %d samples at hop %s" % (name, w.numel(), self.S,
+                                                                                       self.hop))
+        padded, n_frames = self._enc._padded(w, w.numel(), self.hop)
+        mu, _ = self._enc._encode_padded(padded, n_frames, self.hop)
+        self.names.append(str(name))
+        self._lengths.append(w.numel())
+        self._waves.append(padded)
+        self._mus.append(mu)
+        self._n_frames.append(n_frames)
+        self._built = None
+        return n_frames
+
+    def _tables(self):
+        if self._built is None:
+            if not self.names:
+                raise ValueError("the index is empty: add() corpus files first")
+            _, _, row_start, file_of, offset_of = frame_tables(self._lengths, self.S, self.hop)
+            self._built = dict(audio=torch.cat(self._waves), mu=torch.cat(self._mus), file_of=file_of,
+                               offset_of=offset_of, row_start_host=row_start,
+                               row_start=torch.from_numpy(row_start).to(self.device))
+        return self._built
+
+    @property
+    def audio(self):
+        """All files' padded waveforms, concatenated: [sum of padded lengths] fp32 on the device."""
+        return self._tables()["audio"]
+
+    @property
+    def mu(self):
+        """[N, L] fp32 encoder mu of every corpus frame, file by file."""
+        return self._tables()["mu"]
+
+    @property
+    def row_start(self):
+        return self._tables()["row_start_host"]
+
+    @property
+    def file_of(self):
+        return self._tables()["file_of"]
+
+    @property
+    def offset_of(self):
+        return self._tables()["offset_of"]
+
+    @torch.no_grad()
+    def search(self, mu, k, splits=0):
+        """(idx [T, k] int32, dist [T, k] fp32) of the k nearest corpus frames of each row of mu [T, L]."""
+        return knn_topk(mu, self.mu, k, splits)
+
+    def locate(self, idx):
+        """(name, sample offset within the file) of each corpus frame index in idx (any shape; -1 -> (None, -1)),
+        as a nested list of idx's shape."""
+        a = idx.cpu().numpy() if torch.is_tensor(idx) else np.asarray(idx)
+        t = self._tables()
+        N = len(self)
+
+        def one(i):
+            i = int(i)
+            if not 0 <= i < N:
+                return (None, -1)
+            return (self.names[t["file_of"][i]], int(t["offset_of"][i]))
+        if a.ndim == 0:
+            return one(a)
+        return [self.locate(r) if a.ndim > 1 else one(r) for r in a]
+
+    @torch.no_grad()
+    def mosaic(self, target, k=1, hop=None, mode="grains", window=None, return_matches=False):
+        """The target resynthesised from the corpus (see the module doc) -> 1-D fp32 device tensor of the target's
+        length; with return_matches also (idx [T, k], dist [T, k]).  hop=None: the index's framing."""
+        if mode not in MODES:
+            raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
+        k = int(k)
+        N = len(self)
+        if not 1 <= k <= min(K_MAX, N):
+            raise ValueError("k=%d must be in [1, %d] and at most the %d corpus frames" % (k, K_MAX, N))
+        hop = self.hop if hop is None else int(hop)
+        step = self.S if hop is None else hop
+        check_window(self.S, step, window)
+        w = self._enc._wave(target)
+        n = w.numel()
+        padded, T = self._enc._padded(w, n, hop)
+        mu, _ = self._enc._encode_padded(padded, T, hop)
+        t = self._tables()
+        frames = torch.empty((T, self.S), dtype=torch.float32, device=self.device)
+        idx = torch.empty((T, k), dtype=torch.int32, device=self.device)
+        dist = torch.empty((T, k), dtype=torch.float32, device=self.device)
+        cap = min(self.max_rows, T)
+        if mode == "decode":
+            z = torch.empty((cap, self.L), dtype=torch.float32, device=self.device)
+            h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
+        for r0 in range(0, T, self.max_rows):
+            rows = min(self.max_rows, T - r0)
+            i, d = knn_topk(mu[r0:r0 + rows], t["mu"], k)
+            idx[r0:r0 + rows], dist[r0:r0 + rows] = i, d
+            if mode == "grains":
+                gather_mean(t["audio"], i, self.S, row_start=t["row_start"], out=frames[r0:r0 + rows])
+            else:
+                gather_mean(t["mu"], i, self.L, stride=self.L, n_rows=N, out=z[:rows])
+                self._enc._linear(ptr(z), self.L, rows, "fc3", ACT_RELU, ptr(h), self.H)
+                self._enc._linear(ptr(h), self.H, rows, "fc4", ACT_TANH, frames.data_ptr() + 4 * r0 * self.S, self.S)
+        win = None if window is None else torch.from_numpy(window_values(self.S, window)).to(self.device)
+        out = ola(frames, step, n, win)
+        return (out, idx, dist) if return_matches else out

@@ -1,0 +1,101 @@
+"""Numpy restatement of the mosaicing kernels (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py) for the tests.
+
+knn: the direct-form fp32 distance bit for bit -- each term fmaf(d, d, part) in ascending l within tiles of 32, the
+tile sums added in order from +0 -- then the first k candidates in (distance, index) order, NaN excluded.
+gather_mean and ola: fp32 in the kernels' orders."""
+import numpy as np
+
+KT = 32
+
+
+def _fma_sq(d, acc):
+    """fmaf(d, d, acc) elementwise for fp32 arrays: d * d is exact in float64, the float64 sum is corrected by its
+    rounding error where it lands on an fp32 midpoint (the only case where rounding twice differs from once)."""
+    d2 = d.astype(np.float64) ** 2
+    a = acc.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s = d2 + a
+        bp = s - d2
+        err = (d2 - (s - bp)) + (a - bp)
+        r = s.astype(np.float32)
+        rd = r.astype(np.float64)
+        lo = np.where(rd < s, r, np.nextafter(r, np.float32(-np.inf)))
+        hi = np.where(rd > s, r, np.nextafter(r, np.float32(np.inf)))
+        mid = (rd != s) & np.isfinite(s) & (lo.astype(np.float64) + hi.astype(np.float64) == 2.0 * s) & (err != 0)
+        return np.where(mid, np.where(err > 0, hi, lo), r).astype(np.float32)
+
+
+def sq_dist(q, c):
+    """[T, N] fp32: the kernel's distance of every query row to every corpus row."""
+    q = np.asarray(q, np.float32)
+    c = np.asarray(c, np.float32)
+    T, L = q.shape
+    N = c.shape[0]
+    tot = np.zeros((T, N), np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k0 in range(0, L, KT):
+            part = np.zeros((T, N), np.float32)
+            for l in range(k0, min(L, k0 + KT)):
+                d = q[:, l][:, None] - c[:, l][None, :]
+                part = _fma_sq(d, part)
+            tot = tot + part
+    return tot
+
+
+def knn(q, c, k, chunk_elems=1 << 22):
+    """(idx [T, k] int64, dist [T, k] fp32): the first k of each row in (distance, index) order, NaN never taken,
+    -1 / +inf where fewer than k candidates remain."""
+    q = np.asarray(q, np.float32)
+    c = np.asarray(c, np.float32)
+    T, N = q.shape[0], c.shape[0]
+    idx = np.full((T, k), -1, np.int64)
+    dist = np.full((T, k), np.inf, np.float32)
+    rows = max(1, chunk_elems // max(N, 1))
+    cols = np.broadcast_to(np.arange(N), (rows, N))
+    for r0 in range(0, T, rows):
+        dd = sq_dist(q[r0:r0 + rows], c)
+        n = dd.shape[0]
+        bad = np.isnan(dd)
+        key = np.where(bad, np.inf, dd)
+        order = np.lexsort((cols[:n], key, bad), axis=-1)[:, :k]
+        r = np.arange(n)[:, None]
+        ok = ~bad[r, order]
+        idx[r0:r0 + n] = np.where(ok, order, -1)
+        dist[r0:r0 + n] = np.where(ok, dd[r, order], np.inf)
+    return idx, dist
+
+
+def gather_mean(src, starts, idx, width):
+    """[T, width] fp32: (1/k) sum_j src[starts[idx[t, j]] : + width] in ascending j from +0; idx -1 adds nothing."""
+    src = np.asarray(src, np.float32)
+    idx = np.asarray(idx)
+    T, k = idx.shape
+    acc = np.zeros((T, width), np.float32)
+    for j in range(k):
+        i = idx[:, j]
+        ok = i >= 0
+        rows = np.zeros((T, width), np.float32)
+        st = np.asarray(starts)[np.where(ok, i, 0)]
+        rows[ok] = src[st[ok][:, None] + np.arange(width)[None, :]]
+        acc = np.where(ok[:, None], acc + rows, acc).astype(np.float32)
+    return (acc * (np.float32(1.0) / np.float32(k))).astype(np.float32)
+
+
+def ola(frames, hop, n_out, window=None):
+    """[n_out] fp32: sum_f w D_f / sum_f w over the frames covering each position, ascending f from +0, each product
+    rounded before its add; 0 where the normaliser is 0."""
+    frames = np.asarray(frames, np.float32)
+    F, S = frames.shape
+    w = np.ones(S, np.float32) if window is None else np.asarray(window, np.float32)
+    size = max(n_out, (F - 1) * hop + S)
+    num = np.zeros(size, np.float32)
+    den = np.zeros(size, np.float32)
+    for f in range(F):
+        sl = slice(f * hop, f * hop + S)
+        num[sl] = num[sl] + (w * frames[f]).astype(np.float32)
+        den[sl] = den[sl] + w
+    num, den = num[:n_out], den[:n_out]
+    out = np.zeros(n_out, np.float32)
+    nz = den != 0
+    out[nz] = num[nz] / den[nz]
+    return out

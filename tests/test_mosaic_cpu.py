@@ -1,0 +1,167 @@
+"""Latent mosaicing without a GPU: corpus framing tables, the numpy oracle's identities, the header entry and the
+command line's flag checks (rawaudiovae_kelsey_amd/mosaic.py, mosaic.py, tests/mosaic_oracle.py)."""
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+from conftest import REPO  # noqa: E402
+import mosaic_oracle as O  # noqa: E402
+
+
+@pytest.mark.parametrize("hop", [None, 16, 64])
+def test_frame_tables_frame_each_file_on_its_own(hop):
+    from rawaudiovae_kelsey_amd.interpolate import frame_layout
+    from rawaudiovae_kelsey_amd.mosaic import frame_tables
+    S = 64
+    lengths = [64, 1001, 257, 77, 3333, 65]
+    n_frames, padded, row_start, file_of, offset_of = frame_tables(lengths, S, hop)
+    step = S if hop is None else hop
+    assert list(n_frames) == [frame_layout(n, S, hop)[0] for n in lengths]
+    assert list(padded) == [frame_layout(n, S, hop)[1] for n in lengths]
+    base = np.concatenate([[0], np.cumsum(padded)[:-1]])
+    assert row_start.dtype == np.int64 and row_start.size == n_frames.sum() == file_of.size == offset_of.size
+    for f in range(len(lengths)):
+        sel = file_of == f
+        assert np.array_equal(offset_of[sel], np.arange(n_frames[f]) * step)
+        starts = row_start[sel]
+        # every frame lies inside its own file's padded waveform: no frame straddles two files
+        assert starts.min() >= base[f] and starts.max() + S <= base[f] + padded[f]
+        assert starts.max() + S == base[f] + padded[f]      # and the last one ends where the padding does
+    assert np.all(np.diff(file_of) >= 0)
+
+
+def test_knn_oracle_is_exact_on_small_cases():
+    rng = np.random.default_rng(0)
+    c = rng.standard_normal((40, 37)).astype(np.float32)
+    q = np.concatenate([c[[5, 17]], rng.standard_normal((3, 37)).astype(np.float32)])
+    c[30] = c[5]                                            # duplicate: the lower index wins the tie
+    idx, dist = O.knn(q, c, 4)
+    assert idx[0, 0] == 5 and idx[0, 1] == 30 and dist[0, 0] == 0 and dist[0, 1] == 0
+    assert idx[1, 0] == 17 and dist[1, 0] == 0
+    ref = ((q.astype(np.float64)[:, None, :] - c[None].astype(np.float64)) ** 2).sum(-1)
+    for t in range(q.shape[0]):
+        assert np.all(np.diff(dist[t]) >= 0)
+        np.testing.assert_allclose(dist[t], ref[t, idx[t]], rtol=1e-5, atol=0)
+        assert np.array_equal(np.sort(ref[t])[:4], np.sort(ref[t, idx[t]]))
+    cn = c.copy()
+    cn[:, 3] = np.nan
+    cn[2] = c[2]
+    cn[9] = c[9]
+    idx, dist = O.knn(q, cn, 4)
+    assert np.array_equal(np.sort(idx[:, :2], axis=1), np.tile([2, 9], (q.shape[0], 1)))
+    assert np.all(idx[:, 2:] == -1) and np.all(np.isinf(dist[:, 2:]))
+
+
+def test_fma_emulation_rounds_once():
+    # 1 + 2^-24 (a midpoint of fp32 1 and 1 + 2^-23) plus a tiny positive rest must round up, not to even
+    d = np.array([np.float32(2.0 ** -12)], np.float32)          # d^2 = 2^-24 exactly
+    acc = np.array([np.float32(1.0)], np.float32)
+    assert O._fma_sq(d, acc)[0] == np.float32(1.0)              # exact midpoint: ties to even
+    d = np.array([np.float32(2.0 ** -12 * (1 + 2.0 ** -23))], np.float32)
+    assert O._fma_sq(d, acc)[0] == np.nextafter(np.float32(1.0), np.float32(2.0))
+
+
+def test_ola_oracle_identities():
+    rng = np.random.default_rng(1)
+    S, F = 32, 7
+    frames = rng.uniform(-1, 1, (F, S)).astype(np.float32)
+    out = O.ola(frames, S, F * S)
+    assert np.array_equal(out, frames.reshape(-1))               # hop == S, no window: concatenation
+    assert np.array_equal(O.ola(frames, S, F * S - 5), frames.reshape(-1)[:-5])
+    from rawaudiovae_kelsey_amd.stream import window_values
+    w = window_values(S, "hann")
+    out = O.ola(frames, S // 4, (F - 1) * S // 4 + S, w)
+    assert w[0] == 0 and out[0] == 0                             # the normaliser is 0 at t = 0 only
+    assert np.all(np.isfinite(out))
+    x = rng.uniform(-1, 1, (F - 1) * S // 4 + S).astype(np.float32)   # the frames of one signal give it back
+    fr = np.stack([x[f * S // 4:f * S // 4 + S] for f in range(F)])
+    out = O.ola(fr, S // 4, x.size, w)
+    assert out.dtype == np.float32 and out[0] == 0
+    np.testing.assert_allclose(out[1:], x[1:], rtol=0, atol=1e-6)
+    assert np.array_equal(O.ola(frames, S, 3 * S + 1)[3 * S:], frames[3, :1])
+
+
+def test_gather_mean_oracle_is_the_float32_mean():
+    rng = np.random.default_rng(2)
+    src = rng.standard_normal(500).astype(np.float32)
+    starts = np.array([0, 7, 100, 250, 480], np.int64)
+    idx = np.array([[1, 3, -1], [4, 4, 0]])
+    out = O.gather_mean(src, starts, idx, 16)
+    exp0 = ((np.float32(0) + src[7:23] + src[250:266]) * (np.float32(1) / np.float32(3))).astype(np.float32)
+    assert np.array_equal(out[0], exp0)
+    assert np.array_equal(O.gather_mean(src, starts, idx[:, :1], 16)[1], src[480:496])
+
+
+def _decls():
+    with open(os.path.join(REPO, "include", "rawvae_hip.h")) as f:
+        src = re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)
+    return sorted(set(re.findall(r"\b(rv_[a-z0-9_]+)\s*\(", src)))
+
+
+def test_header_declares_the_mosaic_entry_and_binding(tmp_path):
+    from rawaudiovae_kelsey_amd import _lib
+    names = _decls()
+    assert "rv_mosaic" in names and len(names) <= 70 and "rv_mosaic" in _lib.EXPORTED
+    src = tmp_path / "c.c"
+    src.write_text('#include "rawvae_hip.h"\nint main(void) { rv_mosaic_desc d = {0}; d.T = 4; d.k = RV_MOSAIC_OLA; '
+                   'return (int)sizeof(d) > 0 ? 0 : 1; }\n')
+    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-c", "-I", os.path.join(REPO, "include"), str(src), "-o",
+                    str(tmp_path / "c.o")], check=True)
+    from rawaudiovae_kelsey_amd import mosaic
+    # the workspace query touches no device: 1 split needs none, a split corpus T * k * 8 bytes per split
+    assert mosaic.knn_workspace_bytes(20700, 1240000, 256, 4) > 0
+    assert mosaic.knn_workspace_bytes(300, 5000, 64, 1, splits=1) == 0
+    assert mosaic.knn_workspace_bytes(300, 5000, 64, 2, splits=3) == 3 * 300 * 2 * 8
+    for bad in ((4, 10, 8, 0), (4, 10, 8, 17), (4, 3, 8, 4), (0, 10, 8, 1)):
+        with pytest.raises(_lib.RvError):
+            mosaic.knn_workspace_bytes(*bad)
+
+
+def _tiny_ini(tmp_path, S=64, H=96, L=8, sr=8000):
+    p = tmp_path / "tiny.ini"
+    p.write_text("[audio]\nsampling_rate = %d\nhop_length = 8\nsegment_length = %d\n[VAE]\nlatent_dim = %d\n"
+                 "n_units = %d\n" % (sr, S, L, H))
+    return p
+
+
+def test_cli_help_and_bad_flags(tmp_path):
+    r = subprocess.run([sys.executable, os.path.join(REPO, "mosaic.py"), "--help"], capture_output=True, text=True,
+                       cwd=REPO)
+    assert r.returncode == 0 and "--corpus" in r.stdout and "--matches" in r.stdout
+    sys.path.insert(0, REPO)
+    import mosaic as cli
+    from rawaudiovae_kelsey_amd import data as D
+    ini = _tiny_ini(tmp_path)
+    corpus = tmp_path / "corpus"
+    corpus.mkdir()
+    empty = tmp_path / "empty"
+    empty.mkdir()
+    target = tmp_path / "t.wav"
+    D.write_wav(target, np.zeros(300, np.float32), 8000)
+    base = ["--config", str(ini), "--checkpoint", "none.pt", "--target", str(target), "--out", str(tmp_path / "o.wav")]
+    for extra, flag in ((["--k", "0"], "--k"), (["--k", "17"], "--k"), (["--k", "x"], "--k"),
+                        (["--mode", "blend"], "--mode"), (["--window", "hamming"], "--window"),
+                        (["--hop", "0"], "--hop"), (["--hop", "48"], "--hop"), (["--hop", "64", "--window", "hann"],
+                                                                               "--window"),
+                        (["--max-rows", "0"], "--max-rows")):
+        with pytest.raises(ValueError, match=flag):
+            cli.main(base + ["--corpus", str(corpus)] + extra)
+    with pytest.raises(ValueError, match="--corpus"):
+        cli.main(base + ["--corpus", str(empty)])
+    with pytest.raises(ValueError, match="--corpus"):
+        cli.main(base + ["--corpus", str(tmp_path / "missing")])
+    D.write_wav(corpus / "a.wav", np.zeros(130, np.float32), 8000)    # 3 frames of 64 (TestDataset framing)
+    with pytest.raises(ValueError, match="--k"):
+        cli.main(base + ["--corpus", str(corpus), "--k", "4"])
+    D.write_wav(corpus / "b.wav", np.zeros(40, np.float32), 8000)     # no frame of 64 at hop 16
+    with pytest.raises(ValueError, match="b.wav"):
+        cli.main(base + ["--corpus", str(corpus), "--hop", "16"])
+    (corpus / "c.wav").write_bytes(b"not a wav")
+    with pytest.raises(ValueError, match="c.wav"):
+        cli.main(base + ["--corpus", str(corpus)])
