@@ -386,7 +386,7 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
                   double sigma, float* w_new, void* stream);
 
 /* ---- Latent audio mosaicing (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py) ----
- * rv_mosaic(op, d, stream): one entry point for three operations, each reading the fields of *d its op names.
+ * rv_mosaic(op, d, stream): one entry point for the operations below, each reading the fields of *d its op names.
  *
  * RV_MOSAIC_KNN (rv_knn_topk): for each query row of q [T, L] fp32 the k nearest rows of c [N, L] fp32 under the
  * squared distance: idx [T, k] int32 and dist [T, k] fp32 in ascending (distance, index) order.  1 <= k <= 16, k <= N.
@@ -407,11 +407,40 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  * RV_MOSAIC_OLA (rv_ola): offline weighted overlap-add of F frames [F, S] at `hop` into out [n_out]:
  * out[t] = sum_f w[t - f hop] D_f[t - f hop] / sum_f w[t - f hop] over the frames f that cover t, both sums in
  * ascending f from +0 in fp32 (each product rounded before its add), 0 where the normaliser is 0.  window [S] fp32, or
- * NULL for rectangular. */
+ * NULL for rectangular.
+ *
+ * Unit selection over the KNN candidates (Viterbi; DESIGN.md section 7.5 "Continuity"): choose one candidate per row
+ * so that J(p) = sum_t dist[t, p_t] + lambda * sum_{t>=1} trans[t, p_{t-1}, p_t] is least.  idx [T, k] / dist [T, k]
+ * are always the whole tables as RV_MOSAIC_KNN writes them, 1 <= k <= 16; the rows of one call are [row0, row0 + rows).
+ *
+ * RV_MOSAIC_TRANSITION: trans [rows, k, k] fp32, trans[t - row0, i, j] = D(c[next_of[idx[t-1, i]]], c[idx[t, j]]) with
+ * D the search's distance (same arithmetic, so a candidate that is the successor of the previous one costs exactly 0);
+ * +inf when either candidate is -1 (or outside [0, N)) or the value is NaN; row t = 0 is all 0.  c [N, L] fp32 are the
+ * corpus latents, next_of [N] int32 the successor table (0 <= next_of[i] < N; anything else counts as missing).
+ *
+ * RV_MOSAIC_PATH_FORWARD: the forward pass over the rows of `trans` [rows, k, k], in fp32, one row after the other:
+ * m = min_i score[i]; s[i] = score[i] - m when m is finite; new[j] = dist[t, j] + min_i (s[i] + fl(lambda * trans[i, j]))
+ * over the pairs whose s[i] and trans are finite (product rounded before the add, strict < in ascending i: ties go to
+ * the lower i), back[t, j] = that i.  Row t = 0, and a row where no new[j] is finite, starts a new sequence:
+ * new = dist[t] (+inf for -1 / NaN), back = none.  end[t] = the lowest-j argmin of the row's scores, none if no score
+ * is finite.  back, end, the transition cost met at (t, j) and the scores of the last row live in ws; a call with
+ * row0 = 0 resets the scores, and the caller feeds the chunks in ascending order without gaps (the library keeps no
+ * host state and never reads the device).  0 <= lambda < +inf.
+ *
+ * RV_MOSAIC_PATH_BACKTRACK: after the forward pass over all T rows: slot [T] int32 (from end[T-1] backwards through
+ * back; end[t-1] where row t started a sequence or has no candidate; -1 for a row without candidates),
+ * choice [T] int32 = idx[t, slot[t]] (-1 likewise) and cost [2] fp64 = sum_t dist[t, slot[t]] and the sum of the
+ * transition costs met along the path (without lambda), both added in ascending t from +0.
+ *
+ * RV_MOSAIC_PATH_WORKSPACE: stores the bytes of ws the two PATH ops need for (T, k) in d->ws_bytes; launches nothing. */
 #define RV_MOSAIC_KNN 0
 #define RV_MOSAIC_KNN_WORKSPACE 1
 #define RV_MOSAIC_GATHER_MEAN 2
 #define RV_MOSAIC_OLA 3
+#define RV_MOSAIC_TRANSITION 4
+#define RV_MOSAIC_PATH_FORWARD 5
+#define RV_MOSAIC_PATH_BACKTRACK 6
+#define RV_MOSAIC_PATH_WORKSPACE 7
 typedef struct rv_mosaic_desc {
   long T, k;                     /* query / output rows, neighbours per row (KNN, GATHER_MEAN) */
   int* idx;                      /* [T, k]: KNN output, GATHER_MEAN input */
@@ -431,6 +460,13 @@ typedef struct rv_mosaic_desc {
   long F, S, hop;
   const float* window;
   long n_out;
+  const int* next_of;            /* TRANSITION [N] */
+  long row0, rows;               /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T */
+  float* trans;                  /* [rows, k, k]: TRANSITION output, PATH_FORWARD input */
+  float lam;                     /* PATH_FORWARD: lambda, the weight of the transition costs */
+  int* slot;                     /* PATH_BACKTRACK [T] */
+  int* choice;                   /* PATH_BACKTRACK [T] */
+  double* cost;                  /* PATH_BACKTRACK [2] */
 } rv_mosaic_desc;
 int rv_mosaic(int op, rv_mosaic_desc* d, void* stream);
 

@@ -7,7 +7,10 @@ nearest corpus frames in the model's latent space, and the result is overlap-add
   --k N              neighbours per target frame, 1..16 (default 1)
   --mode grains      the mean of the neighbours' audio; `decode`: the decoded mean of their mu
   --window hann|none overlap-add window (default none: rectangular; hann needs hop <= segment_length / 2)
-  --matches FILE     one CSV line per target frame: the k (file, sample offset, distance) triples
+  --continuity X     weight (float >= 0, default 0) of the concatenation cost: with X > 0 one of the k candidates per
+                     frame is chosen by a Viterbi search that prefers corpus frames which follow each other
+  --matches FILE     one CSV line per target frame: the k (file, sample offset, distance) triples; with --continuity
+                     a last column holds the chosen slot (0-based, -1: none)
   --max-rows N       target frames per encoder / search / decoder chunk (the output does not depend on it)
 
 The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
@@ -27,6 +30,17 @@ import interpolate as _interp  # noqa: E402  (read_model_config, load_model)
 from som import _int_flag, load_wav  # noqa: E402
 
 
+def _weight_flag(name, value):
+    """A finite float >= 0; ValueError naming the flag otherwise."""
+    try:
+        v = float(value)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0 <= v < float("inf"):
+        raise ValueError("--%s %r: expected a finite number >= 0" % (name, value))
+    return v
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Latent audio mosaicing: resynthesise a target from a corpus's frames")
     p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
@@ -38,12 +52,14 @@ def parse_args(argv=None):
     p.add_argument("--k", default="1", help="neighbours per target frame (1..16)")
     p.add_argument("--mode", default="grains", help="grains | decode")
     p.add_argument("--window", default="none", help="none | hann")
+    p.add_argument("--continuity", default="0", help="weight >= 0 of the concatenation cost (0: off)")
     p.add_argument("--matches", default=None, help="CSV of the k (file, offset, distance) triples per target frame")
     p.add_argument("--max-rows", default="16384", help="target frames per chunk")
     args = p.parse_args(argv)
     args.k = _int_flag("k", args.k, 1)
     if args.k > 16:
         raise ValueError("--k %d: at most 16" % args.k)
+    args.continuity = _weight_flag("continuity", args.continuity)
     args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
     args.max_rows = _int_flag("max-rows", args.max_rows, 1)
     if args.mode not in ("grains", "decode"):
@@ -78,14 +94,16 @@ def corpus_files(corpus_dir):
     return files
 
 
-def write_matches(path, names_offsets, dist):
-    """One line per target frame: file_1, offset_1, distance_1, ..., file_k, offset_k, distance_k."""
+def write_matches(path, names_offsets, dist, slot=None):
+    """One line per target frame: file_1, offset_1, distance_1, ..., file_k, offset_k, distance_k[, chosen slot]."""
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
-        for row, drow in zip(names_offsets, dist):
+        for t, (row, drow) in enumerate(zip(names_offsets, dist)):
             line = []
             for (name, off), d in zip(row, drow):
                 line += [name if name is not None else "", off, repr(float(d))]
+            if slot is not None:
+                line.append(int(slot[t]))
             wr.writerow(line)
 
 
@@ -115,14 +133,31 @@ def main(argv=None):
     index = LatentIndex(model, hop=framing, max_rows=args.max_rows)
     for f, w in zip(files, waves):
         index.add(w, f)
-    y, idx, dist = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True)
+    y, idx, dist, path = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True,
+                                      continuity=args.continuity, return_path=True)
     y = y.cpu().numpy()
     D.write_wav(args.out, y, sr)
+    slot = None if path is None else path[0].cpu().numpy()
     if args.matches:
-        write_matches(args.matches, index.locate(idx), dist.cpu().numpy())
-    print("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s"
-          % (args.out, y.size, idx.shape[0], len(index), len(files), args.k, args.mode, args.window or "none"))
+        write_matches(args.matches, index.locate(idx), dist.cpu().numpy(), slot)
+    line = ("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s"
+            % (args.out, y.size, idx.shape[0], len(index), len(files), args.k, args.mode, args.window or "none"))
+    if path is not None:
+        choice, cost = path[1].cpu().numpy(), path[2].cpu().numpy()
+        line += (", continuity %g, continuing %.4f, target cost %.6g, transition cost %.6g"
+                 % (args.continuity, continuing_share(choice, index.successor()), cost[0], cost[1]))
+    print(line)
     return y
+
+
+def continuing_share(choice, next_of):
+    """The share of frames t >= 1 whose corpus frame is the successor of frame t - 1's (1.0 for a single frame)."""
+    if len(choice) < 2:
+        return 1.0
+    prev, cur = choice[:-1], choice[1:]
+    ok = (prev >= 0) & (cur >= 0)
+    hit = ok & (cur == next_of[prev.clip(min=0)])
+    return float(hit.sum()) / (len(choice) - 1)
 
 
 if __name__ == "__main__":

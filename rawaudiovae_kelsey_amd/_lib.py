@@ -48,7 +48,9 @@ class MosaicDesc(C.Structure):
                 ("L", c_long), ("splits", c_long), ("dist", c_void_p), ("ws", c_void_p), ("ws_bytes", c_long),
                 ("src", c_void_p), ("src_len", c_long), ("row_start", c_void_p), ("stride", c_long), ("n_rows", c_long),
                 ("width", c_long), ("out", c_void_p), ("ldo", c_long), ("frames", c_void_p), ("F", c_long),
-                ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long)]
+                ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long), ("next_of", c_void_p),
+                ("row0", c_long), ("rows", c_long), ("trans", c_void_p), ("lam", c_float), ("slot", c_void_p),
+                ("choice", c_void_p), ("cost", c_void_p)]
 
 
 class CommDesc(C.Structure):
@@ -74,6 +76,7 @@ PHASE_ANY_ADAM = PHASE_ADAM | PHASE_ADAM_A | PHASE_ADAM_B | PHASE_ADAM_FC4 | PHA
 PHASE_ALL_LOCAL = PHASE_FWD | PHASE_BWD_A | PHASE_BWD_B | PHASE_ADAM
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2   # ACT_TANH: rv_linear_fp32 only
 MOSAIC_KNN, MOSAIC_KNN_WORKSPACE, MOSAIC_GATHER_MEAN, MOSAIC_OLA = 0, 1, 2, 3   # RV_MOSAIC_* (rv_mosaic)
+MOSAIC_TRANSITION, MOSAIC_PATH_FORWARD, MOSAIC_PATH_BACKTRACK, MOSAIC_PATH_WORKSPACE = 4, 5, 6, 7
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

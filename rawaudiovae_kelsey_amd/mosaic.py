@@ -13,6 +13,13 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
       "decode": the mean of their mu decoded through fc3 and fc4 + tanh (rv_linear_fp32);
       then an offline weighted overlap-add (RV_MOSAIC_OLA) with stream.py's window and normaliser rules.  The output
       has the target's length.
+  index.mosaic(..., continuity=w)         w > 0: unit selection.  The k candidates are searched as above, then one per
+                                          frame is chosen by a Viterbi search (best_path) that minimises
+                                          sum_t dist[t, p_t] + w * sum_t trans[t, p_{t-1}, p_t], where trans is the
+                                          distance between the corpus frame that FOLLOWS the previous choice
+                                          (index.successor) and this candidate: 0 when the corpus simply plays on.
+                                          Grains / decode then run on the one chosen frame.  w = 0 is the call above.
+  transition_costs, best_path             the two steps on their own (RV_MOSAIC_TRANSITION, RV_MOSAIC_PATH_*)
 
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
@@ -32,7 +39,8 @@ K_MAX = 16
 
 def _call(op, **fields):
     d = MosaicDesc(**fields)
-    lib().rv_mosaic(op, _lib.C.byref(d), None if op == _lib.MOSAIC_KNN_WORKSPACE else stream_ptr())
+    host_only = op in (_lib.MOSAIC_KNN_WORKSPACE, _lib.MOSAIC_PATH_WORKSPACE)
+    lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else stream_ptr())
     return d
 
 
@@ -65,6 +73,99 @@ def knn_topk(q, c, k, splits=0):
     _call(_lib.MOSAIC_KNN, T=T, N=N, L=L, k=k, splits=int(splits), q=ptr(q), c=ptr(c), idx=ptr(idx), dist=ptr(dist),
           ws=ptr(ws), ws_bytes=nbytes)
     return idx, dist
+
+
+def path_workspace_bytes(T, k):
+    """Bytes of device workspace best_path's forward and backtrack steps share for T rows of k candidates."""
+    return _call(_lib.MOSAIC_PATH_WORKSPACE, T=int(T), k=int(k)).ws_bytes
+
+
+def successor_table(file_of, adv=1):
+    """next_of [N] int32 for corpus frames laid out file by file (frame_tables' file_of): i + adv when that frame exists
+    and lies in the same file, else i (a file's last frames continue as themselves).  adv = target step / index step;
+    ValueError naming `hop` unless it is a positive integer."""
+    a = float(adv)
+    if not (a >= 1 and a == int(a)):
+        raise ValueError("hop: the target's frame step must be a positive integer multiple of the index's "
+                         "(target step / index step = %r)" % (adv,))
+    a = int(a)
+    file_of = np.asarray(file_of)
+    N = file_of.size
+    i = np.arange(N, dtype=np.int64)
+    nxt = i + a
+    same = nxt < N
+    same[same] = file_of[nxt[same]] == file_of[i[same]]
+    return np.where(same, nxt, i).astype(np.int32)
+
+
+def _candidates(idx, dist):
+    if (not torch.is_tensor(idx) or idx.dim() != 2 or idx.dtype != torch.int32 or idx.device.type != "cuda"
+            or idx.shape[0] < 1 or not 1 <= idx.shape[1] <= K_MAX):
+        raise ValueError("idx must be a [T, k] int32 device tensor with T >= 1 and 1 <= k <= %d" % K_MAX)
+    if dist is not None and (not torch.is_tensor(dist) or dist.dtype != torch.float32 or dist.shape != idx.shape
+                             or dist.device != idx.device):
+        raise ValueError("dist must be a float32 device tensor of idx's shape %s" % (tuple(idx.shape),))
+    return idx.contiguous(), None if dist is None else dist.contiguous()
+
+
+def _successors(next_of, N, device):
+    if not torch.is_tensor(next_of):
+        next_of = torch.from_numpy(np.ascontiguousarray(next_of, dtype=np.int32))
+    next_of = next_of.to(device=device, dtype=torch.int32).contiguous()
+    if next_of.dim() != 1 or next_of.numel() != N:
+        raise ValueError("next_of must hold one successor for each of the %d corpus rows" % N)
+    return next_of
+
+
+def transition_costs(mu, idx, next_of, row0=0, rows=None, out=None):
+    """trans [rows, k, k] fp32 for rows [row0, row0 + rows) of the candidates idx [T, k] (the whole table: row row0
+    needs row row0 - 1): trans[t - row0, i, j] = the search's distance between mu[next_of[idx[t-1, i]]] and
+    mu[idx[t, j]]; +inf where a candidate is -1 or the value is NaN; row 0 is all 0."""
+    mu = _rows(mu, "mu")
+    idx, _ = _candidates(idx, None)
+    N, L = mu.shape
+    next_of = _successors(next_of, N, mu.device)
+    T, k = idx.shape
+    row0 = int(row0)
+    rows = T - row0 if rows is None else int(rows)
+    if not (0 <= row0 and 1 <= rows <= T - row0):
+        raise ValueError("rows [%d, %d + %d) outside the %d rows of idx" % (row0, row0, rows, T))
+    if out is None:
+        out = torch.empty((rows, k, k), dtype=torch.float32, device=mu.device)
+    _call(_lib.MOSAIC_TRANSITION, T=T, k=k, idx=ptr(idx), c=ptr(mu), N=N, L=L, next_of=ptr(next_of), row0=row0,
+          rows=rows, trans=ptr(out))
+    return out
+
+
+def best_path(idx, dist, mu, next_of, weight, max_rows=4096):
+    """Viterbi unit selection over the candidates (idx, dist) [T, k] of knn_topk -> (slot [T] int32, choice [T] int32,
+    cost [2] fp64), device tensors: the path p that minimises sum_t dist[t, p_t] + weight * sum_t trans[t, p_{t-1}, p_t]
+    (transition_costs) under the forward rule of include/rawvae_hip.h; choice[t] = idx[t, slot[t]], both -1 for a row
+    without candidates; cost = the two sums along the path.  The forward pass runs in chunks of max_rows rows, each
+    over its own chunk of trans, carrying the scores on the device; the result does not depend on max_rows."""
+    idx, dist = _candidates(idx, dist)
+    mu = _rows(mu, "mu")
+    weight, max_rows = float(weight), int(max_rows)
+    if not 0 <= weight < float("inf"):
+        raise ValueError("weight=%r must be a finite number >= 0" % (weight,))
+    if max_rows < 1:
+        raise ValueError("max_rows=%d must be at least 1" % max_rows)
+    T, k = idx.shape
+    next_of = _successors(next_of, mu.shape[0], mu.device)
+    nbytes = path_workspace_bytes(T, k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=idx.device)
+    trans = torch.empty((min(max_rows, T), k, k), dtype=torch.float32, device=idx.device)
+    for r0 in range(0, T, max_rows):
+        rows = min(max_rows, T - r0)
+        transition_costs(mu, idx, next_of, r0, rows, out=trans)
+        _call(_lib.MOSAIC_PATH_FORWARD, T=T, k=k, idx=ptr(idx), dist=ptr(dist), row0=r0, rows=rows, trans=ptr(trans),
+              lam=weight, ws=ptr(ws), ws_bytes=nbytes)
+    slot = torch.empty(T, dtype=torch.int32, device=idx.device)
+    choice = torch.empty(T, dtype=torch.int32, device=idx.device)
+    cost = torch.empty(2, dtype=torch.float64, device=idx.device)
+    _call(_lib.MOSAIC_PATH_BACKTRACK, T=T, k=k, idx=ptr(idx), dist=ptr(dist), ws=ptr(ws), ws_bytes=nbytes,
+          slot=ptr(slot), choice=ptr(choice), cost=ptr(cost))
+    return slot, choice, cost
 
 
 def gather_mean(src, idx, width, row_start=None, stride=None, n_rows=None, out=None, ldo=None):
@@ -202,6 +303,18 @@ class LatentIndex:
     def offset_of(self):
         return self._tables()["offset_of"]
 
+    def successor(self, adv=1):
+        """next_of [N] int32 (numpy, cached): the corpus frame `adv` index steps after frame i in the same file, or i
+        itself at a file's end (successor_table)."""
+        return self._successor(adv)[0]
+
+    def _successor(self, adv):
+        cache = self._tables().setdefault("next_of", {})
+        if adv not in cache:
+            host = successor_table(self.file_of, adv)
+            cache[adv] = (host, torch.from_numpy(host).to(self.device))
+        return cache[adv]
+
     @torch.no_grad()
     def search(self, mu, k, splits=0):
         """(idx [T, k] int32, dist [T, k] fp32) of the k nearest corpus frames of each row of mu [T, L]."""
@@ -224,9 +337,15 @@ class LatentIndex:
         return [self.locate(r) if a.ndim > 1 else one(r) for r in a]
 
     @torch.no_grad()
-    def mosaic(self, target, k=1, hop=None, mode="grains", window=None, return_matches=False):
+    def mosaic(self, target, k=1, hop=None, mode="grains", window=None, return_matches=False, continuity=0.0,
+               return_path=False):
         """The target resynthesised from the corpus (see the module doc) -> 1-D fp32 device tensor of the target's
-        length; with return_matches also (idx [T, k], dist [T, k]).  hop=None: the index's framing."""
+        length; with return_matches also (idx [T, k], dist [T, k]).  hop=None: the index's framing.
+        continuity > 0 chooses one of the k candidates per frame by best_path with that weight; return_path then
+        appends (slot, choice, cost) to the result (None at continuity 0, where no path is searched)."""
+        continuity = float(continuity)
+        if not 0 <= continuity < float("inf"):
+            raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
         if mode not in MODES:
             raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
         k = int(k)
@@ -236,6 +355,8 @@ class LatentIndex:
         hop = self.hop if hop is None else int(hop)
         step = self.S if hop is None else hop
         check_window(self.S, step, window)
+        if continuity > 0:
+            next_of = self._successor(step / self.step)[1]   # ValueError naming hop unless a whole number of steps
         w = self._enc._wave(target)
         n = w.numel()
         padded, T = self._enc._padded(w, n, hop)
@@ -248,16 +369,32 @@ class LatentIndex:
         if mode == "decode":
             z = torch.empty((cap, self.L), dtype=torch.float32, device=self.device)
             h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
-        for r0 in range(0, T, self.max_rows):
-            rows = min(self.max_rows, T - r0)
-            i, d = knn_topk(mu[r0:r0 + rows], t["mu"], k)
-            idx[r0:r0 + rows], dist[r0:r0 + rows] = i, d
+
+        def synth(i, r0, rows):
+            """frames[r0:r0 + rows] from the corpus frames i [rows, any k]: their mean audio, or their mean mu decoded"""
             if mode == "grains":
                 gather_mean(t["audio"], i, self.S, row_start=t["row_start"], out=frames[r0:r0 + rows])
             else:
                 gather_mean(t["mu"], i, self.L, stride=self.L, n_rows=N, out=z[:rows])
                 self._enc._linear(ptr(z), self.L, rows, "fc3", ACT_RELU, ptr(h), self.H)
                 self._enc._linear(ptr(h), self.H, rows, "fc4", ACT_TANH, frames.data_ptr() + 4 * r0 * self.S, self.S)
+
+        for r0 in range(0, T, self.max_rows):
+            rows = min(self.max_rows, T - r0)
+            i, d = knn_topk(mu[r0:r0 + rows], t["mu"], k)
+            idx[r0:r0 + rows], dist[r0:r0 + rows] = i, d
+            if continuity == 0:
+                synth(i, r0, rows)
+        path = None
+        if continuity > 0:
+            path = best_path(idx, dist, t["mu"], next_of, continuity, max_rows=self.max_rows)
+            one = path[1].view(T, 1)   # the chosen corpus frame: a gather-mean of one is that frame, bit for bit
+            for r0 in range(0, T, self.max_rows):
+                rows = min(self.max_rows, T - r0)
+                synth(one[r0:r0 + rows], r0, rows)
         win = None if window is None else torch.from_numpy(window_values(self.S, window)).to(self.device)
         out = ola(frames, step, n, win)
-        return (out, idx, dist) if return_matches else out
+        res = (out, idx, dist) if return_matches else (out,)
+        if return_path:
+            res += (path,)
+        return res if len(res) > 1 else out

@@ -1,0 +1,266 @@
+"""Continuity-aware mosaicing on the GPU (RV_MOSAIC_TRANSITION / RV_MOSAIC_PATH_* in csrc/mosaic.hip,
+rawaudiovae_kelsey_amd/mosaic.py, mosaic.py) against the numpy statement in tests/mosaic_path_oracle.py."""
+import csv
+import os
+import re
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from conftest import REPO  # noqa: E402
+import mosaic_oracle as O  # noqa: E402
+import mosaic_path_oracle as P  # noqa: E402
+
+SHAPES = [(1, 50, 8, 1), (300, 5000, 64, 4), (1000, 1000, 100, 16), (4097, 70001, 256, 16)]
+_CASES = {}
+
+
+def _M():
+    from rawaudiovae_kelsey_amd import mosaic
+    return mosaic
+
+
+def _dev(a, dtype=np.float32):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+def _case(T, N, L, k):
+    """Candidates from the device's own search over random latents, then rows with -1 candidates, a closed row, a NaN
+    corpus row among the candidates, candidates that follow each other, and the oracle's transitions (cached)."""
+    key = (T, N, L, k)
+    if key not in _CASES:
+        rng = np.random.default_rng(T + N + k)
+        mu = rng.standard_normal((N, L)).astype(np.float32)
+        q = rng.standard_normal((T, L)).astype(np.float32)
+        idx, dist = _M().knn_topk(_dev(q), _dev(mu), k)
+        idx, dist = idx.cpu().numpy(), dist.cpu().numpy()
+        file_of = np.repeat(np.arange(7), -(-N // 7))[:N]
+        next_of = _M().successor_table(file_of)
+        if T > 1:
+            for t in rng.choice(np.arange(1, T), min(T - 1, max(1, T // 3)), replace=False):
+                i, j = rng.integers(0, k, 2)                 # candidate j of row t continues candidate i of row t - 1
+                if next_of[idx[t - 1, i]] not in idx[t]:
+                    idx[t, j] = next_of[idx[t - 1, i]]
+        if T >= 300:
+            idx[T // 2], dist[T // 2] = -1, np.inf            # a closed row
+            idx[5, k - 1], dist[5, k - 1] = -1, np.inf        # short rows
+            idx[T - 2, k // 2:], dist[T - 2, k // 2:] = -1, np.inf
+            mu[idx[9, 0]] = np.nan                            # a NaN corpus row that is a candidate ...
+            mu[next_of[idx[20, 0]]] = np.nan                  # ... and one that is a candidate's successor
+        _CASES[key] = dict(mu=mu, idx=idx.astype(np.int32), dist=dist, next_of=next_of,
+                           tr=P.transitions(mu, idx, next_of))
+    return _CASES[key]
+
+
+@pytest.mark.parametrize("T,N,L,k", SHAPES)
+def test_transition_matches_the_oracle_bit_for_bit_for_any_chunking(T, N, L, k):
+    M, c = _M(), _case(T, N, L, k)
+    mu, idx = _dev(c["mu"]), _dev(c["idx"], np.int32)
+    got = M.transition_costs(mu, idx, c["next_of"]).cpu().numpy()
+    assert got.shape == (T, k, k)
+    bad = np.argwhere(_bits(got) != _bits(c["tr"]))
+    print("transition %s: %d of %d values differ" % ((T, N, L, k), len(bad), got.size))
+    assert len(bad) == 0, (bad[:5], got[tuple(bad[0])], c["tr"][tuple(bad[0])])
+    if T > 1:
+        assert np.all(got[0] == 0) and (got[1:] == 0).sum() >= 1      # a candidate that plays on costs exactly 0
+    for step in (1, 7, 4096):
+        if step < T or step == 1:
+            parts = [M.transition_costs(mu, idx, c["next_of"], r0, min(step, T - r0)) for r0 in range(0, T, step)]
+            assert np.array_equal(_bits(torch.cat(parts).cpu().numpy()), _bits(got)), step
+
+
+def test_transition_takes_unaligned_latent_rows():
+    M = _M()
+    rng = np.random.default_rng(12)
+    mu = rng.standard_normal((200, 37)).astype(np.float32)            # rows of 148 bytes: no 16-byte loads
+    idx = rng.integers(-1, 200, (90, 5)).astype(np.int32)
+    next_of = M.successor_table(np.repeat(np.arange(4), 50))
+    got = M.transition_costs(_dev(mu), _dev(idx, np.int32), next_of).cpu().numpy()
+    assert np.array_equal(_bits(got), _bits(P.transitions(mu, idx, next_of)))
+
+
+@pytest.mark.parametrize("T,N,L,k", SHAPES)
+def test_best_path_matches_the_oracle_exactly(T, N, L, k):
+    M, c = _M(), _case(T, N, L, k)
+    mu, idx, dist = _dev(c["mu"]), _dev(c["idx"], np.int32), _dev(c["dist"])
+    # 0.3: fl(lambda * trans) is inexact, so a product fused into the add would show (the others are powers of two)
+    for lam in (0.0, 0.5, 4.0, 0.3):
+        rs, rc, rcost = P.best_path(c["idx"], c["dist"], c["mu"], c["next_of"], lam, tr=c["tr"])
+        for max_rows in (1, 7, 4096, T):
+            slot, choice, cost = [x.cpu().numpy() for x in M.best_path(idx, dist, mu, c["next_of"], lam, max_rows)]
+            print("path %s lambda %g max_rows %d: %d slots differ, cost %r against %r"
+                  % ((T, N, L, k), lam, max_rows, int((slot != rs).sum()), cost.tolist(), rcost.tolist()))
+            assert np.array_equal(slot, rs), np.argwhere(slot != rs)[:5]
+            assert np.array_equal(choice, rc)
+            assert cost.dtype == np.float64 and np.array_equal(cost, rcost)
+        closed = (c["idx"] < 0).all(1)
+        assert np.array_equal(rs < 0, closed)
+        if lam == 0:
+            # every finite transition is free: slot 0 wherever no infinite transition (a NaN corpus row) between
+            # present candidates touches the row, which stays infinite at lambda = 0 by the contract
+            have = c["idx"] >= 0
+            pairs = np.ones((T, k, k), bool)
+            pairs[1:] = have[:-1, :, None] & have[1:, None, :]
+            clean = (np.isfinite(c["tr"]) | ~pairs).all((1, 2))
+            clean &= np.append(clean[1:], True)
+            assert clean.sum() >= T // 2 and np.all(rs[~closed & clean] == 0)
+
+
+def test_two_file_construction_on_the_device():
+    M = _M()
+    F = 40
+    mu, q, next_of = P.two_file_case(F)
+    idx, dist = M.knn_topk(_dev(q), _dev(mu), 2)
+    ri, rd = O.knn(q, mu, 2)
+    assert np.array_equal(idx.cpu().numpy(), ri) and np.array_equal(dist.cpu().numpy(), rd)
+    for lam, jumps in ((0.0, 39), (1 / 32, 39), (1.0, 0)):
+        slot, choice, cost = [x.cpu().numpy() for x in M.best_path(idx, dist, _dev(mu), next_of, lam)]
+        assert int((choice[1:] != next_of[choice[:-1]]).sum()) == jumps, lam
+        assert cost[1] == jumps and cost[0] == (F * 9 / 64 if jumps else F // 2 * 34 / 64)
+        rs, rc, rcost = P.best_path(ri, rd, mu, next_of, lam)
+        assert np.array_equal(slot, rs) and np.array_equal(choice, rc) and np.array_equal(cost, rcost)
+
+
+def test_path_rejects_bad_arguments():
+    M = _M()
+    from rawaudiovae_kelsey_amd import _lib
+    mu = _dev(np.zeros((10, 8)))
+    idx = torch.zeros((4, 2), dtype=torch.int32, device="cuda")
+    dist = torch.zeros((4, 2), device="cuda")
+    nxt = np.arange(10, dtype=np.int32)
+    for w in (-1.0, float("nan"), float("inf")):
+        with pytest.raises(ValueError, match="weight"):
+            M.best_path(idx, dist, mu, nxt, w)
+    with pytest.raises(ValueError, match="rows"):
+        M.transition_costs(mu, idx, nxt, 3, 2)
+    with pytest.raises(ValueError, match="next_of"):
+        M.transition_costs(mu, idx, nxt[:5])
+    n = M.path_workspace_bytes(4, 2)
+    ws = torch.empty(n, dtype=torch.uint8, device="cuda")
+    tr = torch.zeros((4, 2, 2), device="cuda")
+    ok = dict(T=4, k=2, idx=idx.data_ptr(), dist=dist.data_ptr(), trans=tr.data_ptr(), ws=ws.data_ptr(), ws_bytes=n,
+              row0=0, rows=4, lam=1.0)
+    M._call(_lib.MOSAIC_PATH_FORWARD, **ok)
+    for bad in (dict(lam=-1.0), dict(lam=float("nan")), dict(row0=2, rows=3), dict(rows=0), dict(k=17),
+                dict(ws_bytes=n - 16), dict(trans=None)):
+        with pytest.raises(_lib.RvError):
+            M._call(_lib.MOSAIC_PATH_FORWARD, **dict(ok, **bad))
+    with pytest.raises(_lib.RvError):
+        M._call(_lib.MOSAIC_TRANSITION, T=4, k=2, idx=idx.data_ptr(), c=mu.data_ptr(), N=10, L=8,
+                next_of=_dev(nxt, np.int32).data_ptr(), row0=1, rows=4, trans=tr.data_ptr())
+    torch.cuda.synchronize()
+
+
+def _model(S=64, H=96, L=8, seed=0):
+    from rawvae.model import VAE
+    torch.manual_seed(seed)
+    return VAE(S, H, L).cuda().eval()
+
+
+def _index(M, m, waves, hop, max_rows=16384):
+    index = M.LatentIndex(m, hop=hop, max_rows=max_rows)
+    for i, w in enumerate(waves):
+        index.add(w, "f%d" % i)
+    return index
+
+
+def test_continuity_zero_is_the_plain_mosaic_bit_for_bit():
+    M = _M()
+    rng = np.random.default_rng(21)
+    waves = [(0.4 * rng.standard_normal(n)).astype(np.float32) for n in (900, 333, 1500)]
+    target = (0.4 * rng.standard_normal(1111)).astype(np.float32)
+    index = _index(M, _model(seed=2), waves, 16)
+    for k in (1, 4):
+        for mode in ("grains", "decode"):
+            ref = index.mosaic(target, k=k, mode=mode, window="hann", return_matches=True)
+            got = index.mosaic(target, k=k, mode=mode, window="hann", return_matches=True, continuity=0)
+            assert len(got) == 3 and all(torch.equal(a, b) for a, b in zip(ref, got))
+            assert torch.equal(index.mosaic(target, k=k, mode=mode, window="hann", continuity=0.0), ref[0])
+            assert index.mosaic(target, k=k, mode=mode, window="hann", continuity=0.0, return_path=True)[1] is None
+    for bad in (-1, float("nan")):
+        with pytest.raises(ValueError, match="continuity"):
+            index.mosaic(target, k=2, continuity=bad)
+
+
+def test_identity_the_target_is_an_excerpt_of_a_corpus_file():
+    """The corpus holds X (seeded noise: no two frames are equal), X + 1e-3 noise and another file; the target is a
+    frame-aligned excerpt of X.  The excerpt's own frames are a path with J = 0 (distances and transitions exactly
+    0) and every other path has J > 0."""
+    M = _M()
+    m = _model(seed=1)
+    rng = np.random.default_rng(22)
+    S, hop = 64, 32
+    x = (0.5 * rng.standard_normal(2700)).astype(np.float32)
+    waves = [(0.5 * rng.standard_normal(700)).astype(np.float32), x,
+             (x + 1e-3 * rng.standard_normal(x.size)).astype(np.float32)]
+    f0, nf = 11, 61                                                   # frames f0 .. f0 + nf - 1 of X
+    target = x[f0 * hop:(f0 + nf - 1) * hop + S]
+    outs = {}
+    for max_rows in (16384, 7):
+        index = _index(M, m, waves, hop, max_rows)
+        outs[max_rows] = index.mosaic(target, k=4, window=None, return_matches=True, continuity=1.0, return_path=True)
+    y, idx, dist, (slot, choice, cost) = outs[16384]
+    first = int(np.flatnonzero(index.file_of == 1)[0])
+    choice_h = choice.cpu().numpy()
+    assert np.array_equal(choice_h, first + f0 + np.arange(nf))
+    assert np.array_equal(cost.cpu().numpy(), [0.0, 0.0])
+    assert np.array_equal(choice_h[1:], index.successor()[choice_h[:-1]])   # the share of continuing frames is 1.0
+    assert np.array_equal(idx.cpu().numpy()[np.arange(nf), slot.cpu().numpy()], choice_h)
+    # whole frames of X cover every sample once or twice: a / 1 and (a + a) / 2 are exact
+    assert np.array_equal(y.cpu().numpy(), target)
+    y7, idx7, dist7, path7 = outs[7]
+    assert torch.equal(y7, y) and torch.equal(idx7, idx) and torch.equal(dist7, dist)
+    assert all(torch.equal(a, b) for a, b in zip(path7, (slot, choice, cost)))
+    # decode mode runs on the chosen frame's mu; a coarser target framing advances two index frames per step
+    yd = index.mosaic(target, k=4, mode="decode", continuity=1.0)
+    assert yd.shape == y.shape and bool(torch.isfinite(yd).all())
+    y2, (slot2, choice2, cost2) = index.mosaic(target, k=4, hop=64, continuity=1.0, return_path=True)
+    assert np.array_equal(choice2.cpu().numpy(), first + f0 + 2 * np.arange(31))
+    assert np.array_equal(cost2.cpu().numpy(), [0.0, 0.0]) and np.array_equal(y2.cpu().numpy(), target)
+    index64 = _index(M, m, waves, 64)
+    with pytest.raises(ValueError, match="hop"):
+        index64.mosaic(target, k=2, hop=32, continuity=1.0)           # half an index step per target step
+
+
+def test_cli_writes_the_slot_column_and_the_summary_fields(tmp_path):
+    from rawvae.model import VAE
+    from rawaudiovae_kelsey_amd import data as D
+    S_, H, L, sr, hop = 64, 128, 8, 8000, 16
+    torch.manual_seed(3)
+    torch.save({"epoch": 1, "state_dict": VAE(S_, H, L).state_dict(), "optimizer": {}}, tmp_path / "ckpt_00001")
+    (tmp_path / "tiny.ini").write_text("[audio]\nsampling_rate = %d\nhop_length = 8\nsegment_length = %d\n"
+                                       "[VAE]\nlatent_dim = %d\nn_units = %d\n" % (sr, S_, L, H))
+    corpus = tmp_path / "corpus"
+    corpus.mkdir()
+    rng = np.random.default_rng(4)
+    x = (0.3 * rng.standard_normal(1600)).astype(np.float32)
+    D.write_wav(corpus / "c0.wav", (0.3 * rng.standard_normal(777)).astype(np.float32), sr)
+    D.write_wav(corpus / "c1.wav", x, sr)
+    x_read, _ = D.read_wav(corpus / "c1.wav")                         # the corpus as the index will see it
+    D.write_wav(tmp_path / "t.wav", x_read[5 * hop:5 * hop + 30 * hop + S_], sr)
+    run = [sys.executable, os.path.join(REPO, "mosaic.py"), "--config", str(tmp_path / "tiny.ini"), "--checkpoint",
+           str(tmp_path / "ckpt_00001"), "--corpus", str(corpus), "--target", str(tmp_path / "t.wav"), "--out",
+           str(tmp_path / "out.wav"), "--hop", str(hop), "--k", "3", "--matches", str(tmp_path / "m.csv")]
+    plain = subprocess.run(run, check=True, timeout=300, cwd=str(tmp_path), capture_output=True, text=True)
+    assert "continuity" not in plain.stdout and all(len(r) == 9 for r in csv.reader(open(tmp_path / "m.csv")))
+    r = subprocess.run(run + ["--continuity", "1"], check=True, timeout=300, cwd=str(tmp_path), capture_output=True,
+                       text=True)
+    y, got_sr = D.read_wav(tmp_path / "out.wav")
+    assert got_sr == sr and y.size == 30 * hop + S_ and np.all(np.isfinite(y))
+    rows = list(csv.reader(open(tmp_path / "m.csv")))
+    assert len(rows) == 31 and all(len(row) == 10 for row in rows)
+    for t, row in enumerate(rows):
+        s = int(row[9])
+        assert 0 <= s < 3 and row[3 * s] == "c1.wav" and int(row[3 * s + 1]) == (5 + t) * hop
+    m = re.search(r"continuity 1, continuing ([0-9.]+), target cost (\S+), transition cost (\S+)", r.stdout)
+    assert m and float(m.group(1)) == 1.0 and float(m.group(2).rstrip(",")) == 0.0 and float(m.group(3)) == 0.0
+    assert r.stdout.startswith(plain.stdout.rstrip("\n"))             # the plain summary line, then the new fields
