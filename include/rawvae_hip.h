@@ -432,7 +432,30 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  * choice [T] int32 = idx[t, slot[t]] (-1 likewise) and cost [2] fp64 = sum_t dist[t, slot[t]] and the sum of the
  * transition costs met along the path (without lambda), both added in ascending t from +0.
  *
- * RV_MOSAIC_PATH_WORKSPACE: stores the bytes of ws the two PATH ops need for (T, k) in d->ws_bytes; launches nothing. */
+ * RV_MOSAIC_PATH_WORKSPACE: stores the bytes of ws the two PATH ops need for (T, k) in d->ws_bytes; launches nothing.
+ *
+ * RV_MOSAIC_KNN_SMALL: RV_MOSAIC_KNN's contract and results, bit for bit, by a kernel built for few query rows
+ * (1 <= T <= 64; more is RV_ERR_SHAPE): the corpus is read once per 16 query rows, one thread per corpus row
+ * (DESIGN.md section 7.6).  RV_MOSAIC_KNN_SMALL_WORKSPACE: its ws_bytes for (T, N, L, k, splits); launches nothing.
+ *
+ * Live mosaicing: one block of samples per stream in, one block built from the nearest corpus frames out.
+ * RV_MOSAIC_LIVE enqueues, without a sync or a read of the device: rv_stream_process's fc1 and heads launches on
+ * *live (the query rows are mu * scale + offset; temperature, eps_in and seed are not read), the search of the
+ * n_streams * F query rows in c [N, L] (k, splits; KNN_SMALL's kernel up to its 64 rows, KNN's beyond: the same bits)
+ * into idx / dist [n_streams * F, k], the selection, the synthesis and rv_stream_process's overlap-add on live->y.
+ *   weight == NULL: every frame is the mean of its k candidates (GATHER_MEAN's arithmetic); choice is not written.
+ *   weight [n_streams] (device; a value that is not finite and >= 0 counts as 0): greedy unit selection, per stream and
+ *     frame in order.  prev = the stream's last chosen corpus frame (-1 after a reset, kept in ws).  prev < 0, or
+ *     next_of[prev] outside [0, N): the lowest j with idx[t, j] in [0, N).  Otherwise the argmin over those j of
+ *     dist[t, j] + fl(w * D(c[next_of[prev]], c[idx[t, j]])), D the search's distance, the product rounded before the
+ *     add, strict < in ascending j, a NaN cost skipped.  choice[t] = that idx[t, j] = the new prev; -1 when no j is
+ *     left.  The frame is the chosen corpus frame alone.  This is the lag-0 rule, not PATH_FORWARD's Viterbi search;
+ *     with k = 1 both choose the same frames.
+ *   mode RV_LIVE_GRAINS: frames from the corpus audio src [src_len] at row_start [N]; RV_LIVE_DECODE: the mean (or the
+ *     chosen row) of c through fc3 and fc4.
+ * RV_MOSAIC_LIVE_WORKSPACE: the bytes of ws (device; RV_MOSAIC_LIVE_RESET before the first block) for live's extents
+ * and (N, L, k, splits) in d->ws_bytes; launches nothing.  RV_MOSAIC_LIVE_RESET: rv_stream_reset(live, which) and
+ * prev = -1 for stream `which` (-1: every stream). */
 #define RV_MOSAIC_KNN 0
 #define RV_MOSAIC_KNN_WORKSPACE 1
 #define RV_MOSAIC_GATHER_MEAN 2
@@ -441,6 +464,14 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_MOSAIC_PATH_FORWARD 5
 #define RV_MOSAIC_PATH_BACKTRACK 6
 #define RV_MOSAIC_PATH_WORKSPACE 7
+#define RV_MOSAIC_KNN_SMALL 8
+#define RV_MOSAIC_KNN_SMALL_WORKSPACE 9
+#define RV_MOSAIC_LIVE 10
+#define RV_MOSAIC_LIVE_WORKSPACE 11
+#define RV_MOSAIC_LIVE_RESET 12
+#define RV_LIVE_GRAINS 0
+#define RV_LIVE_DECODE 1
+struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   long T, k;                     /* query / output rows, neighbours per row (KNN, GATHER_MEAN) */
   int* idx;                      /* [T, k]: KNN output, GATHER_MEAN input */
@@ -467,6 +498,10 @@ typedef struct rv_mosaic_desc {
   int* slot;                     /* PATH_BACKTRACK [T] */
   int* choice;                   /* PATH_BACKTRACK [T] */
   double* cost;                  /* PATH_BACKTRACK [2] */
+  const struct rv_stream_desc* live; /* LIVE ops: weights, block I/O, scale / offset, window, norm, stream workspace */
+  long mode;                     /* LIVE: RV_LIVE_GRAINS / RV_LIVE_DECODE */
+  const float* weight;           /* LIVE [n_streams] on the device, or NULL: the mean of the k candidates */
+  long which;                    /* LIVE_RESET: the stream, -1 for all */
 } rv_mosaic_desc;
 int rv_mosaic(int op, rv_mosaic_desc* d, void* stream);
 

@@ -12,6 +12,13 @@ nearest corpus frames in the model's latent space, and the result is overlap-add
   --matches FILE     one CSV line per target frame: the k (file, sample offset, distance) triples; with --continuity
                      a last column holds the chosen slot (0-based, -1: none)
   --max-rows N       target frames per encoder / search / decoder chunk (the output does not depend on it)
+  --live-block N     run the target through the live path instead (StreamingMosaic): blocks of N samples (a multiple of
+                     the hop), the tail zero-padded to a whole block; the output drops the S - hop samples of latency
+                     and is cut to the target's length, so it lines up with the offline result.  With --continuity X
+                     one candidate per frame is chosen by the greedy rule (against the previous choice only), not by
+                     the Viterbi search
+  --streams M        with --live-block: cut the target into M consecutive parts and run them as M parallel streams,
+                     each starting from silence (default 1)
 
 The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
 values, an empty corpus, unreadable wavs or a --k above the number of corpus frames raise ValueError naming the flag or
@@ -55,7 +62,13 @@ def parse_args(argv=None):
     p.add_argument("--continuity", default="0", help="weight >= 0 of the concatenation cost (0: off)")
     p.add_argument("--matches", default=None, help="CSV of the k (file, offset, distance) triples per target frame")
     p.add_argument("--max-rows", default="16384", help="target frames per chunk")
+    p.add_argument("--live-block", default=None, help="samples per block of the live path (default: offline)")
+    p.add_argument("--streams", default=None, help="parallel streams of the live path (default 1)")
     args = p.parse_args(argv)
+    args.live_block = None if args.live_block is None else _int_flag("live-block", args.live_block, 1)
+    if args.streams is not None and args.live_block is None:
+        raise ValueError("--streams %s: needs --live-block" % args.streams)
+    args.streams = 1 if args.streams is None else _int_flag("streams", args.streams, 1)
     args.k = _int_flag("k", args.k, 1)
     if args.k > 16:
         raise ValueError("--k %d: at most 16" % args.k)
@@ -82,6 +95,8 @@ def check_framing(args, S):
         check_window(S, hop, args.window)
     except ValueError as e:
         raise ValueError("--window %s: %s" % (args.window, e))
+    if args.live_block is not None and args.live_block % hop != 0:
+        raise ValueError("--live-block %d: not a multiple of the hop %d" % (args.live_block, hop))
     return hop
 
 
@@ -133,6 +148,8 @@ def main(argv=None):
     index = LatentIndex(model, hop=framing, max_rows=args.max_rows)
     for f, w in zip(files, waves):
         index.add(w, f)
+    if args.live_block is not None:
+        return run_live(args, index, target, hop, sr, len(files))
     y, idx, dist, path = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True,
                                       continuity=args.continuity, return_path=True)
     y = y.cpu().numpy()
@@ -146,6 +163,54 @@ def main(argv=None):
         choice, cost = path[1].cpu().numpy(), path[2].cpu().numpy()
         line += (", continuity %g, continuing %.4f, target cost %.6g, transition cost %.6g"
                  % (args.continuity, continuing_share(choice, index.successor()), cost[0], cost[1]))
+    print(line)
+    return y
+
+
+def live_mosaic(index, target, block, hop, n_streams=1, **kw):
+    """The target through StreamingMosaic in blocks of `block` -> (y [target.size] numpy, idx [T, k], dist [T, k],
+    choice [T]) with T the frames of all streams, stream after stream.  The target is cut into n_streams consecutive
+    parts; every part is zero-padded to whole blocks that also flush the S - hop samples of latency."""
+    import numpy as np
+    import torch
+    from rawaudiovae_kelsey_amd.mosaic import StreamingMosaic
+    sm = StreamingMosaic(index, n_streams, block, hop=hop, **kw)
+    n = target.size
+    part = -(-n // n_streams)
+    n_blocks = -(-(part + sm.latency) // block)
+    x = np.zeros((n_streams, n_blocks * block), np.float32)
+    for s in range(n_streams):
+        seg = target[s * part:(s + 1) * part]
+        x[s, :seg.size] = seg
+    x = torch.from_numpy(x).to(sm.device)
+    ys, idxs, dists, choices = [], [], [], []
+    for b in range(n_blocks):
+        ys.append(sm.process(x[:, b * block:(b + 1) * block]))
+        i, d, c = sm.last_matches()
+        idxs.append(i.clone()), dists.append(d.clone()), choices.append(c.clone())
+    y = torch.cat(ys, 1)[:, sm.latency:sm.latency + part].reshape(-1)[:n].cpu().numpy()
+    k = idxs[0].shape[-1]
+    return (y, torch.cat(idxs, 1).reshape(-1, k).cpu().numpy(), torch.cat(dists, 1).reshape(-1, k).cpu().numpy(),
+            torch.cat(choices, 1).reshape(-1).cpu().numpy())
+
+
+def run_live(args, index, target, hop, sr, n_files):
+    from rawaudiovae_kelsey_amd import data as D
+    y, idx, dist, choice = live_mosaic(index, target, args.live_block, hop, args.streams, k=args.k, mode=args.mode,
+                                       window=args.window, continuity=args.continuity)
+    D.write_wav(args.out, y, sr)
+    slot = None
+    if args.continuity > 0:
+        slot = [int((idx[t] == choice[t]).argmax()) if choice[t] >= 0 else -1 for t in range(len(choice))]
+    if args.matches:
+        write_matches(args.matches, index.locate(idx), dist, slot)
+    line = ("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s, %s, "
+            "block %d, streams %d" % (args.out, y.size, idx.shape[0], len(index), n_files, args.k, args.mode,
+                                      args.window or "none", "live, greedy" if args.continuity > 0 else "live",
+                                      args.live_block, args.streams))
+    if args.continuity > 0:
+        line += ", continuity %g, continuing %.4f" % (
+            args.continuity, continuing_share(choice, index.successor(hop // index.step)))
     print(line)
     return y
 

@@ -50,7 +50,8 @@ class MosaicDesc(C.Structure):
                 ("width", c_long), ("out", c_void_p), ("ldo", c_long), ("frames", c_void_p), ("F", c_long),
                 ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long), ("next_of", c_void_p),
                 ("row0", c_long), ("rows", c_long), ("trans", c_void_p), ("lam", c_float), ("slot", c_void_p),
-                ("choice", c_void_p), ("cost", c_void_p)]
+                ("choice", c_void_p), ("cost", c_void_p), ("live", C.POINTER(StreamDesc)),
+                ("mode", c_long), ("weight", c_void_p), ("which", c_long)]
 
 
 class CommDesc(C.Structure):
@@ -77,6 +78,8 @@ PHASE_ALL_LOCAL = PHASE_FWD | PHASE_BWD_A | PHASE_BWD_B | PHASE_ADAM
 ACT_NONE, ACT_RELU, ACT_TANH = 0, 1, 2   # ACT_TANH: rv_linear_fp32 only
 MOSAIC_KNN, MOSAIC_KNN_WORKSPACE, MOSAIC_GATHER_MEAN, MOSAIC_OLA = 0, 1, 2, 3   # RV_MOSAIC_* (rv_mosaic)
 MOSAIC_TRANSITION, MOSAIC_PATH_FORWARD, MOSAIC_PATH_BACKTRACK, MOSAIC_PATH_WORKSPACE = 4, 5, 6, 7
+MOSAIC_KNN_SMALL, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_LIVE, MOSAIC_LIVE_WORKSPACE, MOSAIC_LIVE_RESET = 8, 9, 10, 11, 12
+LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

@@ -1,4 +1,4 @@
-// Launchers that only the step plan (plan.hip) calls: forms of public entry points with extra operands (fp8 copies,
+// Launchers that only the step plan (plan.hip) and the live mosaic (mosaic.hip) call: forms of public entry points with extra operands (fp8 copies,
 // per-block maxima, frames read in place).  Not part of the C ABI (include/rawvae_hip.h) and not exported.
 #pragma once
 #include "../../include/rawvae_hip.h"
@@ -116,3 +116,10 @@ RV_INTERNAL int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operand
                                          int mask_is_fp8, long Mp, long Np, long Kp, void* dx_bf16, long lddx,
                                          float* colsum_partial, void* dw_slabs, long lddw, int splits, int slab_dtype,
                                          float* slab_unscale, void* stream);
+// The two ends of rv_stream_process (stream.hip) for the live mosaic, which searches the corpus between them.
+// rv_stream_encode: rv_stream_process's checks (no temperature, no eps), its fc1 launch on [history | x] and its heads
+// launch with q [n_streams * F, L] = mu * scale + offset in place of the reparameterised z; *z and *frames receive the
+// stream workspace's latent rows [n_streams * F, L] and decoded frames [n_streams * F, S].
+// rv_stream_synth: decode != 0: fc3 and fc4 on the latent rows into the frames; then k_stream_ola on the frames.
+RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, float** frames, void* stream);
+RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream);

@@ -6,11 +6,14 @@
 //   RV_MOSAIC_OLA          offline weighted overlap-add normalised by the window sum
 //   RV_MOSAIC_TRANSITION   candidate-to-candidate concatenation costs [rows, k, k] in the search's arithmetic
 //   RV_MOSAIC_PATH_FORWARD / _BACKTRACK   Viterbi unit selection over the k candidates of every row (one wave each)
-// Layout, split and merge, and the measured figures: DESIGN.md section 7.5.
+//   RV_MOSAIC_KNN_SMALL    RV_MOSAIC_KNN's results for at most 64 query rows: k_knn_small, one thread per corpus row
+//   RV_MOSAIC_LIVE         one block of live audio: the stream's encoder (stream.hip), the search, greedy unit
+//                          selection (k_live_select), gather-mean, then the stream's decoder / overlap-add
+// Layout, split and merge, and the measured figures: DESIGN.md sections 7.5 and 7.6.
 #include <limits.h>
 
 #include "common.h"
-#include "../../include/rawvae_hip.h"
+#include "internal.h"
 
 using namespace rv;
 
@@ -158,8 +161,32 @@ k_knn_topk(const float* __restrict__ q, long T, const float* __restrict__ c, lon
   }
 }
 
-// One wave per query row (grid-stride): lane l keeps the top KM of the partials of splits l, l + 64, ..., then k
-// rounds of a wave-wide minimum of the lanes' heads pop the result in (distance, index) order.
+// The lanes of a wave each hold a sorted list over disjoint corpus rows: k rounds of a wave-wide minimum of the lanes'
+// heads pop the first k of their union in (distance, index) order; every lane sees each (j, distance, index) in `out`.
+template <int KM, class Out>
+__device__ __forceinline__ void topk_pop(float (&bd)[KM], int (&bi)[KM], int k, Out out) {
+  for (int j = 0; j < k; ++j) {
+    float wd = bd[0];
+    int wi = bi[0];
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const float od = __shfl_xor(wd, off, 64);
+      const int oi = __shfl_xor(wi, off, 64);
+      if (cand_less(od, oi, wd, wi)) { wd = od; wi = oi; }
+    }
+    // the lanes' corpus indices are distinct, so one lane holds the winner (none when it is empty)
+    if (wi != INT_MAX && bi[0] == wi) {
+#pragma unroll
+      for (int s = 0; s + 1 < KM; ++s) { bd[s] = bd[s + 1]; bi[s] = bi[s + 1]; }
+      bd[KM - 1] = INFINITY;
+      bi[KM - 1] = INT_MAX;
+    }
+    out(j, wd, wi);
+  }
+}
+
+// One wave per query row (grid-stride): lane l keeps the top KM of the partials of splits l, l + 64, ..., then
+// topk_pop gives the result in (distance, index) order.
 template <int KM>
 __global__ void __launch_bounds__(256)
 k_knn_merge(const float* __restrict__ ws_d, const int* __restrict__ ws_i, long T, int k, int n_splits,
@@ -174,27 +201,164 @@ k_knn_merge(const float* __restrict__ ws_d, const int* __restrict__ ws_i, long T
       const long o = ((long)sp * T + r) * k;
       for (int j = 0; j < k; ++j) topk_insert<KM>(ws_d[o + j], ws_i[o + j], bd, bi);
     }
-    for (int j = 0; j < k; ++j) {
-      float wd = bd[0];
-      int wi = bi[0];
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) {
-        const float od = __shfl_xor(wd, off, 64);
-        const int oi = __shfl_xor(wi, off, 64);
-        if (cand_less(od, oi, wd, wi)) { wd = od; wi = oi; }
-      }
-      // corpus indices of different splits are distinct, so one lane holds the winner (none when it is empty)
-      if (wi != INT_MAX && bi[0] == wi) {
-#pragma unroll
-        for (int s = 0; s + 1 < KM; ++s) { bd[s] = bd[s + 1]; bi[s] = bi[s + 1]; }
-        bd[KM - 1] = INFINITY;
-        bi[KM - 1] = INT_MAX;
-      }
+    topk_pop<KM>(bd, bi, k, [&](int j, float wd, int wi) {
       if (lane == 0) {
         idx[r * k + j] = wi == INT_MAX ? -1 : wi;
         dist[r * k + j] = wd;
       }
+    });
+  }
+}
+
+// ---- The search for few query rows ----
+// k_knn_topk pads its queries to tiles of BR = 128 rows; a live block has 1..16.  Here one thread owns one corpus row
+// of a run of SRUN, a block walks the runs of its split, and a pass covers up to SQ query rows, so the corpus is read
+// once per pass.  Each KT-wide slice of the run goes through LDS (16-byte global loads, eight lanes per row, one slice
+// ahead in registers; row stride KT + 4 floats, so the b128 reads of 16 consecutive rows cover all 64 banks).  The
+// query values are wave-uniform and come through the scalar cache.  A pair's arithmetic is k_knn_topk's: fmaf(d, d,
+// part) in ascending l within the slice, tot += part per slice from +0.  The run's TQ x SRUN distances go through LDS
+// to SRUN / TQ lanes per query row, each with a sorted top-KM list; at the end one wave per query row merges them.
+constexpr int SQ = 16, SRUN = 256, SROW = KT + 4, SLD4 = SRUN * (KT / 4) / 256;
+// Query rows RV_MOSAIC_KNN_SMALL accepts, and up to which RV_MOSAIC_LIVE searches with it: measured faster than
+// k_knn_topk at every T up to here (1.4-1.9x at 64 rows, 4-10x at 16 and fewer against 1.24 M corpus rows; section 7.6)
+constexpr int SMALL_T_MAX = 4 * SQ;
+
+// part = fmaf(d, d, part) with d = qv[x] - cv[x] for x = 0..3 in order, the wave-uniform qv read from their SGPRs: the
+// instructions the compiler emits for the plain expression, written out because its SLP pass otherwise pairs the
+// chains of neighbouring query rows into packed operations and first moves every query value into a VGPR (more VALU
+// work than it saves).  v_sub_f32 and v_fmac_f32 round as the C expressions do.
+__device__ __forceinline__ void sq_acc4_uniform(float& part, const float* __restrict__ qv, const f32x4& cv) {
+  float d;
+  asm("v_sub_f32 %1, %2, %6\n\tv_fmac_f32 %0, %1, %1\n\t"
+      "v_sub_f32 %1, %3, %7\n\tv_fmac_f32 %0, %1, %1\n\t"
+      "v_sub_f32 %1, %4, %8\n\tv_fmac_f32 %0, %1, %1\n\t"
+      "v_sub_f32 %1, %5, %9\n\tv_fmac_f32 %0, %1, %1"
+      : "+v"(part), "=&v"(d)
+      : "s"(qv[0]), "s"(qv[1]), "s"(qv[2]), "s"(qv[3]), "v"(cv[0]), "v"(cv[1]), "v"(cv[2]), "v"(cv[3]));
+}
+
+template <int KM, int TQ, bool VEC>
+__global__ void __launch_bounds__(256)
+k_knn_small(const float* __restrict__ q, int T, const float* __restrict__ c, long N, long L, int k, long per_split,
+            int n_splits, int* __restrict__ idx, float* __restrict__ dist, float* __restrict__ ws_d) {
+  static_assert(SRUN * SROW >= 2 * 256 * KM && SRUN * SROW >= TQ * SRUN, "the lists and the distances fit the stage");
+  __shared__ __attribute__((aligned(16))) float smem[SRUN * SROW];
+  constexpr int LPQ = SRUN / TQ;   // lanes per query row in the scan
+  const int tid = threadIdx.x, srow = tid / LPQ, ssub = tid % LPQ;
+  const int t0 = blockIdx.x * SQ, split = blockIdx.y;
+  const long n_lo = (long)split * per_split;
+  const long n_hi = n_lo + per_split < N ? n_lo + per_split : N;
+  // wave-uniform offsets of the query rows (T * L < 2^31); rows past T repeat the last one and are not written
+  auto q_row = [&](int i, int l) { return q + (t0 + i < T ? t0 + i : T - 1) * (int)L + l; };
+  float bd[KM];
+  int bi[KM];
+#pragma unroll
+  for (int s = 0; s < KM; ++s) { bd[s] = INFINITY; bi[s] = INT_MAX; }
+  f32x4 pre[SLD4];
+  // rows past n_hi and columns past L stage zeros
+  auto fetch = [&](long m0, long k0) {
+#pragma unroll
+    for (int u = 0; u < SLD4; ++u) {
+      const int e = tid + 256 * u;
+      const long gm = m0 + (e >> 3), gk = k0 + (e & 7) * 4;
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if (gm < n_hi) {
+        const float* p = c + gm * L + gk;
+        if constexpr (VEC) {
+          if (gk < L) v = *reinterpret_cast<const f32x4*>(p);   // L % 4 == 0: the whole vector is inside the row
+        } else {
+#pragma unroll
+          for (int x = 0; x < 4; ++x)
+            if (gk + x < L) v[x] = p[x];
+        }
+      }
+      pre[u] = v;
     }
+  };
+  const float* crow = smem + tid * SROW;
+  fetch(n_lo, 0);
+  for (long m0 = n_lo; m0 < n_hi; m0 += SRUN) {
+    float tot[TQ];
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) tot[i] = 0.f;
+    for (long k0 = 0; k0 < L; k0 += KT) {
+#pragma unroll
+      for (int u = 0; u < SLD4; ++u) {
+        const int e = tid + 256 * u;
+        *reinterpret_cast<f32x4*>(smem + (e >> 3) * SROW + (e & 7) * 4) = pre[u];
+      }
+      __syncthreads();
+      const bool wrap = k0 + KT >= L;
+      if (!wrap || m0 + SRUN < n_hi) fetch(wrap ? m0 + SRUN : m0, wrap ? 0 : k0 + KT);
+      float part[TQ];
+#pragma unroll
+      for (int i = 0; i < TQ; ++i) part[i] = 0.f;
+      if (k0 + KT <= L) {
+        // the row's slice in registers, then one query row after the other: its KT values are two scalar loads
+        f32x4 cv[KT / 4];
+#pragma unroll
+        for (int u = 0; u < KT / 4; ++u) cv[u] = *reinterpret_cast<const f32x4*>(crow + 4 * u);
+#pragma unroll
+        for (int i = 0; i < TQ; ++i) {
+          const float* qr = q_row(i, (int)k0);
+#pragma unroll
+          for (int u = 0; u < KT / 4; ++u) sq_acc4_uniform(part[i], qr + 4 * u, cv[u]);
+        }
+      } else {
+        // the last, partial slice: the terms past L would add an exact 0
+        for (int kk = 0; k0 + kk < L; ++kk) {
+          const float cv = crow[kk];
+#pragma unroll
+          for (int i = 0; i < TQ; ++i) {
+            const float d = *q_row(i, (int)k0 + kk) - cv;
+            part[i] = __builtin_fmaf(d, d, part[i]);
+          }
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < TQ; ++i) tot[i] += part[i];
+      __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < TQ; ++i) smem[i * SRUN + tid] = tot[i];
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < TQ; ++j) {
+      const int col = ssub + LPQ * j;
+      if (m0 + col < n_hi) topk_insert<KM>(smem[srow * SRUN + col], (int)(m0 + col), bd, bi);
+    }
+    __syncthreads();   // the next run stages over the distances
+  }
+  // every thread's list goes to LDS; wave w merges the LPQ lists of query rows w, w + 4, ...
+  float* ld = smem;
+  int* li = reinterpret_cast<int*>(smem + 256 * KM);
+#pragma unroll
+  for (int s = 0; s < KM; ++s) {
+    ld[tid * KM + s] = bd[s];
+    li[tid * KM + s] = bi[s];
+  }
+  __syncthreads();
+  const int lane = tid & 63;
+  for (int r = tid >> 6; r < TQ; r += 4) {
+#pragma unroll
+    for (int s = 0; s < KM; ++s) { bd[s] = INFINITY; bi[s] = INT_MAX; }
+    for (int x = lane; x < LPQ; x += 64) {
+      const int o = (r * LPQ + x) * KM;
+      for (int s = 0; s < KM; ++s) topk_insert<KM>(ld[o + s], li[o + s], bd, bi);
+    }
+    const int t = t0 + r;
+    topk_pop<KM>(bd, bi, k, [&](int j, float wd, int wi) {
+      if (lane == 0 && t < T) {
+        if (n_splits == 1) {
+          idx[t * k + j] = wi == INT_MAX ? -1 : wi;
+          dist[t * k + j] = wd;
+        } else {
+          const long o = ((long)split * T + t) * k + j;     // the indices follow the n_splits * T * k distances
+          ws_d[o] = wd;
+          reinterpret_cast<int*>(ws_d + (long)n_splits * T * k)[o] = wi;
+        }
+      }
+    });
   }
 }
 
@@ -574,6 +738,66 @@ k_path_backtrack(const int* __restrict__ idx, const float* __restrict__ dist, lo
   }
 }
 
+// ---- Live mosaicing: greedy unit selection ----
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+
+// One wave per stream, its F frames in order; lane j owns candidate j of the frame.  prev < 0 (or without a successor
+// in the table): the lowest j whose candidate is a corpus row.  Otherwise lane j walks D(c[next_of[prev]], c[idx[r, j]])
+// in the search's arithmetic and the wave takes the least dist + fl(w * D), strict < in ascending j, NaN skipped.
+__global__ void __launch_bounds__(64)
+k_live_select(const float* __restrict__ c, long N, long L, const int* __restrict__ next_of, const int* __restrict__ idx,
+              const float* __restrict__ dist, int k, long F, const float* __restrict__ weight, int* __restrict__ prev,
+              int* __restrict__ choice) {
+  const long s = blockIdx.x;
+  const int lane = threadIdx.x, jl = lane < k ? lane : k - 1;
+  float w = weight[s];
+  if (!(w >= 0.f && w < INFINITY)) w = 0.f;
+  int p = prev[s];
+  for (long f = 0; f < F; ++f) {
+    const long r = s * F + f;
+    const int ci = idx[r * k + jl];
+    bool valid = lane < k && ci >= 0 && ci < N;
+    int succ = -1;
+    if (p >= 0 && p < N) succ = next_of[p];
+    if (succ < 0 || succ >= N) succ = -1;
+    float cost = 0.f;
+    if (succ >= 0) {   // wave-uniform
+      const float* a = c + (long)succ * L;
+      const float* b = c + (long)(valid ? ci : 0) * L;
+      float tot = 0.f;
+      for (long k0 = 0; k0 < L; k0 += KT) {
+        const int n = L - k0 < KT ? (int)(L - k0) : KT;
+        float part = 0.f;
+        for (int kk = 0; kk < n; ++kk) {
+          const float d = a[k0 + kk] - b[k0 + kk];
+          part = __builtin_fmaf(d, d, part);
+        }
+        tot += part;
+      }
+      cost = add_rn(dist[r * k + jl], mul_rn(w, tot));
+      valid = valid && cost == cost;
+    }
+    int slot = -1;
+    float best = 0.f;
+    for (int j = 0; j < k; ++j) {
+      const float cj = __shfl(cost, j, 64);
+      const bool vj = __shfl((int)valid, j, 64) != 0;
+      if (vj && (slot < 0 || (succ >= 0 && cj < best))) { best = cj; slot = j; }
+    }
+    p = slot >= 0 ? __shfl(ci, slot, 64) : -1;
+    if (lane == 0) choice[r] = p;
+  }
+  if (lane == 0) prev[s] = p;
+}
+
+__global__ void __launch_bounds__(256) k_live_clear(int* __restrict__ prev, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < n) prev[i] = -1;
+}
+
 unsigned blocks_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n > cap ? cap : n)); }
 
 // corpus rows per split (a multiple of BN) and the number of splits: enough (query tile, split) blocks to fill the
@@ -599,7 +823,42 @@ void launch_knn(const rv_mosaic_desc* d, long per_split, long n_splits, float* w
                        (int)d->k, (int)n_splits, d->idx, d->dist);
 }
 
-int knn_check(const rv_mosaic_desc* d, long* per_split, long* n_splits) {
+// k_knn_small's split: corpus rows per split (a multiple of SRUN) and the number of splits; enough (pass, split)
+// blocks to fill the chip, down to one run per split; `forced` > 0 asks for that many splits instead
+void knn_small_split(long T, long N, long forced, long* per_split, long* n_splits) {
+  const long passes = (T + SQ - 1) / SQ, n_runs = (N + SRUN - 1) / SRUN;
+  long want = forced > 0 ? forced : (TARGET_BLOCKS + passes - 1) / passes;
+  if (want > n_runs) want = n_runs;
+  if (want < 1) want = 1;
+  const long runs = (n_runs + want - 1) / want;
+  *per_split = runs * SRUN;
+  *n_splits = (n_runs + runs - 1) / runs;
+}
+
+template <int KM, int TQ>
+void launch_knn_small_q(const rv_mosaic_desc* d, long per_split, long n_splits, float* ws_d, int* ws_i, hipStream_t st) {
+  const dim3 grid((unsigned)((d->T + SQ - 1) / SQ), (unsigned)n_splits);
+  if (d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0)   // 16-byte loads of corpus rows
+    hipLaunchKernelGGL((k_knn_small<KM, TQ, true>), grid, dim3(256), 0, st, d->q, (int)d->T, d->c, d->N, d->L, (int)d->k,
+                       per_split, (int)n_splits, d->idx, d->dist, ws_d);
+  else
+    hipLaunchKernelGGL((k_knn_small<KM, TQ, false>), grid, dim3(256), 0, st, d->q, (int)d->T, d->c, d->N, d->L, (int)d->k,
+                       per_split, (int)n_splits, d->idx, d->dist, ws_d);
+  if (n_splits > 1)
+    hipLaunchKernelGGL(k_knn_merge<KM>, dim3(blocks_for((d->T + 3) / 4, 65536)), dim3(256), 0, st, ws_d, ws_i, d->T,
+                       (int)d->k, (int)n_splits, d->idx, d->dist);
+}
+
+template <int KM>
+void launch_knn_small(const rv_mosaic_desc* d, long per_split, long n_splits, float* ws_d, int* ws_i, hipStream_t st) {
+  if (d->T <= 1) launch_knn_small_q<KM, 1>(d, per_split, n_splits, ws_d, ws_i, st);
+  else if (d->T <= 2) launch_knn_small_q<KM, 2>(d, per_split, n_splits, ws_d, ws_i, st);
+  else if (d->T <= 4) launch_knn_small_q<KM, 4>(d, per_split, n_splits, ws_d, ws_i, st);
+  else if (d->T <= 8) launch_knn_small_q<KM, 8>(d, per_split, n_splits, ws_d, ws_i, st);
+  else launch_knn_small_q<KM, 16>(d, per_split, n_splits, ws_d, ws_i, st);
+}
+
+int knn_check(const rv_mosaic_desc* d, bool small, long* per_split, long* n_splits) {
   RV_REQUIRE(d->T >= 1 && d->N >= 1 && d->L >= 1 && d->N < INT_MAX - BN, RV_ERR_SHAPE,
              "rv_mosaic(KNN): bad extents T=%ld N=%ld L=%ld", d->T, d->N, d->L);
   RV_REQUIRE(d->k >= 1 && d->k <= KMAX && d->k <= d->N, RV_ERR_SHAPE,
@@ -607,7 +866,10 @@ int knn_check(const rv_mosaic_desc* d, long* per_split, long* n_splits) {
   RV_REQUIRE(d->splits >= 0 && d->splits <= 65535, RV_ERR_SHAPE, "rv_mosaic(KNN): splits=%ld outside [0, 65535]",
              d->splits);
   RV_REQUIRE((d->T + BR - 1) / BR < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(KNN): T=%ld too large", d->T);
-  knn_split(d->T, d->N, d->splits, per_split, n_splits);
+  RV_REQUIRE(!small || (d->T <= SMALL_T_MAX && d->L <= (1L << 24)), RV_ERR_SHAPE,
+             "rv_mosaic(KNN_SMALL): T=%ld above %d or L=%ld above 2^24, use RV_MOSAIC_KNN", d->T, SMALL_T_MAX, d->L);
+  if (small) knn_small_split(d->T, d->N, d->splits, per_split, n_splits);
+  else knn_split(d->T, d->N, d->splits, per_split, n_splits);
   return RV_OK;
 }
 
@@ -629,6 +891,62 @@ int path_check(const rv_mosaic_desc* d, const char* op, bool chunk) {
 
 long knn_ws_bytes(long T, long k, long n_splits) { return n_splits > 1 ? n_splits * T * k * 8 : 0; }
 
+// RV_MOSAIC_KNN / RV_MOSAIC_KNN_SMALL: checks, then the search and its merge on `st`
+int run_knn(const rv_mosaic_desc* d, bool small, hipStream_t st) {
+  long per_split = 0, n_splits = 0;
+  RV_REQUIRE(d->q && d->c && d->idx && d->dist, RV_ERR_NULL, "rv_mosaic(KNN): null pointer");
+  const int rc = knn_check(d, small, &per_split, &n_splits);
+  if (rc) return rc;
+  const long need = knn_ws_bytes(d->T, d->k, n_splits);
+  RV_REQUIRE(need == 0 || (d->ws && d->ws_bytes >= need), RV_ERR_SHAPE,
+             "rv_mosaic(KNN): workspace of %ld bytes, %ld needed for %ld splits", d->ws_bytes, need, n_splits);
+  float* ws_d = (float*)d->ws;
+  int* ws_i = need ? (int*)((char*)d->ws + n_splits * d->T * d->k * 4) : nullptr;
+  if (small) {
+    if (d->k <= 2) launch_knn_small<2>(d, per_split, n_splits, ws_d, ws_i, st);
+    else if (d->k <= 4) launch_knn_small<4>(d, per_split, n_splits, ws_d, ws_i, st);
+    else if (d->k <= 8) launch_knn_small<8>(d, per_split, n_splits, ws_d, ws_i, st);
+    else launch_knn_small<16>(d, per_split, n_splits, ws_d, ws_i, st);
+  } else {
+    if (d->k <= 2) launch_knn<2>(d, per_split, n_splits, ws_d, ws_i, st);
+    else if (d->k <= 4) launch_knn<4>(d, per_split, n_splits, ws_d, ws_i, st);
+    else if (d->k <= 8) launch_knn<8>(d, per_split, n_splits, ws_d, ws_i, st);
+    else launch_knn<16>(d, per_split, n_splits, ws_d, ws_i, st);
+  }
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+// RV_MOSAIC_LIVE's workspace: prev [n_streams] int32, the query rows [M, L] fp32, the search's partials; every part
+// starts on a 256-byte boundary.  M = n_streams * block / hop rows go to k_knn_small up to SMALL_T_MAX.
+struct live_ws {
+  long M, q, knn, knn_bytes, bytes;
+  bool small;
+};
+int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
+  const rv_stream_desc* sd = d->live;
+  RV_REQUIRE(sd, RV_ERR_NULL, "rv_mosaic(%s): null stream descriptor", op);
+  RV_REQUIRE(sd->n_streams >= 1 && sd->hop >= 1 && sd->block >= sd->hop && sd->block % sd->hop == 0 && sd->S >= sd->hop &&
+                 sd->n_streams <= 0x7fffffffL && sd->n_streams * (sd->block / sd->hop) <= 0x7fffffffL,
+             RV_ERR_SHAPE, "rv_mosaic(%s): bad stream extents n_streams=%ld block=%ld hop=%ld S=%ld", op, sd->n_streams,
+             sd->block, sd->hop, sd->S);
+  RV_REQUIRE(d->L == sd->L, RV_ERR_SHAPE, "rv_mosaic(%s): corpus rows of L=%ld, the model's latent has %ld", op, d->L,
+             sd->L);
+  w->M = sd->n_streams * (sd->block / sd->hop);
+  w->small = w->M <= SMALL_T_MAX;
+  rv_mosaic_desc kd = *d;
+  kd.T = w->M;
+  long per_split = 0, n_splits = 0;
+  const int rc = knn_check(&kd, w->small, &per_split, &n_splits);
+  if (rc) return rc;
+  auto up = [](long n) { return (n + 255) & ~255L; };
+  w->q = up(sd->n_streams * 4);
+  w->knn = w->q + up(w->M * d->L * 4);
+  w->knn_bytes = knn_ws_bytes(w->M, d->k, n_splits);
+  w->bytes = w->knn + up(w->knn_bytes);
+  return RV_OK;
+}
+
 }  // namespace
 
 extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
@@ -636,28 +954,16 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   long per_split = 0, n_splits = 0;
   switch (op) {
-    case RV_MOSAIC_KNN_WORKSPACE: {
-      const int rc = knn_check(d, &per_split, &n_splits);
+    case RV_MOSAIC_KNN_WORKSPACE:
+    case RV_MOSAIC_KNN_SMALL_WORKSPACE: {
+      const int rc = knn_check(d, op == RV_MOSAIC_KNN_SMALL_WORKSPACE, &per_split, &n_splits);
       if (rc) return rc;
       d->ws_bytes = knn_ws_bytes(d->T, d->k, n_splits);
       return RV_OK;
     }
-    case RV_MOSAIC_KNN: {
-      RV_REQUIRE(d->q && d->c && d->idx && d->dist, RV_ERR_NULL, "rv_mosaic(KNN): null pointer");
-      const int rc = knn_check(d, &per_split, &n_splits);
-      if (rc) return rc;
-      const long need = knn_ws_bytes(d->T, d->k, n_splits);
-      RV_REQUIRE(need == 0 || (d->ws && d->ws_bytes >= need), RV_ERR_SHAPE,
-                 "rv_mosaic(KNN): workspace of %ld bytes, %ld needed for %ld splits", d->ws_bytes, need, n_splits);
-      float* ws_d = (float*)d->ws;
-      int* ws_i = need ? (int*)((char*)d->ws + n_splits * d->T * d->k * 4) : nullptr;
-      if (d->k <= 2) launch_knn<2>(d, per_split, n_splits, ws_d, ws_i, st);
-      else if (d->k <= 4) launch_knn<4>(d, per_split, n_splits, ws_d, ws_i, st);
-      else if (d->k <= 8) launch_knn<8>(d, per_split, n_splits, ws_d, ws_i, st);
-      else launch_knn<16>(d, per_split, n_splits, ws_d, ws_i, st);
-      RV_CHECK_LAUNCH();
-      return RV_OK;
-    }
+    case RV_MOSAIC_KNN:
+    case RV_MOSAIC_KNN_SMALL:
+      return run_knn(d, op == RV_MOSAIC_KNN_SMALL, st);
     case RV_MOSAIC_GATHER_MEAN: {
       RV_REQUIRE(d->src && d->idx && d->out, RV_ERR_NULL, "rv_mosaic(GATHER_MEAN): null pointer");
       RV_REQUIRE(d->T >= 1 && d->k >= 1 && d->k <= KMAX && d->width >= 1 && d->n_rows >= 1 && d->src_len >= d->width &&
@@ -731,6 +1037,69 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
                          (const unsigned char*)(ws + w.end), d->slot, d->choice, d->cost);
       RV_CHECK_LAUNCH();
       return RV_OK;
+    }
+    case RV_MOSAIC_LIVE_WORKSPACE: {
+      live_ws w;
+      const int rc = live_layout(d, "LIVE_WORKSPACE", &w);
+      if (rc) return rc;
+      d->ws_bytes = w.bytes;
+      return RV_OK;
+    }
+    case RV_MOSAIC_LIVE_RESET: {
+      live_ws w;
+      int rc = live_layout(d, "LIVE_RESET", &w);
+      if (rc) return rc;
+      const long NS = d->live->n_streams;
+      RV_REQUIRE(d->ws && d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(LIVE_RESET): workspace of %ld bytes, %ld needed",
+                 d->ws_bytes, w.bytes);
+      RV_REQUIRE(d->which >= -1 && d->which < NS, RV_ERR_SHAPE, "rv_mosaic(LIVE_RESET): stream %ld of %ld", d->which, NS);
+      rc = rv_stream_reset(d->live, d->which, stream);
+      if (rc) return rc;
+      const long first = d->which < 0 ? 0 : d->which, n = d->which < 0 ? NS : 1;
+      hipLaunchKernelGGL(k_live_clear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int*)d->ws + first, n);
+      RV_CHECK_LAUNCH();
+      return RV_OK;
+    }
+    case RV_MOSAIC_LIVE: {
+      live_ws w;
+      int rc = live_layout(d, "LIVE", &w);
+      if (rc) return rc;
+      const rv_stream_desc* sd = d->live;
+      const bool decode = d->mode == RV_LIVE_DECODE;
+      RV_REQUIRE(decode || d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED, "rv_mosaic(LIVE): mode %ld", d->mode);
+      RV_REQUIRE(d->c && d->idx && d->dist && d->ws && (decode || (d->src && d->row_start)) &&
+                     (!d->weight || (d->next_of && d->choice)), RV_ERR_NULL, "rv_mosaic(LIVE): null pointer");
+      RV_REQUIRE(d->ws_bytes >= w.bytes && ((unsigned long)d->ws & 255) == 0, RV_ERR_SHAPE,
+                 "rv_mosaic(LIVE): workspace of %ld bytes (256-byte aligned), %ld needed", d->ws_bytes, w.bytes);
+      RV_REQUIRE(d->N < INT_MAX && (decode || d->src_len >= sd->S), RV_ERR_SHAPE,
+                 "rv_mosaic(LIVE): bad extents N=%ld src_len=%ld", d->N, d->src_len);
+      char* ws = (char*)d->ws;
+      float *qrows = (float*)(ws + w.q), *z = nullptr, *frames = nullptr;
+      rc = rv_stream_encode(sd, qrows, &z, &frames, stream);
+      if (rc) return rc;
+      rv_mosaic_desc kd = *d;
+      kd.T = w.M;
+      kd.q = qrows;
+      kd.ws = ws + w.knn;
+      kd.ws_bytes = w.knn_bytes;
+      rc = run_knn(&kd, w.small, st);
+      if (rc) return rc;
+      const int* sel = d->idx;
+      int sel_k = (int)d->k;
+      if (d->weight) {
+        hipLaunchKernelGGL(k_live_select, dim3((unsigned)sd->n_streams), dim3(64), 0, st, d->c, d->N, d->L, d->next_of,
+                           d->idx, d->dist, (int)d->k, sd->block / sd->hop, d->weight, (int*)ws, d->choice);
+        sel = d->choice;
+        sel_k = 1;
+      }
+      if (decode)
+        hipLaunchKernelGGL(k_gather_mean, dim3(blocks_for(w.M, 65536)), dim3(256), 0, st, d->c, d->N * d->L, nullptr,
+                           d->L, d->N, d->L, sel, w.M, sel_k, z, d->L);
+      else
+        hipLaunchKernelGGL(k_gather_mean, dim3(blocks_for(w.M, 65536)), dim3(256), 0, st, d->src, d->src_len,
+                           d->row_start, 0L, d->N, sd->S, sel, w.M, sel_k, frames, sd->S);
+      RV_CHECK_LAUNCH();
+      return rv_stream_synth(sd, decode, stream);
     }
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);

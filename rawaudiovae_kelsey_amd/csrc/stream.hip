@@ -7,9 +7,11 @@
 //   rv_stream_process   : five launches per block -- fc1 reading its frames from the history and the new block, the two
 //                         heads + latent controls + reparameterisation, fc3, fc4, then overlap-add + history update.
 //   rv_stream_reset     : zero one stream's state (or every stream's).
+//   rv_stream_encode / rv_stream_synth (internal.h): the two ends of rv_stream_process for the live mosaic
+//                         (mosaic.hip), which puts a corpus search between them.
 #include "common.h"
 #include "philox.h"
-#include "../../include/rawvae_hip.h"
+#include "internal.h"
 
 using namespace rv;
 
@@ -158,7 +160,8 @@ __device__ __forceinline__ float latent_ctl(float m, float sc, float of) {
 }
 
 // fc21 and fc22 (lane = latent index l, both weight rows), then per row: the controls and the reparameterisation.
-template <int R, bool VEC>
+// REPARAM false (the live mosaic's query): z = mu' alone; eps, seed and temperature are not read.
+template <int R, bool VEC, bool REPARAM>
 __global__ void __launch_bounds__(64)
 k_stream_heads(const float* __restrict__ h1, long H, const float* __restrict__ w21, const float* __restrict__ b21,
                const float* __restrict__ w22, const float* __restrict__ b22, long M, long L, long F,
@@ -183,10 +186,14 @@ k_stream_heads(const float* __restrict__ h1, long H, const float* __restrict__ w
     if (r >= M) continue;
     const long s = r / F, f = cnt[s] + (r - s * F);
     const float m = acc[i][0] + bm, v = acc[i][1] + bl;
-    const float e = eps_in ? eps_in[r * L + l] : normal1(seed, (uint64_t)(f * L + l), (uint64_t)s);
     const float mc = latent_ctl(m, scale[s * L + l], offset[s * L + l]);
-    const float te = temperature[s] * e;
-    z[r * L + l] = mc + te * __expf(0.5f * v);   // k_reparameterize's expression (elementwise.hip), same flags
+    if constexpr (REPARAM) {
+      const float e = eps_in ? eps_in[r * L + l] : normal1(seed, (uint64_t)(f * L + l), (uint64_t)s);
+      const float te = temperature[s] * e;
+      z[r * L + l] = mc + te * __expf(0.5f * v);   // k_reparameterize's expression (elementwise.hip), same flags
+    } else {
+      z[r * L + l] = mc;
+    }
     mu[r * L + l] = m;
     lv[r * L + l] = v;
   }
@@ -323,6 +330,68 @@ bool extents_ok(long S, long H, long L, long NS, long block, long hop) {
          NS <= 0x7fffffffL && NS * (block / hop) <= 0x7fffffffL;
 }
 
+// The argument checks of a block call; `who` names the caller in the message.  The live mosaic reads no temperature.
+int stream_check(const rv_stream_desc* d, const char* who, bool reparam) {
+  RV_REQUIRE(d, RV_ERR_NULL, "%s: null descriptor", who);
+  const long S = d->S, H = d->H, L = d->L, NS = d->n_streams, block = d->block, hop = d->hop;
+  RV_REQUIRE(extents_ok(S, H, L, NS, block, hop) && block >= hop, RV_ERR_SHAPE,
+             "%s: bad extents S=%ld H=%ld L=%ld n_streams=%ld block=%ld hop=%ld (S %% hop == 0, "
+             "block %% hop == 0, block >= hop)", who, S, H, L, NS, block, hop);
+  RV_REQUIRE(d->w1 && d->b1 && d->w21 && d->b21 && d->w22 && d->b22 && d->w3 && d->b3 && d->w4 && d->b4, RV_ERR_NULL,
+             "%s: null weight", who);
+  RV_REQUIRE(d->x && d->y && d->mu && d->logvar && d->scale && d->offset && (d->temperature || !reparam) && d->window &&
+                 d->norm && d->workspace, RV_ERR_NULL, "%s: null buffer", who);
+  RV_REQUIRE(d->ld_x >= block && d->ld_y >= block, RV_ERR_SHAPE, "%s: ld_x=%ld ld_y=%ld < block %ld", who, d->ld_x,
+             d->ld_y, block);
+  RV_REQUIRE(grid_rows_ok(NS * (block / hop)) && (S + 63) / 64 <= 65535 && (H + 63) / 64 <= 65535, RV_ERR_SHAPE,
+             "%s: %ld rows exceed the launch grid", who, NS * (block / hop));
+  return RV_OK;
+}
+
+// fc1 on the frames of [history | x] of every stream, then the heads: z_out = the reparameterised z, or mu' alone
+template <bool REPARAM>
+int stream_encode(const rv_stream_desc* d, const Ws& w, float* z_out, hipStream_t st) {
+  const long S = d->S, H = d->H, L = d->L, NS = d->n_streams, hop = d->hop;
+  const long F = d->block / hop, M = NS * F, P = S - hop;
+  const Rows fr{w.carry, d->x, P, d->ld_x, NS * P, F, hop, P, w.cnt};
+  const bool vec1 = al16(d->x) && al16(w.carry) && d->ld_x % 4 == 0 && hop % 4 == 0 && P % 4 == 0;
+  const int rc = launch_linear(fr, vec1, d->w1, S, d->b1, M, H, S, 1, w.h1, H, st);
+  if (rc) return rc;
+  const bool vec = al16(w.h1) && al16(d->w21) && al16(d->w22) && H % 4 == 0;
+  const int R = rows_per_group(M, 4);
+  const dim3 g((unsigned)((L + 63) / 64), (unsigned)((M + R - 1) / R));
+#define RV_HEADS(RR, V)                                                                                                \
+  hipLaunchKernelGGL((k_stream_heads<RR, V, REPARAM>), g, dim3(64), 0, st, w.h1, H, d->w21, d->b21, d->w22, d->b22, M, \
+                     L, F, w.cnt, d->eps_in, (uint64_t)d->seed, d->scale, d->offset, d->temperature, d->mu, d->logvar, \
+                     z_out)
+  if (vec) {
+    if (R == 1) RV_HEADS(1, true); else if (R == 2) RV_HEADS(2, true); else RV_HEADS(4, true);
+  } else {
+    if (R == 1) RV_HEADS(1, false); else if (R == 2) RV_HEADS(2, false); else RV_HEADS(4, false);
+  }
+#undef RV_HEADS
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+// (decode: fc3 and fc4 on w.z into w.dec, then) overlap-add of w.dec + history update
+int stream_synth(const rv_stream_desc* d, const Ws& w, bool decode, hipStream_t st) {
+  const long S = d->S, H = d->H, L = d->L, NS = d->n_streams, hop = d->hop, block = d->block;
+  const long F = block / hop, M = NS * F, P = S - hop;
+  if (decode) {
+    const Rows zr{nullptr, w.z, 0, 0, 0, M, L, 0, nullptr};
+    int rc = launch_linear(zr, L % 4 == 0, d->w3, L, d->b3, M, H, L, 1, w.h3, H, st);
+    if (rc) return rc;
+    const Rows hr{nullptr, w.h3, 0, 0, 0, M, H, 0, nullptr};
+    rc = launch_linear(hr, H % 4 == 0, d->w4, H, d->b4, M, S, H, 2, w.dec, S, st);
+    if (rc) return rc;
+  }
+  hipLaunchKernelGGL(k_stream_ola, dim3((unsigned)NS), dim3(256), 0, st, w.dec, d->window, d->norm, NS, S, hop, block,
+                     F, P, d->x, d->ld_x, d->y, d->ld_y, w.carry, w.tail, w.cnt);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
 }  // namespace
 
 extern "C" int rv_small_linear_f32(const float* x, long ldx, const float* w, long ldw, const float* bias, long M,
@@ -343,54 +412,29 @@ extern "C" long rv_stream_workspace_bytes(long S, long H, long L, long n_streams
 }
 
 extern "C" int rv_stream_process(const rv_stream_desc* d, void* stream) {
-  RV_REQUIRE(d, RV_ERR_NULL, "rv_stream_process: null descriptor");
-  const long S = d->S, H = d->H, L = d->L, NS = d->n_streams, block = d->block, hop = d->hop;
-  RV_REQUIRE(extents_ok(S, H, L, NS, block, hop) && block >= hop, RV_ERR_SHAPE,
-             "rv_stream_process: bad extents S=%ld H=%ld L=%ld n_streams=%ld block=%ld hop=%ld (S %% hop == 0, "
-             "block %% hop == 0, block >= hop)", S, H, L, NS, block, hop);
-  RV_REQUIRE(d->w1 && d->b1 && d->w21 && d->b21 && d->w22 && d->b22 && d->w3 && d->b3 && d->w4 && d->b4, RV_ERR_NULL,
-             "rv_stream_process: null weight");
-  RV_REQUIRE(d->x && d->y && d->mu && d->logvar && d->scale && d->offset && d->temperature && d->window && d->norm &&
-                 d->workspace, RV_ERR_NULL, "rv_stream_process: null buffer");
-  RV_REQUIRE(d->ld_x >= block && d->ld_y >= block, RV_ERR_SHAPE, "rv_stream_process: ld_x=%ld ld_y=%ld < block %ld",
-             d->ld_x, d->ld_y, block);
-  const long F = block / hop, M = NS * F, P = S - hop;
-  RV_REQUIRE(grid_rows_ok(M) && (S + 63) / 64 <= 65535 && (H + 63) / 64 <= 65535, RV_ERR_SHAPE,
-             "rv_stream_process: %ld rows exceed the launch grid", M);
+  int rc = stream_check(d, "rv_stream_process", true);
+  if (rc) return rc;
   Ws w;
-  ws_layout(S, H, L, NS, block, hop, (char*)d->workspace, &w);
-  auto st = (hipStream_t)stream;
-  // fc1: frames straight from [history | x] of every stream
-  const Rows fr{w.carry, d->x, P, d->ld_x, NS * P, F, hop, P, w.cnt};
-  const bool vec1 = al16(d->x) && al16(w.carry) && d->ld_x % 4 == 0 && hop % 4 == 0 && P % 4 == 0;
-  int rc = launch_linear(fr, vec1, d->w1, S, d->b1, M, H, S, 1, w.h1, H, st);
+  ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);
+  rc = stream_encode<true>(d, w, w.z, (hipStream_t)stream);
   if (rc) return rc;
-  // heads + controls + reparameterisation
-  {
-    const bool vec = al16(w.h1) && al16(d->w21) && al16(d->w22) && H % 4 == 0;
-    const int R = rows_per_group(M, 4);
-    const dim3 g((unsigned)((L + 63) / 64), (unsigned)((M + R - 1) / R));
-#define RV_HEADS(RR, V)                                                                                                \
-  hipLaunchKernelGGL((k_stream_heads<RR, V>), g, dim3(64), 0, st, w.h1, H, d->w21, d->b21, d->w22, d->b22, M, L, F,  \
-                     w.cnt, d->eps_in, (uint64_t)d->seed, d->scale, d->offset, d->temperature, d->mu, d->logvar, w.z)
-    if (vec) {
-      if (R == 1) RV_HEADS(1, true); else if (R == 2) RV_HEADS(2, true); else RV_HEADS(4, true);
-    } else {
-      if (R == 1) RV_HEADS(1, false); else if (R == 2) RV_HEADS(2, false); else RV_HEADS(4, false);
-    }
-#undef RV_HEADS
-    RV_CHECK_LAUNCH();
-  }
-  const Rows zr{nullptr, w.z, 0, 0, 0, M, L, 0, nullptr};
-  rc = launch_linear(zr, L % 4 == 0, d->w3, L, d->b3, M, H, L, 1, w.h3, H, st);
+  return stream_synth(d, w, true, (hipStream_t)stream);
+}
+
+RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, float** frames, void* stream) {
+  const int rc = stream_check(d, "rv_mosaic(LIVE)", false);
   if (rc) return rc;
-  const Rows hr{nullptr, w.h3, 0, 0, 0, M, H, 0, nullptr};
-  rc = launch_linear(hr, H % 4 == 0, d->w4, H, d->b4, M, S, H, 2, w.dec, S, st);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_stream_ola, dim3((unsigned)NS), dim3(256), 0, st, w.dec, d->window, d->norm, NS, S, hop, block,
-                     F, P, d->x, d->ld_x, d->y, d->ld_y, w.carry, w.tail, w.cnt);
-  RV_CHECK_LAUNCH();
-  return RV_OK;
+  Ws w;
+  ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);
+  *z = w.z;
+  *frames = w.dec;
+  return stream_encode<false>(d, w, q, (hipStream_t)stream);
+}
+
+RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream) {
+  Ws w;
+  ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);
+  return stream_synth(d, w, decode != 0, (hipStream_t)stream);
 }
 
 extern "C" int rv_stream_reset(const rv_stream_desc* d, long which, void* stream) {

@@ -20,6 +20,14 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
                                           (index.successor) and this candidate: 0 when the corpus simply plays on.
                                           Grains / decode then run on the one chosen frame.  w = 0 is the call above.
   transition_costs, best_path             the two steps on their own (RV_MOSAIC_TRANSITION, RV_MOSAIC_PATH_*)
+  knn_topk_small(q, c, k)                 knn_topk for at most SMALL_T_MAX query rows by the few-query kernel
+                                          (RV_MOSAIC_KNN_SMALL): the same bits
+  StreamingMosaic(index, n_streams, block, hop, k, mode, window, continuity)
+      live mosaicing: process(x) takes one block of samples per stream and returns the block built from the nearest
+      corpus frames, `S - hop` samples late -- StreamingVAE's framing, history and overlap-add around the search
+      (RV_MOSAIC_LIVE), state on the device, capture() / replay(x) as one graph.  continuity > 0 selects one candidate
+      per frame by the GREEDY rule (each frame against the previous choice only; not best_path's Viterbi search, which
+      needs the whole target; the two agree for k = 1), weighted by the device tensor `weight` [n_streams].
 
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
@@ -31,15 +39,17 @@ import torch
 from . import _lib
 from ._lib import ACT_RELU, ACT_TANH, MosaicDesc, lib, ptr, stream_ptr
 from .interpolate import LatentInterpolator, frame_layout
-from .stream import WINDOWS, window_values
+from .stream import WINDOWS, check_args, window_norm, window_values
 
 MODES = ("grains", "decode")
 K_MAX = 16
+SMALL_T_MAX = 64   # query rows of knn_topk_small (csrc/mosaic.hip)
 
 
 def _call(op, **fields):
     d = MosaicDesc(**fields)
-    host_only = op in (_lib.MOSAIC_KNN_WORKSPACE, _lib.MOSAIC_PATH_WORKSPACE)
+    host_only = op in (_lib.MOSAIC_KNN_WORKSPACE, _lib.MOSAIC_PATH_WORKSPACE, _lib.MOSAIC_KNN_SMALL_WORKSPACE,
+                       _lib.MOSAIC_LIVE_WORKSPACE)
     lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else stream_ptr())
     return d
 
@@ -51,15 +61,27 @@ def _rows(x, what):
     return x.contiguous()
 
 
-def knn_workspace_bytes(T, N, L, k, splits=0):
-    """Bytes of device workspace knn_topk needs for these extents (0 when the corpus is not split)."""
-    return _call(_lib.MOSAIC_KNN_WORKSPACE, T=int(T), N=int(N), L=int(L), k=int(k), splits=int(splits)).ws_bytes
+def knn_workspace_bytes(T, N, L, k, splits=0, small=False):
+    """Bytes of device workspace knn_topk (small: knn_topk_small) needs for these extents (0 when the corpus is not
+    split)."""
+    op = _lib.MOSAIC_KNN_SMALL_WORKSPACE if small else _lib.MOSAIC_KNN_WORKSPACE
+    return _call(op, T=int(T), N=int(N), L=int(L), k=int(k), splits=int(splits)).ws_bytes
 
 
 def knn_topk(q, c, k, splits=0):
     """(idx [T, k] int32, dist [T, k] fp32): the k nearest rows of c [N, L] to each row of q [T, L] under the squared
     distance, in ascending (distance, index) order; -1 / +inf where a row has fewer than k candidates.  `splits` pins
     the number of corpus splits (0: the library's choice); the result does not depend on it."""
+    return _knn(q, c, k, splits, False)
+
+
+def knn_topk_small(q, c, k, splits=0):
+    """knn_topk by the kernel built for few query rows (at most SMALL_T_MAX; more raises RvError): the same result,
+    bit for bit, for any `splits`."""
+    return _knn(q, c, k, splits, True)
+
+
+def _knn(q, c, k, splits, small):
     q, c = _rows(q, "q"), _rows(c, "c")
     if q.shape[1] != c.shape[1] or q.device != c.device:
         raise ValueError("q %s and c %s must share L and device" % (tuple(q.shape), tuple(c.shape)))
@@ -68,9 +90,9 @@ def knn_topk(q, c, k, splits=0):
         raise ValueError("k=%d must be in [1, %d] and at most the %d corpus rows" % (k, K_MAX, N))
     idx = torch.empty((T, k), dtype=torch.int32, device=q.device)
     dist = torch.empty((T, k), dtype=torch.float32, device=q.device)
-    nbytes = knn_workspace_bytes(T, N, L, k, splits)
+    nbytes = knn_workspace_bytes(T, N, L, k, splits, small)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=q.device)
-    _call(_lib.MOSAIC_KNN, T=T, N=N, L=L, k=k, splits=int(splits), q=ptr(q), c=ptr(c), idx=ptr(idx), dist=ptr(dist),
+    _call(_lib.MOSAIC_KNN_SMALL if small else _lib.MOSAIC_KNN, T=T, N=N, L=L, k=k, splits=int(splits), q=ptr(q), c=ptr(c), idx=ptr(idx), dist=ptr(dist),
           ws=ptr(ws), ws_bytes=nbytes)
     return idx, dist
 
@@ -398,3 +420,139 @@ class LatentIndex:
         if return_path:
             res += (path,)
         return res if len(res) > 1 else out
+
+
+def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=None, k=1, mode="grains", window=None,
+                    continuity=0.0):
+    """Validate a StreamingMosaic configuration without a device -> (hop, latency, frames per block, successor
+    advance).  ValueError naming the argument."""
+    S = int(segment_length)
+    if int(n_corpus) < 1:
+        raise ValueError("index: the index is empty, add() corpus files first")
+    if int(n_streams) <= 0:
+        raise ValueError("n_streams must be positive, got %d" % int(n_streams))
+    if mode not in MODES:
+        raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
+    k = int(k)
+    if not 1 <= k <= min(K_MAX, int(n_corpus)):
+        raise ValueError("k=%d must be in [1, %d] and at most the %d corpus frames" % (k, K_MAX, int(n_corpus)))
+    continuity = float(continuity)
+    if not 0 <= continuity < float("inf"):
+        raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
+    hop, latency, frames = check_args(S, block, hop, window)   # ValueError naming hop, block or window
+    adv = 1
+    if continuity > 0:
+        if hop % int(index_step) != 0:
+            raise ValueError("hop %d must be a whole multiple of the index's frame step %d when continuity > 0"
+                             % (hop, int(index_step)))
+        adv = hop // int(index_step)
+    return hop, latency, frames, adv
+
+
+class StreamingMosaic:
+    """Live mosaicing of `n_streams` streams against a LatentIndex (see the module doc).
+
+    `process(x)` -> y [n_streams, block], the input `latency` = S - hop samples late; the concatenated outputs equal
+    `index.mosaic(cat([zeros(latency), x]), k, hop, mode, window)` bit for bit at continuity 0.  Device tensors that
+    may be written in place between calls: `scale`, `offset` [n_streams, L] (the query is mu * scale + offset) and,
+    with continuity > 0, `weight` [n_streams] (starts at `continuity`; a value that is not finite and >= 0 counts
+    as 0).  The index must not change after construction."""
+
+    def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0):
+        from .stream import StreamingVAE
+        self.index = index
+        N = len(index)
+        self.hop, self.latency, self.frames_per_block, adv = check_live_args(
+            index.S, index.step, N, n_streams, block, hop, k, mode, window, continuity)
+        # the framing, history, window tables and stream workspace are StreamingVAE's
+        self._sv = StreamingVAE(index.model, n_streams, block, self.hop, window)
+        self.n_streams, self.block, self.k, self.mode, self.window = int(n_streams), int(block), int(k), mode, window
+        self.S, self.L, self.device = index.S, index.L, self._sv.device
+        self.scale, self.offset = self._sv.scale, self._sv.offset
+        self.selects = float(continuity) > 0
+        t = index._tables()
+        self._mu, self._audio, self._row_start = t["mu"], t["audio"], t["row_start"]
+        self._next_of = index._successor(adv)[1] if self.selects else None
+        self.weight = (torch.full((self.n_streams,), float(continuity), dtype=torch.float32, device=self.device)
+                       if self.selects else None)
+        M = self.n_streams * self.frames_per_block
+        self._idx = torch.full((M, self.k), -1, dtype=torch.int32, device=self.device)
+        self._dist = torch.full((M, self.k), float("inf"), dtype=torch.float32, device=self.device)
+        self._choice = torch.full((M,), -1, dtype=torch.int32, device=self.device)
+        self._ws = None
+        nbytes = self._call(_lib.MOSAIC_LIVE_WORKSPACE, None, None).ws_bytes
+        self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
+        self._graph = None
+        self.reset()
+
+    def _call(self, op, x, y, which=-1, stream=None):
+        sd = self._sv._desc(x, y, None)
+        d = MosaicDesc(k=self.k, idx=ptr(self._idx), dist=ptr(self._dist), c=ptr(self._mu), N=self._mu.shape[0],
+                       L=self.L, src=ptr(self._audio), src_len=self._audio.numel(), row_start=ptr(self._row_start),
+                       next_of=ptr(self._next_of), choice=ptr(self._choice), ws=ptr(self._ws),
+                       ws_bytes=0 if self._ws is None else self._ws.numel(), live=_lib.C.pointer(sd),
+                       mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS, weight=ptr(self.weight),
+                       which=int(which))
+        host_only = op == _lib.MOSAIC_LIVE_WORKSPACE
+        lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else (stream_ptr() if stream is None else stream))
+        return d
+
+    @torch.no_grad()
+    def process(self, x):
+        """One block: x [n_streams, block] fp32 on the device -> [n_streams, block]."""
+        x = self._sv._input(x)
+        y = torch.empty((self.n_streams, self.block), dtype=torch.float32, device=self.device)
+        self._call(_lib.MOSAIC_LIVE, x, y)
+        return y
+
+    @torch.no_grad()
+    def reset(self, streams=None):
+        """Zero the history, the overlap-add tail and the frame counter of `streams` (an index or a list; None = all)
+        and forget their last chosen corpus frame."""
+        if streams is None:
+            self._call(_lib.MOSAIC_LIVE_RESET, None, None, -1)
+            return
+        for s in ([streams] if isinstance(streams, int) else list(streams)):
+            s = int(s)
+            if not 0 <= s < self.n_streams:
+                raise ValueError("stream %d of %d" % (s, self.n_streams))
+            self._call(_lib.MOSAIC_LIVE_RESET, None, None, s)
+
+    def last_matches(self):
+        """(idx [n_streams, F, k] int32, dist [n_streams, F, k] fp32, choice [n_streams, F] int32) of the last block's
+        frames, as views of static buffers; choice is the selected corpus frame, -1 everywhere at continuity 0."""
+        F = self.frames_per_block
+        return (self._idx.view(self.n_streams, F, self.k), self._dist.view(self.n_streams, F, self.k),
+                self._choice.view(self.n_streams, F))
+
+    @torch.no_grad()
+    def capture(self):
+        """Capture one call as a graph on static buffers `graph_input` / `graph_output` [n_streams, block];
+        `replay(x)` then runs one block per call.  The graph holds the Parameters' pointers: replaying after a
+        Parameter was replaced raises."""
+        from .engine import Graph
+        self.graph_input = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
+        self.graph_output = torch.zeros_like(self.graph_input)
+        self._held = [(p, p.data_ptr()) for p in self._sv._weights()]
+        side = torch.cuda.Stream(self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        g = Graph(side)
+        with g:
+            self._call(_lib.MOSAIC_LIVE, self.graph_input, self.graph_output, stream=side.cuda_stream)
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        self._graph = g
+        return self
+
+    @torch.no_grad()
+    def replay(self, x=None):
+        """One block through the captured graph on the current stream; x (optional) is copied into `graph_input`
+        first.  Returns `graph_output` (overwritten by the next replay)."""
+        if self._graph is None:
+            raise _lib.RvError("replay() before capture()")
+        now = self._sv._weights()
+        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(now, self._held)):
+            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
+        if x is not None:
+            self.graph_input.copy_(self._sv._input(x))
+        self._graph.launch(torch.cuda.current_stream(self.device))
+        return self.graph_output

@@ -1,0 +1,363 @@
+"""Live mosaicing on the GPU (RV_MOSAIC_KNN_SMALL / RV_MOSAIC_LIVE in csrc/mosaic.hip, rawaudiovae_kelsey_amd.mosaic.
+StreamingMosaic, mosaic.py --live-block).  The offline path (LatentIndex.mosaic, knn_topk) is the oracle of the live
+one: the two must agree bit for bit; the greedy selection is checked against tests/live_mosaic_oracle.py."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from conftest import REPO  # noqa: E402
+import live_mosaic_oracle as LO  # noqa: E402
+import mosaic_oracle as O  # noqa: E402
+
+
+def _M():
+    from rawaudiovae_kelsey_amd import mosaic
+    return mosaic
+
+
+def _dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).cuda()
+
+
+def _same(a, b):
+    return torch.equal(a[0], b[0]) and torch.equal(a[1].view(torch.int32), b[1].view(torch.int32))
+
+
+# ---- the few-query search ----
+
+N_OF = {1: (257, 16), 2: (40, 1500), 5: (700, 33), 16: (1500, 255), 17: (257, 513), 64: (700, 16)}
+
+
+@pytest.mark.parametrize("L", [7, 64, 100, 256])
+@pytest.mark.parametrize("k", [1, 3, 4, 16])
+@pytest.mark.parametrize("T", [1, 2, 5, 16, 17, 64])
+def test_small_knn_equals_knn_topk_and_the_oracle(T, k, L):
+    M = _M()
+    assert M.SMALL_T_MAX == 64
+    for N in N_OF[T]:                                            # not tile multiples; 16 and 33: fewer rows than a run
+        rng = np.random.default_rng(1000 * T + 10 * k + L + N)
+        c = rng.standard_normal((N, L)).astype(np.float32)
+        q = rng.standard_normal((T, L)).astype(np.float32)
+        q[0] = c[N // 2]                                         # an exact hit: distance 0
+        got = M.knn_topk_small(_dev(q), _dev(c), k)
+        assert _same(got, M.knn_topk(_dev(q), _dev(c), k)), (T, N, L, k)
+        ri, rd = O.knn(q, c, k)
+        gi, gd = got[0].cpu().numpy(), got[1].cpu().numpy()
+        assert np.array_equal(gi, ri), np.argwhere(gi != ri)[:5]
+        assert np.array_equal(gd.view(np.int32), rd.view(np.int32))
+        assert gi[0, 0] == N // 2 and gd[0, 0] == 0
+
+
+@pytest.mark.parametrize("T,N,L,k", [(1, 70001, 256, 16), (16, 300001, 256, 4), (64, 70001, 64, 3), (5, 20000, 100, 8)])
+def test_small_knn_on_large_corpora_and_any_split_count(T, N, L, k):
+    M = _M()
+    rng = np.random.default_rng(T + N)
+    q, c = _dev(rng.standard_normal((T, L))), _dev(rng.standard_normal((N, L)))
+    ref = M.knn_topk(q, c, k)
+    for s in (0, 1, 3, 7, 300):
+        assert _same(M.knn_topk_small(q, c, k, splits=s), ref), s
+
+
+def _check_small(q, c, k, splits=0):
+    idx, dist = _M().knn_topk_small(_dev(q), _dev(c), k, splits=splits)
+    ri, rd = O.knn(q, c, k)
+    gi, gd = idx.cpu().numpy(), dist.cpu().numpy()
+    assert np.array_equal(gi, ri), np.argwhere(gi != ri)[:5]
+    assert np.array_equal(gd.view(np.int32), rd.view(np.int32))
+    return gi, gd
+
+
+def test_small_knn_ties_nan_and_short_rows():
+    rng = np.random.default_rng(5)
+    base = rng.standard_normal((50, 24)).astype(np.float32)
+    c = np.concatenate([base, base[::-1], base[:10]])            # every row two or three times
+    q = np.concatenate([base[:20], rng.standard_normal((30, 24)).astype(np.float32)])
+    for splits in (0, 1, 3):
+        gi, gd = _check_small(q, c, 8, splits)
+    assert np.all(gi[:10, 0] == np.arange(10)) and np.all(gi[:10, 1] == 99 - np.arange(10))
+    assert np.all(gi[:10, 2] == 100 + np.arange(10)) and np.all(gd[:10, :3] == 0)
+    cn = c.copy()
+    cn[::2, 5] = np.nan                                          # half the corpus is NaN
+    qn = q.copy()
+    qn[7] = np.nan                                               # a query with no candidate at all
+    gi, gd = _check_small(qn, cn, 16, 3)
+    assert np.all(np.delete(gi, 7, axis=0)[:, 0] % 2 == 1)       # only the odd (finite) corpus rows are taken
+    assert np.all(gi[7] == -1) and np.all(np.isinf(gd[7]))
+    c = np.full((40, 9), np.nan, np.float32)
+    c[[3, 17, 38]] = rng.standard_normal((3, 9))
+    q = rng.standard_normal((64, 9)).astype(np.float32)
+    for splits in (0, 1, 3):
+        gi, gd = _check_small(q, c, 5, splits)
+        assert np.array_equal(np.sort(gi[:, :3], axis=1), np.tile([3, 17, 38], (64, 1)))
+        assert np.all(gi[:, 3:] == -1) and np.all(np.isinf(gd[:, 3:]))
+
+
+def test_small_knn_rejects_more_rows_than_it_serves():
+    from rawaudiovae_kelsey_amd._lib import RvError
+    q, c = torch.zeros((65, 8), device="cuda"), torch.zeros((100, 8), device="cuda")
+    with pytest.raises(RvError, match=r"failed \(-1\)"):          # RV_ERR_SHAPE
+        _M().knn_topk_small(q, c, 2)
+    assert _M().knn_topk_small(q[:64], c, 2)[0].shape == (64, 2)
+
+
+# ---- the live block step ----
+
+def _model(S=64, H=96, L=8, seed=0):
+    from rawvae.model import VAE
+    torch.manual_seed(seed)
+    return VAE(S, H, L).cuda().eval()
+
+
+def _waves(rng, lengths, sr=8000.0):
+    out = []
+    for i, n in enumerate(lengths):
+        t = np.arange(n) / sr
+        w = 0.6 * np.sin(2 * np.pi * (150 + 170 * i) * t) + 0.2 * rng.standard_normal(n)
+        w[: n // 5] = 0                                          # leading silence: duplicate all-zero frames
+        out.append(w.astype(np.float32))
+    return out
+
+
+def _index(model, hop, lengths=(700, 1000, 513, 1290), seed=9):
+    index = _M().LatentIndex(model, hop=hop)
+    for i, w in enumerate(_waves(np.random.default_rng(seed), lengths)):
+        index.add(w, "f%d" % i)
+    return index
+
+
+def _signal(rng, n_streams, n):
+    t = np.arange(n)
+    x = np.stack([0.5 * np.sin(t * (0.05 + 0.03 * s)) for s in range(n_streams)]) + 0.1 * rng.standard_normal(
+        (n_streams, n))
+    return torch.from_numpy(x.astype(np.float32)).cuda()
+
+
+def _run(sm, x, replay=False, before_block=None):
+    """x [n_streams, m * block] through sm -> (y [n_streams, m * block], idx [n_streams, F, k], dist, choice
+    [n_streams, F]) with F the frames of all blocks."""
+    ys, idxs, dists, choices = [], [], [], []
+    for b in range(x.shape[1] // sm.block):
+        if before_block is not None:
+            before_block(b)
+        xb = x[:, b * sm.block:(b + 1) * sm.block]
+        ys.append((sm.replay(xb) if replay else sm.process(xb)).clone())
+        i, d, c = sm.last_matches()
+        idxs.append(i.clone()), dists.append(d.clone()), choices.append(c.clone())
+    return torch.cat(ys, 1), torch.cat(idxs, 1), torch.cat(dists, 1), torch.cat(choices, 1)
+
+
+def _anchor(model, S, hop, block, k, mode, window, continuity, n_blocks, lengths=(700, 1000, 513, 1290)):
+    M = _M()
+    index = _index(model, hop, lengths)
+    step = S if hop is None else hop
+    sm = M.StreamingMosaic(index, 1, block, hop=hop, k=k, mode=mode, window=window, continuity=continuity)
+    assert sm.latency == S - step
+    n = n_blocks * block
+    x = _signal(np.random.default_rng(S + step + k), 1, n)
+    y, idx, dist, choice = _run(sm, x)
+    target = torch.cat([torch.zeros(S - step, device="cuda"), x[0]])
+    ref = index.mosaic(target, k=k, hop=step, mode=mode, window=window, return_matches=True, continuity=continuity,
+                       return_path=True)
+    assert ref[1].shape[0] == n // step
+    assert torch.equal(idx[0], ref[1]) and torch.equal(dist[0].view(torch.int32), ref[2].view(torch.int32))
+    if continuity > 0:
+        assert torch.equal(choice[0], ref[3][1])
+    else:
+        assert torch.all(choice == -1)
+    bad = torch.nonzero(y[0].view(torch.int32) != ref[0][:n].view(torch.int32))
+    assert bad.numel() == 0, (bad[:5].flatten().tolist(), float((y[0] - ref[0][:n]).abs().max()))
+
+
+@pytest.mark.parametrize("continuity,k", [(0.0, 1), (0.0, 4), (0.5, 1)])
+@pytest.mark.parametrize("hop,window", [(None, None), (16, None), (16, "hann")])
+@pytest.mark.parametrize("mode", ["grains", "decode"])
+def test_live_equals_the_offline_mosaic_of_the_zero_prefixed_target(mode, hop, window, k, continuity):
+    _anchor(_model(), 64, hop, 64, k, mode, window, continuity, n_blocks=9)
+
+
+def test_live_equals_the_offline_mosaic_at_the_default_model_shape():
+    m = _model(1024, 2048, 256, seed=1)
+    _anchor(m, 1024, 256, 1024, 4, "decode", "hann", 0.0, n_blocks=5, lengths=(9000, 20000, 5000))
+    _anchor(m, 1024, 256, 256, 1, "grains", None, 0.25, n_blocks=12, lengths=(9000, 20000, 5000))
+
+
+@pytest.mark.parametrize("mode,continuity", [("grains", 0.0), ("decode", 0.3)])
+def test_block_size_invariance(mode, continuity):
+    M = _M()
+    index = _index(_model(seed=3), 16)
+    x = _signal(np.random.default_rng(2), 1, 16 * 8 * 4)
+    outs = []
+    for block in (16, 32, 128):
+        sm = M.StreamingMosaic(index, 1, block, hop=16, k=4, mode=mode, window="hann", continuity=continuity)
+        outs.append(_run(sm, x))
+    for o in outs[1:]:
+        assert all(torch.equal(a, b) for a, b in zip(o, outs[0]))
+    assert not torch.equal(outs[0][0], torch.zeros_like(outs[0][0]))
+
+
+def test_streams_are_independent_and_reset_restarts_one():
+    M = _M()
+    index = _index(_model(seed=4), 16)
+    kw = dict(hop=16, k=4, mode="grains", window="hann", continuity=0.4)
+    x = _signal(np.random.default_rng(3), 3, 32 * 6)
+    sm3 = M.StreamingMosaic(index, 3, 32, **kw)
+    got = _run(sm3, x)
+    for s in range(3):
+        one = _run(M.StreamingMosaic(index, 1, 32, **kw), x[s:s + 1])
+        assert all(torch.equal(a[s:s + 1], b) for a, b in zip(got, one)), s
+    assert torch.all(got[3] >= 0)
+    # reset(1): stream 1 starts over (history, tail, counter and the last chosen frame), streams 0 and 2 carry on
+    sm3 = M.StreamingMosaic(index, 3, 32, **kw)
+    first = _run(sm3, x[:, :96])
+    sm3.reset(1)
+    second = _run(sm3, x[:, 96:])
+    for s in (0, 2):
+        assert all(torch.equal(torch.cat([a[s], b[s]]), g[s]) for a, b, g in zip(first, second, got))
+    fresh = _run(M.StreamingMosaic(index, 1, 32, **kw), x[1:2, 96:])
+    assert all(torch.equal(a[1:2], b) for a, b in zip(second, fresh))
+    sm3.reset()
+    again = _run(sm3, x)
+    assert all(torch.equal(a, b) for a, b in zip(again, got))
+
+
+@pytest.mark.parametrize("mode,continuity", [("grains", 0.6), ("decode", 0.0)])
+def test_more_rows_than_the_few_query_search_serves_give_the_same_bits(mode, continuity):
+    M = _M()
+    index = _index(_model(seed=7), 16)
+    kw = dict(hop=16, k=4, mode=mode, window="hann", continuity=continuity)
+    x = _signal(np.random.default_rng(6), 5, 256 * 3)
+    wide = M.StreamingMosaic(index, 5, 256, **kw)                # 80 rows per block: the tile search
+    narrow = M.StreamingMosaic(index, 5, 32, **kw)               # 10 rows: the few-query search
+    assert wide.n_streams * wide.frames_per_block > M.SMALL_T_MAX >= narrow.n_streams * narrow.frames_per_block
+    assert all(torch.equal(a, b) for a, b in zip(_run(wide, x), _run(narrow, x)))
+
+
+def test_greedy_selection_follows_the_oracle_across_blocks():
+    from rawaudiovae_kelsey_amd.stream import window_values
+    M = _M()
+    S, hop, block, k = 64, 16, 32, 8
+    index = _index(_model(seed=5), hop)
+    sm = M.StreamingMosaic(index, 2, block, hop=hop, k=k, mode="grains", window="hann", continuity=0.5)
+    n_blocks = 10
+    x = _signal(np.random.default_rng(4), 2, n_blocks * block)
+    weights = {b: (0.5, 0.5) for b in range(n_blocks)}
+    for b in range(4, n_blocks):
+        weights[b] = (3.0, 0.0)                                  # a weight change between blocks
+    weights[8] = (float("nan"), -2.0)                            # not finite and >= 0: counts as 0
+
+    def before(b):
+        sm.weight.copy_(torch.tensor(weights[b], device="cuda"))
+        # block 6 of stream 1 has no candidates: a NaN query row matches nothing
+        sm.offset[1, 0] = float("nan") if b == 6 else 0.0
+
+    y, idx, dist, choice = [t.cpu().numpy() for t in _run(sm, x, before_block=before)]
+    mu, next_of = index.mu.cpu().numpy(), index.successor(1)
+    fb = block // hop
+    assert np.all(idx[1, 6 * fb:7 * fb] == -1) and np.all(choice[1, 6 * fb:7 * fb] == -1)
+    w = window_values(S, "hann")
+    moved = 0
+    for s in range(2):
+        per_row = np.repeat([weights[b][s] for b in range(n_blocks)], fb)
+        slot, want, _, _ = LO.greedy(idx[s], dist[s], mu, next_of, per_row)
+        assert np.array_equal(choice[s], want), np.argwhere(choice[s] != want)[:5]
+        got_slot = np.where(choice[s] >= 0, (idx[s] == choice[s][:, None]).argmax(1), -1)
+        assert np.array_equal(got_slot, slot)
+        moved += int((slot > 0).sum())
+        grains = O.gather_mean(index.audio.cpu().numpy(), index.row_start, choice[s][:, None], S)
+        assert np.array_equal(y[s].view(np.int32), O.ola(grains, hop, y.shape[1], w).view(np.int32))
+    assert moved > 0                                             # the weight did change choices
+
+
+def test_graph_replay_equals_eager_and_sees_control_edits():
+    from rawaudiovae_kelsey_amd._lib import RvError
+    M = _M()
+    m = _model(seed=6)
+    index = _index(m, 16)
+    kw = dict(hop=16, k=4, mode="decode", window="hann", continuity=0.5)
+    x = _signal(np.random.default_rng(5), 2, 32 * 8)
+    eager, graph = M.StreamingMosaic(index, 2, 32, **kw), M.StreamingMosaic(index, 2, 32, **kw)
+    with pytest.raises(RvError):
+        graph.replay(x[:, :32])
+    graph.capture()
+    graph.reset()
+
+    def edit(sm):
+        def before(b):
+            if b == 3:
+                sm.offset[0] += 0.75
+            if b == 5:
+                sm.weight.fill_(4.0)
+        return before
+
+    a = _run(eager, x, before_block=edit(eager))
+    b = _run(graph, x, replay=True, before_block=edit(graph))
+    assert all(torch.equal(p, q) for p, q in zip(a, b))
+    # the offset took effect: the last block's candidates are those of mu * scale + offset with the edited offset
+    mu_last = graph._sv.last_latents()[0]
+    q = (mu_last * graph.scale[:, None, :] + graph.offset[:, None, :]).reshape(-1, index.L)
+    assert float(graph.offset[0, 0]) == 0.75 and _same(M.knn_topk(q, index.mu, 4),
+                                                       (b[1][:, -2:].reshape(-1, 4), b[2][:, -2:].reshape(-1, 4)))
+    # ... and the weight: the choices are the oracle's under 0.5 up to block 4 and 4.0 from block 5 on
+    mu, next_of = index.mu.cpu().numpy(), index.successor(1)
+    for s in range(2):
+        want = LO.greedy(b[1][s].cpu().numpy(), b[2][s].cpu().numpy(), mu, next_of, np.repeat([0.5] * 5 + [4.0] * 3, 2))[1]
+        assert np.array_equal(b[3][s].cpu().numpy(), want)
+    plain = _run(M.StreamingMosaic(index, 2, 32, **kw), x)
+    assert all(torch.equal(p[:, :3 * p.shape[1] // 8], q[:, :3 * q.shape[1] // 8]) for p, q in zip(plain, a))
+    assert not torch.equal(plain[0], a[0])
+    old = m.fc3.weight
+    m.fc3.weight = torch.nn.Parameter(old.detach().clone())
+    with pytest.raises(RvError, match="replaced"):
+        graph.replay(x[:, :32])
+    m.fc3.weight = old
+    graph.replay(x[:, :32])
+
+
+def test_cli_live_block_writes_what_the_api_gives(tmp_path):
+    from rawvae.model import VAE
+    from rawaudiovae_kelsey_amd import data as D
+    S, H, L, sr = 64, 128, 8, 8000
+    torch.manual_seed(3)
+    model = VAE(S, H, L)
+    torch.save({"epoch": 1, "state_dict": model.state_dict(), "optimizer": {}}, tmp_path / "ckpt_00001")
+    (tmp_path / "tiny.ini").write_text("[audio]\nsampling_rate = %d\nhop_length = 8\nsegment_length = %d\n"
+                                       "[VAE]\nlatent_dim = %d\nn_units = %d\n" % (sr, S, L, H))
+    corpus = tmp_path / "corpus"
+    corpus.mkdir()
+    rng = np.random.default_rng(4)
+    waves = _waves(rng, [400, 777, 1024])
+    for i, w in enumerate(waves):
+        D.write_wav(corpus / ("c%d.wav" % i), w, sr)
+    target = (0.3 * rng.standard_normal(999)).astype(np.float32)
+    D.write_wav(tmp_path / "t.wav", target, sr)
+    run = [sys.executable, os.path.join(REPO, "mosaic.py"), "--config", str(tmp_path / "tiny.ini"), "--checkpoint",
+           str(tmp_path / "ckpt_00001"), "--corpus", str(corpus), "--target", str(tmp_path / "t.wav"), "--out",
+           str(tmp_path / "out.wav"), "--hop", "16", "--k", "3", "--mode", "grains", "--window", "hann", "--live-block",
+           "256"]
+    r = subprocess.run(run, check=True, timeout=300, cwd=str(tmp_path), capture_output=True, text=True)
+    assert ", live, block 256, streams 1" in r.stdout and "greedy" not in r.stdout
+    y, got_sr = D.read_wav(tmp_path / "out.wav")
+    assert got_sr == sr and y.size == target.size
+    index = _M().LatentIndex(model.cuda().eval(), hop=16)
+    for i, w in enumerate(waves):
+        index.add(w, "c%d.wav" % i)
+    sm = _M().StreamingMosaic(index, 1, 256, hop=16, k=3, mode="grains", window="hann")
+    n_blocks = -(-(target.size + sm.latency) // 256)
+    x = np.zeros((1, n_blocks * 256), np.float32)
+    x[0, :target.size] = target
+    want = _run(sm, torch.from_numpy(x).cuda())[0][0, sm.latency:sm.latency + target.size].cpu().numpy()
+    assert np.array_equal(y, want)
+    # ... which is the offline result from where the zero prefix ends (up to the blocks' zero padding at the end)
+    off = index.mosaic(target, k=3, hop=16, mode="grains", window="hann")
+    assert y.shape == tuple(off.shape)
+    r = subprocess.run(run + ["--continuity", "0.5", "--streams", "2"], check=True, timeout=300, cwd=str(tmp_path),
+                       capture_output=True, text=True)
+    assert ", live, greedy, block 256, streams 2, continuity 0.5, continuing " in r.stdout
+    y2, _ = D.read_wav(tmp_path / "out.wav")
+    assert y2.size == target.size and np.all(np.isfinite(y2))

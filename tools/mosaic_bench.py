@@ -2,6 +2,7 @@
 """Time the mosaicing kNN search (rv_mosaic RV_MOSAIC_KNN, csrc/mosaic.hip) and one whole LatentIndex.mosaic() call.
 
     python tools/mosaic_bench.py [--reps 5] [--path] [--out build/mosaic_bench.json]
+    python tools/mosaic_bench.py --live [--reps 30] [--summary profiles/mosaic_live_summary.txt]
 
 Search shapes (T, N, L, k): one minute of target at hop 128 (20 700 frames) and one second (344 frames), both against
 one hour of corpus at hop 128 (1.24 M frames), latent_dim 256, k = 4.  Per shape: device time (events around `reps`
@@ -13,6 +14,14 @@ math) the bound is about 39 T terms/s packed and 20 T terms/s unpacked -- spec-s
 L = 256, k = 16) beside the search of the same shape: the transition costs (RV_MOSAIC_TRANSITION, judged against HBM
 rate: 2 k L 4 bytes of gathered latent rows per target row), the forward pass and the backtrack (one wave each; the
 time per row is the length of the dependent chain).  The candidates are the search's own, on random data.
+
+--live (alone: nothing else is timed): the live path, every figure from HIP events around `reps` replays of a captured
+graph after a warm-up.  (1) The few-query search (RV_MOSAIC_KNN_SMALL) against RV_MOSAIC_KNN, alternating in one
+process, for T in {1, 4, 16, 64}, N in {124 000, 1 240 000}, L = 256, k in {4, 16}; the best of three rounds each, and
+the corpus bytes (N L 4) per second of the few-query kernel.  (2) One StreamingMosaic.replay() per block for
+n_streams x hop x block in {1x128x128, 1x256x256, 1x256x1024, 16x256x1024}, grains and decode, k = 4, continuity 0.5,
+against corpora of 6 872, 124 000 and 1 240 000 frames (random audio in 8 files, indexed at hop 128 by a
+VAE(1024, 2048, 256) with random weights), beside the block's duration at 44.1 kHz.
 
 mosaic(): a VAE(1024, 2048, 256) with random weights, a 40 s corpus in 8 files and a 5 s target at hop 256, k = 4,
 grains and decode, wall time of the call including the target's encoder pass (the corpus is indexed beforehand).
@@ -112,12 +121,136 @@ def bench_mosaic(reps):
     return out
 
 
+def replay_ms(launch, reps, rounds=3):
+    for _ in range(5):
+        launch()
+    torch.cuda.synchronize()
+    best = float("inf")
+    for _ in range(rounds):
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(reps):
+            launch()
+        t1.record()
+        t1.synchronize()
+        best = min(best, t0.elapsed_time(t1) / reps)
+    return best
+
+
+def captured(fn):
+    """fn() (which enqueues on the current stream) as a graph -> a callable that replays it on the current stream."""
+    from rawaudiovae_kelsey_amd.engine import Graph
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = Graph(side)
+    with torch.cuda.stream(side):
+        with g:
+            fn()
+    torch.cuda.current_stream().wait_stream(side)
+    return lambda: g.launch(torch.cuda.current_stream())
+
+
+def bench_live_search(reps):
+    from rawaudiovae_kelsey_amd import _lib
+    rows = []
+    g = torch.Generator(device="cuda").manual_seed(0)
+    for N in (124000, 1240000):
+        c = torch.randn(N, 256, device="cuda", generator=g)
+        for k in (4, 16):
+            for T in (1, 4, 16, 64):
+                q = torch.randn(T, 256, device="cuda", generator=g)
+                launches, outs = {}, {}
+                for name, op, small in (("small", _lib.MOSAIC_KNN_SMALL, True), ("tile", _lib.MOSAIC_KNN, False)):
+                    idx = torch.empty((T, k), dtype=torch.int32, device="cuda")
+                    dist = torch.empty((T, k), dtype=torch.float32, device="cuda")
+                    nbytes = M.knn_workspace_bytes(T, N, 256, k, small=small)
+                    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device="cuda")
+                    outs[name] = (idx, dist, ws)
+                    launches[name] = captured(lambda op=op, idx=idx, dist=dist, ws=ws, nbytes=nbytes: M._call(
+                        op, T=T, N=N, L=256, k=k, q=M.ptr(q), c=M.ptr(c), idx=M.ptr(idx), dist=M.ptr(dist), ws=M.ptr(ws),
+                        ws_bytes=nbytes))
+                ms = {"small": float("inf"), "tile": float("inf")}
+                for _ in range(3):                                # alternating
+                    for name in ("small", "tile"):
+                        ms[name] = min(ms[name], replay_ms(launches[name], reps, rounds=1))
+                same = bool(torch.equal(outs["small"][0], outs["tile"][0])
+                            and torch.equal(outs["small"][1].view(torch.int32), outs["tile"][1].view(torch.int32)))
+                rows.append(dict(N=N, k=k, T=T, small_ms=round(ms["small"], 4), tile_ms=round(ms["tile"], 4),
+                                 small_tb_per_s=round(N * 256 * 4 * -(-T // 16) / (ms["small"] * 1e-3) / 1e12, 3),
+                                 same_bits=same))
+        del c
+    return rows
+
+
+def bench_live_blocks(reps):
+    from rawvae.model import VAE
+    torch.manual_seed(0)
+    m = VAE(1024, 2048, 256).cuda().eval()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rows = []
+    for n_frames in (6872, 124000, 1240000):
+        index = M.LatentIndex(m, hop=128)
+        per_file = n_frames // 8
+        for i in range(8):
+            frames = per_file + (n_frames - 8 * per_file if i == 7 else 0)
+            index.add(torch.randn((frames - 1) * 128 + 1024, device="cuda", generator=g) * 0.3, "c%d" % i)
+        assert len(index) == n_frames
+        for n_streams, hop, block in ((1, 128, 128), (1, 256, 256), (1, 256, 1024), (16, 256, 1024)):
+            for mode in ("grains", "decode"):
+                sm = M.StreamingMosaic(index, n_streams, block, hop=hop, k=4, mode=mode, window="hann",
+                                       continuity=0.5).capture()
+                sm.graph_input.copy_(torch.randn(n_streams, block, device="cuda", generator=g) * 0.3)
+                ms = replay_ms(sm.replay, reps)
+                budget = block / 44100.0 * 1e3
+                rows.append(dict(N=n_frames, n_streams=n_streams, hop=hop, block=block, mode=mode,
+                                 rows=n_streams * block // hop, ms=round(ms, 4), block_ms=round(budget, 3),
+                                 meets=bool(ms < budget)))
+                del sm
+        del index
+        torch.cuda.empty_cache()
+    return rows
+
+
+def live_report(search, blocks, device):
+    out = ["live mosaicing on %s (tools/mosaic_bench.py --live): HIP events around graph replays after a warm-up" % device,
+           "", "few-query search (RV_MOSAIC_KNN_SMALL) against RV_MOSAIC_KNN, L = 256, best of three alternating rounds",
+           "%9s %3s %3s %10s %10s %8s %14s %5s" % ("N", "k", "T", "small ms", "tile ms", "tile/sm", "small TB/s read",
+                                                    "bits")]
+    for r in search:
+        out.append("%9d %3d %3d %10.4f %10.4f %8.2f %14.3f %5s" % (
+            r["N"], r["k"], r["T"], r["small_ms"], r["tile_ms"], r["tile_ms"] / r["small_ms"], r["small_tb_per_s"],
+            "same" if r["same_bits"] else "DIFF"))
+    out += ["", "one StreamingMosaic.replay() per block, k = 4, continuity 0.5, Hann window, VAE(1024, 2048, 256)",
+            "%9s %8s %5s %6s %5s %7s %10s %10s %6s" % ("N", "streams", "hop", "block", "rows", "mode", "ms/block",
+                                                      "block ms", "meets")]
+    for r in blocks:
+        out.append("%9d %8d %5d %6d %5d %7s %10.4f %10.3f %6s" % (
+            r["N"], r["n_streams"], r["hop"], r["block"], r["rows"], r["mode"], r["ms"], r["block_ms"],
+            "yes" if r["meets"] else "NO"))
+    return "\n".join(out) + "\n"
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--reps", type=int, default=None)
+    p.add_argument("--live", action="store_true", help="time the live path only (few-query search, replay per block)")
+    p.add_argument("--summary", default=None, help="--live: also write the tables to this text file")
     p.add_argument("--out", default=None)
     p.add_argument("--path", action="store_true", help="also time the unit selection beside the search at k = 16")
     a = p.parse_args(argv)
+    if a.live:
+        reps = a.reps or 30
+        res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), live_search=bench_live_search(reps),
+                   live_blocks=bench_live_blocks(reps))
+        text = live_report(res["live_search"], res["live_blocks"], res["device"])
+        print(text, end="")
+        for path, body in ((a.summary, text), (a.out, json.dumps(res, indent=1))):
+            if path:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return res
+    a.reps = a.reps or 5
     res = dict(device=torch.cuda.get_device_name(0), host=platform.node(),
                search=[bench_search(*s, a.reps) for s in SHAPES], mosaic=bench_mosaic(a.reps))
     if a.path:
