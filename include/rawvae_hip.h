@@ -449,13 +449,32 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  *     next_of[prev] outside [0, N): the lowest j with idx[t, j] in [0, N).  Otherwise the argmin over those j of
  *     dist[t, j] + fl(w * D(c[next_of[prev]], c[idx[t, j]])), D the search's distance, the product rounded before the
  *     add, strict < in ascending j, a NaN cost skipped.  choice[t] = that idx[t, j] = the new prev; -1 when no j is
- *     left.  The frame is the chosen corpus frame alone.  This is the lag-0 rule, not PATH_FORWARD's Viterbi search;
- *     with k = 1 both choose the same frames.
+ *     left.  The frame is the chosen corpus frame alone.  This is the lag-0 rule, not PATH_FORWARD's Viterbi search
+ *     (`rows` below buys look-ahead); with k = 1 both choose the same frames.
  *   mode RV_LIVE_GRAINS: frames from the corpus audio src [src_len] at row_start [N]; RV_LIVE_DECODE: the mean (or the
  *     chosen row) of c through fc3 and fc4.
+ *   rows = D, the lag in frames, 0 <= D <= 64 (read by LIVE, LIVE_DRAIN, LIVE_WORKSPACE and LIVE_RESET; D > 0 needs
+ *     weight): fixed-lag Viterbi selection.  D = 0 is the greedy rule above: the same launches, workspace and bits.
+ *     Per stream the workspace keeps prev and the PENDING rows: the frames searched but not yet committed, oldest
+ *     first, at most D + 1, each with its idx[k], dist[k] and the unweighted transitions [k, k] from the row before it.
+ *     Window solve: commits the oldest pending row a, given the pending rows a..b.  Row a's scores are the greedy
+ *     rule's expression: prev < 0, or next_of[prev] outside [0, N): score[j] = dist[a, j]; otherwise score[j] =
+ *     dist[a, j] + fl(w * D(c[next_of[prev]], c[idx[a, j]])); +inf where idx[a, j] is outside [0, N) or the value is NaN.
+ *     Rows a+1..b follow PATH_FORWARD's row rule with lambda = w over TRANSITION's trans (a row where no new[j] is
+ *     finite starts a new sequence), end = the lowest-j argmin of row b's scores, and the walk back to row a is
+ *     PATH_BACKTRACK's.  The committed frame = idx[a, slot], -1 when row a has no slot; it becomes prev and row a
+ *     leaves.  w = weight[stream] as read by the call, for every row of the window.
+ *     Per new frame: it joins the pending rows; with D + 1 pending one window solve commits a frame, otherwise
+ *     (the first D frames after a reset) nothing is committed.  choice[t] = the frame committed at new frame t, which
+ *     is frame t - D's, or -1; the block is synthesised from choice, so the audio is D * hop samples later than at
+ *     D = 0, and a -1 adds what a frame without candidates adds.  idx / dist are the new frames', as at D = 0.
+ * RV_MOSAIC_LIVE_DRAIN (rows = D > 0): one block that plays out pending rows: no encoder, no search, no new row; per
+ *   stream up to F window solves on the shrinking window (choice as above, -1 once nothing is pending), then the
+ *   synthesis and rv_stream_process's overlap-add, history roll and frame count as for a block of input: live->x must
+ *   be a block of zeros.  prev is kept and RV_MOSAIC_LIVE may follow.
  * RV_MOSAIC_LIVE_WORKSPACE: the bytes of ws (device; RV_MOSAIC_LIVE_RESET before the first block) for live's extents
- * and (N, L, k, splits) in d->ws_bytes; launches nothing.  RV_MOSAIC_LIVE_RESET: rv_stream_reset(live, which) and
- * prev = -1 for stream `which` (-1: every stream). */
+ * and (N, L, k, splits, rows) in d->ws_bytes; launches nothing.  RV_MOSAIC_LIVE_RESET: rv_stream_reset(live, which),
+ * prev = -1 and no pending rows for stream `which` (-1: every stream). */
 #define RV_MOSAIC_KNN 0
 #define RV_MOSAIC_KNN_WORKSPACE 1
 #define RV_MOSAIC_GATHER_MEAN 2
@@ -469,6 +488,7 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_MOSAIC_LIVE 10
 #define RV_MOSAIC_LIVE_WORKSPACE 11
 #define RV_MOSAIC_LIVE_RESET 12
+#define RV_MOSAIC_LIVE_DRAIN 13
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
 struct rv_stream_desc;
@@ -492,7 +512,7 @@ typedef struct rv_mosaic_desc {
   const float* window;
   long n_out;
   const int* next_of;            /* TRANSITION [N] */
-  long row0, rows;               /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T */
+  long row0, rows;               /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T; LIVE ops: rows = the lag */
   float* trans;                  /* [rows, k, k]: TRANSITION output, PATH_FORWARD input */
   float lam;                     /* PATH_FORWARD: lambda, the weight of the transition costs */
   int* slot;                     /* PATH_BACKTRACK [T] */

@@ -16,9 +16,12 @@ nearest corpus frames in the model's latent space, and the result is overlap-add
                      the hop), the tail zero-padded to a whole block; the output drops the S - hop samples of latency
                      and is cut to the target's length, so it lines up with the offline result.  With --continuity X
                      one candidate per frame is chosen by the greedy rule (against the previous choice only), not by
-                     the Viterbi search
+                     the Viterbi search over the whole target; --lag buys look-ahead
   --streams M        with --live-block: cut the target into M consecutive parts and run them as M parallel streams,
                      each starting from silence (default 1)
+  --lag N            with --live-block and --continuity X > 0: N frames of look-ahead, 0..64 (default 0: the greedy
+                     rule).  Every frame is chosen by a Viterbi search over itself and the N frames after it; the live
+                     output comes N * hop samples later, which the file drops as well
 
 The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
 values, an empty corpus, unreadable wavs or a --k above the number of corpus frames raise ValueError naming the flag or
@@ -64,6 +67,7 @@ def parse_args(argv=None):
     p.add_argument("--max-rows", default="16384", help="target frames per chunk")
     p.add_argument("--live-block", default=None, help="samples per block of the live path (default: offline)")
     p.add_argument("--streams", default=None, help="parallel streams of the live path (default 1)")
+    p.add_argument("--lag", default=None, help="frames of look-ahead of the live path's unit selection (0..64, default 0)")
     args = p.parse_args(argv)
     args.live_block = None if args.live_block is None else _int_flag("live-block", args.live_block, 1)
     if args.streams is not None and args.live_block is None:
@@ -73,6 +77,15 @@ def parse_args(argv=None):
     if args.k > 16:
         raise ValueError("--k %d: at most 16" % args.k)
     args.continuity = _weight_flag("continuity", args.continuity)
+    if args.lag is not None:
+        if args.live_block is None:
+            raise ValueError("--lag %s: needs --live-block" % args.lag)
+        args.lag = _int_flag("lag", args.lag, 0)
+        if args.lag > 64:
+            raise ValueError("--lag %d: at most 64" % args.lag)
+        if args.lag > 0 and args.continuity == 0:
+            raise ValueError("--lag %d: needs --continuity > 0" % args.lag)
+    args.lag = args.lag or 0
     args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
     args.max_rows = _int_flag("max-rows", args.max_rows, 1)
     if args.mode not in ("grains", "decode"):
@@ -170,7 +183,9 @@ def main(argv=None):
 def live_mosaic(index, target, block, hop, n_streams=1, **kw):
     """The target through StreamingMosaic in blocks of `block` -> (y [target.size] numpy, idx [T, k], dist [T, k],
     choice [T]) with T the frames of all streams, stream after stream.  The target is cut into n_streams consecutive
-    parts; every part is zero-padded to whole blocks that also flush the S - hop samples of latency."""
+    parts; every part is zero-padded to whole blocks that also flush the S - hop samples of latency.  With lag=N the
+    frames still held back are drained, the output is cut N * hop samples later, and choice[t] is the frame committed
+    for frame t (N frames after its candidates were found)."""
     import numpy as np
     import torch
     from rawaudiovae_kelsey_amd.mosaic import StreamingMosaic
@@ -188,16 +203,28 @@ def live_mosaic(index, target, block, hop, n_streams=1, **kw):
         ys.append(sm.process(x[:, b * block:(b + 1) * block]))
         i, d, c = sm.last_matches()
         idxs.append(i.clone()), dists.append(d.clone()), choices.append(c.clone())
-    y = torch.cat(ys, 1)[:, sm.latency:sm.latency + part].reshape(-1)[:n].cpu().numpy()
+    for b in range(-(-sm.lag_samples // block)):                 # every frame fed is committed and played
+        ys.append(sm.drain())
+        choices.append(sm.last_matches()[2].clone())
+    late = sm.latency + sm.lag_samples
+    y = torch.cat(ys, 1)[:, late:late + part].reshape(-1)[:n].cpu().numpy()
     k = idxs[0].shape[-1]
+    frames = n_blocks * sm.frames_per_block
+    choice = torch.cat(choices, 1)[:, sm.lag:sm.lag + frames]
     return (y, torch.cat(idxs, 1).reshape(-1, k).cpu().numpy(), torch.cat(dists, 1).reshape(-1, k).cpu().numpy(),
-            torch.cat(choices, 1).reshape(-1).cpu().numpy())
+            choice.reshape(-1).cpu().numpy())
+
+
+def _live_rule(args):
+    if args.continuity > 0:
+        return "live, lag %d" % args.lag if args.lag > 0 else "live, greedy"
+    return "live"
 
 
 def run_live(args, index, target, hop, sr, n_files):
     from rawaudiovae_kelsey_amd import data as D
     y, idx, dist, choice = live_mosaic(index, target, args.live_block, hop, args.streams, k=args.k, mode=args.mode,
-                                       window=args.window, continuity=args.continuity)
+                                       window=args.window, continuity=args.continuity, lag=args.lag)
     D.write_wav(args.out, y, sr)
     slot = None
     if args.continuity > 0:
@@ -206,7 +233,7 @@ def run_live(args, index, target, hop, sr, n_files):
         write_matches(args.matches, index.locate(idx), dist, slot)
     line = ("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s, %s, "
             "block %d, streams %d" % (args.out, y.size, idx.shape[0], len(index), n_files, args.k, args.mode,
-                                      args.window or "none", "live, greedy" if args.continuity > 0 else "live",
+                                      args.window or "none", _live_rule(args),
                                       args.live_block, args.streams))
     if args.continuity > 0:
         line += ", continuity %g, continuing %.4f" % (

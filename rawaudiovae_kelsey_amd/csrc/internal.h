@@ -119,7 +119,8 @@ RV_INTERNAL int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operand
 // The two ends of rv_stream_process (stream.hip) for the live mosaic, which searches the corpus between them.
 // rv_stream_encode: rv_stream_process's checks (no temperature, no eps), its fc1 launch on [history | x] and its heads
 // launch with q [n_streams * F, L] = mu * scale + offset in place of the reparameterised z; *z and *frames receive the
-// stream workspace's latent rows [n_streams * F, L] and decoded frames [n_streams * F, S].
+// stream workspace's latent rows [n_streams * F, L] and decoded frames [n_streams * F, S].  q == NULL: the checks and
+// the two pointers only, nothing is launched (RV_MOSAIC_LIVE_DRAIN).
 // rv_stream_synth: decode != 0: fc3 and fc4 on the latent rows into the frames; then k_stream_ola on the frames.
 RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, float** frames, void* stream);
 RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream);

@@ -7,9 +7,11 @@
 //   RV_MOSAIC_TRANSITION   candidate-to-candidate concatenation costs [rows, k, k] in the search's arithmetic
 //   RV_MOSAIC_PATH_FORWARD / _BACKTRACK   Viterbi unit selection over the k candidates of every row (one wave each)
 //   RV_MOSAIC_KNN_SMALL    RV_MOSAIC_KNN's results for at most 64 query rows: k_knn_small, one thread per corpus row
-//   RV_MOSAIC_LIVE         one block of live audio: the stream's encoder (stream.hip), the search, greedy unit
-//                          selection (k_live_select), gather-mean, then the stream's decoder / overlap-add
-// Layout, split and merge, and the measured figures: DESIGN.md sections 7.5 and 7.6.
+//   RV_MOSAIC_LIVE         one block of live audio: the stream's encoder (stream.hip), the search, unit selection
+//                          (k_live_select: greedy; k_live_lag: Viterbi over a window of lag + 1 frames, committing
+//                          the oldest), gather-mean, then the stream's decoder / overlap-add
+//   RV_MOSAIC_LIVE_DRAIN   one block that plays out the frames a lag still holds back: no encoder, no search
+// Layout, split and merge, and the measured figures: DESIGN.md sections 7.5, 7.6 and 7.7.
 #include <limits.h>
 
 #include "common.h"
@@ -409,6 +411,45 @@ k_ola(const float* __restrict__ frames, long F, long S, long hop, const float* _
 
 // ---- Unit selection over the candidates ("Continuity") ----
 
+// The search's distance, shared by every kernel of the unit selection (k_transition, k_live_select, k_live_lag) so that
+// their costs are k_knn_topk's bit for bit: part = fmaf(d, d, part) in ascending l within tiles of KT, tot += part per
+// tile, from +0.
+__device__ __forceinline__ void sq_acc4(float& part, const f32x4& a, const f32x4& b) {
+#pragma unroll
+  for (int x = 0; x < 4; ++x) {
+    const float d = a[x] - b[x];
+    part = __builtin_fmaf(d, d, part);
+  }
+}
+
+// D(a, b) of two latent rows in global memory, element by element
+__device__ __forceinline__ float row_sq_dist(const float* __restrict__ a, const float* __restrict__ b, long L) {
+  float tot = 0.f;
+  for (long k0 = 0; k0 < L; k0 += KT) {
+    const int n = L - k0 < KT ? (int)(L - k0) : KT;
+    float part = 0.f;
+    for (int kk = 0; kk < n; ++kk) {
+      const float d = a[k0 + kk] - b[k0 + kk];
+      part = __builtin_fmaf(d, d, part);
+    }
+    tot += part;
+  }
+  return tot;
+}
+
+// the same by 16-byte loads: L % 4 == 0 and rows on 16-byte boundaries
+__device__ __forceinline__ float row_sq_dist4(const float* __restrict__ a, const float* __restrict__ b, long L) {
+  float tot = 0.f;
+  for (long k0 = 0; k0 < L; k0 += KT) {
+    const int n = L - k0 < KT ? (int)(L - k0) : KT;
+    float part = 0.f;
+    for (int kk = 0; kk < n; kk += 4)
+      sq_acc4(part, *reinterpret_cast<const f32x4*>(a + k0 + kk), *reinterpret_cast<const f32x4*>(b + k0 + kk));
+    tot += part;
+  }
+  return tot;
+}
+
 // k_transition stages latent rows in LDS tile by tile (KT elements); a row stride of KT + 4 floats keeps rows 16-byte
 // aligned and spreads the 16 candidate rows a wave reads with b128 over all 64 banks.
 constexpr int TROW = KT + 4;
@@ -494,11 +535,7 @@ k_transition(const float* __restrict__ mu, long N, long L, const int* __restrict
       for (int kk = 0; kk < KT; kk += 4) {
         const f32x4 xa = *reinterpret_cast<const f32x4*>(&V[ra][kk]);
         const f32x4 wb = *reinterpret_cast<const f32x4*>(&V[rb][kk]);
-#pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          const float d = xa[x] - wb[x];
-          part = __builtin_fmaf(d, d, part);
-        }
+        sq_acc4(part, xa, wb);
       }
       tot += part;
     }
@@ -561,6 +598,50 @@ __device__ __forceinline__ void path_min_j(float& v, int& i) {
   path_take(v, i, __shfl_xor(v, 32, 64), __shfl_xor(i, 32, 64));
 }
 
+// The forward rule's pieces, shared by k_path_forward and k_live_lag; lane = 4 j + q as described below.
+// fl(lambda * trans), never 0 * inf
+__device__ __forceinline__ float path_weigh(float lam, float tr) { return tr < INFINITY ? mul_rn(lam, tr) : INFINITY; }
+// a candidate's own cost: +inf for a missing candidate or NaN
+__device__ __forceinline__ float path_target(bool jv, int ci, float d) { return (jv && ci >= 0 && d == d) ? d : INFINITY; }
+// hands every lane the new scores of its 4 predecessors (raw, not yet reduced by their minimum) and the row's
+// (minimum, lowest-j argmin)
+__device__ __forceinline__ void path_spread(float nw, int j, int q, float (&raw)[4], float& m, int& mj) {
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) raw[ii] = __shfl(nw, (4 * q + ii) * 4, 64);
+  m = nw;
+  mj = j;
+  path_min_j(m, mj);
+}
+// One row: p = the weighted transitions from this lane's 4 predecessors into column j, tg = column j's own cost.
+// Updates the carried (nw, raw, m, mj) and returns back[t, j] (PATH_NONE where the row starts a sequence: `first`, or
+// no new[j] finite).
+__device__ __forceinline__ int path_step(const float (&p)[4], float tg, bool first, int j, int q, float& nw,
+                                         float (&raw)[4], float& m, int& mj) {
+  const bool fin = m < INFINITY;
+  float best = INFINITY;
+  int bi = PATH_NONE;
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    const float c = (fin ? raw[ii] - m : raw[ii]) + p[ii];   // +inf where s[i] or the transition is
+    if (c < best) { best = c; bi = 4 * q + ii; }
+  }
+  path_min_q(best, bi);
+  nw = bi != PATH_NONE ? tg + best : INFINITY;
+  int bk = nw < INFINITY ? bi : PATH_NONE;
+  path_spread(nw, j, q, raw, m, mj);
+  if (first || !(m < INFINITY)) {   // wave-uniform: the row starts a new sequence
+    nw = tg;
+    bk = PATH_NONE;
+    path_spread(nw, j, q, raw, m, mj);
+  }
+  return bk;
+}
+// the backtrack's step from row t to row t - 1: b = back[t, slot[t]] (PATH_NONE for a row without a slot), e = end[t - 1]
+__device__ __forceinline__ int path_back(int b, int e, int k) {
+  if (b >= k) b = PATH_NONE;
+  return b != PATH_NONE ? b : (e < k ? e : -1);
+}
+
 // The forward pass of rows [row0, row0 + rows): ONE wave, lane = 4 j + q owns column j and the predecessors
 // i = 4 q .. 4 q + 3.  Per row the dependent chain is: 4 adds and compares, 2 DPP steps over q, + dist, 2 DPP and 2
 // shuffle steps over j (minimum and end), while the 4 shuffles that hand every lane its predecessors' new scores run
@@ -603,12 +684,9 @@ k_path_forward(const float* __restrict__ trans, const int* __restrict__ idx, con
   for (int s = 0; s < PATH_PF; ++s) load(s);
   // the carried scores: raw (not yet reduced by their minimum); a call at row 0 starts from nothing
   float nw = (row0 > 0 && jv) ? score[j] : INFINITY;
-  float m = nw;
-  int mj = j;
-  path_min_j(m, mj);
-  float raw[4];
-#pragma unroll
-  for (int ii = 0; ii < 4; ++ii) raw[ii] = __shfl(nw, (4 * q + ii) * 4, 64);
+  float m, raw[4];
+  int mj;
+  path_spread(nw, j, q, raw, m, mj);
   unsigned char* bp = back + row0 * k + j;
   float* mp = btr + row0 * k + j;
   for (long base = 0; base < rows; base += PATH_PF) {
@@ -621,39 +699,14 @@ k_path_forward(const float* __restrict__ trans, const int* __restrict__ idx, con
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
           tr[ii] = iv[ii] ? trr[s][ii] : INFINITY;
-          p[ii] = tr[ii] < INFINITY ? mul_rn(lam, tr[ii]) : INFINITY;   // never 0 * inf
+          p[ii] = path_weigh(lam, tr[ii]);
         }
-        const float d = tdr[s];
-        float tg = (jv && tir[s] >= 0 && d == d) ? d : INFINITY;
+        float tg = path_target(jv, tir[s], tdr[s]);
         // pin tg here: computed any later, the ring slot's old value would outlive the load that refills it, and the
         // ring would be copied (behind a full wait) at the loop's back edge
         asm volatile("" : "+v"(tg));
         load(s);
-        const bool fin = m < INFINITY;
-        float best = INFINITY;
-        int bi = PATH_NONE;
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-          const float c = (fin ? raw[ii] - m : raw[ii]) + p[ii];   // +inf where s[i] or the transition is
-          if (c < best) { best = c; bi = 4 * q + ii; }
-        }
-        path_min_q(best, bi);
-        nw = bi != PATH_NONE ? tg + best : INFINITY;
-        int bk = nw < INFINITY ? bi : PATH_NONE;
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) raw[ii] = __shfl(nw, (4 * q + ii) * 4, 64);
-        m = nw;
-        mj = j;
-        path_min_j(m, mj);
-        if (t == 0 || !(m < INFINITY)) {   // wave-uniform: the row starts a new sequence
-          nw = tg;
-          bk = PATH_NONE;
-#pragma unroll
-          for (int ii = 0; ii < 4; ++ii) raw[ii] = __shfl(nw, (4 * q + ii) * 4, 64);
-          m = nw;
-          mj = j;
-          path_min_j(m, mj);
-        }
+        const int bk = path_step(p, tg, t == 0, j, q, nw, raw, m, mj);
         // the lane that holds the chosen predecessor's transition cost writes (t, j)
         if (jv && q == (bk == PATH_NONE ? 0 : bk >> 2)) {
           const int w = bk & 3;
@@ -699,9 +752,7 @@ k_path_backtrack(const int* __restrict__ idx, const float* __restrict__ dist, lo
         slotL[x] = c;
         if (c0 + x > 0) {
           const int e = endL[x];
-          int b = c < 0 ? PATH_NONE : backL[x * k + c];
-          if (b >= k) b = PATH_NONE;
-          c = b != PATH_NONE ? b : (e < k ? e : -1);
+          c = path_back(c < 0 ? PATH_NONE : backL[x * k + c], e, k);
         }
       }
       curL = c;
@@ -744,6 +795,31 @@ __device__ __forceinline__ float add_rn(float a, float b) {
   return a + b;
 }
 
+// The cost of entering a frame from the stream's previous choice p, lane j < k (own) holding candidate ci = idx[t, j]
+// and dp = &dist[t, j]: succ = next_of[p] (-1 when p or it lies outside [0, N)); with a successor,
+// cost = dist + fl(w * D(c[succ], c[ci])) in the search's arithmetic.  Returns whether the candidate stands: a corpus
+// row whose cost is not NaN.
+__device__ __forceinline__ bool live_entry(const float* __restrict__ c, long N, long L, const int* __restrict__ next_of,
+                                           int p, int ci, const float* __restrict__ dp, float w, bool own, int vec,
+                                           int& succ, float& cost) {
+  bool valid = own && ci >= 0 && ci < N;
+  succ = -1;
+  if (p >= 0 && p < N) succ = next_of[p];
+  if (succ < 0 || succ >= N) succ = -1;
+  cost = 0.f;
+  if (succ >= 0) {   // wave-uniform
+    const float* a = c + (long)succ * L;
+    const float* b = c + (long)(valid ? ci : 0) * L;
+    const float tot = vec ? row_sq_dist4(a, b, L) : row_sq_dist(a, b, L);
+    cost = add_rn(*dp, mul_rn(w, tot));
+    valid = valid && cost == cost;
+  }
+  return valid;
+}
+
+// a weight that is not finite and >= 0 counts as 0
+__device__ __forceinline__ float live_weight(float w) { return (w >= 0.f && w < INFINITY) ? w : 0.f; }
+
 // One wave per stream, its F frames in order; lane j owns candidate j of the frame.  prev < 0 (or without a successor
 // in the table): the lowest j whose candidate is a corpus row.  Otherwise lane j walks D(c[next_of[prev]], c[idx[r, j]])
 // in the search's arithmetic and the wave takes the least dist + fl(w * D), strict < in ascending j, NaN skipped.
@@ -753,33 +829,14 @@ k_live_select(const float* __restrict__ c, long N, long L, const int* __restrict
               int* __restrict__ choice) {
   const long s = blockIdx.x;
   const int lane = threadIdx.x, jl = lane < k ? lane : k - 1;
-  float w = weight[s];
-  if (!(w >= 0.f && w < INFINITY)) w = 0.f;
+  const float w = live_weight(weight[s]);
   int p = prev[s];
   for (long f = 0; f < F; ++f) {
     const long r = s * F + f;
     const int ci = idx[r * k + jl];
-    bool valid = lane < k && ci >= 0 && ci < N;
-    int succ = -1;
-    if (p >= 0 && p < N) succ = next_of[p];
-    if (succ < 0 || succ >= N) succ = -1;
-    float cost = 0.f;
-    if (succ >= 0) {   // wave-uniform
-      const float* a = c + (long)succ * L;
-      const float* b = c + (long)(valid ? ci : 0) * L;
-      float tot = 0.f;
-      for (long k0 = 0; k0 < L; k0 += KT) {
-        const int n = L - k0 < KT ? (int)(L - k0) : KT;
-        float part = 0.f;
-        for (int kk = 0; kk < n; ++kk) {
-          const float d = a[k0 + kk] - b[k0 + kk];
-          part = __builtin_fmaf(d, d, part);
-        }
-        tot += part;
-      }
-      cost = add_rn(dist[r * k + jl], mul_rn(w, tot));
-      valid = valid && cost == cost;
-    }
+    int succ;
+    float cost;
+    const bool valid = live_entry(c, N, L, next_of, p, ci, dist + r * k + jl, w, lane < k, 0, succ, cost);
     int slot = -1;
     float best = 0.f;
     for (int j = 0; j < k; ++j) {
@@ -791,6 +848,162 @@ k_live_select(const float* __restrict__ c, long N, long L, const int* __restrict
     if (lane == 0) choice[r] = p;
   }
   if (lane == 0) prev[s] = p;
+}
+
+// ---- Live mosaicing with look-ahead: fixed-lag Viterbi unit selection ----
+constexpr int LAG_MAX = 64;   // frames of look-ahead at most: a window holds up to LAG_MAX + 1 rows
+constexpr int LAG_PF = 8;     // ring rows held in registers ahead of the forward pass's dependent chain
+
+// One window solve by ONE wave (all 64 lanes; k_path_forward's layout, lane = 4 j + q): the n pending rows of a stream
+// start at ring row `head`.  The oldest row's scores are live_entry's costs from the previous choice p, the rows after
+// it follow path_step over their raw transitions weighted by w; back and end go to LDS, lane 0 walks them back to the
+// oldest row.  Returns the corpus frame committed for that row (-1: it has no candidate), in every lane.
+__device__ __forceinline__ int lag_solve(const float* __restrict__ c, long N, long L, const int* __restrict__ next_of,
+                                         int k, float w, int p, int vec, const int* ri, const float* rd, const float* rt,
+                                         int head, int n, int R, unsigned char* backL, unsigned char* endL) {
+  const int lane = threadIdx.x & 63, j = lane >> 2, q = lane & 3;
+  const bool jv = j < k;
+  const int jc = jv ? j : k - 1, jl = lane < k ? lane : k - 1;
+  const long kk = (long)k * k;
+  float trr[LAG_PF][4], tdr[LAG_PF];
+  int tir[LAG_PF], ioff[4];
+  bool iv[4];
+#pragma unroll
+  for (int ii = 0; ii < 4; ++ii) {
+    iv[ii] = jv && 4 * q + ii < k;
+    ioff[ii] = (4 * q + ii < k ? 4 * q + ii : k - 1) * k;
+  }
+  // rows 1 .. n - 1 of the window are loaded strictly in order, the ring position wrapping at R; past the last row
+  // (and with n = 1) the position stays on a row of the window: every load reads a valid address
+  int lpos = n > 1 ? (head + 1 == R ? 0 : head + 1) : head, ld = 1;
+  auto load = [&](int s) {
+#pragma unroll
+    for (int ii = 0; ii < 4; ++ii) trr[s][ii] = rt[lpos * kk + ioff[ii] + jc];
+    tdr[s] = rd[lpos * k + jc];
+    tir[s] = ri[lpos * k + jc];
+    ++ld;
+    if (ld < n) lpos = lpos + 1 == R ? 0 : lpos + 1;   // wave-uniform
+  };
+#pragma unroll
+  for (int s = 0; s < LAG_PF; ++s) load(s);
+  // the oldest row: lane l < k owns its candidate l
+  const int ci = ri[head * k + jl];
+  const float* dp = rd + head * k + jl;
+  int succ;
+  float cost;
+  const bool valid = live_entry(c, N, L, next_of, p, ci, dp, w, lane < k, vec, succ, cost);
+  float e = succ >= 0 ? cost : *dp;
+  if (!valid || !(e == e)) e = INFINITY;
+  e = __shfl(e, jc, 64);
+  float nw = jv ? e : INFINITY;
+  float m, raw[4];
+  int mj;
+  path_spread(nw, j, q, raw, m, mj);
+  if (lane == 0) endL[0] = (unsigned char)(m < INFINITY ? mj : PATH_NONE);
+  for (int base = 1; base < n; base += LAG_PF) {
+#pragma unroll
+    for (int s = 0; s < LAG_PF; ++s) {
+      const int r = base + s;
+      if (r < n) {
+        float pw[4];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) pw[ii] = path_weigh(w, iv[ii] ? trr[s][ii] : INFINITY);
+        float tg = path_target(jv, tir[s], tdr[s]);
+        asm volatile("" : "+v"(tg));   // as in k_path_forward: the ring slot is free before its refill is issued
+        load(s);
+        const int bk = path_step(pw, tg, false, j, q, nw, raw, m, mj);
+        if (jv && q == 0) backL[r * KMAX + j] = (unsigned char)bk;
+        if (lane == 0) endL[r] = (unsigned char)(m < INFINITY ? mj : PATH_NONE);
+      }
+    }
+  }
+  // this wave's own LDS stores, in order; the fence keeps the compiler from moving the walk above them
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+  __builtin_amdgcn_wave_barrier();
+  int slot = -1;
+  if (lane == 0) {
+    slot = path_back(PATH_NONE, endL[n - 1], k);
+    for (int r = n - 1; r >= 1; --r) slot = path_back(slot < 0 ? PATH_NONE : backL[r * KMAX + slot], endL[r - 1], k);
+  }
+  slot = __shfl(slot, 0, 64);
+  return slot >= 0 ? ri[head * k + slot] : -1;
+}
+
+// Selection with a lag of R - 1 frames: one workgroup per stream, its frames in order.  The stream's pending rows (idx,
+// dist and the raw transitions from the row before, [R] each) live in a ring in the workspace with (head, count) in
+// `state`; prev is k_live_select's.  push != 0, per new frame: (a) all threads, one per (i, j) pair: the frame's
+// transition row against the last pending row, in k_transition's arithmetic, stored raw beside its idx and dist;
+// (b) wave 0: once R rows are pending, lag_solve commits the oldest.  choice[r] = that corpus frame, -1 while fewer
+// rows are pending.  push == 0 (drain): no new rows; up to F times, lag_solve on the shrinking window while rows are
+// pending, -1 after.  No index is used as an address before it is checked against [0, N).  The ring is written by
+// some threads and read by others across the barriers, so its pointers are not __restrict__.
+__global__ void __launch_bounds__(256)
+k_live_lag(const float* __restrict__ c, long N, long L, const int* __restrict__ next_of, const int* __restrict__ idx,
+           const float* __restrict__ dist, int k, long F, int push, int R, int vec, const float* __restrict__ weight,
+           int* __restrict__ prev, int* __restrict__ state, int* ridx, float* rdist, float* rtrans,
+           int* __restrict__ choice) {
+  __shared__ unsigned char backL[(LAG_MAX + 1) * KMAX];
+  __shared__ unsigned char endL[LAG_MAX + 1];
+  const long s = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int kk = k * k;
+  int* ri = ridx + s * R * k;
+  float* rd = rdist + s * R * k;
+  float* rt = rtrans + s * R * kk;
+  // between calls at most R - 1 rows are pending; anything else in the workspace counts as an empty ring
+  int head = state[2 * s], cnt = state[2 * s + 1];
+  if (head < 0 || head >= R || cnt < 0 || cnt >= R) head = cnt = 0;
+  const float w = live_weight(weight[s]);
+  int p = prev[s];
+  const int pi = tid / k, pj = tid - pi * k;
+  for (long f = 0; f < F; ++f) {
+    const long r = s * F + f;
+    if (push) {
+      const int pos = (head + cnt) % R;   // free: cnt < R here
+      if (tid < kk) {
+        float v = INFINITY;
+        if (cnt > 0) {
+          const int ia = ri[(pos == 0 ? R - 1 : pos - 1) * k + pi], ib = idx[r * k + pj];
+          int succ = -1;
+          if (ia >= 0 && ia < N) succ = next_of[ia];
+          if (succ >= 0 && succ < N && ib >= 0 && ib < N) {
+            const float* a = c + (long)succ * L;
+            const float* b = c + (long)ib * L;
+            const float tot = vec ? row_sq_dist4(a, b, L) : row_sq_dist(a, b, L);
+            if (tot == tot) v = tot;
+          }
+        }
+        rt[pos * kk + tid] = v;
+      }
+      if (tid < k) {
+        ri[pos * k + tid] = idx[r * k + tid];
+        rd[pos * k + tid] = dist[r * k + tid];
+      }
+      ++cnt;
+      __syncthreads();   // the row is in the ring for wave 0, and for the next frame's transitions
+    }
+    if (push ? cnt == R : cnt > 0) {   // uniform over the workgroup
+      if (tid < 64) {
+        p = lag_solve(c, N, L, next_of, k, w, p, vec, ri, rd, rt, head, cnt, R, backL, endL);
+        if (tid == 0) choice[r] = p;
+      }
+      head = head + 1 == R ? 0 : head + 1;
+      --cnt;
+    } else if (tid == 0) {
+      choice[r] = -1;
+    }
+    __syncthreads();   // wave 0 has read the committed row before the next frame overwrites it
+  }
+  if (tid == 0) {
+    prev[s] = p;
+    state[2 * s] = head;
+    state[2 * s + 1] = cnt;
+  }
+}
+
+__global__ void __launch_bounds__(256) k_live_lag_clear(int* __restrict__ state, long n) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < 2 * n) state[i] = 0;
 }
 
 __global__ void __launch_bounds__(256) k_live_clear(int* __restrict__ prev, long n) {
@@ -917,11 +1130,14 @@ int run_knn(const rv_mosaic_desc* d, bool small, hipStream_t st) {
   return RV_OK;
 }
 
-// RV_MOSAIC_LIVE's workspace: prev [n_streams] int32, the query rows [M, L] fp32, the search's partials; every part
-// starts on a 256-byte boundary.  M = n_streams * block / hop rows go to k_knn_small up to SMALL_T_MAX.
+// RV_MOSAIC_LIVE's workspace: prev [n_streams] int32, the query rows [M, L] fp32, the search's partials; with a lag of
+// D = d->rows > 0 frames then the lagged selection's state: (head, count) [n_streams, 2] int32 and the rings of
+// R = D + 1 rows per stream, idx [n_streams, R, k] int32, dist [n_streams, R, k] fp32, trans [n_streams, R, k, k] fp32.
+// Every part starts on a 256-byte boundary.  M = n_streams * block / hop rows go to k_knn_small up to SMALL_T_MAX.
 struct live_ws {
   long M, q, knn, knn_bytes, bytes;
   bool small;
+  long lag, state, ridx, rdist, rtrans;
 };
 int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
   const rv_stream_desc* sd = d->live;
@@ -932,6 +1148,10 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
              sd->block, sd->hop, sd->S);
   RV_REQUIRE(d->L == sd->L, RV_ERR_SHAPE, "rv_mosaic(%s): corpus rows of L=%ld, the model's latent has %ld", op, d->L,
              sd->L);
+  RV_REQUIRE(d->rows >= 0 && d->rows <= LAG_MAX, RV_ERR_SHAPE, "rv_mosaic(%s): lag (rows)=%ld outside [0, %d]", op,
+             d->rows, LAG_MAX);
+  RV_REQUIRE(d->rows == 0 || d->weight, RV_ERR_NULL,
+             "rv_mosaic(%s): lag (rows)=%ld needs unit selection: weight is null", op, d->rows);
   w->M = sd->n_streams * (sd->block / sd->hop);
   w->small = w->M <= SMALL_T_MAX;
   rv_mosaic_desc kd = *d;
@@ -944,6 +1164,15 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
   w->knn = w->q + up(w->M * d->L * 4);
   w->knn_bytes = knn_ws_bytes(w->M, d->k, n_splits);
   w->bytes = w->knn + up(w->knn_bytes);
+  w->lag = d->rows;
+  if (w->lag > 0) {
+    const long rows = sd->n_streams * (w->lag + 1);
+    w->state = w->bytes;
+    w->ridx = w->state + up(sd->n_streams * 8);
+    w->rdist = w->ridx + up(rows * d->k * 4);
+    w->rtrans = w->rdist + up(rows * d->k * 4);
+    w->bytes = w->rtrans + up(rows * d->k * d->k * 4);
+  }
   return RV_OK;
 }
 
@@ -1057,38 +1286,59 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       if (rc) return rc;
       const long first = d->which < 0 ? 0 : d->which, n = d->which < 0 ? NS : 1;
       hipLaunchKernelGGL(k_live_clear, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (int*)d->ws + first, n);
+      if (w.lag > 0)   // nothing pending
+        hipLaunchKernelGGL(k_live_lag_clear, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st,
+                           (int*)((char*)d->ws + w.state) + 2 * first, n);
       RV_CHECK_LAUNCH();
       return RV_OK;
     }
-    case RV_MOSAIC_LIVE: {
+    case RV_MOSAIC_LIVE:
+    case RV_MOSAIC_LIVE_DRAIN: {
+      const bool drain = op == RV_MOSAIC_LIVE_DRAIN;
+      const char* who = drain ? "LIVE_DRAIN" : "LIVE";
       live_ws w;
-      int rc = live_layout(d, "LIVE", &w);
+      int rc = live_layout(d, who, &w);
       if (rc) return rc;
       const rv_stream_desc* sd = d->live;
       const bool decode = d->mode == RV_LIVE_DECODE;
-      RV_REQUIRE(decode || d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED, "rv_mosaic(LIVE): mode %ld", d->mode);
+      RV_REQUIRE(decode || d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED, "rv_mosaic(%s): mode %ld", who, d->mode);
+      RV_REQUIRE(!drain || w.lag > 0, RV_ERR_SHAPE, "rv_mosaic(LIVE_DRAIN): lag (rows)=%ld: nothing is pending without a lag",
+                 d->rows);
       RV_REQUIRE(d->c && d->idx && d->dist && d->ws && (decode || (d->src && d->row_start)) &&
-                     (!d->weight || (d->next_of && d->choice)), RV_ERR_NULL, "rv_mosaic(LIVE): null pointer");
+                     (!d->weight || (d->next_of && d->choice)), RV_ERR_NULL,
+                 "rv_mosaic(%s): null pointer (lag (rows)=%ld; unit selection needs weight, next_of and choice)", who,
+                 d->rows);
       RV_REQUIRE(d->ws_bytes >= w.bytes && ((unsigned long)d->ws & 255) == 0, RV_ERR_SHAPE,
-                 "rv_mosaic(LIVE): workspace of %ld bytes (256-byte aligned), %ld needed", d->ws_bytes, w.bytes);
+                 "rv_mosaic(%s): workspace of %ld bytes (256-byte aligned), %ld needed at lag (rows)=%ld", who, d->ws_bytes,
+                 w.bytes, d->rows);
       RV_REQUIRE(d->N < INT_MAX && (decode || d->src_len >= sd->S), RV_ERR_SHAPE,
-                 "rv_mosaic(LIVE): bad extents N=%ld src_len=%ld", d->N, d->src_len);
+                 "rv_mosaic(%s): bad extents N=%ld src_len=%ld", who, d->N, d->src_len);
       char* ws = (char*)d->ws;
       float *qrows = (float*)(ws + w.q), *z = nullptr, *frames = nullptr;
-      rc = rv_stream_encode(sd, qrows, &z, &frames, stream);
+      rc = rv_stream_encode(sd, drain ? nullptr : qrows, &z, &frames, stream);   // a drain encodes nothing
       if (rc) return rc;
-      rv_mosaic_desc kd = *d;
-      kd.T = w.M;
-      kd.q = qrows;
-      kd.ws = ws + w.knn;
-      kd.ws_bytes = w.knn_bytes;
-      rc = run_knn(&kd, w.small, st);
-      if (rc) return rc;
+      if (!drain) {
+        rv_mosaic_desc kd = *d;
+        kd.T = w.M;
+        kd.q = qrows;
+        kd.ws = ws + w.knn;
+        kd.ws_bytes = w.knn_bytes;
+        rc = run_knn(&kd, w.small, st);
+        if (rc) return rc;
+      }
       const int* sel = d->idx;
       int sel_k = (int)d->k;
       if (d->weight) {
-        hipLaunchKernelGGL(k_live_select, dim3((unsigned)sd->n_streams), dim3(64), 0, st, d->c, d->N, d->L, d->next_of,
-                           d->idx, d->dist, (int)d->k, sd->block / sd->hop, d->weight, (int*)ws, d->choice);
+        if (w.lag > 0) {
+          const int vec = d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0;   // 16-byte loads of latent rows
+          hipLaunchKernelGGL(k_live_lag, dim3((unsigned)sd->n_streams), dim3(256), 0, st, d->c, d->N, d->L, d->next_of,
+                             d->idx, d->dist, (int)d->k, sd->block / sd->hop, drain ? 0 : 1, (int)w.lag + 1, vec, d->weight,
+                             (int*)ws, (int*)(ws + w.state), (int*)(ws + w.ridx), (float*)(ws + w.rdist),
+                             (float*)(ws + w.rtrans), d->choice);
+        } else {
+          hipLaunchKernelGGL(k_live_select, dim3((unsigned)sd->n_streams), dim3(64), 0, st, d->c, d->N, d->L, d->next_of,
+                             d->idx, d->dist, (int)d->k, sd->block / sd->hop, d->weight, (int*)ws, d->choice);
+        }
         sel = d->choice;
         sel_k = 1;
       }

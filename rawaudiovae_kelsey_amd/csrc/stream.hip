@@ -428,6 +428,7 @@ RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, f
   ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);
   *z = w.z;
   *frames = w.dec;
+  if (!q) return RV_OK;
   return stream_encode<false>(d, w, q, (hipStream_t)stream);
 }
 

@@ -22,12 +22,17 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
   transition_costs, best_path             the two steps on their own (RV_MOSAIC_TRANSITION, RV_MOSAIC_PATH_*)
   knn_topk_small(q, c, k)                 knn_topk for at most SMALL_T_MAX query rows by the few-query kernel
                                           (RV_MOSAIC_KNN_SMALL): the same bits
-  StreamingMosaic(index, n_streams, block, hop, k, mode, window, continuity)
+  StreamingMosaic(index, n_streams, block, hop, k, mode, window, continuity, lag)
       live mosaicing: process(x) takes one block of samples per stream and returns the block built from the nearest
       corpus frames, `S - hop` samples late -- StreamingVAE's framing, history and overlap-add around the search
       (RV_MOSAIC_LIVE), state on the device, capture() / replay(x) as one graph.  continuity > 0 selects one candidate
-      per frame by the GREEDY rule (each frame against the previous choice only; not best_path's Viterbi search, which
-      needs the whole target; the two agree for k = 1), weighted by the device tensor `weight` [n_streams].
+      per frame, weighted by the device tensor `weight` [n_streams].  lag = 0: the GREEDY rule (each frame against the
+      previous choice only; not best_path's Viterbi search, which needs the whole target; the two agree for k = 1).
+      lag = D in [1, 64]: fixed-lag Viterbi.  The last D + 1 searched frames wait in a window; every new frame runs
+      best_path's forward rule over the window, entered from the last committed choice, and commits the window's
+      oldest frame, so each choice has seen D frames of its future and the audio comes `lag_samples` = D * hop samples
+      later still (the first D frames of a stream are silent in grains mode).  drain() plays out what the window
+      still holds, one block per call (drain_replay() after capture()).  The rule: include/rawvae_hip.h.
 
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
@@ -422,8 +427,11 @@ class LatentIndex:
         return res if len(res) > 1 else out
 
 
+LAG_MAX = 64       # frames of look-ahead of the live selection at most (csrc/mosaic.hip)
+
+
 def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=None, k=1, mode="grains", window=None,
-                    continuity=0.0):
+                    continuity=0.0, lag=0):
     """Validate a StreamingMosaic configuration without a device -> (hop, latency, frames per block, successor
     advance).  ValueError naming the argument."""
     S = int(segment_length)
@@ -439,6 +447,11 @@ def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=
     continuity = float(continuity)
     if not 0 <= continuity < float("inf"):
         raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
+    if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
+        raise ValueError("lag=%r must be an integer in [0, %d]" % (lag, LAG_MAX))
+    if int(lag) > 0 and continuity == 0:
+        raise ValueError("lag=%d needs continuity > 0: without unit selection there is nothing to look ahead for"
+                         % int(lag))
     hop, latency, frames = check_args(S, block, hop, window)   # ValueError naming hop, block or window
     adv = 1
     if continuity > 0:
@@ -456,14 +469,19 @@ class StreamingMosaic:
     `index.mosaic(cat([zeros(latency), x]), k, hop, mode, window)` bit for bit at continuity 0.  Device tensors that
     may be written in place between calls: `scale`, `offset` [n_streams, L] (the query is mu * scale + offset) and,
     with continuity > 0, `weight` [n_streams] (starts at `continuity`; a value that is not finite and >= 0 counts
-    as 0).  The index must not change after construction."""
+    as 0).  The index must not change after construction.
 
-    def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0):
+    `lag` > 0 (needs continuity > 0): fixed-lag Viterbi selection.  The choices, and with them the audio, come
+    `lag_samples` = lag * hop samples later on top of `latency`; `drain()` plays out the frames still held back."""
+
+    def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0, lag=0):
         from .stream import StreamingVAE
         self.index = index
         N = len(index)
         self.hop, self.latency, self.frames_per_block, adv = check_live_args(
-            index.S, index.step, N, n_streams, block, hop, k, mode, window, continuity)
+            index.S, index.step, N, n_streams, block, hop, k, mode, window, continuity, lag)
+        self.lag = int(lag)
+        self.lag_samples = self.lag * self.hop
         # the framing, history, window tables and stream workspace are StreamingVAE's
         self._sv = StreamingVAE(index.model, n_streams, block, self.hop, window)
         self.n_streams, self.block, self.k, self.mode, self.window = int(n_streams), int(block), int(k), mode, window
@@ -482,7 +500,8 @@ class StreamingMosaic:
         self._ws = None
         nbytes = self._call(_lib.MOSAIC_LIVE_WORKSPACE, None, None).ws_bytes
         self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self._graph = None
+        self._graph = self._drain_graph = None
+        self._zeros = None
         self.reset()
 
     def _call(self, op, x, y, which=-1, stream=None):
@@ -492,7 +511,7 @@ class StreamingMosaic:
                        next_of=ptr(self._next_of), choice=ptr(self._choice), ws=ptr(self._ws),
                        ws_bytes=0 if self._ws is None else self._ws.numel(), live=_lib.C.pointer(sd),
                        mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS, weight=ptr(self.weight),
-                       which=int(which))
+                       which=int(which), rows=self.lag)
         host_only = op == _lib.MOSAIC_LIVE_WORKSPACE
         lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else (stream_ptr() if stream is None else stream))
         return d
@@ -505,10 +524,33 @@ class StreamingMosaic:
         self._call(_lib.MOSAIC_LIVE, x, y)
         return y
 
+    def _zero_block(self):
+        if self.lag == 0:
+            raise ValueError("lag=0: nothing is held back, there is nothing to drain")
+        if self._zeros is None:
+            self._zeros = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
+        return self._zeros
+
+    @torch.no_grad()
+    def drain(self):
+        """One block [n_streams, block] that plays out frames the lag still holds back (RV_MOSAIC_LIVE_DRAIN): no input,
+        no search; the history, the frame counter and the overlap-add move on as for a block of silence.  After
+        `drain_blocks` calls everything fed so far has been played; process() may follow.  ValueError at lag 0."""
+        x = self._zero_block()
+        y = torch.empty((self.n_streams, self.block), dtype=torch.float32, device=self.device)
+        self._call(_lib.MOSAIC_LIVE_DRAIN, x, y)
+        return y
+
+    @property
+    def drain_blocks(self):
+        """drain() calls after the last process() until every frame fed has left the overlap-add."""
+        frames = self.lag + (self.S - self.hop) // self.hop
+        return -(-frames // self.frames_per_block)
+
     @torch.no_grad()
     def reset(self, streams=None):
         """Zero the history, the overlap-add tail and the frame counter of `streams` (an index or a list; None = all)
-        and forget their last chosen corpus frame."""
+        and forget their last chosen corpus frame and the frames their lag holds back."""
         if streams is None:
             self._call(_lib.MOSAIC_LIVE_RESET, None, None, -1)
             return
@@ -520,7 +562,10 @@ class StreamingMosaic:
 
     def last_matches(self):
         """(idx [n_streams, F, k] int32, dist [n_streams, F, k] fp32, choice [n_streams, F] int32) of the last block's
-        frames, as views of static buffers; choice is the selected corpus frame, -1 everywhere at continuity 0."""
+        frames, as views of static buffers; choice is the selected corpus frame, -1 everywhere at continuity 0.
+        With a lag, choice is `lag` frames behind idx / dist: choice[s, f] is the frame committed when the block's
+        frame f arrived, chosen among the candidates of the frame `lag` frames earlier (-1 for the first `lag` frames
+        after a reset); after drain() idx / dist still hold the last process() call's frames."""
         F = self.frames_per_block
         return (self._idx.view(self.n_streams, F, self.k), self._dist.view(self.n_streams, F, self.k),
                 self._choice.view(self.n_streams, F))
@@ -528,7 +573,8 @@ class StreamingMosaic:
     @torch.no_grad()
     def capture(self):
         """Capture one call as a graph on static buffers `graph_input` / `graph_output` [n_streams, block];
-        `replay(x)` then runs one block per call.  The graph holds the Parameters' pointers: replaying after a
+        `replay(x)` then runs one block per call.  With a lag a second graph holds one drain() call for
+        `drain_replay()`, writing `graph_output` too.  The graphs hold the Parameters' pointers: replaying after a
         Parameter was replaced raises."""
         from .engine import Graph
         self.graph_input = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
@@ -541,18 +587,37 @@ class StreamingMosaic:
             self._call(_lib.MOSAIC_LIVE, self.graph_input, self.graph_output, stream=side.cuda_stream)
         torch.cuda.current_stream(self.device).wait_stream(side)
         self._graph = g
+        if self.lag > 0:
+            zeros = self._zero_block()
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            g = Graph(side)
+            with g:
+                self._call(_lib.MOSAIC_LIVE_DRAIN, zeros, self.graph_output, stream=side.cuda_stream)
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            self._drain_graph = g
         return self
+
+    def _check_held(self, what):
+        if self._graph is None:
+            raise _lib.RvError("%s before capture()" % what)
+        now = self._sv._weights()
+        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(now, self._held)):
+            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
 
     @torch.no_grad()
     def replay(self, x=None):
         """One block through the captured graph on the current stream; x (optional) is copied into `graph_input`
         first.  Returns `graph_output` (overwritten by the next replay)."""
-        if self._graph is None:
-            raise _lib.RvError("replay() before capture()")
-        now = self._sv._weights()
-        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(now, self._held)):
-            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
+        self._check_held("replay()")
         if x is not None:
             self.graph_input.copy_(self._sv._input(x))
         self._graph.launch(torch.cuda.current_stream(self.device))
+        return self.graph_output
+
+    @torch.no_grad()
+    def drain_replay(self):
+        """drain() through its captured graph on the current stream.  Returns `graph_output`."""
+        self._zero_block()
+        self._check_held("drain_replay()")
+        self._drain_graph.launch(torch.cuda.current_stream(self.device))
         return self.graph_output

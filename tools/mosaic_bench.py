@@ -3,6 +3,7 @@
 
     python tools/mosaic_bench.py [--reps 5] [--path] [--out build/mosaic_bench.json]
     python tools/mosaic_bench.py --live [--reps 30] [--summary profiles/mosaic_live_summary.txt]
+    python tools/mosaic_bench.py --live --lag [--reps 30] [--summary profiles/mosaic_live_lag_summary.txt]
 
 Search shapes (T, N, L, k): one minute of target at hop 128 (20 700 frames) and one second (344 frames), both against
 one hour of corpus at hop 128 (1.24 M frames), latent_dim 256, k = 4.  Per shape: device time (events around `reps`
@@ -22,6 +23,12 @@ the corpus bytes (N L 4) per second of the few-query kernel.  (2) One StreamingM
 n_streams x hop x block in {1x128x128, 1x256x256, 1x256x1024, 16x256x1024}, grains and decode, k = 4, continuity 0.5,
 against corpora of 6 872, 124 000 and 1 240 000 frames (random audio in 8 files, indexed at hop 128 by a
 VAE(1024, 2048, 256) with random weights), beside the block's duration at 44.1 kHz.
+
+--live --lag (nothing else is timed): the live path's unit selection with look-ahead.  One StreamingMosaic.replay()
+per block, grains, continuity 0.5, for lag 0 (k_live_select, the greedy rule) and lag in {1, 4, 16, 64} (k_live_lag),
+alternating in one process, the best of three rounds each, every window full before the clock starts; k in {4, 16},
+N in {124 000, 1 240 000}, n_streams x hop x block in {1x128x128, 16x256x1024}.  Beside each time: the block's duration
+at 44.1 kHz, and for lag > 0 the time over lag 0 per frame and window row (the length of the forward pass's chain).
 
 mosaic(): a VAE(1024, 2048, 256) with random weights, a 40 s corpus in 8 files and a 5 s target at hop 256, k = 4,
 grains and decode, wall time of the call including the target's encoder pass (the corpus is indexed beforehand).
@@ -211,6 +218,64 @@ def bench_live_blocks(reps):
     return rows
 
 
+LAGS = (0, 1, 4, 16, 64)
+
+
+def bench_live_lag(reps):
+    from rawvae.model import VAE
+    torch.manual_seed(0)
+    m = VAE(1024, 2048, 256).cuda().eval()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    rows = []
+    for n_frames in (124000, 1240000):
+        index = M.LatentIndex(m, hop=128)
+        per_file = n_frames // 8
+        for i in range(8):
+            frames = per_file + (n_frames - 8 * per_file if i == 7 else 0)
+            index.add(torch.randn((frames - 1) * 128 + 1024, device="cuda", generator=g) * 0.3, "c%d" % i)
+        assert len(index) == n_frames
+        for k in (4, 16):
+            for n_streams, hop, block in ((1, 128, 128), (16, 256, 1024)):
+                x = torch.randn(n_streams, block, device="cuda", generator=g) * 0.3
+                sms = {}
+                for lag in LAGS:
+                    sm = M.StreamingMosaic(index, n_streams, block, hop=hop, k=k, mode="grains", window="hann",
+                                           continuity=0.5, lag=lag).capture()
+                    sm.graph_input.copy_(x)
+                    for _ in range(-(-(lag + 1) // sm.frames_per_block)):   # fill the window: steady state
+                        sm.replay()
+                    sms[lag] = sm
+                ms = dict.fromkeys(LAGS, float("inf"))
+                for _ in range(3):                                # alternating
+                    for lag in LAGS:
+                        ms[lag] = min(ms[lag], replay_ms(sms[lag].replay, reps, rounds=1))
+                budget = block / 44100.0 * 1e3
+                for lag in LAGS:
+                    per_row = (ms[lag] - ms[0]) * 1e6 / ((block // hop) * (lag + 1)) if lag else 0.0
+                    rows.append(dict(N=n_frames, k=k, n_streams=n_streams, hop=hop, block=block, lag=lag,
+                                     ms=round(ms[lag], 4), block_ms=round(budget, 3), meets=bool(ms[lag] < budget),
+                                     over_lag0_ns_per_frame_row=round(per_row, 1)))
+                del sms
+        del index
+        torch.cuda.empty_cache()
+    return rows
+
+
+def live_lag_report(rows, device):
+    out = ["live mosaicing with a lag on %s (tools/mosaic_bench.py --live --lag): HIP events around graph replays after a "
+           "warm-up that fills every window" % device, "",
+           "one StreamingMosaic.replay() per block, grains, continuity 0.5, Hann window, VAE(1024, 2048, 256); lag 0 is "
+           "k_live_select,", "lag > 0 is k_live_lag; alternating in one process, best of three rounds; ns/row = (ms - ms "
+           "at lag 0) per frame of the block", "and row of the window (lag + 1)",
+           "%9s %3s %8s %5s %6s %4s %10s %10s %6s %8s" % ("N", "k", "streams", "hop", "block", "lag", "ms/block", "block ms",
+                                                          "meets", "ns/row")]
+    for r in rows:
+        out.append("%9d %3d %8d %5d %6d %4d %10.4f %10.3f %6s %8s" % (
+            r["N"], r["k"], r["n_streams"], r["hop"], r["block"], r["lag"], r["ms"], r["block_ms"],
+            "yes" if r["meets"] else "NO", "%.1f" % r["over_lag0_ns_per_frame_row"] if r["lag"] else "-"))
+    return "\n".join(out) + "\n"
+
+
 def live_report(search, blocks, device):
     out = ["live mosaicing on %s (tools/mosaic_bench.py --live): HIP events around graph replays after a warm-up" % device,
            "", "few-query search (RV_MOSAIC_KNN_SMALL) against RV_MOSAIC_KNN, L = 256, best of three alternating rounds",
@@ -237,7 +302,20 @@ def main(argv=None):
     p.add_argument("--summary", default=None, help="--live: also write the tables to this text file")
     p.add_argument("--out", default=None)
     p.add_argument("--path", action="store_true", help="also time the unit selection beside the search at k = 16")
+    p.add_argument("--lag", action="store_true", help="with --live: time the lagged unit selection against lag 0 instead")
     a = p.parse_args(argv)
+    if a.lag and not a.live:
+        raise ValueError("--lag: needs --live")
+    if a.lag:
+        res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), live_lag=bench_live_lag(a.reps or 30))
+        text = live_lag_report(res["live_lag"], res["device"])
+        print(text, end="")
+        for path, body in ((a.summary, text), (a.out, json.dumps(res, indent=1))):
+            if path:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return res
     if a.live:
         reps = a.reps or 30
         res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), live_search=bench_live_search(reps),
