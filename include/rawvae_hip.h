@@ -23,6 +23,18 @@
  *     GEMM tile (rows of the batch: 128; feature dims: 128; latent: 64) with zero
  *     padding -- see rv_pad_dims().  fp32 tensors at the reference boundary
  *     (frames, recon, mu, logvar, parameters, gradients) keep their exact shapes.
+ *   - leading dimensions (every `ld*` argument of the bf16 GEMM family below) count ELEMENTS of the tensor they
+ *     belong to and must be at least that tensor's row width as the entry point states it: a smaller one is
+ *     RV_ERR_SHAPE before anything is launched (rows never overlap; rv_linear_fp32 / rv_small_linear_f32 are the
+ *     exceptions and say so).  Alignment: a multiple of 8 for a bf16 tensor (operand, mask or output: rows of whole
+ *     16-byte pieces) and for fp16 slabs, a multiple of 4 for fp32 slabs; the exact-shape fp32 tensors x and recon of
+ *     rv_decode_out_loss_fwd and the source of rv_cast_pad_bf16 take any leading dimension >= their width.  The base
+ *     pointer of every bf16 tensor and of every slab is 16-byte aligned.  A kernel touches columns [0, width) of a
+ *     row only: the gap [width, ld) is neither read nor written.
+ *   - split outputs: an entry point that writes `splits` partial slabs of a [rows, cols] result with leading
+ *     dimension ld writes slab s at element offset s * rows * ld (NOT s * rows * cols): element (r, c) of slab s is
+ *     at s * rows * ld + r * ld + c, `rows` being the padded row count the entry point names.  The same stride goes
+ *     into rv_param_desc.grad_split_stride.
  */
 #ifndef RAWVAE_HIP_H
 #define RAWVAE_HIP_H
@@ -59,7 +71,8 @@ int rv_pad_dims(long B, long S, long H, long L, long* Bp, long* Sp, long* Hp, lo
 enum { RV_PLAN_GEMM = 0, RV_PLAN_TILE = 1, RV_PLAN_PAIR = 2 };
 int rv_gemm_plan(int what, long Mp, long Np, long Kp, int splits_in, int* bm, int* bn, int* splits, int* paired);
 
-/* fp32 [rows, cols] (leading dim ld_src) -> zero-padded bf16 [rows_p, cols_p] (leading dim ld_dst).
+/* fp32 [rows, cols] (leading dim ld_src >= cols, any alignment) -> zero-padded bf16 [rows_p, cols_p] (leading dim
+ * ld_dst >= cols_p, a multiple of 8; columns [cols_p, ld_dst) are left alone).
  * Replaces the implicit fp32 operand read of F.linear (model.py:20) for frames and
  * is how weight shadows are (re)built after load_state_dict.  If `step_counter` is
  * non-NULL the kernel also increments *step_counter (device int64) once: it is the
@@ -68,12 +81,14 @@ int rv_cast_pad_bf16(const float* src, long rows, long cols, long ld_src, void* 
                      long rows_p, long cols_p, long ld_dst, long long* step_counter, void* stream);
 
 /* y = act(x W^T + b) -> bf16.  nn.Linear + F.relu, model.py:20 (fc1) and :29 (fc3).
- * x [Mp,Kp] bf16, w [Np,Kp] bf16 (nn.Linear [out,in] layout), bias [Np] fp32 or NULL. */
+ * x [Mp,Kp] bf16, w [Np,Kp] bf16 (nn.Linear [out,in] layout), bias [Np] fp32 or NULL.
+ * ldx >= Kp, ldw >= Kp, ldy >= Np, each a multiple of 8. */
 int rv_linear_fwd(const void* x_bf16, long ldx, const void* w_bf16, long ldw, const float* bias,
                   long Mp, long Np, long Kp, int act, void* y_bf16, long ldy, void* stream);
 
 /* Same contraction, fp32 output written as `splits` partial slabs of [Mp,Np]
  * (slab s covers K range s*Kp/splits..); bias (may be NULL) is added by slab 0 only.
+ * ldx >= Kp, ldw >= Kp (multiples of 8), ldy >= Np (a multiple of 4); consecutive slabs are Mp * ldy elements apart.
  * Used for the fused mu|logvar head GEMM, model.py:21 (fc21, fc22). */
 int rv_linear_fwd_f32(const void* x_bf16, long ldx, const void* w_bf16, long ldw,
                       const float* bias, long Mp, long Np, long Kp, int splits, float* y_f32,
@@ -95,7 +110,9 @@ int rv_linear_fp32(const float* x, long ldx, const float* w, long ldw, const flo
  *   if x != NULL: mse_partial[block] = sum (recon-x)^2 over the block's valid elements
  *                 dP4 bf16 [Bp,Sp]   = (2/(B*S)) (recon-x)(1-recon^2)   (0 in padding)
  *                 db4_partial [Bp/bm][Sp] column sums of dP4 (optional)
- * with (bm, bn) = rv_gemm_plan(RV_PLAN_TILE, Bp, Sp, Hp, 1, ...): n_mse_partials = (Bp/bm)*(Sp/bn). */
+ * with (bm, bn) = rv_gemm_plan(RV_PLAN_TILE, Bp, Sp, Hp, 1, ...): n_mse_partials = (Bp/bm)*(Sp/bn).
+ * h3 [Bp,Hp] and w4 [Sp,Hp] bf16: ldh >= Hp, ldw >= Hp, multiples of 8.  x and recon [B,S] fp32: ldx >= S, ld_recon >= S,
+ * any alignment; rows [B, Bp) and columns [S, Sp) of them are not touched.  ld_dp4 >= Sp, a multiple of 8. */
 int rv_decode_out_loss_fwd(const void* h3_bf16, long ldh, const void* w4_bf16, long ldw,
                            const float* b4, long Bp, long Sp, long Hp, long B, long S,
                            const float* x, long ldx, float* recon, long ld_recon,
@@ -107,7 +124,9 @@ int rv_decode_out_loss_fwd(const void* h3_bf16, long ldh, const void* w4_bf16, l
  *   mask != NULL : dx_bf16 = (mask > 0) ? dX : 0   (ReLU', threshold_backward) and
  *                  colsum_partial [Mp/bm][Np] (optional) = column sums = bias grads,
  *                  bm from rv_gemm_plan(RV_PLAN_TILE, Mp, Np, Kp, 1, ...)
- *   mask == NULL : dx_f32 written as `splits` fp32 partial slabs [Mp,Np]. */
+ *   mask == NULL : dx_f32 written as `splits` fp32 partial slabs [Mp,Np], Mp * lddx32 elements apart.
+ * lddy >= Kp, ldw >= Np (multiples of 8); mask and dx_bf16 [Mp,Np]: ldmask >= Np, lddx >= Np (multiples of 8);
+ * lddx32 >= Np (a multiple of 4).  The leading dimensions of the form that is not used are not read. */
 int rv_linear_dgrad(const void* dy_bf16, long lddy, const void* w_bf16, long ldw, long Mp,
                     long Np, long Kp, const void* mask_bf16, long ldmask, void* dx_bf16,
                     long lddx, float* colsum_partial, float* dx_f32, long lddx32, int splits,
@@ -129,7 +148,10 @@ enum { RV_SLAB_F32 = 0, RV_SLAB_F16 = 1 };
  * dy [Mp(batch), Kp(out)], w [Kp, Np] ([out,in]), x [Mp, Np] = the layer's ReLU output (mask AND
  * wgrad operand).  `splits` and `bm` must come from rv_gemm_plan(RV_PLAN_PAIR, Mp, Np, Kp, ...); when the
  * 256x256 pairing does not apply (e.g. the heads: Kp = 2 Lp) the two GEMMs still go out in one
- * launch if they share a small tile, otherwise as rv_linear_dgrad + rv_linear_wgrad. */
+ * launch if they share a small tile, otherwise as rv_linear_dgrad + rv_linear_wgrad.
+ * lddy >= Kp, ldw >= Np, ldx >= Np, lddx >= Np (multiples of 8); lddw >= Np, a multiple of 4 (fp32 slabs) or 8 (fp16 slabs);
+ * consecutive dw slabs are Kp * lddw elements apart (fp32 or fp16 elements alike).  The slab_unscale table and the column-sum
+ * partials are packed and have no leading dimension. */
 int rv_linear_dgrad_wgrad(const void* dy_bf16, long lddy, const void* w_bf16, long ldw, const void* x_bf16, long ldx,
                           long Mp, long Np, long Kp, void* dx_bf16, long lddx, float* colsum_partial, void* dw_slabs,
                           long lddw, int splits, int slab_dtype, float* slab_unscale, void* stream);
@@ -137,7 +159,9 @@ int rv_linear_dgrad_wgrad(const void* dy_bf16, long lddy, const void* w_bf16, lo
 /* Backward of a Linear layer whose input had no activation (fc3, whose input is z): dX = dY W as
  * `dgrad_splits` fp32 slabs [Mp, Np] and dW = dY^T X as `wgrad_splits` slabs [Kp, Np], in ONE launch
  * when both GEMMs run on the same small tile (they read the same dY; each alone is mostly launch and
- * store-tail time).  dy [Mp(batch), Kp(out)], w [Kp, Np], x [Mp, Np].  Autograd of F.linear, train.py:191. */
+ * store-tail time).  dy [Mp(batch), Kp(out)], w [Kp, Np], x [Mp, Np].  Autograd of F.linear, train.py:191.
+ * lddy >= Kp, ldw >= Np, ldx >= Np (multiples of 8); lddx >= Np, lddw >= Np (multiples of 4); dx slabs are Mp * lddx elements
+ * apart, dw slabs Kp * lddw. */
 int rv_linear_dgrad_wgrad_f32(const void* dy_bf16, long lddy, const void* w_bf16, long ldw,
                               const void* x_bf16, long ldx, long Mp, long Np, long Kp, float* dx_slabs,
                               long lddx, int dgrad_splits, float* dw_slabs, long lddw, int wgrad_splits,
@@ -147,7 +171,9 @@ int rv_linear_dgrad_wgrad_f32(const void* dy_bf16, long lddy, const void* w_bf16
  * dy [Kp(batch), Mp] bf16, x [Kp(batch), Np] bf16; both read through transposing LDS
  * reads.  Autograd of F.linear w.r.t. weight, train.py:191.  `tile`: RV_TILE_AUTO (the picker's choice) or a named
  * block tile (extents must be multiples of it; `splits` must divide Kp/64; RV_TILE_256x256 runs the ping-pong main
- * loop when Kp/64/splits is even). */
+ * loop when Kp/64/splits is even).
+ * lddy >= Mp, ldx >= Np (multiples of 8); lddw >= Np, a multiple of 4 (fp32 slabs) or 8 (fp16 slabs); consecutive slabs are
+ * Mp * lddw elements apart (fp32 or fp16 elements alike); slab_unscale is packed, [splits][Mp / 32][Np / 32]. */
 enum { RV_TILE_AUTO = -1, RV_TILE_64x64 = 0, RV_TILE_128x128 = 4, RV_TILE_256x128 = 2, RV_TILE_256x256 = 7 };
 int rv_linear_wgrad(const void* dy_bf16, long lddy, const void* x_bf16, long ldx, long Mp, long Np, long Kp,
                     int splits, int tile, void* dw_slabs, long lddw, int slab_dtype, float* slab_unscale, void* stream);
@@ -172,7 +198,9 @@ int rv_reparam_fwd(const float* mulv_slabs, int splits, long Bp, long Lp, long B
  * blocks, and combining split-K partials inside a launch (release fence + arrival ticket + acquire, 5-13 us per seam
  * on this chip: MI355X_MICROARCH.md, price list row "splitk-seam") costs more than the ~1.5 us kernel boundary it
  * removes; without split-K every block re-streams the whole head weight through its CU's ~60 GB/s L2->LDS port
- * (12-14 us for any row tile from 16 to 64 against 12.9 us for the two launches).  See DESIGN.md section 3. */
+ * (12-14 us for any row tile from 16 to 64 against 12.9 us for the two launches).  See DESIGN.md section 3.
+ * h [Bp,Kp], wh [2Lp,Kp] bf16: ldh >= Kp, ldw >= Kp, multiples of 8.  mulv_slabs, mulv, z, eps and the KL partials are packed
+ * (slabs Bp * 2Lp elements apart). */
 int rv_heads_reparam_fwd(const void* h_bf16, long ldh, const void* wh_bf16, long ldw, const float* bias_heads,
                          long Bp, long Lp, long Kp, long B, long L, int splits, float* mulv_slabs,
                          const float* eps_in, float* eps_out, unsigned long long seed, const long long* step_counter,
@@ -195,7 +223,9 @@ int rv_heads_reparam_fwd(const void* h_bf16, long ldh, const void* wh_bf16, long
  * hidden widths (multiples of 128): the same call runs its GEMM form -- the heads GEMM on 64 x 128 tiles (256-row tiles at
  * large batches: 256 x 128, from Lp = 128 on 256 x 256 ping-pong) with bias, eps, exp, z and the KL partials in the
  * epilogue, then fc3 as a forward GEMM.  Same outputs and eps draws; kl_partial [Bp Lp / 1024] then holds one non-zero
- * slot per tile and zeros in the others (only the sum is defined). */
+ * slot per tile and zeros in the others (only the sum is defined).
+ * h [Bp,Hp], wh [2Lp,Hp], w3 [Hp,Lp], h3 [Bp,Hp] bf16: ldh >= Hp, ldwh >= Hp, ldw3 >= Lp, ldh3 >= Hp, multiples of 8 (ldw3 and
+ * ldh3 are not read when w3_bf16 == NULL).  mulv, z, eps and kl_partial are packed. */
 int rv_latent_fwd(const void* h_bf16, long ldh, const void* wh_bf16, long ldwh, const float* bias_heads,
                   const void* w3_bf16, long ldw3, const float* bias3, long Bp, long Hp, long Lp, long B, long L,
                   const float* eps_in, float* eps_out, unsigned long long seed, const long long* step_counter,
@@ -211,7 +241,10 @@ int rv_latent_fwd(const void* h_bf16, long ldh, const void* wh_bf16, long ldwh, 
  * GEMM form (same shapes as rv_latent_fwd's): dz tiles of 64 rows (256 at large batches; ONE 256 x 256 ping-pong tile per
  * 256 rows at Lp = 256) with the reparameterisation backward in the epilogue, dW3 on the launch's first workgroups.
  * dbh_partial [Bp / 16][2 Lp] keeps its layout: the row-local kernel fills every row, the GEMM forms the first row of each
- * dz tile's rows and ZEROS in the rest (a reader may sum every row, or every (tile rows / 16)-th). */
+ * dz tile's rows and ZEROS in the rest (a reader may sum every row, or every (tile rows / 16)-th).
+ * dP3 [Bp,Hp], W3 [Hp,Lp], z [Bp,Lp] bf16: lddp >= Hp, ldw3 >= Lp, ldz >= Lp, multiples of 8; lddw3 >= Lp, a multiple of 4;
+ * consecutive dW3 slabs are Hp * lddw3 elements apart (ldz and lddw3 are not read when z_bf16 == NULL).  mulv, eps, dmulv,
+ * dbh_partial and loss_out are packed. */
 int rv_latent_bwd(const void* dp3_bf16, long lddp, const void* w3_bf16, long ldw3, long Bp, long Hp, long Lp, long B,
                   long L, long S, const float* mulv, const float* eps, float kl_beta, const float* dmu_ext,
                   const float* dlv_ext, void* dmulv_bf16, float* dbh_partial, const float* mse_partial, int n_mse,
@@ -225,7 +258,9 @@ int rv_latent_bwd(const void* dp3_bf16, long lddp, const void* w3_bf16, long ldw
  * columns 0..63, logvar 64..127: rv_reparam_bwd's output), wh [128, Hp] bf16 (fc21 | fc22, [out, in]), h1 [Bp, Hp]
  * bf16.  A workgroup keeps its 64-column slice of Wh in LDS and walks 512 rows in tiles of 64; the same staged h1
  * tile is the ReLU mask of the first product and the operand of the second.  RV_ERR_UNSUPPORTED unless Lp == 64,
- * Bp % 512 == 0 and Hp % 64 == 0. */
+ * Bp % 512 == 0 and Hp % 64 == 0.
+ * ldw >= Hp, ldh >= Hp, ldp >= Hp (multiples of 8); lddw >= Hp, a multiple of 4; consecutive dWh slabs are 128 * lddw
+ * elements apart.  dmulv [Bp, 128] and db1_partial are packed. */
 int rv_heads_bwd(const void* dmulv_bf16, const void* wh_bf16, long ldw, const void* h1_bf16, long ldh, long Bp, long Hp,
                  long Lp, void* dp1_bf16, long ldp, float* db1_partial, float* dwh_slabs, long lddw, void* stream);
 

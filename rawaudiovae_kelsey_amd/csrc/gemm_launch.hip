@@ -190,6 +190,9 @@ int launch_tile_fp8(int tile, const GemmArgs& a, long Mp, long Np, long Kp, hipS
 int set_slabs(GemmArgs& g, void* dw, long lddw, long split_stride, int dtype, float* unscale, long Mp, long Np) {
   RV_REQUIRE(dtype == RV_SLAB_F32 || dtype == RV_SLAB_F16, RV_ERR_UNSUPPORTED, "weight gradient: slab dtype %d", dtype);
   RV_REQUIRE(dtype == RV_SLAB_F32 || unscale, RV_ERR_NULL, "weight gradient: fp16 slabs need the table of per-tile scales");
+  RV_REQUIRE(lddw >= Np && lddw % (dtype == RV_SLAB_F16 ? 8 : 4) == 0, RV_ERR_SHAPE,
+             "weight gradient: slab leading dim %ld must be at least the row width %ld and a multiple of %d", lddw, Np,
+             dtype == RV_SLAB_F16 ? 8 : 4);
   g.ld_f32 = lddw; g.split_stride_f32 = split_stride;
   g.out_f32 = (float*)dw; g.out_f16 = nullptr; g.f16_unscale = nullptr;
   if (dtype == RV_SLAB_F16) {
@@ -202,12 +205,16 @@ int set_slabs(GemmArgs& g, void* dw, long lddw, long split_stride, int dtype, fl
 // A / B operands and K tiling of `g` (rv_gemm_operands).  fp8 (e4m3) operands are bytes viewed as bf16 pairs: leading
 // dims and K halve, so a staged 64-pair K tile holds 128 fp8 values per row and every tile / swizzle / ring rule of the
 // bf16 kernels carries over.  `K`: the contraction one block walks (one split's share).  Rows of 16 bytes, whole K tiles
-// and 16-byte aligned operands (the LDS-DMA pieces) are checked here for every launcher.
-int set_operands(const char* who, GemmArgs& g, const rv_gemm_operands& op, long K) {
+// and 16-byte aligned operands (the LDS-DMA pieces) are checked here for every launcher.  `wa` / `wb`: the row widths of A
+// and B as they lie in memory (elements; the whole contraction for a K-major operand, the M / N extent otherwise) -- a
+// leading dim below its row width would make rows overlap; 0 = not checked (the frames path sets its own lda afterwards).
+int set_operands(const char* who, GemmArgs& g, const rv_gemm_operands& op, long K, long wa, long wb) {
   const bool fp8 = op.dq != nullptr;
   const long kt = fp8 ? 128 : 64, ld = fp8 ? 16 : 8;
   RV_REQUIRE(K % kt == 0 && op.lda % ld == 0 && op.ldb % ld == 0, RV_ERR_SHAPE,
              "%s: K and leading dims must be multiples of %ld / %ld%s elements", who, kt, ld, fp8 ? " fp8" : "");
+  RV_REQUIRE(op.lda >= wa && op.ldb >= wb, RV_ERR_SHAPE, "%s: operand leading dims %ld / %ld are smaller than the row widths %ld / %ld",
+             who, op.lda, op.ldb, wa, wb);
   RV_REQUIRE((((uintptr_t)op.a | (uintptr_t)op.b) & 15) == 0, RV_ERR_SHAPE, "%s: operands must be 16-byte aligned", who);
   const int per = fp8 ? 2 : 1;   // elements per bf16 slot
   g.A = (const bf16_t*)op.a; g.lda = op.lda / per;
@@ -415,7 +422,9 @@ int rv_linear_fwd_ex(rv_gemm_operands op, const float* bias, long Mp, long Np, l
                "rv_linear_fwd_frames: the framed copy needs 16-byte aligned rows of at least Kp elements");
   }
   GemmArgs a{};
-  const int rc = set_operands(who, a, op, Kp);
+  RV_REQUIRE(ldy >= Np && ldy % 8 == 0, RV_ERR_SHAPE, "%s: output leading dim %ld must be at least the row width %ld and a multiple of 8",
+             who, ldy, Np);
+  const int rc = set_operands(who, a, op, Kp, fr ? 0 : Kp, Kp);
   if (rc) return rc;
   a.M_valid = (int)Mp; a.N_valid = (int)Np;
   a.relu = act == RV_ACT_RELU; a.bias = bias; a.out_bf16 = (bf16_t*)y; a.ld_bf16 = ldy;
@@ -435,7 +444,9 @@ int rv_linear_fwd_f32(const void* x, long ldx, const void* w, long ldw, const fl
                       long Mp, long Np, long Kp, int splits, float* y, long ldy, void* stream) {
   RV_REQUIRE(x && w && y, RV_ERR_NULL, "rv_linear_fwd_f32: null operand");
   GemmArgs a{};
-  const int rc = set_operands("rv_linear_fwd_f32", a, {x, ldx, w, ldw, nullptr}, Kp / (splits > 0 ? splits : 1));
+  RV_REQUIRE(ldy >= Np && ldy % 4 == 0, RV_ERR_SHAPE,
+             "rv_linear_fwd_f32: output leading dim %ld must be at least the row width %ld and a multiple of 4", ldy, Np);
+  const int rc = set_operands("rv_linear_fwd_f32", a, {x, ldx, w, ldw, nullptr}, Kp / (splits > 0 ? splits : 1), Kp, Kp);
   if (rc) return rc;
   a.M_valid = (int)Mp; a.N_valid = (int)Np;
   a.bias = bias; a.out_f32 = y; a.ld_f32 = ldy; a.split_stride_f32 = Mp * ldy;
@@ -464,8 +475,11 @@ int rv_decode_out_loss_fwd_ex(rv_gemm_operands op, const float* b4, long Bp, lon
   RV_REQUIRE(!x || dP4 || dP4_fp8, RV_ERR_NULL, "%s: x given without dP4 output", who);
   RV_REQUIRE(!dP4_fp8 || (op.dq && dp4_scale && ld_dp4q % 8 == 0 && ((uintptr_t)dP4_fp8 & 7) == 0), RV_ERR_SHAPE,
              "%s: the fp8 image of dP4 belongs to the fp8 forward and needs its scale and 8-byte aligned rows", who);
+  RV_REQUIRE((!x || fr || ldx >= S) && (!recon || ld_recon >= S) && (!dP4 || (ld_dp4 >= Sp && ld_dp4 % 8 == 0)), RV_ERR_SHAPE,
+             "%s: leading dims of x / recon / dP4 (%ld, %ld, %ld) must be at least S, S and Sp (dP4: a multiple of 8)", who, ldx,
+             ld_recon, ld_dp4);
   GemmArgs a{};
-  const int rc = set_operands(who, a, op, Hp);
+  const int rc = set_operands(who, a, op, Hp, Hp, Hp);
   if (rc) return rc;
   a.M_valid = (int)B; a.N_valid = (int)S;
   a.bias = b4; a.x = x; a.ld_x = ldx; a.recon = recon; a.ld_recon = ld_recon;
@@ -482,16 +496,21 @@ int rv_linear_dgrad(const void* dy, long lddy, const void* w, long ldw, long Mp,
                     float* dx32, long lddx32, int splits, void* stream) {
   RV_REQUIRE(dy && w, RV_ERR_NULL, "rv_linear_dgrad: null operand");
   GemmArgs a{};
-  const int rc = set_operands("rv_linear_dgrad", a, {dy, lddy, w, ldw, nullptr}, mask ? Kp : Kp / (splits > 0 ? splits : 1));
+  const int rc = set_operands("rv_linear_dgrad", a, {dy, lddy, w, ldw, nullptr}, mask ? Kp : Kp / (splits > 0 ? splits : 1), Kp, Np);
   if (rc) return rc;
   a.M_valid = (int)Mp; a.N_valid = (int)Np;
   if (mask) {
     RV_REQUIRE(dx, RV_ERR_NULL, "rv_linear_dgrad: mask given without bf16 output");
+    RV_REQUIRE(ldmask >= Np && ldmask % 8 == 0 && lddx >= Np && lddx % 8 == 0, RV_ERR_SHAPE,
+               "rv_linear_dgrad: leading dims of mask / dx (%ld, %ld) must be at least the row width %ld and multiples of 8", ldmask,
+               lddx, Np);
     a.mask = (const bf16_t*)mask; a.ld_mask = ldmask;
     a.out_bf16 = (bf16_t*)dx; a.ld_bf16 = lddx; a.colsum = colsum;
     return launch_auto<true, false, EPI_MASK_BF16>(a, Mp, Np, Kp, 1, (hipStream_t)stream);
   }
   RV_REQUIRE(dx32, RV_ERR_NULL, "rv_linear_dgrad: no output given");
+  RV_REQUIRE(lddx32 >= Np && lddx32 % 4 == 0, RV_ERR_SHAPE,
+             "rv_linear_dgrad: slab leading dim %ld must be at least the row width %ld and a multiple of 4", lddx32, Np);
   a.out_f32 = dx32; a.ld_f32 = lddx32; a.split_stride_f32 = Mp * lddx32;
   return launch_auto<true, false, EPI_F32>(a, Mp, Np, Kp, splits, (hipStream_t)stream);
 }
@@ -504,7 +523,7 @@ int rv_linear_wgrad(const void* dy, long lddy, const void* x, long ldx, long Mp,
                  tile == RV_TILE_64x64, RV_ERR_UNSUPPORTED, "rv_linear_wgrad: unknown tile %d", tile);
   RV_REQUIRE(splits >= 1, RV_ERR_SHAPE, "rv_linear_wgrad: splits %d", splits);
   GemmArgs a{};
-  int rc = set_operands("rv_linear_wgrad", a, {dy, lddy, x, ldx, nullptr}, Kp / splits);
+  int rc = set_operands("rv_linear_wgrad", a, {dy, lddy, x, ldx, nullptr}, Kp / splits, Mp, Np);
   if (rc) return rc;
   a.M_valid = (int)Mp; a.N_valid = (int)Np;
   rc = set_slabs(a, dw, lddw, Mp * lddw, slab_dtype, slab_unscale, Mp, Np);
@@ -536,7 +555,7 @@ extern "C" int rv_linear_wgrad_riders(rv_gemm_operands op, long Mp, long Np, lon
   RV_REQUIRE(!fp8 || (Kp / kt / splits) % 2 == 0, RV_ERR_SHAPE, "%s: fp8 operands need an even number of 128-deep K tiles per split", who);
   RV_REQUIRE(n_rider_blocks >= 1 && n_rider_blocks <= 4096, RV_ERR_SHAPE, "%s: %d rider blocks", who, n_rider_blocks);
   GemmArgs g{};
-  int rc = set_operands(who, g, op, Kp / splits);
+  int rc = set_operands(who, g, op, Kp / splits, Mp, Np);
   if (rc) return rc;
   DescTable tab;
   rc = adam_build_table(descs, n_desc, &tab);
@@ -660,10 +679,12 @@ int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operands wgrad, con
   }
   RV_REQUIRE(ldmask % (mask_is_fp8 ? 16 : 8) == 0 && ((uintptr_t)mask & 15) == 0, RV_ERR_SHAPE,
              "%s: the mask needs 16-byte aligned rows of a multiple of 16 bytes", who);
+  RV_REQUIRE(ldmask >= Np && lddx >= Np && lddx % 8 == 0, RV_ERR_SHAPE,
+             "%s: leading dims of mask / dx (%ld, %ld) must be at least the row width %ld (dx: a multiple of 8)", who, ldmask, lddx, Np);
   GemmArgs d{}, g{};
-  rc = set_operands(who, d, dgrad, Kp);
+  rc = set_operands(who, d, dgrad, Kp, Kp, Np);
   if (rc) return rc;
-  rc = set_operands(who, g, wgrad, Mp / splits);
+  rc = set_operands(who, g, wgrad, Mp / splits, Kp, Np);
   if (rc) return rc;
   d.M_valid = (int)Mp; d.N_valid = (int)Np;
   d.mask = (const bf16_t*)mask; d.ld_mask = ldmask; d.mask_fp8 = mask_is_fp8 ? 1 : 0;
@@ -698,14 +719,17 @@ int rv_linear_dgrad_wgrad_f32(const void* dy, long lddy, const void* w, long ldw
   RV_REQUIRE(dy && w && x && dx_slabs && dw_slabs, RV_ERR_NULL, "rv_linear_dgrad_wgrad_f32: null operand");
   RV_REQUIRE(dgrad_splits >= 1 && wgrad_splits >= 1 && (Kp / 64) % dgrad_splits == 0 && (Mp / 64) % wgrad_splits == 0,
              RV_ERR_SHAPE, "rv_linear_dgrad_wgrad_f32: splits %d / %d do not divide the K tiles", dgrad_splits, wgrad_splits);
+  RV_REQUIRE(lddx >= Np && lddx % 4 == 0 && lddw >= Np && lddw % 4 == 0, RV_ERR_SHAPE,
+             "rv_linear_dgrad_wgrad_f32: slab leading dims %ld / %ld must be at least the row width %ld and multiples of 4", lddx, lddw,
+             Np);
   const int td = choose_tile(Mp, Np, dgrad_splits, Kp), tw = choose_tile(Kp, Np, wgrad_splits, Mp);
-  int rc;
+  // (both GEMMs' operands are checked before either is launched, whichever way they go out)
+  GemmArgs d{}, g{};
+  int rc = set_operands("rv_linear_dgrad_wgrad_f32", d, {dy, lddy, w, ldw, nullptr}, Kp / dgrad_splits, Kp, Np);
+  if (rc) return rc;
+  rc = set_operands("rv_linear_dgrad_wgrad_f32", g, {dy, lddy, x, ldx, nullptr}, Mp / wgrad_splits, Kp, Np);
+  if (rc) return rc;
   if (td == tw) {
-    GemmArgs d{}, g{};
-    rc = set_operands("rv_linear_dgrad_wgrad_f32", d, {dy, lddy, w, ldw, nullptr}, Kp / dgrad_splits);
-    if (rc) return rc;
-    rc = set_operands("rv_linear_dgrad_wgrad_f32", g, {dy, lddy, x, ldx, nullptr}, Mp / wgrad_splits);
-    if (rc) return rc;
     d.M_valid = (int)Mp; d.N_valid = (int)Np;
     d.out_f32 = dx_slabs; d.ld_f32 = lddx; d.split_stride_f32 = Mp * lddx;
     g.M_valid = (int)Kp; g.N_valid = (int)Np;

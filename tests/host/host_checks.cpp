@@ -15,6 +15,83 @@ static int expect(int rc, int code, const char* prefix, int line) {
 }
 #define EXPECT(call, code, prefix) expect((call), (code), (prefix), __LINE__)
 
+// A leading dimension smaller than the row width it belongs to (rows would overlap) is RV_ERR_SHAPE before any launch, for
+// every operand and every output of the bf16 GEMM entry points; each line has exactly one offending value, 8 (or 4) below
+// its width, so the alignment rules are kept.  Extents (M, N, K) = (256, 256, 512).
+static int ld_checks() {
+  alignas(16) static char buf[64];
+  float* f = (float*)buf;
+  const long M = 256, N = 256, K = 512;
+  const char* opnd = "operand leading dims";
+  char msg[160];
+  int fails = 0;
+  snprintf(msg, sizeof msg, "rv_linear_fwd: %s", opnd);
+  fails += EXPECT(rv_linear_fwd(buf, K - 8, buf, K, NULL, M, N, K, RV_ACT_RELU, buf, N, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd(buf, K, buf, K - 8, NULL, M, N, K, RV_ACT_RELU, buf, N, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd(buf, K, buf, K, NULL, M, N, K, RV_ACT_RELU, buf, N - 8, NULL), RV_ERR_SHAPE,
+                  "rv_linear_fwd: output leading dim 248");
+  snprintf(msg, sizeof msg, "rv_linear_fwd_f32: %s", opnd);
+  fails += EXPECT(rv_linear_fwd_f32(buf, K - 8, buf, K, NULL, M, N, K, 2, f, N, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd_f32(buf, K, buf, K - 8, NULL, M, N, K, 2, f, N, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_fwd_f32(buf, K, buf, K, NULL, M, N, K, 2, f, N - 4, NULL), RV_ERR_SHAPE,
+                  "rv_linear_fwd_f32: output leading dim 252");
+  // (a packed per-split K share is smaller than the row: the check is against the whole row, not the split's share)
+  fails += EXPECT(rv_linear_fwd_f32(buf, K / 2, buf, K, NULL, M, N, K, 2, f, N, NULL), RV_ERR_SHAPE, msg);
+  snprintf(msg, sizeof msg, "rv_decode_out_loss_fwd: %s", opnd);
+  fails += EXPECT(rv_decode_out_loss_fwd(buf, K - 8, buf, K, NULL, M, N, K, M - 3, N - 5, f, N - 5, f, N - 5, buf, N, f, NULL, NULL),
+                  RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_decode_out_loss_fwd(buf, K, buf, K - 8, NULL, M, N, K, M - 3, N - 5, f, N - 5, f, N - 5, buf, N, f, NULL, NULL),
+                  RV_ERR_SHAPE, msg);
+  const char* dec = "rv_decode_out_loss_fwd: leading dims of x / recon / dP4";
+  fails += EXPECT(rv_decode_out_loss_fwd(buf, K, buf, K, NULL, M, N, K, M - 3, N - 5, f, N - 6, f, N - 5, buf, N, f, NULL, NULL),
+                  RV_ERR_SHAPE, dec);
+  fails += EXPECT(rv_decode_out_loss_fwd(buf, K, buf, K, NULL, M, N, K, M - 3, N - 5, f, N - 5, f, N - 6, buf, N, f, NULL, NULL),
+                  RV_ERR_SHAPE, dec);
+  fails += EXPECT(rv_decode_out_loss_fwd(buf, K, buf, K, NULL, M, N, K, M - 3, N - 5, f, N - 5, f, N - 5, buf, N - 8, f, NULL, NULL),
+                  RV_ERR_SHAPE, dec);
+  // dgrad: dy [M, K], w [K, N]
+  snprintf(msg, sizeof msg, "rv_linear_dgrad: %s", opnd);
+  fails += EXPECT(rv_linear_dgrad(buf, K - 8, buf, N, M, N, K, NULL, 0, NULL, 0, NULL, f, N, 2, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad(buf, K, buf, N - 8, M, N, K, NULL, 0, NULL, 0, NULL, f, N, 2, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad(buf, K, buf, N, M, N, K, NULL, 0, NULL, 0, NULL, f, N - 4, 2, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad: slab leading dim 252");
+  fails += EXPECT(rv_linear_dgrad(buf, K, buf, N, M, N, K, buf, N - 8, buf, N, NULL, NULL, 0, 1, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad: leading dims of mask / dx (248, 256)");
+  fails += EXPECT(rv_linear_dgrad(buf, K, buf, N, M, N, K, buf, N, buf, N - 8, NULL, NULL, 0, 1, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad: leading dims of mask / dx (256, 248)");
+  // wgrad: dy [K(batch), M], x [K, N]
+  snprintf(msg, sizeof msg, "rv_linear_wgrad: %s", opnd);
+  fails += EXPECT(rv_linear_wgrad(buf, M - 8, buf, N, M, N, K, 2, RV_TILE_AUTO, f, N, RV_SLAB_F32, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_wgrad(buf, M, buf, N - 8, M, N, K, 2, RV_TILE_AUTO, f, N, RV_SLAB_F32, NULL, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_wgrad(buf, M, buf, N, M, N, K, 2, RV_TILE_AUTO, f, N - 4, RV_SLAB_F32, NULL, NULL), RV_ERR_SHAPE,
+                  "weight gradient: slab leading dim 252");
+  fails += EXPECT(rv_linear_wgrad(buf, M, buf, N, M, N, K, 2, RV_TILE_AUTO, f, N + 4, RV_SLAB_F16, f, NULL), RV_ERR_SHAPE,
+                  "weight gradient: slab leading dim 260");   // fp16 slabs: rows of whole 16-byte pieces
+  // dgrad + wgrad of one layer: dy [M, K], w [K, N], x [M, N]
+  int paired = 0, bm = 0, sp = 0;
+  fails += rv_gemm_plan(RV_PLAN_PAIR, M, N, K, 0, &bm, NULL, &sp, &paired) != 0;
+  snprintf(msg, sizeof msg, "rv_linear_dgrad_wgrad: %s", opnd);
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, K - 8, buf, N, buf, N, M, N, K, buf, N, NULL, f, N, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, K, buf, N - 8, buf, N, M, N, K, buf, N, NULL, f, N, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, K, buf, N, buf, N - 8, M, N, K, buf, N, NULL, f, N, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_SHAPE, "rv_linear_dgrad_wgrad: leading dims of mask / dx (248, 256)");
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, K, buf, N, buf, N, M, N, K, buf, N - 8, NULL, f, N, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_SHAPE, "rv_linear_dgrad_wgrad: leading dims of mask / dx (256, 248)");
+  fails += EXPECT(rv_linear_dgrad_wgrad(buf, K, buf, N, buf, N, M, N, K, buf, N, NULL, f, N - 4, sp, RV_SLAB_F32, NULL, NULL),
+                  RV_ERR_SHAPE, "weight gradient: slab leading dim 252");
+  snprintf(msg, sizeof msg, "rv_linear_dgrad_wgrad_f32: %s", opnd);
+  fails += EXPECT(rv_linear_dgrad_wgrad_f32(buf, K - 8, buf, N, buf, N, M, N, K, f, N, 1, f, N, 2, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad_f32(buf, K, buf, N - 8, buf, N, M, N, K, f, N, 1, f, N, 2, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad_f32(buf, K, buf, N, buf, N - 8, M, N, K, f, N, 1, f, N, 2, NULL), RV_ERR_SHAPE, msg);
+  fails += EXPECT(rv_linear_dgrad_wgrad_f32(buf, K, buf, N, buf, N, M, N, K, f, N - 4, 1, f, N, 2, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad_wgrad_f32: slab leading dims 252 / 256");
+  fails += EXPECT(rv_linear_dgrad_wgrad_f32(buf, K, buf, N, buf, N, M, N, K, f, N, 1, f, N - 4, 2, NULL), RV_ERR_SHAPE,
+                  "rv_linear_dgrad_wgrad_f32: slab leading dims 256 / 252");
+  return fails;
+}
+
 // The rejections of the GEMM launchers that return before any HIP call.
 static int launcher_checks() {
   alignas(16) static char buf[64];
@@ -85,6 +162,7 @@ static int launcher_checks() {
     fails += EXPECT(rv_linear_wgrad_riders({buf, 2048, buf, 1024, dq}, 2048, 1024, 4096, 4, buf, 1024, RV_SLAB_F32, NULL, d, 1, fin,
                                            n, NULL), RV_ERR_SHAPE, msg);
   }
+  fails += ld_checks();
   return fails;
 }
 
