@@ -509,7 +509,34 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  *   be a block of zeros.  prev is kept and RV_MOSAIC_LIVE may follow.
  * RV_MOSAIC_LIVE_WORKSPACE: the bytes of ws (device; RV_MOSAIC_LIVE_RESET before the first block) for live's extents
  * and (N, L, k, splits, rows) in d->ws_bytes; launches nothing.  RV_MOSAIC_LIVE_RESET: rv_stream_reset(live, which),
- * prev = -1 and no pending rows for stream `which` (-1: every stream). */
+ * prev = -1 and no pending rows for stream `which` (-1: every stream).
+ *
+ * Grain fitting (csrc/grain.hip; DESIGN.md section 7.5 "Grain fitting"): after the selection, fit each candidate grain
+ * to its target frame by a shift of at most R samples and a gain.  THE RULE.  For target frame t, x[n] =
+ * frames[t hop + n], n < S.  For candidate j, i = idx[t, j] in [0, n_rows).  room [n_rows, 2] int32 (host-built, passed
+ * in `next_of`) says how far frame i's start may move back (room[i, 0]) and forward (room[i, 1]) while the grain stays
+ * inside its own file's padded waveform (a negative entry counts as 0), so a shifted grain never reads a neighbouring
+ * file of src.  Every shift delta with max(-R, -room[i, 0]) <= delta <= min(R, room[i, 1]) is considered (the range is
+ * cut further where a grain would leave src [src_len]; delta = 0 is always permitted):
+ *   g[n] = src[row_start[i] + delta + n];  c(delta) = sum_n x[n] g[n];  e(delta) = sum_n g[n]^2, both in fp32, every
+ *   term one fma, c = fmaf(x[n], g[n], c) and e = fmaf(g[n], g[n], e), one plain chain each in ascending n from +0.
+ *   The order depends on nothing else (not T, k, R, the candidate's position or the launch): equal data, equal bits.
+ *   score(delta) = (double)c * (double)c / (double)e when c > 0, e > 0 and both are finite, otherwise 0 (a NaN never
+ *   wins).  The choice is the delta of greatest score; ties go to the smaller |delta|, then to the negative delta; when
+ *   every score is 0 that is delta = 0.
+ *   gain: 1 when gain_max == 0 ("shift only"); otherwise min(fl32(c / e), gain_max) at the chosen delta when its score
+ *   is > 0, else 0.
+ *   A candidate outside [0, n_rows), or whose unshifted grain is not inside src, gets shift 0, gain 0 and score 0.
+ * RV_GRAIN_FIT: T, k, idx [T, k]; frames = the target's padded waveform [n_out] with (T - 1) hop + S <= n_out; hop, S;
+ *   src, src_len, row_start [n_rows], n_rows; next_of = room; width = R, 0 <= R <= 1024; lam = gain_max, finite and
+ *   >= 0.  Outputs: slot [T, k] int32 = the shift, trans [T, k] fp32 = the gain, cost [T, k] fp64 = the score.  Any
+ *   S >= 1.  One launch; no sync and no read of the device (it may run under capture).
+ * RV_GRAIN_GATHER: RV_MOSAIC_GATHER_MEAN's fields and contract with slot [T, k] as the shift and trans [T, k] as the
+ *   gain: out[t, n] = (1/k) sum_j fl(trans[t, j] * src[start(idx[t, j]) + slot[t, j] + n]), each product rounded
+ *   before its add, the sum in ascending j from +0, 1/k applied once; a candidate outside [0, n_rows) or a shifted
+ *   grain that would leave src adds nothing.  With shift 0 and gain 1 it is RV_MOSAIC_GATHER_MEAN bit for bit.
+ * Both return an RV_ERR_* whose message names the field before anything is launched: R (width), T, k, a null table,
+ * frames that overrun n_out, gain_max (lam). */
 #define RV_MOSAIC_KNN 0
 #define RV_MOSAIC_KNN_WORKSPACE 1
 #define RV_MOSAIC_GATHER_MEAN 2
@@ -524,6 +551,8 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_MOSAIC_LIVE_WORKSPACE 11
 #define RV_MOSAIC_LIVE_RESET 12
 #define RV_MOSAIC_LIVE_DRAIN 13
+#define RV_GRAIN_FIT 14
+#define RV_GRAIN_GATHER 15
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
 struct rv_stream_desc;
@@ -546,11 +575,11 @@ typedef struct rv_mosaic_desc {
   long F, S, hop;
   const float* window;
   long n_out;
-  const int* next_of;            /* TRANSITION [N] */
+  const int* next_of;            /* TRANSITION [N]; GRAIN_FIT: room [n_rows, 2] */
   long row0, rows;               /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T; LIVE ops: rows = the lag */
   float* trans;                  /* [rows, k, k]: TRANSITION output, PATH_FORWARD input */
-  float lam;                     /* PATH_FORWARD: lambda, the weight of the transition costs */
-  int* slot;                     /* PATH_BACKTRACK [T] */
+  float lam;                     /* PATH_FORWARD: lambda, the weight of the transition costs; GRAIN_FIT: gain_max */
+  int* slot;                     /* PATH_BACKTRACK [T]; GRAIN ops: the shifts [T, k] */
   int* choice;                   /* PATH_BACKTRACK [T] */
   double* cost;                  /* PATH_BACKTRACK [2] */
   const struct rv_stream_desc* live; /* LIVE ops: weights, block I/O, scale / offset, window, norm, stream workspace */

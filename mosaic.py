@@ -23,6 +23,13 @@ nearest corpus frames in the model's latent space, and the result is overlap-add
                      rule).  Every frame is chosen by a Viterbi search over itself and the N frames after it; the live
                      output comes N * hop samples later, which the file drops as well
 
+  --fit N            grains mode, offline: move every selected grain by up to N samples (0..1024) to where it lines up
+                     best with its target frame (the shift of the least-squares fit; a grain stays inside its file)
+  --gain-max X       grains mode, offline: scale every selected grain by the gain of that fit, at most X (float >= 0;
+                     0: leave the corpus's level).  With either flag the summary line names both values, and --matches
+                     holds (file, sample offset, distance, shift, gain) per candidate, or with --continuity the chosen
+                     frame's shift and gain after the slot
+
 The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
 values, an empty corpus, unreadable wavs or a --k above the number of corpus frames raise ValueError naming the flag or
 the file.
@@ -68,6 +75,8 @@ def parse_args(argv=None):
     p.add_argument("--live-block", default=None, help="samples per block of the live path (default: offline)")
     p.add_argument("--streams", default=None, help="parallel streams of the live path (default 1)")
     p.add_argument("--lag", default=None, help="frames of look-ahead of the live path's unit selection (0..64, default 0)")
+    p.add_argument("--fit", default=None, help="samples a grain may be shifted to fit its target frame (0..1024)")
+    p.add_argument("--gain-max", default=None, help="largest gain of the fit (float >= 0; 0: no gain)")
     args = p.parse_args(argv)
     args.live_block = None if args.live_block is None else _int_flag("live-block", args.live_block, 1)
     if args.streams is not None and args.live_block is None:
@@ -93,6 +102,18 @@ def parse_args(argv=None):
     if args.window not in ("none", "hann"):
         raise ValueError("--window %r: expected none or hann" % args.window)
     args.window = None if args.window == "none" else args.window
+    for flag, value in (("fit", args.fit), ("gain-max", args.gain_max)):
+        if value is None:
+            continue
+        if args.live_block is not None:
+            raise ValueError("--%s %s: the live path (--live-block) does not fit grains" % (flag, value))
+        if args.mode == "decode":
+            raise ValueError("--%s %s: needs --mode grains, --mode decode plays no corpus audio" % (flag, value))
+    args.fitted = args.fit is not None or args.gain_max is not None
+    args.fit = 0 if args.fit is None else _int_flag("fit", args.fit, 0)
+    if args.fit > 1024:
+        raise ValueError("--fit %d: at most 1024" % args.fit)
+    args.gain_max = 0.0 if args.gain_max is None else _weight_flag("gain-max", args.gain_max)
     if not os.path.isdir(args.corpus):
         raise ValueError("--corpus %r: not a folder" % args.corpus)
     return args
@@ -122,16 +143,23 @@ def corpus_files(corpus_dir):
     return files
 
 
-def write_matches(path, names_offsets, dist, slot=None):
-    """One line per target frame: file_1, offset_1, distance_1, ..., file_k, offset_k, distance_k[, chosen slot]."""
+def write_matches(path, names_offsets, dist, slot=None, fit=None):
+    """One line per target frame: file_1, offset_1, distance_1, ..., file_k, offset_k, distance_k[, chosen slot].
+    fit = (shift, gain): [T, k] adds each candidate's shift and gain behind its distance; [T, 1] (the chosen frame's)
+    adds the two behind the slot."""
+    per_candidate = fit is not None and slot is None
     with open(path, "w", newline="") as f:
         wr = csv.writer(f)
         for t, (row, drow) in enumerate(zip(names_offsets, dist)):
             line = []
-            for (name, off), d in zip(row, drow):
+            for j, ((name, off), d) in enumerate(zip(row, drow)):
                 line += [name if name is not None else "", off, repr(float(d))]
+                if per_candidate:
+                    line += [int(fit[0][t][j]), repr(float(fit[1][t][j]))]
             if slot is not None:
                 line.append(int(slot[t]))
+                if fit is not None:
+                    line += [int(fit[0][t][0]), repr(float(fit[1][t][0]))]
             wr.writerow(line)
 
 
@@ -163,15 +191,20 @@ def main(argv=None):
         index.add(w, f)
     if args.live_block is not None:
         return run_live(args, index, target, hop, sr, len(files))
-    y, idx, dist, path = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True,
-                                      continuity=args.continuity, return_path=True)
+    y, idx, dist, path, fits = index.mosaic(target, k=args.k, mode=args.mode, window=args.window, return_matches=True,
+                                            continuity=args.continuity, return_path=True, fit=args.fit,
+                                            gain_max=args.gain_max, return_fit=True)
     y = y.cpu().numpy()
     D.write_wav(args.out, y, sr)
     slot = None if path is None else path[0].cpu().numpy()
+    if args.fitted and fits is not None:
+        fits = (fits[0].cpu().numpy(), fits[1].cpu().numpy())
     if args.matches:
-        write_matches(args.matches, index.locate(idx), dist.cpu().numpy(), slot)
+        write_matches(args.matches, index.locate(idx), dist.cpu().numpy(), slot, fits if args.fitted else None)
     line = ("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s"
             % (args.out, y.size, idx.shape[0], len(index), len(files), args.k, args.mode, args.window or "none"))
+    if args.fitted:
+        line += ", fit %d, gain-max %g" % (args.fit, args.gain_max)
     if path is not None:
         choice, cost = path[1].cpu().numpy(), path[2].cpu().numpy()
         line += (", continuity %g, continuing %.4f, target cost %.6g, transition cost %.6g"

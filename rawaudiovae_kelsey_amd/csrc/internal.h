@@ -124,3 +124,7 @@ RV_INTERNAL int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operand
 // rv_stream_synth: decode != 0: fc3 and fc4 on the latent rows into the frames; then k_stream_ola on the frames.
 RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, float** frames, void* stream);
 RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream);
+// The two grain-fitting ops of rv_mosaic (grain.hip): RV_GRAIN_FIT and RV_GRAIN_GATHER on the fields the public header
+// names for them; checks first, then one launch each, no sync and no read of the device.
+RV_INTERNAL int rv_grain_fit(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_grain_gather(const rv_mosaic_desc* d, void* stream);

@@ -11,6 +11,7 @@
 //                          (k_live_select: greedy; k_live_lag: Viterbi over a window of lag + 1 frames, committing
 //                          the oldest), gather-mean, then the stream's decoder / overlap-add
 //   RV_MOSAIC_LIVE_DRAIN   one block that plays out the frames a lag still holds back: no encoder, no search
+//   RV_GRAIN_FIT / RV_GRAIN_GATHER   shift-and-gain fit of every candidate grain to its target frame: grain.hip
 // Layout, split and merge, and the measured figures: DESIGN.md sections 7.5, 7.6 and 7.7.
 #include <limits.h>
 
@@ -1351,6 +1352,10 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       RV_CHECK_LAUNCH();
       return rv_stream_synth(sd, decode, stream);
     }
+    case RV_GRAIN_FIT:
+      return rv_grain_fit(d, stream);
+    case RV_GRAIN_GATHER:
+      return rv_grain_gather(d, stream);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }

@@ -20,6 +20,14 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
                                           (index.successor) and this candidate: 0 when the corpus simply plays on.
                                           Grains / decode then run on the one chosen frame.  w = 0 is the call above.
   transition_costs, best_path             the two steps on their own (RV_MOSAIC_TRANSITION, RV_MOSAIC_PATH_*)
+  index.mosaic(..., fit=R, gain_max=g)    grain fitting ("grains" mode): every selected grain is moved by the shift in
+                                          [-R, R] samples and scaled by the gain of its least-squares fit to the target
+                                          frame before the overlap-add (the rule: include/rawvae_hip.h, "Grain
+                                          fitting").  g = 0: shift only; g > 0: the gain, at most g.  A shifted grain
+                                          stays inside its own file (index.room).  With k candidates each is fitted on
+                                          its own and the k fitted grains are averaged; with continuity > 0 the one
+                                          chosen frame is fitted.  fit=0, gain_max=0 is the call without them.
+  shift_room, fit_grains, gather_fitted   the steps on their own (RV_GRAIN_FIT, RV_GRAIN_GATHER)
   knn_topk_small(q, c, k)                 knn_topk for at most SMALL_T_MAX query rows by the few-query kernel
                                           (RV_MOSAIC_KNN_SMALL): the same bits
   StreamingMosaic(index, n_streams, block, hop, k, mode, window, continuity, lag)
@@ -48,6 +56,7 @@ from .stream import WINDOWS, check_args, window_norm, window_values
 
 MODES = ("grains", "decode")
 K_MAX = 16
+FIT_MAX = 1024     # samples a grain may be shifted at most (csrc/grain.hip)
 SMALL_T_MAX = 64   # query rows of knn_topk_small (csrc/mosaic.hip)
 
 
@@ -217,6 +226,84 @@ def gather_mean(src, idx, width, row_start=None, stride=None, n_rows=None, out=N
     return out
 
 
+def check_fit(fit, gain_max):
+    """(R, gain_max) of a grain fit: ValueError naming `fit` unless it is an integer in [0, FIT_MAX], naming `gain_max`
+    unless it is a finite number >= 0."""
+    if isinstance(fit, bool) or not isinstance(fit, (int, np.integer)) or not 0 <= int(fit) <= FIT_MAX:
+        raise ValueError("fit=%r must be an integer number of samples in [0, %d]" % (fit, FIT_MAX))
+    try:
+        g = float(gain_max)
+    except (TypeError, ValueError):
+        g = float("nan")
+    if not 0 <= g < float("inf"):
+        raise ValueError("gain_max=%r must be a finite number >= 0" % (gain_max,))
+    return int(fit), g
+
+
+def shift_room(lengths, segment_length, hop=None):
+    """room [N, 2] int32 for the corpus layout of frame_tables: how many samples frame i's start may move back
+    (room[i, 0]) and forward (room[i, 1]) while its segment_length samples stay inside its own file's padded
+    waveform."""
+    _, padded, _, file_of, offset_of = frame_tables(lengths, segment_length, hop)
+    room = np.empty((file_of.size, 2), dtype=np.int32)
+    room[:, 0] = offset_of
+    room[:, 1] = padded[file_of] - int(segment_length) - offset_of
+    return room
+
+
+def fit_grains(target, idx, hop, segment_length, src, row_start, room, fit, gain_max=0.0):
+    """(shift [T, k] int32, gain [T, k] fp32, score [T, k] fp64): the shift-and-gain fit (RV_GRAIN_FIT; the rule:
+    include/rawvae_hip.h) of corpus grain idx[t, j] to target frame t = target[t * hop : t * hop + segment_length].
+    target: 1-D fp32 device tensor holding all T frames; src: the corpus audio; row_start [N] int64 and room [N, 2]
+    int32 device tensors (frame_tables, shift_room); fit = R samples; gain_max = 0: shift only (gain 1)."""
+    R, g = check_fit(fit, gain_max)
+    idx, _ = _candidates(idx, None)
+    T, k = idx.shape
+    S, hop = int(segment_length), int(hop)
+    if (not torch.is_tensor(target) or target.dim() != 1 or target.dtype != torch.float32
+            or target.device != idx.device or not target.is_contiguous()):
+        raise ValueError("target must be a contiguous 1-D float32 tensor on idx's device")
+    if hop < 1 or S < 1 or (T - 1) * hop + S > target.numel():
+        raise ValueError("target: %d frames of %d samples at hop %d overrun its %d samples" % (T, S, hop, target.numel()))
+    src = src.contiguous().view(-1)
+    row_start = row_start.to(torch.int64).contiguous()
+    N = row_start.numel()
+    if (not torch.is_tensor(room) or room.dtype != torch.int32 or tuple(room.shape) != (N, 2)
+            or room.device != idx.device):
+        raise ValueError("room must be an int32 device tensor of shape [%d, 2] (shift_room)" % N)
+    room = room.contiguous()
+    shift = torch.empty((T, k), dtype=torch.int32, device=idx.device)
+    gain = torch.empty((T, k), dtype=torch.float32, device=idx.device)
+    score = torch.empty((T, k), dtype=torch.float64, device=idx.device)
+    _call(_lib.GRAIN_FIT, T=T, k=k, idx=ptr(idx), frames=ptr(target), n_out=target.numel(), hop=hop, S=S, src=ptr(src),
+          src_len=src.numel(), row_start=ptr(row_start), n_rows=N, next_of=ptr(room), width=R, lam=g, slot=ptr(shift),
+          trans=ptr(gain), cost=ptr(score))
+    return shift, gain, score
+
+
+def gather_fitted(src, idx, shift, gain, width, row_start, out=None, ldo=None):
+    """out [T, width] fp32: gather_mean with candidate j of row t read shift[t, j] samples later and scaled by
+    gain[t, j] (RV_GRAIN_GATHER): (1/k) sum_j fl(gain * src[row_start[idx[t, j]] + shift[t, j] : + width]), ascending
+    j from +0.  Shift 0 and gain 1 give gather_mean's bits."""
+    src = src.contiguous().view(-1)
+    idx, _ = _candidates(idx, None)
+    T, k = idx.shape
+    if (not torch.is_tensor(shift) or shift.dtype != torch.int32 or shift.shape != idx.shape
+            or shift.device != idx.device):
+        raise ValueError("shift must be an int32 device tensor of idx's shape %s" % (tuple(idx.shape),))
+    if not torch.is_tensor(gain) or gain.dtype != torch.float32 or gain.shape != idx.shape or gain.device != idx.device:
+        raise ValueError("gain must be a float32 device tensor of idx's shape %s" % (tuple(idx.shape),))
+    shift, gain = shift.contiguous(), gain.contiguous()
+    width = int(width)
+    row_start = row_start.to(torch.int64).contiguous()
+    ldo = width if ldo is None else int(ldo)
+    if out is None:
+        out = torch.empty((T, ldo), dtype=torch.float32, device=src.device)
+    _call(_lib.GRAIN_GATHER, T=T, k=k, idx=ptr(idx), src=ptr(src), src_len=src.numel(), row_start=ptr(row_start),
+          n_rows=row_start.numel(), width=width, out=ptr(out), ldo=ldo, slot=ptr(shift), trans=ptr(gain))
+    return out
+
+
 def ola(frames, hop, n_out, window=None, out=None):
     """[n_out] fp32 weighted overlap-add of frames [F, S] at `hop` (window: [S] fp32 device tensor or None)."""
     frames = frames.contiguous()
@@ -330,6 +417,18 @@ class LatentIndex:
     def offset_of(self):
         return self._tables()["offset_of"]
 
+    @property
+    def room(self):
+        """[N, 2] int32 (numpy): how far each corpus frame may be shifted back / forward inside its file (shift_room)."""
+        return self._room()[0]
+
+    def _room(self):
+        t = self._tables()
+        if "room" not in t:
+            host = shift_room(self._lengths, self.S, self.hop)
+            t["room"] = (host, torch.from_numpy(host).to(self.device))
+        return t["room"]
+
     def successor(self, adv=1):
         """next_of [N] int32 (numpy, cached): the corpus frame `adv` index steps after frame i in the same file, or i
         itself at a file's end (successor_table)."""
@@ -365,11 +464,20 @@ class LatentIndex:
 
     @torch.no_grad()
     def mosaic(self, target, k=1, hop=None, mode="grains", window=None, return_matches=False, continuity=0.0,
-               return_path=False):
+               return_path=False, fit=0, gain_max=0.0, return_fit=False):
         """The target resynthesised from the corpus (see the module doc) -> 1-D fp32 device tensor of the target's
         length; with return_matches also (idx [T, k], dist [T, k]).  hop=None: the index's framing.
         continuity > 0 chooses one of the k candidates per frame by best_path with that weight; return_path then
-        appends (slot, choice, cost) to the result (None at continuity 0, where no path is searched)."""
+        appends (slot, choice, cost) to the result (None at continuity 0, where no path is searched).
+        fit = R > 0 or gain_max > 0 ("grains" mode only): every grain is fitted to its target frame by a shift of at
+        most R samples and, with gain_max > 0, a gain of at most gain_max (fit_grains) before the overlap-add;
+        return_fit then appends (shift, gain, score), each [T, k], or [T, 1] with continuity > 0 (None when nothing
+        is fitted)."""
+        fit, gain_max = check_fit(fit, gain_max)
+        fitted = fit > 0 or gain_max > 0
+        if fitted and mode == "decode":
+            raise ValueError("fit=%d, gain_max=%g: grains are fitted in mode 'grains' only, mode 'decode' plays no "
+                             "corpus audio" % (fit, gain_max))
         continuity = float(continuity)
         if not 0 <= continuity < float("inf"):
             raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
@@ -397,9 +505,25 @@ class LatentIndex:
             z = torch.empty((cap, self.L), dtype=torch.float32, device=self.device)
             h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
 
+        fits = None
+        if fitted:
+            room = self._room()[1]
+            kf = k if continuity == 0 else 1
+            fits = (torch.empty((T, kf), dtype=torch.int32, device=self.device),
+                    torch.empty((T, kf), dtype=torch.float32, device=self.device),
+                    torch.empty((T, kf), dtype=torch.float64, device=self.device))
+
         def synth(i, r0, rows):
-            """frames[r0:r0 + rows] from the corpus frames i [rows, any k]: their mean audio, or their mean mu decoded"""
-            if mode == "grains":
+            """frames[r0:r0 + rows] from the corpus frames i [rows, any k]: their mean audio (each fitted to its
+            target frame first when a fit is asked for), or their mean mu decoded"""
+            if fitted:
+                i = i.contiguous()
+                sh, gn, sc = fit_grains(padded[r0 * step:], i, step, self.S, t["audio"], t["row_start"], room, fit,
+                                        gain_max)
+                for dst, part in zip(fits, (sh, gn, sc)):
+                    dst[r0:r0 + rows] = part
+                gather_fitted(t["audio"], i, sh, gn, self.S, t["row_start"], out=frames[r0:r0 + rows])
+            elif mode == "grains":
                 gather_mean(t["audio"], i, self.S, row_start=t["row_start"], out=frames[r0:r0 + rows])
             else:
                 gather_mean(t["mu"], i, self.L, stride=self.L, n_rows=N, out=z[:rows])
@@ -424,6 +548,8 @@ class LatentIndex:
         res = (out, idx, dist) if return_matches else (out,)
         if return_path:
             res += (path,)
+        if return_fit:
+            res += (fits,)
         return res if len(res) > 1 else out
 
 

@@ -1,0 +1,323 @@
+"""Grain fitting on the GPU (RV_GRAIN_FIT / RV_GRAIN_GATHER in csrc/grain.hip, fit_grains / gather_fitted /
+LatentIndex.mosaic(fit=, gain_max=) in rawaudiovae_kelsey_amd/mosaic.py, mosaic.py --fit / --gain-max) against the numpy
+restatement of the rule in tests/grain_fit_oracle.py: shifts, gains and scores bit for bit."""
+import csv
+import os
+import sys
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from conftest import REPO  # noqa: E402
+import grain_fit_oracle as F  # noqa: E402
+import mosaic_oracle as O  # noqa: E402
+
+
+def _M():
+    from rawaudiovae_kelsey_amd import mosaic
+    return mosaic
+
+
+def _dev(a, dtype=np.float32):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dtype)).cuda()
+
+
+def _noise(rng, n):
+    w = rng.standard_normal(n + 4)
+    return np.convolve(w, np.ones(5) / 5, mode="valid").astype(np.float32)
+
+
+def _corpus(rng, S, chop):
+    """Four files, stored padded one after the other as LatentIndex stores them: smoothed noise, one NaN sample in file
+    1, file 3 all zeros -> (src, row_start, room, first frame of every file, last frame of every file)."""
+    M = _M()
+    lengths = (3 * S + 37, 5 * S + 11, 2 * S, 2 * S + 1)
+    n_frames, padded, row_start, file_of, _ = M.frame_tables(lengths, S, chop)
+    src = np.zeros(int(padded.sum()), np.float32)
+    base = np.concatenate([[0], np.cumsum(padded)[:-1]])
+    for f, n in enumerate(lengths[:3]):
+        src[base[f]:base[f] + n] = _noise(rng, n)
+    src[base[1] + 2 * S + 5] = np.nan
+    firsts = np.concatenate([[0], np.cumsum(n_frames)[:-1]])
+    return src, row_start, M.shift_room(lengths, S, chop), firsts, firsts + n_frames - 1
+
+
+def _fit_both(target, hop, S, idx, src, row_start, room, R, g):
+    M = _M()
+    got = M.fit_grains(_dev(target), _dev(idx, np.int32), hop, S, _dev(src), _dev(row_start, np.int64),
+                       _dev(room, np.int32), R, g)
+    return [t.cpu().numpy() for t in got], F.fit(target, hop, S, idx, src, row_start, room, R, g)
+
+
+def _assert_same_fit(got, ref, what=None):
+    (gs, gg, gc), (rs, rg, rc) = got, ref
+    assert gs.dtype == np.int32 and gg.dtype == np.float32 and gc.dtype == np.float64
+    assert np.array_equal(gs, rs), (what, np.argwhere(gs != rs)[:5])
+    assert np.array_equal(gg.view(np.int32), rg.view(np.int32)), (what, np.argwhere(gg != rg)[:5])
+    assert np.array_equal(gc.view(np.int64), rc.view(np.int64)), (what, np.argwhere(gc != rc)[:5])
+
+
+# S, target hop, R, k, T, gain_max: T k (2R + 1) S <= 6e6 each.  S = 50: no multiple of 4; S = 2501: more than one
+# staged chunk of 1024 samples, with a tail; R = 300 > S at the small S; R = 1024 needs three passes over the shifts
+FIT_CASES = [(50, 7, 0, 16, 37, 0.25), (64, 16, 1, 3, 37, 1e3), (64, 16, 24, 16, 37, 0.25), (50, 7, 300, 3, 37, 1e3),
+             (64, 16, 300, 1, 1, 0.0), (50, 49, 24, 3, 1, 0.0), (1024, 256, 24, 3, 37, 1e3), (1024, 256, 300, 3, 1, 0.25),
+             (1024, 1023, 1024, 1, 2, 1e3), (1024, 256, 1, 16, 1, 0.0), (2501, 100, 24, 1, 3, 1e3)]
+
+
+@pytest.mark.parametrize("S,hop,R,k,T,g", FIT_CASES)
+def test_fit_matches_the_oracle_bit_for_bit(S, hop, R, k, T, g):
+    rng = np.random.default_rng(S + R + k + T)
+    chop = S // 2 if S % 2 == 0 else None
+    src, row_start, room, firsts, lasts = _corpus(rng, S, chop)
+    N = row_start.size
+    idx = rng.integers(0, N, (T, k))
+    step = S if chop is None else chop
+    target = _noise(rng, (T - 1) * hop + S)
+    for t in range(T):                                           # plant: frame t is candidate 0's grain, moved and scaled
+        i = idx[t, 0]
+        d = int(rng.integers(-min(R, room[i, 0]), min(R, room[i, 1]) + 1))
+        if t % 3 == 0 and not np.isnan(src[row_start[i] + d:row_start[i] + d + S]).any():
+            target[t * hop:t * hop + S] = np.float32(0.75) * src[row_start[i] + d:row_start[i] + d + S]
+    flat = idx.reshape(-1)
+    nan_frame = firsts[1] + (2 * S) // step                      # its grain holds the NaN sample at every shift >= -5
+    special = np.concatenate([[firsts[1], lasts[0], -1, N, nan_frame, firsts[3], N + 5], firsts, lasts])
+    where = rng.permutation(flat.size)[:special.size]            # as many as fit: k T may be smaller
+    flat[where] = special[:where.size]
+    if R == 1024:                                                # room for all 2049 shifts, without and with the NaN
+        flat[:2] = [firsts[0] + 2, firsts[1] + 4]
+        assert np.all(room[flat[:2]] >= 1024)
+    if T > 20:
+        target[20 * hop:20 * hop + S] = 0                        # an all-zero target frame
+    got, ref = _fit_both(target, hop, S, idx, src, row_start, room, R, g)
+    _assert_same_fit(got, ref)
+    shift, gain, score = got
+    inside = (idx >= 0) & (idx < N)
+    ii = np.where(inside, idx, 0)
+    assert np.all(shift >= -np.minimum(R, room[ii, 0])) and np.all(shift <= np.minimum(R, room[ii, 1]))
+    assert np.all(shift[~inside] == 0) and np.all(gain[~inside] == 0) and np.all(score[~inside] == 0)
+    assert np.all(np.isfinite(score)) and np.all(np.isfinite(gain)) and np.all(gain <= (g if g > 0 else 1))
+    if g == 0:
+        assert np.all(gain[inside] == 1)
+    zero_file = inside & (ii >= firsts[3])
+    assert np.all(shift[zero_file] == 0) and np.all(score[zero_file] == 0)
+
+
+def test_periodic_ties_and_silent_frames():
+    S, R = 32, 12
+    pattern = np.array([3, -1, 4, 1, -5, 9, 2, -6], np.float32)
+    wave = np.tile(pattern, 16)
+    row_start = np.array([0, 48], np.int64)
+    room = np.array([[0, 96], [48, 48]], np.int32)
+    target = np.concatenate([wave[53:53 + S], np.zeros(S, np.float32), wave[52:52 + S]])
+    idx = np.array([[1, 0, -1], [1, 0, 2], [0, 1, 1]])
+    for g in (0.0, 0.25, 4.0):
+        got, ref = _fit_both(target, S, S, idx, wave, row_start, room, R, g)
+        _assert_same_fit(got, ref, g)
+        shift, gain, score = got
+        assert shift.tolist() == [[-3, 5, 0], [0, 0, 0], [4, -4, -4]]
+        assert gain[0].tolist() == ([1, 1, 0] if g in (0.0, 4.0) else [0.25, 0.25, 0])
+        assert gain[1].tolist() == ([1, 1, 0] if g == 0 else [0, 0, 0]) and np.all(score[1] == 0)
+        assert score[0, 0] == score[0, 1] == float((target[:S].astype(np.float64) ** 2).sum())
+
+
+def test_rows_fitted_alone_equal_the_rows_among_many():
+    M = _M()
+    rng = np.random.default_rng(3)
+    S, hop, R, k, T = 64, 16, 24, 3, 37
+    src, row_start, room, _, _ = _corpus(rng, S, 32)
+    idx = rng.integers(-1, row_start.size + 1, (T, k)).astype(np.int32)
+    target = _noise(rng, (T - 1) * hop + S)
+    args = (_dev(src), _dev(row_start, np.int64), _dev(room, np.int32), R, 2.0)
+    whole = M.fit_grains(_dev(target), _dev(idx, np.int32), hop, S, *args)
+    for r0, rows in ((0, 1), (5, 3), (36, 1)):
+        part = M.fit_grains(_dev(target[r0 * hop:]), _dev(idx[r0:r0 + rows], np.int32), hop, S, *args)
+        for a, b in zip(part, whole):
+            assert torch.equal(a, b[r0:r0 + rows])
+        one = M.fit_grains(_dev(target[r0 * hop:]), _dev(idx[r0:r0 + 1, 1:2], np.int32), hop, S, *args)   # another k
+        for a, b in zip(one, whole):
+            assert torch.equal(a[:, 0], b[r0:r0 + 1, 1])
+
+
+def test_fitted_gather_matches_the_oracle_and_gather_mean():
+    M = _M()
+    rng = np.random.default_rng(8)
+    src = rng.standard_normal(20000).astype(np.float32)
+    starts = np.sort(rng.choice(20000 - 96, 300, replace=False)).astype(np.int64)
+    idx = rng.integers(-1, 302, (257, 7)).astype(np.int32)
+    shift = rng.integers(-150, 151, idx.shape).astype(np.int32)            # some grains leave src: they add nothing
+    gain = rng.standard_normal(idx.shape).astype(np.float32)
+    gain[::5, 2] = 0
+    idx[0, 0], shift[0, 0] = 5, -30000
+    d = (_dev(src), _dev(idx, np.int32))
+    got = M.gather_fitted(*d, _dev(shift, np.int32), _dev(gain), 96, _dev(starts, np.int64)).cpu().numpy()
+    assert np.array_equal(got.view(np.int32), F.gather(src, starts, idx, shift, gain, 96).view(np.int32))
+    assert np.any((starts[idx.clip(0, 299)] + shift < 0) | (starts[idx.clip(0, 299)] + shift + 96 > 20000))
+    plain = M.gather_fitted(*d, torch.zeros_like(d[1]), torch.ones(idx.shape, device="cuda"), 96, _dev(starts, np.int64))
+    mean = M.gather_mean(d[0], d[1], 96, row_start=_dev(starts, np.int64))
+    assert torch.equal(plain.view(torch.int32), mean.view(torch.int32))
+    assert np.array_equal(mean.cpu().numpy(), O.gather_mean(src, starts, np.where(idx < 300, idx, -1), 96))
+
+
+def _model(S=64, H=96, L=8, seed=0):
+    from rawvae.model import VAE
+    torch.manual_seed(seed)
+    return VAE(S, H, L).cuda().eval()
+
+
+def _waves(rng, lengths):
+    out = []
+    for i, n in enumerate(lengths):
+        t = np.arange(n) / 8000.0
+        w = 0.6 * np.sin(2 * np.pi * (150 + 170 * i) * t) + 0.2 * rng.standard_normal(n)
+        w[: n // 5] = 0                                          # leading silence: all-zero grains
+        out.append(w.astype(np.float32))
+    return out
+
+
+@pytest.fixture(scope="module")
+def indexed():
+    """(model, index at hop 16, the corpus waves, a target that is corpus audio off the grid at another level + noise)"""
+    M = _M()
+    m = _model(seed=2)
+    rng = np.random.default_rng(10)
+    waves = _waves(rng, [900, 333, 1500])
+    index = M.LatentIndex(m, hop=16)
+    for i, w in enumerate(waves):
+        index.add(w, "w%d" % i)
+    target = (0.4 * waves[2][205:205 + 1111] + 0.05 * rng.standard_normal(1111)).astype(np.float32)
+    return m, index, waves, target
+
+
+def _padded(target, S, hop):
+    from rawaudiovae_kelsey_amd.interpolate import frame_layout
+    T, n = frame_layout(target.size, S, hop)
+    out = np.zeros(n, np.float32)
+    out[:target.size] = target
+    return out, T
+
+
+@pytest.mark.parametrize("k,hop,win,R,g", [(1, 64, None, 24, 4.0), (4, 64, None, 7, 0.0), (1, 16, "hann", 24, 0.25),
+                                           (4, 16, "hann", 24, 4.0), (4, 16, None, 0, 1e3)])
+def test_mosaic_with_a_fit_is_the_oracle_on_the_devices_candidates(indexed, k, hop, win, R, g):
+    from rawaudiovae_kelsey_amd.stream import window_values
+    _, index, _, target = indexed
+    S = 64
+    w = None if win is None else window_values(S, win)
+    audio, room = index.audio.cpu().numpy(), index.room
+    pad, T = _padded(target, S, hop)
+    for continuity in (0.0, 0.5):
+        y, idx, dist, path, fits = index.mosaic(target, k=k, hop=hop, window=win, fit=R, gain_max=g, return_matches=True,
+                                                continuity=continuity, return_path=True, return_fit=True)
+        plain = index.mosaic(target, k=k, hop=hop, window=win, return_matches=True, continuity=continuity)
+        assert torch.equal(idx, plain[1]) and torch.equal(dist, plain[2])        # the fit changes no selection
+        cand = idx.cpu().numpy() if continuity == 0 else path[1].cpu().numpy()[:, None]
+        assert cand.shape == (T, k if continuity == 0 else 1)
+        ref = F.fit(pad, hop, S, cand, audio, index.row_start, room, R, g)
+        _assert_same_fit([t.cpu().numpy() for t in fits], ref, continuity)
+        grains = F.gather(audio, index.row_start, cand, ref[0], ref[1], S)
+        assert np.array_equal(y.cpu().numpy().view(np.int32), O.ola(grains, hop, target.size, w).view(np.int32))
+
+
+def test_the_fit_never_raises_a_frames_residual(indexed):
+    _, index, _, target = indexed
+    S = 64
+    target = target[:17 * S]
+    y1, idx, _, fits = index.mosaic(target, k=1, hop=S, fit=24, gain_max=1e3, return_matches=True, return_fit=True)
+    y0 = index.mosaic(target, k=1, hop=S)
+    assert float(fits[1].max()) < 1e3                                             # no gain reached the clamp
+    x = target.astype(np.float64).reshape(-1, S)
+    r1 = ((x - y1.cpu().numpy().astype(np.float64).reshape(-1, S)) ** 2).sum(1)
+    r0 = ((x - y0.cpu().numpy().astype(np.float64).reshape(-1, S)) ** 2).sum(1)
+    assert np.all(r1 <= r0 * (1 + 1e-5)), (r1 / r0).max()
+    assert r1.sum() < r0.sum()
+    # the fitted residual is |x|^2 - score up to the rounding of the fp32 sums: c and e carry at most S u relative to
+    # |x| |g| and |g|^2 (u = 2^-24), so c^2 / e is within 3 S u |x|^2, and the rounding of y adds a few u more
+    x2 = (x ** 2).sum(1)
+    assert np.abs(r1 - (x2 - fits[2].cpu().numpy()[:, 0])).max() <= 8 * S * 2.0 ** -24 * x2.max()
+
+
+def test_defaults_launch_nothing_new_and_chunking_changes_no_bit(indexed):
+    M = _M()
+    m, index, waves, target = indexed
+    for kw in (dict(k=3, hop=16, window="hann"), dict(k=2, hop=64, continuity=0.5)):
+        a = index.mosaic(target, return_matches=True, **kw)
+        b = index.mosaic(target, return_matches=True, fit=0, gain_max=0.0, return_fit=True, **kw)
+        assert b[-1] is None and len(b) == len(a) + 1
+        assert all(torch.equal(p.view(torch.int32), q.view(torch.int32)) for p, q in zip(a, b))
+    small = M.LatentIndex(m, hop=16, max_rows=5)
+    for i, w in enumerate(waves):
+        small.add(w, "w%d" % i)
+    for kw in (dict(k=3, hop=16, window="hann", fit=24, gain_max=4.0), dict(k=4, hop=32, continuity=0.5, fit=9, gain_max=0.0)):
+        a = index.mosaic(target, return_matches=True, return_fit=True, **kw)
+        b = small.mosaic(target, return_matches=True, return_fit=True, **kw)
+        flat = lambda r: list(r[:-1]) + list(r[-1])   # noqa: E731
+        for p, q in zip(flat(a), flat(b)):
+            assert p.dtype == q.dtype and torch.equal(p.view(torch.uint8), q.view(torch.uint8))
+
+
+def test_refused_combinations_raise(indexed):
+    _, index, _, target = indexed
+    sys.path.insert(0, REPO)
+    import mosaic as cli
+    with pytest.raises(ValueError, match="fit"):
+        index.mosaic(target, mode="decode", fit=8)
+    with pytest.raises(ValueError, match="gain_max"):
+        index.mosaic(target, mode="decode", gain_max=2.0)
+    for bad in (-1, 1025, 2.5):
+        with pytest.raises(ValueError, match="fit"):
+            index.mosaic(target, fit=bad)
+    for bad in (-1.0, float("inf"), float("nan")):
+        with pytest.raises(ValueError, match="gain_max"):
+            index.mosaic(target, gain_max=bad)
+    base = ["--config", "none.ini", "--checkpoint", "none.pt", "--target", "t.wav", "--out", "o.wav", "--corpus", REPO]
+    with pytest.raises(ValueError, match="--fit"):
+        cli.parse_args(base + ["--fit", "8", "--live-block", "64"])
+    with pytest.raises(ValueError, match="--gain-max"):
+        cli.parse_args(base + ["--gain-max", "2", "--mode", "decode"])
+
+
+def test_cli_writes_the_apis_samples(tmp_path, capsys):
+    from rawvae.model import VAE
+    from rawaudiovae_kelsey_amd import data as D
+    sys.path.insert(0, REPO)
+    import interpolate as interp_cli
+    import mosaic as cli
+    S_, H, L, sr = 64, 128, 8, 8000
+    torch.manual_seed(3)
+    torch.save({"epoch": 1, "state_dict": VAE(S_, H, L).state_dict(), "optimizer": {}}, tmp_path / "ckpt_00001")
+    (tmp_path / "tiny.ini").write_text("[audio]\nsampling_rate = %d\nhop_length = 8\nsegment_length = %d\n"
+                                       "[VAE]\nlatent_dim = %d\nn_units = %d\n" % (sr, S_, L, H))
+    corpus = tmp_path / "corpus"
+    corpus.mkdir()
+    rng = np.random.default_rng(4)
+    for i, w in enumerate(_waves(rng, [400, 777, 1024])):
+        D.write_wav(corpus / ("c%d.wav" % i), w, sr)
+    D.write_wav(tmp_path / "t.wav", (0.3 * rng.standard_normal(999)).astype(np.float32), sr)
+    argv = ["--config", str(tmp_path / "tiny.ini"), "--checkpoint", str(tmp_path / "ckpt_00001"), "--corpus", str(corpus),
+            "--target", str(tmp_path / "t.wav"), "--out", str(tmp_path / "out.wav"), "--hop", "16", "--k", "3", "--window",
+            "hann", "--matches", str(tmp_path / "m.csv")]
+    y = cli.main(argv + ["--fit", "16", "--gain-max", "4"])
+    said = capsys.readouterr().out
+    assert "fit 16, gain-max 4" in said
+    cfg = interp_cli.read_model_config(str(tmp_path / "tiny.ini"))
+    index = _M().LatentIndex(interp_cli.load_model(str(tmp_path / "ckpt_00001"), cfg), hop=16)
+    for f in sorted(os.listdir(corpus)):
+        index.add(cli.load_wav(str(corpus / f), sr), f)
+    target = cli.load_wav(str(tmp_path / "t.wav"), sr)
+    ref, _, _, fits = index.mosaic(target, k=3, window="hann", fit=16, gain_max=4.0, return_matches=True, return_fit=True)
+    assert np.array_equal(y, ref.cpu().numpy())
+    D.write_wav(tmp_path / "ref.wav", ref.cpu().numpy(), sr)
+    assert (tmp_path / "out.wav").read_bytes() == (tmp_path / "ref.wav").read_bytes()
+    rows = list(csv.reader(open(tmp_path / "m.csv")))
+    assert len(rows) == fits[0].shape[0] and all(len(r) == 15 for r in rows)
+    assert [[int(r[3]), int(r[8]), int(r[13])] for r in rows] == fits[0].cpu().numpy().tolist()
+    assert [[float(r[4]), float(r[9]), float(r[14])] for r in rows] == fits[1].cpu().numpy().astype(np.float64).tolist()
+    plain = cli.main(argv)
+    assert ", fit " not in capsys.readouterr().out and not np.array_equal(plain, y)
+    assert all(len(r) == 9 for r in csv.reader(open(tmp_path / "m.csv")))
+    cli.main(argv + ["--fit", "16", "--continuity", "0.5"])
+    assert "fit 16, gain-max 0" in capsys.readouterr().out
+    assert all(len(r) == 12 for r in csv.reader(open(tmp_path / "m.csv")))

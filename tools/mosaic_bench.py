@@ -4,6 +4,7 @@
     python tools/mosaic_bench.py [--reps 5] [--path] [--out build/mosaic_bench.json]
     python tools/mosaic_bench.py --live [--reps 30] [--summary profiles/mosaic_live_summary.txt]
     python tools/mosaic_bench.py --live --lag [--reps 30] [--summary profiles/mosaic_live_lag_summary.txt]
+    python tools/mosaic_bench.py --fit [--reps 5] [--summary profiles/mosaic_fit_summary.txt]
 
 Search shapes (T, N, L, k): one minute of target at hop 128 (20 700 frames) and one second (344 frames), both against
 one hour of corpus at hop 128 (1.24 M frames), latent_dim 256, k = 4.  Per shape: device time (events around `reps`
@@ -29,6 +30,13 @@ per block, grains, continuity 0.5, for lag 0 (k_live_select, the greedy rule) an
 alternating in one process, the best of three rounds each, every window full before the clock starts; k in {4, 16},
 N in {124 000, 1 240 000}, n_streams x hop x block in {1x128x128, 16x256x1024}.  Beside each time: the block's duration
 at 44.1 kHz, and for lag > 0 the time over lag 0 per frame and window row (the length of the forward pass's chain).
+
+--fit (alone: nothing else is timed): grain fitting (RV_GRAIN_FIT, csrc/grain.hip) at the search's minute shape -- one
+minute of target at hop 128 (T = 20 700), k = 4, S = 1024, R = 256, the candidates the search's own over one hour of
+corpus audio (1.24 M frames at hop 128 in 8 files, random samples) -- beside the search and the fitted gather
+(RV_GRAIN_GATHER), alternating in one process, HIP events around `reps` calls, the best of three rounds each.  The rate
+is in fmas/s, 2 T k (2R + 1) S per call (the c and the e chain), against 78.6 T fma/s (the fp32 vector spec, unpacked
+fmas: 39.3 T/s).
 
 mosaic(): a VAE(1024, 2048, 256) with random weights, a 40 s corpus in 8 files and a 5 s target at hop 256, k = 4,
 grains and decode, wall time of the call including the target's encoder pass (the corpus is indexed beforehand).
@@ -126,6 +134,52 @@ def bench_mosaic(reps):
         out[mode + "_ms"] = round((time.perf_counter() - t0) * 1e3 / reps, 3)
     out.update(corpus_frames=len(index), target_samples=int(target.numel()))
     return out
+
+
+def bench_fit(reps, T=20700, N=1240000, L=256, k=4, S=1024, hop=128, R=256, gain_max=4.0):
+    g = torch.Generator(device="cuda").manual_seed(0)
+    q = torch.randn(T, L, device="cuda", generator=g)
+    c = torch.randn(N, L, device="cuda", generator=g)
+    per_file = N // 8
+    lengths = [((per_file + (N - 8 * per_file if i == 7 else 0)) - 1) * hop + S for i in range(8)]
+    _, padded, row_start, _, _ = M.frame_tables(lengths, S, hop)
+    assert row_start.size == N
+    room = torch.from_numpy(M.shift_room(lengths, S, hop)).cuda()
+    row_start = torch.from_numpy(row_start).cuda()
+    audio = torch.randn(int(padded.sum()), device="cuda", generator=g) * 0.3
+    target = torch.randn((T - 1) * hop + S, device="cuda", generator=g) * 0.3
+    idx, _ = M.knn_topk(q, c, k)
+    shift, gain, _ = M.fit_grains(target, idx, hop, S, audio, row_start, room, R, gain_max)
+    out = torch.empty((T, S), dtype=torch.float32, device="cuda")
+    calls = dict(search=lambda: M.knn_topk(q, c, k),
+                 fit=lambda: M.fit_grains(target, idx, hop, S, audio, row_start, room, R, gain_max),
+                 gather=lambda: M.gather_fitted(audio, idx, shift, gain, S, row_start, out=out),
+                 gather_mean=lambda: M.gather_mean(audio, idx, S, row_start=row_start, out=out))
+    ms = dict.fromkeys(calls, float("inf"))
+    for _ in range(3):                                            # alternating
+        for name, fn in calls.items():
+            ms[name] = min(ms[name], timed(fn, reps))
+    fmas = 2.0 * T * k * (2 * R + 1) * S
+    return dict(T=T, N=N, L=L, k=k, S=S, hop=hop, R=R, reps=reps, search_ms=round(ms["search"], 3),
+                fit_ms=round(ms["fit"], 3), gather_ms=round(ms["gather"], 4), gather_mean_ms=round(ms["gather_mean"], 4),
+                fit_over_search=round(ms["fit"] / ms["search"], 4), fit_fmas=fmas,
+                fit_fmas_per_s=fmas / (ms["fit"] * 1e-3), of_unpacked_bound=round(fmas / (ms["fit"] * 1e-3) / 39.3e12, 4),
+                moved=float((shift != 0).float().mean()), clamped=float((gain >= gain_max).float().mean()))
+
+
+def fit_report(r, device):
+    return "\n".join([
+        "grain fitting on %s (tools/mosaic_bench.py --fit): HIP events around %d calls after a warm-up, alternating in "
+        "one process," % (device, r["reps"]),
+        "best of three rounds", "",
+        "T = %d target frames at hop %d, k = %d, S = %d, R = %d; corpus N = %d frames at hop %d in 8 files, L = %d"
+        % (r["T"], r["hop"], r["k"], r["S"], r["R"], r["N"], r["hop"], r["L"]),
+        "search   (RV_MOSAIC_KNN)          %10.3f ms" % r["search_ms"],
+        "fit      (RV_GRAIN_FIT)           %10.3f ms   = %.4f of the search; %.3g fmas -> %.3g fma/s = %.3f of 39.3 T/s"
+        % (r["fit_ms"], r["fit_over_search"], r["fit_fmas"], r["fit_fmas_per_s"], r["of_unpacked_bound"]),
+        "gather   (RV_GRAIN_GATHER)        %10.4f ms" % r["gather_ms"],
+        "gather   (RV_MOSAIC_GATHER_MEAN)  %10.4f ms" % r["gather_mean_ms"],
+        "grains moved off the grid: %.4f; gains at gain_max: %.4f (random data)" % (r["moved"], r["clamped"])]) + "\n"
 
 
 def replay_ms(launch, reps, rounds=3):
@@ -299,11 +353,22 @@ def main(argv=None):
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--reps", type=int, default=None)
     p.add_argument("--live", action="store_true", help="time the live path only (few-query search, replay per block)")
-    p.add_argument("--summary", default=None, help="--live: also write the tables to this text file")
+    p.add_argument("--summary", default=None, help="--live / --fit: also write the tables to this text file")
     p.add_argument("--out", default=None)
     p.add_argument("--path", action="store_true", help="also time the unit selection beside the search at k = 16")
     p.add_argument("--lag", action="store_true", help="with --live: time the lagged unit selection against lag 0 instead")
+    p.add_argument("--fit", action="store_true", help="time the grain fit beside the search (nothing else is timed)")
     a = p.parse_args(argv)
+    if a.fit:
+        res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), fit=bench_fit(a.reps or 5))
+        text = fit_report(res["fit"], res["device"])
+        print(text, end="")
+        for path, body in ((a.summary, text), (a.out, json.dumps(res, indent=1))):
+            if path:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return res
     if a.lag and not a.live:
         raise ValueError("--lag: needs --live")
     if a.lag:
