@@ -511,6 +511,34 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  * and (N, L, k, splits, rows) in d->ws_bytes; launches nothing.  RV_MOSAIC_LIVE_RESET: rv_stream_reset(live, which),
  * prev = -1 and no pending rows for stream `which` (-1: every stream).
  *
+ * Live grain fitting (mode RV_LIVE_GRAINS only): width = R > 0 or lam = gain_max > 0, read by LIVE, LIVE_DRAIN,
+ * LIVE_WORKSPACE and LIVE_RESET as they read `rows`; both 0 = no fit: the launches, workspace bytes and bits above.
+ *   Every corpus frame a block is about to play is first fitted, by THE RULE of "Grain fitting" below (the c / e
+ *   chains, the score, the tie order, the gain and the room limits unchanged), to the TARGET FRAME IT STANDS FOR, and
+ *   the fitted grains are gathered by RV_GRAIN_GATHER's arithmetic in place of GATHER_MEAN's.
+ *   Target frame n of a stream (n counted from the stream's last reset, as the stream's frame counter counts) is
+ *   samples [n hop, n hop + S) of the stream's input since the reset prefixed by P = S - hop zeros: the frame the
+ *   encoder saw.  A LIVE_DRAIN block counts as input (zeros).
+ *   weight == NULL: each of the k candidates of new frame n is fitted to target frame n on its own and the k fitted
+ *     grains are averaged; the fit's rows are idx [M, k], M = n_streams * F, and its outputs [M, k].
+ *   weight != NULL: the one chosen or committed frame is fitted; the rows are choice [M, 1] and the outputs [M, 1].
+ *     With rows = D > 0 the frame committed at new frame n is fitted to the target frame that was new when its
+ *     candidates arrived: n - D while blocks follow one another, older for a row that waited through a LIVE_DRAIN
+ *     (at most 2 D frames old).  A choice of -1 (the first D frames after a reset, a dry drain, a frame without
+ *     candidates) gets shift 0, gain 0 and score 0 and adds nothing: the contract for a missing candidate.
+ *   Fields: slot [M, kf] int32 = the shifts, trans [M, kf] fp32 = the gains, cost [M, kf] fp64 = the scores of the
+ *     block's frames (kf = k without weight, 1 with); next_of = ONE table [3 N] int32: the successor table [N] (unread
+ *     without weight) followed by room [N, 2]; src, src_len, row_start as for RV_LIVE_GRAINS, n_rows = N.
+ *   State, in ws after the parts above: per stream a TARGET RING of C = P + 2 D hop + block floats, input sample a
+ *     (counted from the reset) at ring[a mod C], zeros before the reset.  One small launch writes the block at the
+ *     stream's frame count before the fit reads the ring, which then holds the block and the P + 2 D hop samples
+ *     before it, for any block length and any number of wraps; with D > 0 also the arrival frame of every pending row
+ *     [n_streams, D + 1] int64 and the target frame of every committed row [M] int64.  LIVE_RESET zeroes the rings of
+ *     the streams it resets.  LIVE / LIVE_DRAIN launch, between the selection and the overlap-add: the ring update,
+ *     the fit, the gather; no sync, no read of the device, capturable as before.
+ *   Errors before any launch, naming the field: R (width) outside [0, 1024]; gain_max (lam) not finite or negative; a
+ *     fit in mode RV_LIVE_DECODE; next_of, shift (slot), gain (trans) or score (cost) null; ws_bytes too small.
+ *
  * Grain fitting (csrc/grain.hip; DESIGN.md section 7.5 "Grain fitting"): after the selection, fit each candidate grain
  * to its target frame by a shift of at most R samples and a gain.  THE RULE.  For target frame t, x[n] =
  * frames[t hop + n], n < S.  For candidate j, i = idx[t, j] in [0, n_rows).  room [n_rows, 2] int32 (host-built, passed
@@ -575,7 +603,7 @@ typedef struct rv_mosaic_desc {
   long F, S, hop;
   const float* window;
   long n_out;
-  const int* next_of;            /* TRANSITION [N]; GRAIN_FIT: room [n_rows, 2] */
+  const int* next_of;            /* TRANSITION [N]; GRAIN_FIT: room [n_rows, 2]; LIVE with a fit: [3 N], successors then room */
   long row0, rows;               /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T; LIVE ops: rows = the lag */
   float* trans;                  /* [rows, k, k]: TRANSITION output, PATH_FORWARD input */
   float lam;                     /* PATH_FORWARD: lambda, the weight of the transition costs; GRAIN_FIT: gain_max */

@@ -29,6 +29,12 @@ nearest corpus frames in the model's latent space, and the result is overlap-add
                      0: leave the corpus's level).  With either flag the summary line names both values, and --matches
                      holds (file, sample offset, distance, shift, gain) per candidate, or with --continuity the chosen
                      frame's shift and gain after the slot
+  --live-fit N       with --live-block, grains mode: --fit for the live path.  Every corpus frame a block plays is
+                     first moved by up to N samples (0..1024) to where it lines up best with the target frame it stands
+                     for (with --lag L that frame is L frames old; the stream's input is kept on the device for it)
+  --live-gain-max X  with --live-block, grains mode: --gain-max for the live path (float >= 0; 0: the corpus's level).
+                     With either flag the summary line ends its live part with `, fit N, gain-max X` and --matches
+                     gains the shift and gain columns in the offline layout
 
 The corpus is the sorted *.wav in --corpus, each loaded at the .ini's sampling_rate and framed on its own.  Bad flag
 values, an empty corpus, unreadable wavs or a --k above the number of corpus frames raise ValueError naming the flag or
@@ -77,6 +83,8 @@ def parse_args(argv=None):
     p.add_argument("--lag", default=None, help="frames of look-ahead of the live path's unit selection (0..64, default 0)")
     p.add_argument("--fit", default=None, help="samples a grain may be shifted to fit its target frame (0..1024)")
     p.add_argument("--gain-max", default=None, help="largest gain of the fit (float >= 0; 0: no gain)")
+    p.add_argument("--live-fit", default=None, help="--fit for the live path (0..1024; needs --live-block)")
+    p.add_argument("--live-gain-max", default=None, help="--gain-max for the live path (needs --live-block)")
     args = p.parse_args(argv)
     args.live_block = None if args.live_block is None else _int_flag("live-block", args.live_block, 1)
     if args.streams is not None and args.live_block is None:
@@ -106,7 +114,7 @@ def parse_args(argv=None):
         if value is None:
             continue
         if args.live_block is not None:
-            raise ValueError("--%s %s: the live path (--live-block) does not fit grains" % (flag, value))
+            raise ValueError("--%s %s: fits the offline path only; with --live-block use --live-%s" % (flag, value, flag))
         if args.mode == "decode":
             raise ValueError("--%s %s: needs --mode grains, --mode decode plays no corpus audio" % (flag, value))
     args.fitted = args.fit is not None or args.gain_max is not None
@@ -114,6 +122,18 @@ def parse_args(argv=None):
     if args.fit > 1024:
         raise ValueError("--fit %d: at most 1024" % args.fit)
     args.gain_max = 0.0 if args.gain_max is None else _weight_flag("gain-max", args.gain_max)
+    for flag, value in (("live-fit", args.live_fit), ("live-gain-max", args.live_gain_max)):
+        if value is None:
+            continue
+        if args.live_block is None:
+            raise ValueError("--%s %s: needs --live-block" % (flag, value))
+        if args.mode == "decode":
+            raise ValueError("--%s %s: needs --mode grains, --mode decode plays no corpus audio" % (flag, value))
+    args.live_fitted = args.live_fit is not None or args.live_gain_max is not None
+    args.live_fit = 0 if args.live_fit is None else _int_flag("live-fit", args.live_fit, 0)
+    if args.live_fit > 1024:
+        raise ValueError("--live-fit %d: at most 1024" % args.live_fit)
+    args.live_gain_max = 0.0 if args.live_gain_max is None else _weight_flag("live-gain-max", args.live_gain_max)
     if not os.path.isdir(args.corpus):
         raise ValueError("--corpus %r: not a folder" % args.corpus)
     return args
@@ -218,7 +238,8 @@ def live_mosaic(index, target, block, hop, n_streams=1, **kw):
     choice [T]) with T the frames of all streams, stream after stream.  The target is cut into n_streams consecutive
     parts; every part is zero-padded to whole blocks that also flush the S - hop samples of latency.  With lag=N the
     frames still held back are drained, the output is cut N * hop samples later, and choice[t] is the frame committed
-    for frame t (N frames after its candidates were found)."""
+    for frame t (N frames after its candidates were found).  With fit= / gain_max= (StreamingMosaic's) a fifth element
+    holds the fits (shift, gain, score), each [T, kf] numpy and aligned with choice: row t is frame t's fit."""
     import numpy as np
     import torch
     from rawaudiovae_kelsey_amd.mosaic import StreamingMosaic
@@ -231,21 +252,29 @@ def live_mosaic(index, target, block, hop, n_streams=1, **kw):
         seg = target[s * part:(s + 1) * part]
         x[s, :seg.size] = seg
     x = torch.from_numpy(x).to(sm.device)
-    ys, idxs, dists, choices = [], [], [], []
+    ys, idxs, dists, choices, fits = [], [], [], [], []
     for b in range(n_blocks):
         ys.append(sm.process(x[:, b * block:(b + 1) * block]))
         i, d, c = sm.last_matches()
         idxs.append(i.clone()), dists.append(d.clone()), choices.append(c.clone())
+        if sm.fitted:
+            fits.append([t.clone() for t in sm.last_fit()])
     for b in range(-(-sm.lag_samples // block)):                 # every frame fed is committed and played
         ys.append(sm.drain())
         choices.append(sm.last_matches()[2].clone())
+        if sm.fitted:
+            fits.append([t.clone() for t in sm.last_fit()])
     late = sm.latency + sm.lag_samples
     y = torch.cat(ys, 1)[:, late:late + part].reshape(-1)[:n].cpu().numpy()
     k = idxs[0].shape[-1]
     frames = n_blocks * sm.frames_per_block
     choice = torch.cat(choices, 1)[:, sm.lag:sm.lag + frames]
-    return (y, torch.cat(idxs, 1).reshape(-1, k).cpu().numpy(), torch.cat(dists, 1).reshape(-1, k).cpu().numpy(),
-            choice.reshape(-1).cpu().numpy())
+    res = (y, torch.cat(idxs, 1).reshape(-1, k).cpu().numpy(), torch.cat(dists, 1).reshape(-1, k).cpu().numpy(),
+           choice.reshape(-1).cpu().numpy())
+    if sm.fitted:
+        parts = [torch.cat(p, 1)[:, sm.lag:sm.lag + frames] for p in zip(*fits)]
+        res += (tuple(p.reshape(-1, p.shape[-1]).cpu().numpy() for p in parts),)
+    return res
 
 
 def _live_rule(args):
@@ -256,18 +285,25 @@ def _live_rule(args):
 
 def run_live(args, index, target, hop, sr, n_files):
     from rawaudiovae_kelsey_amd import data as D
-    y, idx, dist, choice = live_mosaic(index, target, args.live_block, hop, args.streams, k=args.k, mode=args.mode,
-                                       window=args.window, continuity=args.continuity, lag=args.lag)
+    fits = None
+    kw = dict(k=args.k, mode=args.mode, window=args.window, continuity=args.continuity, lag=args.lag)
+    if args.live_fitted:
+        kw.update(fit=args.live_fit, gain_max=args.live_gain_max)
+    y, idx, dist, choice, *rest = live_mosaic(index, target, args.live_block, hop, args.streams, **kw)
+    if rest:                                                     # fitted: fit 0 with gain-max 0 fits nothing
+        fits = rest[0][:2]
     D.write_wav(args.out, y, sr)
     slot = None
     if args.continuity > 0:
         slot = [int((idx[t] == choice[t]).argmax()) if choice[t] >= 0 else -1 for t in range(len(choice))]
     if args.matches:
-        write_matches(args.matches, index.locate(idx), dist, slot)
+        write_matches(args.matches, index.locate(idx), dist, slot, fits)
     line = ("wrote %s: %d samples from %d target frames, %d corpus frames in %d files, k %d, mode %s, window %s, %s, "
             "block %d, streams %d" % (args.out, y.size, idx.shape[0], len(index), n_files, args.k, args.mode,
                                       args.window or "none", _live_rule(args),
                                       args.live_block, args.streams))
+    if args.live_fitted:
+        line += ", fit %d, gain-max %g" % (args.live_fit, args.live_gain_max)
     if args.continuity > 0:
         line += ", continuity %g, continuing %.4f" % (
             args.continuity, continuing_share(choice, index.successor(hop // index.step)))

@@ -4,6 +4,9 @@
 //   RV_GRAIN_FIT     per (target frame, candidate) the shift in [-R, R] and the gain of the least-squares fit of the
 //                    shifted grain to the frame: k_grain_fit, one workgroup per pair
 //   RV_GRAIN_GATHER  RV_MOSAIC_GATHER_MEAN with a shift and a gain per candidate: k_grain_gather
+// and the live path's use of both (RV_MOSAIC_LIVE / LIVE_DRAIN with a fit, mosaic.hip): rv_grain_live_* keep the
+// streams' input in a TARGET RING (k_live_target), fit the frames a block is about to play against the target frames
+// they stand for (k_grain_fit reading its frame from the ring) and gather them into the stream's frame buffer.
 #include <limits.h>
 #include <math.h>
 
@@ -30,17 +33,32 @@ __device__ __forceinline__ bool fit_before(double sa, int da, double sb, int db)
   return aa < ab || (aa == ab && da < db);
 }
 
+// Where the live path's target frames live (header, "Live grain fitting").  Per stream a ring of C floats: input
+// sample a (counted from the stream's last reset; a < 0 is the silence before it) sits at ring[a mod C].  Target frame
+// n is samples [n hop - P, n hop - P + S).  Row r of the fit is stream r / F, frame r % F of the block; it stands for
+// target frame tfr[r] (the lagged selection's stamp of the committed row) or, tfr == NULL, cnt[stream] + r % F, the
+// frame arriving now.  A frame older than max_age frames has left the ring and is not fitted.
+struct fit_ring {
+  const long long* cnt;
+  const long long* tfr;
+  long F, C, P;
+  long max_age;
+};
+
 // One workgroup per (t, j).  Shift delta = lo + d, d in [0, nsh): thread u of a pass owns d = 4 u .. 4 u + 3 and
 // walks n with two accumulators per shift, c = fmaf(x[n], g[n + d], c) and e = fmaf(g[n + d], g[n + d], e), each a
 // plain ascending chain over n from +0 -- the chain of a (delta, n) term never depends on which thread, pass or chunk
 // holds it.  The frame x and the span g[0 .. len + nsh - 1) are staged in LDS per chunk of FIT_CH samples; per four n
 // a thread reads x as one broadcast b128 and four new grain samples as one b128 at consecutive 16-byte slots across
 // lanes (conflict-free), and keeps the other four in registers (the sliding window).
+// RING false: the frame is tgt[t hop, t hop + S) of one waveform (RV_GRAIN_FIT).  RING true: tgt holds the streams'
+// target rings and `ring` says where row t's frame starts; only the staging of x differs.
+template <bool RING>
 __global__ void __launch_bounds__(FIT_THREADS)
 k_grain_fit(const float* __restrict__ tgt, long hop, int S, const int* __restrict__ idx, int k,
             const float* __restrict__ src, long src_len, const long long* __restrict__ row_start, long n_rows,
             const int* __restrict__ room, int R, float gain_max, int* __restrict__ shift, float* __restrict__ gain,
-            double* __restrict__ score) {
+            double* __restrict__ score, fit_ring ring) {
   __shared__ __attribute__((aligned(16))) float xs[FIT_CH];
   __shared__ __attribute__((aligned(16))) float gs[FIT_SPAN];
   __shared__ double red_s[FIT_THREADS / 64];
@@ -55,6 +73,18 @@ k_grain_fit(const float* __restrict__ tgt, long hop, int S, const int* __restric
     st = row_start[i];
     ok = st >= 0 && st <= src_len - S;
   }
+  const float* x = tgt + t * hop;
+  long xb = 0;   // RING: the frame's first sample in the stream's ring, in [0, C)
+  if constexpr (RING) {
+    const long sr = t / ring.F, j = t - sr * ring.F;
+    const long long now = ring.cnt[sr] + j, tf = ring.tfr ? ring.tfr[t] : now;
+    ok = ok && tf <= now && now - tf <= ring.max_age;
+    x = tgt + sr * ring.C;
+    if (ok) {
+      xb = (long)((tf * hop - ring.P) % ring.C);
+      if (xb < 0) xb += ring.C;
+    }
+  }
   if (!ok) {
     if (threadIdx.x == 0) {
       shift[tj] = 0;
@@ -68,7 +98,6 @@ k_grain_fit(const float* __restrict__ tgt, long hop, int S, const int* __restric
   if (st + lo < 0) lo = (int)-st;                              // whatever room says, a grain never leaves src
   if (st + hi > src_len - S) hi = (int)(src_len - S - st);
   const int nsh = hi - lo + 1;
-  const float* x = tgt + t * hop;
   const float* g = src + st + lo;
 
   double best_s = -1.0;   // below every score: the first permitted shift replaces it
@@ -85,7 +114,15 @@ k_grain_fit(const float* __restrict__ tgt, long hop, int S, const int* __restric
       const int xlen = (len + 3) & ~3;          // the reads below reach xs[0, xlen) and gs[0, glen + 7)
       const int glen = len + nsh - 1;           // <= FIT_CH + 2 FIT_RMAX
       __syncthreads();
-      for (int m = threadIdx.x; m < xlen; m += blockDim.x) xs[m] = m < len ? x[n0 + m] : 0.f;
+      if constexpr (RING) {
+        for (int m = threadIdx.x; m < xlen; m += blockDim.x) {
+          long p = xb + n0 + m;   // < 2 C: S <= C
+          if (p >= ring.C) p -= ring.C;
+          xs[m] = m < len ? x[p] : 0.f;
+        }
+      } else {
+        for (int m = threadIdx.x; m < xlen; m += blockDim.x) xs[m] = m < len ? x[n0 + m] : 0.f;
+      }
       for (int m = threadIdx.x; m < glen + 8; m += blockDim.x) gs[m] = m < glen ? g[n0 + m] : 0.f;
       __syncthreads();
       if (!active) continue;
@@ -205,6 +242,28 @@ k_grain_gather(const float* __restrict__ src, long src_len, const long long* __r
   }
 }
 
+// The block of every stream into its target ring at the stream's frame count (k_stream_ola moves the count on at the
+// end of the call, so every kernel of one call reads the same count).  Grid (ceil(block / 256), n_streams).
+__global__ void __launch_bounds__(256)
+k_live_target(const float* __restrict__ x, long ld_x, long block, long hop, long C, const long long* __restrict__ cnt,
+              float* __restrict__ ring) {
+  const long s = blockIdx.y, i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= block) return;
+  const long p = (long)((cnt[s] * hop + i) % C);
+  ring[s * C + p] = x[s * ld_x + i];
+}
+
+// Grid (ceil(C / 256), streams): silence in the rings of streams [first, first + gridDim.y)
+__global__ void __launch_bounds__(256) k_live_target_clear(float* __restrict__ ring, long C, long first) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < C) ring[(first + blockIdx.y) * C + i] = 0.f;
+}
+
+unsigned fit_threads(long R) {
+  const long units = (2 * R + 1 + FIT_NS - 1) / FIT_NS;
+  return (unsigned)(units >= FIT_THREADS ? FIT_THREADS : (units + 63) / 64 * 64);
+}
+
 int fit_tk_check(const rv_mosaic_desc* d, const char* op) {
   RV_REQUIRE(d->T >= 1 && d->T < (1L << 40), RV_ERR_SHAPE, "rv_mosaic(%s): T=%ld outside [1, 2^40)", op, d->T);
   RV_REQUIRE(d->k >= 1 && d->k <= KMAX, RV_ERR_SHAPE, "rv_mosaic(%s): k=%ld must be in [1, %d]", op, d->k, KMAX);
@@ -238,11 +297,9 @@ int rv_grain_fit(const rv_mosaic_desc* d, void* stream) {
              d->S);
   RV_REQUIRE(d->T * d->k < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(GRAIN_FIT): T=%ld rows of k=%ld too many for one call",
              d->T, d->k);
-  const long units = (2 * d->width + 1 + FIT_NS - 1) / FIT_NS;
-  const long threads = units >= FIT_THREADS ? FIT_THREADS : (units + 63) / 64 * 64;
-  hipLaunchKernelGGL(k_grain_fit, dim3((unsigned)(d->T * d->k)), dim3((unsigned)threads), 0, (hipStream_t)stream,
-                     d->frames, d->hop, (int)d->S, d->idx, (int)d->k, d->src, d->src_len, d->row_start, d->n_rows,
-                     d->next_of, (int)d->width, d->lam, d->slot, d->trans, d->cost);
+  hipLaunchKernelGGL(k_grain_fit<false>, dim3((unsigned)(d->T * d->k)), dim3(fit_threads(d->width)), 0,
+                     (hipStream_t)stream, d->frames, d->hop, (int)d->S, d->idx, (int)d->k, d->src, d->src_len,
+                     d->row_start, d->n_rows, d->next_of, (int)d->width, d->lam, d->slot, d->trans, d->cost, fit_ring{});
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -263,6 +320,56 @@ int rv_grain_gather(const rv_mosaic_desc* d, void* stream) {
   hipLaunchKernelGGL(k_grain_gather, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d->src, d->src_len,
                      d->row_start, d->stride, d->n_rows, d->width, d->idx, d->slot, d->trans, d->T, (int)d->k, d->out,
                      d->ldo);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+long rv_grain_live_ring(long S, long hop, long block, long lag) { return S - hop + 2 * lag * hop + block; }
+
+int rv_grain_live_check(const rv_mosaic_desc* d, const char* op, int run) {
+  RV_REQUIRE(d->width >= 0 && d->width <= FIT_RMAX, RV_ERR_SHAPE, "rv_mosaic(%s): R (width)=%ld outside [0, %d]", op,
+             d->width, FIT_RMAX);
+  RV_REQUIRE(d->lam >= 0.f && d->lam < INFINITY, RV_ERR_SHAPE,
+             "rv_mosaic(%s): gain_max (lam)=%g must be finite and not negative", op, (double)d->lam);
+  if (d->width == 0 && d->lam == 0.f) return RV_OK;
+  RV_REQUIRE(d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED,
+             "rv_mosaic(%s): a fit (R (width)=%ld, gain_max (lam)=%g) needs mode RV_LIVE_GRAINS, mode=%ld plays no "
+             "corpus audio", op, d->width, (double)d->lam, d->mode);
+  const rv_stream_desc* sd = d->live;
+  RV_REQUIRE(sd->S < INT_MAX && sd->hop < (1L << 20) && sd->n_streams * (sd->block / sd->hop) * d->k < (1L << 31) &&
+                 (sd->block + 255) / 256 < (1L << 31) && sd->n_streams <= 65535, RV_ERR_SHAPE,
+             "rv_mosaic(%s): a fit takes S=%ld < 2^31, hop=%ld < 2^20, n_streams=%ld <= 65535 and fewer than 2^31 "
+             "(frame, candidate) pairs", op, sd->S, sd->hop, sd->n_streams);
+  if (!run) return RV_OK;
+  RV_REQUIRE(d->next_of, RV_ERR_NULL, "rv_mosaic(%s): with a fit next_of [3 N] holds the successors and room: it is null",
+             op);
+  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(%s): shift (slot) is null", op);
+  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(%s): gain (trans) is null", op);
+  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(%s): score (cost) is null", op);
+  return RV_OK;
+}
+
+int rv_grain_live_reset(float* ring, long C, long first, long n, void* stream) {
+  hipLaunchKernelGGL(k_live_target_clear, dim3((unsigned)((C + 255) / 256), (unsigned)n), dim3(256), 0,
+                     (hipStream_t)stream, ring, C, first);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+int rv_grain_live(const rv_mosaic_desc* d, const int* sel, int sel_k, float* ring, const long long* cnt,
+                  const long long* tfr, float* frames, void* stream) {
+  const rv_stream_desc* sd = d->live;
+  const hipStream_t st = (hipStream_t)stream;
+  const long F = sd->block / sd->hop, M = sd->n_streams * F;
+  const long C = rv_grain_live_ring(sd->S, sd->hop, sd->block, d->rows);
+  hipLaunchKernelGGL(k_live_target, dim3((unsigned)((sd->block + 255) / 256), (unsigned)sd->n_streams), dim3(256), 0, st,
+                     sd->x, sd->ld_x, sd->block, sd->hop, C, cnt, ring);
+  const fit_ring fr{cnt, tfr, F, C, sd->S - sd->hop, 2 * d->rows};
+  hipLaunchKernelGGL(k_grain_fit<true>, dim3((unsigned)(M * sel_k)), dim3(fit_threads(d->width)), 0, st, ring, sd->hop,
+                     (int)sd->S, sel, sel_k, d->src, d->src_len, d->row_start, d->N, d->next_of + d->N, (int)d->width,
+                     d->lam, d->slot, d->trans, d->cost, fr);
+  hipLaunchKernelGGL(k_grain_gather, dim3((unsigned)(M > 65536 ? 65536 : M)), dim3(256), 0, st, d->src, d->src_len,
+                     d->row_start, 0L, d->N, sd->S, sel, d->slot, d->trans, M, sel_k, frames, sd->S);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

@@ -124,7 +124,22 @@ RV_INTERNAL int rv_linear_dgrad_wgrad_ex(rv_gemm_operands dgrad, rv_gemm_operand
 // rv_stream_synth: decode != 0: fc3 and fc4 on the latent rows into the frames; then k_stream_ola on the frames.
 RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, float** frames, void* stream);
 RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream);
+// the streams' frame counters [n_streams] int64 in the stream workspace (frames since the stream's last reset; moved on
+// by the overlap-add at the end of a block call)
+RV_INTERNAL const long long* rv_stream_counters(const rv_stream_desc* d);
 // The two grain-fitting ops of rv_mosaic (grain.hip): RV_GRAIN_FIT and RV_GRAIN_GATHER on the fields the public header
 // names for them; checks first, then one launch each, no sync and no read of the device.
 RV_INTERNAL int rv_grain_fit(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_grain_gather(const rv_mosaic_desc* d, void* stream);
+// The live mosaic's grain fit (grain.hip; the rule: the public header, "Live grain fitting"), on the fields the header
+// names: width = R, lam = gain_max, slot / trans / cost [M, sel_k], next_of [3 N] = successors then room.
+// rv_grain_live_check: the fit's argument checks for op `op` (d->live is not null); run: also the tables and outputs.
+// rv_grain_live_ring: floats of one stream's target ring.  rv_grain_live_reset: silence in the rings of n streams from
+// `first`.  rv_grain_live: the block into the rings, the fit of sel [M, sel_k] against the target frames the rows stand
+// for (tfr [M] from the lagged selection, or NULL: the frames arriving now) and the gather of the fitted grains into
+// frames [M, S]; three launches, no sync and no read of the device.
+RV_INTERNAL int rv_grain_live_check(const rv_mosaic_desc* d, const char* op, int run);
+RV_INTERNAL long rv_grain_live_ring(long S, long hop, long block, long lag);
+RV_INTERNAL int rv_grain_live_reset(float* ring, long C, long first, long n, void* stream);
+RV_INTERNAL int rv_grain_live(const rv_mosaic_desc* d, const int* sel, int sel_k, float* ring, const long long* cnt,
+                              const long long* tfr, float* frames, void* stream);

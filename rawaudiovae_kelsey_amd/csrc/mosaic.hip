@@ -938,11 +938,14 @@ __device__ __forceinline__ int lag_solve(const float* __restrict__ c, long N, lo
 // rows are pending.  push == 0 (drain): no new rows; up to F times, lag_solve on the shrinking window while rows are
 // pending, -1 after.  No index is used as an address before it is checked against [0, N).  The ring is written by
 // some threads and read by others across the barriers, so its pointers are not __restrict__.
+// stamp != NULL (a grain fit follows): every pending row also keeps the frame count at which it arrived, fcnt[s] + f,
+// in stamp [n_streams, R], and tfr[r] = the committed row's stamp: the target frame it stands for.  Thread 0 alone
+// writes and reads the stamps.
 __global__ void __launch_bounds__(256)
 k_live_lag(const float* __restrict__ c, long N, long L, const int* __restrict__ next_of, const int* __restrict__ idx,
            const float* __restrict__ dist, int k, long F, int push, int R, int vec, const float* __restrict__ weight,
            int* __restrict__ prev, int* __restrict__ state, int* ridx, float* rdist, float* rtrans,
-           int* __restrict__ choice) {
+           int* __restrict__ choice, const long long* __restrict__ fcnt, long long* stamp, long long* __restrict__ tfr) {
   __shared__ unsigned char backL[(LAG_MAX + 1) * KMAX];
   __shared__ unsigned char endL[LAG_MAX + 1];
   const long s = blockIdx.x;
@@ -980,13 +983,17 @@ k_live_lag(const float* __restrict__ c, long N, long L, const int* __restrict__ 
         ri[pos * k + tid] = idx[r * k + tid];
         rd[pos * k + tid] = dist[r * k + tid];
       }
+      if (stamp && tid == 0) stamp[s * R + pos] = fcnt[s] + f;
       ++cnt;
       __syncthreads();   // the row is in the ring for wave 0, and for the next frame's transitions
     }
     if (push ? cnt == R : cnt > 0) {   // uniform over the workgroup
       if (tid < 64) {
         p = lag_solve(c, N, L, next_of, k, w, p, vec, ri, rd, rt, head, cnt, R, backL, endL);
-        if (tid == 0) choice[r] = p;
+        if (tid == 0) {
+          choice[r] = p;
+          if (stamp) tfr[r] = stamp[s * R + head];
+        }
       }
       head = head + 1 == R ? 0 : head + 1;
       --cnt;
@@ -1134,13 +1141,20 @@ int run_knn(const rv_mosaic_desc* d, bool small, hipStream_t st) {
 // RV_MOSAIC_LIVE's workspace: prev [n_streams] int32, the query rows [M, L] fp32, the search's partials; with a lag of
 // D = d->rows > 0 frames then the lagged selection's state: (head, count) [n_streams, 2] int32 and the rings of
 // R = D + 1 rows per stream, idx [n_streams, R, k] int32, dist [n_streams, R, k] fp32, trans [n_streams, R, k, k] fp32.
+// With a grain fit (d->width > 0 or d->lam > 0) then the TARGET RINGS [n_streams, C] fp32, C = P + 2 D hop + block:
+// input sample a of a stream (counted from its last reset) at ring[a mod C], silence before the reset; the block is
+// written at the stream's frame count before the fit reads it, so the ring holds the block and the P + 2 D hop samples
+// before it (a row that drains interleave with blocks can wait up to 2 D frames).  With a lag also the pending rows'
+// arrival stamps [n_streams, R] int64 and the committed rows' target frames [M] int64.
 // Every part starts on a 256-byte boundary.  M = n_streams * block / hop rows go to k_knn_small up to SMALL_T_MAX.
 struct live_ws {
   long M, q, knn, knn_bytes, bytes;
   bool small;
   long lag, state, ridx, rdist, rtrans;
+  bool fit;
+  long C, ring, stamp, tfr;
 };
-int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
+int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w, bool run = false) {
   const rv_stream_desc* sd = d->live;
   RV_REQUIRE(sd, RV_ERR_NULL, "rv_mosaic(%s): null stream descriptor", op);
   RV_REQUIRE(sd->n_streams >= 1 && sd->hop >= 1 && sd->block >= sd->hop && sd->block % sd->hop == 0 && sd->S >= sd->hop &&
@@ -1153,6 +1167,8 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
              d->rows, LAG_MAX);
   RV_REQUIRE(d->rows == 0 || d->weight, RV_ERR_NULL,
              "rv_mosaic(%s): lag (rows)=%ld needs unit selection: weight is null", op, d->rows);
+  const int frc = rv_grain_live_check(d, op, run);
+  if (frc) return frc;
   w->M = sd->n_streams * (sd->block / sd->hop);
   w->small = w->M <= SMALL_T_MAX;
   rv_mosaic_desc kd = *d;
@@ -1173,6 +1189,17 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w) {
     w->rdist = w->ridx + up(rows * d->k * 4);
     w->rtrans = w->rdist + up(rows * d->k * 4);
     w->bytes = w->rtrans + up(rows * d->k * d->k * 4);
+  }
+  w->fit = d->width > 0 || d->lam > 0.f;
+  if (w->fit) {
+    w->C = rv_grain_live_ring(sd->S, sd->hop, sd->block, w->lag);
+    w->ring = w->bytes;
+    w->bytes = w->ring + up(sd->n_streams * w->C * 4);
+    if (w->lag > 0) {
+      w->stamp = w->bytes;
+      w->tfr = w->stamp + up(sd->n_streams * (w->lag + 1) * 8);
+      w->bytes = w->tfr + up(w->M * 8);
+    }
   }
   return RV_OK;
 }
@@ -1291,6 +1318,7 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
         hipLaunchKernelGGL(k_live_lag_clear, dim3((unsigned)((2 * n + 255) / 256)), dim3(256), 0, st,
                            (int*)((char*)d->ws + w.state) + 2 * first, n);
       RV_CHECK_LAUNCH();
+      if (w.fit) return rv_grain_live_reset((float*)((char*)d->ws + w.ring), w.C, first, n, stream);
       return RV_OK;
     }
     case RV_MOSAIC_LIVE:
@@ -1298,7 +1326,7 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       const bool drain = op == RV_MOSAIC_LIVE_DRAIN;
       const char* who = drain ? "LIVE_DRAIN" : "LIVE";
       live_ws w;
-      int rc = live_layout(d, who, &w);
+      int rc = live_layout(d, who, &w, true);
       if (rc) return rc;
       const rv_stream_desc* sd = d->live;
       const bool decode = d->mode == RV_LIVE_DECODE;
@@ -1329,13 +1357,20 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       }
       const int* sel = d->idx;
       int sel_k = (int)d->k;
+      // with a fit the lagged selection stamps its rows: tfr [M] = the target frame each committed row stands for
+      const long long* fcnt = w.fit ? rv_stream_counters(sd) : nullptr;
+      long long *stamp = nullptr, *tfr = nullptr;
+      if (w.fit && w.lag > 0) {
+        stamp = (long long*)(ws + w.stamp);
+        tfr = (long long*)(ws + w.tfr);
+      }
       if (d->weight) {
         if (w.lag > 0) {
           const int vec = d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0;   // 16-byte loads of latent rows
           hipLaunchKernelGGL(k_live_lag, dim3((unsigned)sd->n_streams), dim3(256), 0, st, d->c, d->N, d->L, d->next_of,
                              d->idx, d->dist, (int)d->k, sd->block / sd->hop, drain ? 0 : 1, (int)w.lag + 1, vec, d->weight,
                              (int*)ws, (int*)(ws + w.state), (int*)(ws + w.ridx), (float*)(ws + w.rdist),
-                             (float*)(ws + w.rtrans), d->choice);
+                             (float*)(ws + w.rtrans), d->choice, fcnt, stamp, tfr);
         } else {
           hipLaunchKernelGGL(k_live_select, dim3((unsigned)sd->n_streams), dim3(64), 0, st, d->c, d->N, d->L, d->next_of,
                              d->idx, d->dist, (int)d->k, sd->block / sd->hop, d->weight, (int*)ws, d->choice);
@@ -1343,12 +1378,16 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
         sel = d->choice;
         sel_k = 1;
       }
-      if (decode)
+      if (decode) {
         hipLaunchKernelGGL(k_gather_mean, dim3(blocks_for(w.M, 65536)), dim3(256), 0, st, d->c, d->N * d->L, nullptr,
                            d->L, d->N, d->L, sel, w.M, sel_k, z, d->L);
-      else
+      } else if (w.fit) {   // each grain fitted to the target frame it stands for, then gathered
+        rc = rv_grain_live(d, sel, sel_k, (float*)(ws + w.ring), fcnt, tfr, frames, stream);
+        if (rc) return rc;
+      } else {
         hipLaunchKernelGGL(k_gather_mean, dim3(blocks_for(w.M, 65536)), dim3(256), 0, st, d->src, d->src_len,
                            d->row_start, 0L, d->N, sd->S, sel, w.M, sel_k, frames, sd->S);
+      }
       RV_CHECK_LAUNCH();
       return rv_stream_synth(sd, decode, stream);
     }

@@ -432,6 +432,12 @@ RV_INTERNAL int rv_stream_encode(const rv_stream_desc* d, float* q, float** z, f
   return stream_encode<false>(d, w, q, (hipStream_t)stream);
 }
 
+RV_INTERNAL const long long* rv_stream_counters(const rv_stream_desc* d) {
+  Ws w;
+  ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);
+  return w.cnt;
+}
+
 RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* stream) {
   Ws w;
   ws_layout(d->S, d->H, d->L, d->n_streams, d->block, d->hop, (char*)d->workspace, &w);

@@ -41,6 +41,13 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
       oldest frame, so each choice has seen D frames of its future and the audio comes `lag_samples` = D * hop samples
       later still (the first D frames of a stream are silent in grains mode).  drain() plays out what the window
       still holds, one block per call (drain_replay() after capture()).  The rule: include/rawvae_hip.h.
+  StreamingMosaic(..., fit=R, gain_max=g)
+      live grain fitting ("grains" mode): every corpus frame the block is about to play is first fitted, by the rule of
+      index.mosaic(fit=, gain_max=), to the target frame it stands for -- the frame of the stream's own input that the
+      encoder saw, which with a lag is `lag` frames old (older still for a frame that drain() plays out).  The input
+      is kept per stream in a ring on the device; nothing syncs, capture() / replay() / drain() / reset() work as
+      before, and last_fit() returns the block's (shift, gain, score).  At continuity 0 the output equals
+      index.mosaic(..., fit=R, gain_max=g) of the same input bit for bit.  fit=0, gain_max=0 is the class without them.
 
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
@@ -557,10 +564,11 @@ LAG_MAX = 64       # frames of look-ahead of the live selection at most (csrc/mo
 
 
 def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=None, k=1, mode="grains", window=None,
-                    continuity=0.0, lag=0):
+                    continuity=0.0, lag=0, fit=0, gain_max=0.0):
     """Validate a StreamingMosaic configuration without a device -> (hop, latency, frames per block, successor
-    advance).  ValueError naming the argument."""
+    advance).  ValueError naming the argument (`fit` / `gain_max`: check_fit's ranges, and mode "grains" only)."""
     S = int(segment_length)
+    fit, gain_max = check_fit(fit, gain_max)
     if int(n_corpus) < 1:
         raise ValueError("index: the index is empty, add() corpus files first")
     if int(n_streams) <= 0:
@@ -578,6 +586,9 @@ def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=
     if int(lag) > 0 and continuity == 0:
         raise ValueError("lag=%d needs continuity > 0: without unit selection there is nothing to look ahead for"
                          % int(lag))
+    if (fit > 0 or gain_max > 0) and mode == "decode":
+        raise ValueError("fit=%d, gain_max=%g: grains are fitted in mode 'grains' only, mode 'decode' plays no "
+                         "corpus audio" % (fit, gain_max))
     hop, latency, frames = check_args(S, block, hop, window)   # ValueError naming hop, block or window
     adv = 1
     if continuity > 0:
@@ -598,14 +609,21 @@ class StreamingMosaic:
     as 0).  The index must not change after construction.
 
     `lag` > 0 (needs continuity > 0): fixed-lag Viterbi selection.  The choices, and with them the audio, come
-    `lag_samples` = lag * hop samples later on top of `latency`; `drain()` plays out the frames still held back."""
+    `lag_samples` = lag * hop samples later on top of `latency`; `drain()` plays out the frames still held back.
 
-    def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0, lag=0):
+    `fit` = R > 0 or `gain_max` > 0 (mode "grains"): every frame played is fitted to the target frame it stands for
+    (see the module doc); with them the equality above holds against `index.mosaic(..., fit=R, gain_max=gain_max)`,
+    and `last_fit()` returns the block's shifts, gains and scores."""
+
+    def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0, lag=0,
+                 fit=0, gain_max=0.0):
         from .stream import StreamingVAE
         self.index = index
         N = len(index)
         self.hop, self.latency, self.frames_per_block, adv = check_live_args(
-            index.S, index.step, N, n_streams, block, hop, k, mode, window, continuity, lag)
+            index.S, index.step, N, n_streams, block, hop, k, mode, window, continuity, lag, fit, gain_max)
+        self.fit, self.gain_max = check_fit(fit, gain_max)
+        self.fitted = self.fit > 0 or self.gain_max > 0
         self.lag = int(lag)
         self.lag_samples = self.lag * self.hop
         # the framing, history, window tables and stream workspace are StreamingVAE's
@@ -623,6 +641,15 @@ class StreamingMosaic:
         self._idx = torch.full((M, self.k), -1, dtype=torch.int32, device=self.device)
         self._dist = torch.full((M, self.k), float("inf"), dtype=torch.float32, device=self.device)
         self._choice = torch.full((M,), -1, dtype=torch.int32, device=self.device)
+        self._fit = None
+        if self.fitted:
+            # the library reads one table with a fit: the successors [N] (unread without unit selection), then room
+            succ = self._next_of if self.selects else torch.zeros(N, dtype=torch.int32, device=self.device)
+            self._next_of = torch.cat([succ, index._room()[1].reshape(-1)]).contiguous()
+            kf = 1 if self.selects else self.k
+            self._fit = (torch.zeros((M, kf), dtype=torch.int32, device=self.device),
+                         torch.zeros((M, kf), dtype=torch.float32, device=self.device),
+                         torch.zeros((M, kf), dtype=torch.float64, device=self.device))
         self._ws = None
         nbytes = self._call(_lib.MOSAIC_LIVE_WORKSPACE, None, None).ws_bytes
         self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
@@ -638,6 +665,9 @@ class StreamingMosaic:
                        ws_bytes=0 if self._ws is None else self._ws.numel(), live=_lib.C.pointer(sd),
                        mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS, weight=ptr(self.weight),
                        which=int(which), rows=self.lag)
+        if self.fitted:
+            d.width, d.lam = self.fit, self.gain_max
+            d.slot, d.trans, d.cost = (ptr(t) for t in self._fit)
         host_only = op == _lib.MOSAIC_LIVE_WORKSPACE
         lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else (stream_ptr() if stream is None else stream))
         return d
@@ -676,7 +706,8 @@ class StreamingMosaic:
     @torch.no_grad()
     def reset(self, streams=None):
         """Zero the history, the overlap-add tail and the frame counter of `streams` (an index or a list; None = all)
-        and forget their last chosen corpus frame and the frames their lag holds back."""
+        and forget their last chosen corpus frame and the frames their lag holds back; with a fit their target
+        history is silence again."""
         if streams is None:
             self._call(_lib.MOSAIC_LIVE_RESET, None, None, -1)
             return
@@ -695,6 +726,15 @@ class StreamingMosaic:
         F = self.frames_per_block
         return (self._idx.view(self.n_streams, F, self.k), self._dist.view(self.n_streams, F, self.k),
                 self._choice.view(self.n_streams, F))
+
+    def last_fit(self):
+        """(shift [n_streams, F, kf] int32, gain [n_streams, F, kf] fp32, score [n_streams, F, kf] fp64) of the last
+        block's frames as views of static buffers, or None when nothing is fitted; kf = k at continuity 0 (one fit per
+        candidate), 1 with unit selection (the chosen or committed frame's fit; (0, 0, 0) where choice is -1)."""
+        if self._fit is None:
+            return None
+        F = self.frames_per_block
+        return tuple(t.view(self.n_streams, F, -1) for t in self._fit)
 
     @torch.no_grad()
     def capture(self):

@@ -5,6 +5,7 @@
     python tools/mosaic_bench.py --live [--reps 30] [--summary profiles/mosaic_live_summary.txt]
     python tools/mosaic_bench.py --live --lag [--reps 30] [--summary profiles/mosaic_live_lag_summary.txt]
     python tools/mosaic_bench.py --fit [--reps 5] [--summary profiles/mosaic_fit_summary.txt]
+    python tools/mosaic_bench.py --live --fit [--reps 30] [--summary profiles/mosaic_live_fit_summary.txt]
 
 Search shapes (T, N, L, k): one minute of target at hop 128 (20 700 frames) and one second (344 frames), both against
 one hour of corpus at hop 128 (1.24 M frames), latent_dim 256, k = 4.  Per shape: device time (events around `reps`
@@ -37,6 +38,15 @@ corpus audio (1.24 M frames at hop 128 in 8 files, random samples) -- beside the
 (RV_GRAIN_GATHER), alternating in one process, HIP events around `reps` calls, the best of three rounds each.  The rate
 is in fmas/s, 2 T k (2R + 1) S per call (the c and the e chain), against 78.6 T fma/s (the fp32 vector spec, unpacked
 fmas: 39.3 T/s).
+
+--live --fit (nothing else is timed): live grain fitting, StreamingMosaic(fit=R, gain_max=4).  One replay() per block,
+grains, k = 4, hop = block = 256, S = 1024 (one frame per block and stream), n_streams in {1, 8}, against the 124 000
+frame corpus of the --live --lag table; once at continuity 0 (k fits per frame) and once at continuity 0.5 with lag 8
+(one fit per frame); R in {0 (the gain alone), 64, 256, 1024}.  Each fitted replay alternates in one process with the
+unfitted replay of the same configuration, the best of three rounds each, every window full before the clock starts.
+Beside each time: the time over the unfitted replay (the ring update, the fit and the fitted gather in place of the
+plain one: with a handful of workgroups per block this is the latency of one workgroup's 2R + 1 shifts, not a
+throughput) and the block's duration at 44.1 kHz.
 
 mosaic(): a VAE(1024, 2048, 256) with random weights, a 40 s corpus in 8 files and a 5 s target at hop 256, k = 4,
 grains and decode, wall time of the call including the target's encoder pass (the corpus is indexed beforehand).
@@ -315,6 +325,65 @@ def bench_live_lag(reps):
     return rows
 
 
+FIT_RS = (0, 64, 256, 1024)
+
+
+def bench_live_fit(reps, n_frames=124000, k=4, hop=256, block=256, gain_max=4.0):
+    from rawvae.model import VAE
+    torch.manual_seed(0)
+    m = VAE(1024, 2048, 256).cuda().eval()
+    g = torch.Generator(device="cuda").manual_seed(1)
+    index = M.LatentIndex(m, hop=128)
+    per_file = n_frames // 8
+    for i in range(8):
+        frames = per_file + (n_frames - 8 * per_file if i == 7 else 0)
+        index.add(torch.randn((frames - 1) * 128 + 1024, device="cuda", generator=g) * 0.3, "c%d" % i)
+    assert len(index) == n_frames
+    rows = []
+    for continuity, lag in ((0.0, 0), (0.5, 8)):
+        for n_streams in (1, 8):
+            x = torch.randn(n_streams, block, device="cuda", generator=g) * 0.3
+            sms = {}
+            for R in (None,) + FIT_RS:                            # None: no fit
+                kw = {} if R is None else dict(fit=R, gain_max=gain_max)
+                sm = M.StreamingMosaic(index, n_streams, block, hop=hop, k=k, mode="grains", window="hann",
+                                       continuity=continuity, lag=lag, **kw).capture()
+                sm.graph_input.copy_(x)
+                for _ in range(lag + 4):                          # fill the window and the target ring: steady state
+                    sm.replay()
+                sms[R] = sm
+            ms = dict.fromkeys(sms, float("inf"))
+            for _ in range(3):                                    # alternating
+                for R in sms:
+                    ms[R] = min(ms[R], replay_ms(sms[R].replay, reps, rounds=1))
+            budget = block / 44100.0 * 1e3
+            for R in FIT_RS:
+                shift = sms[R].last_fit()[0]
+                rows.append(dict(N=n_frames, k=k, n_streams=n_streams, hop=hop, block=block, continuity=continuity,
+                                 lag=lag, R=R, gain_max=gain_max, fits_per_block=int(shift.numel()),
+                                 ms=round(ms[R], 4), unfitted_ms=round(ms[None], 4), over_ms=round(ms[R] - ms[None], 4),
+                                 block_ms=round(budget, 3), meets=bool(ms[R] < budget),
+                                 moved=float((shift != 0).float().mean())))
+            del sms
+    return rows
+
+
+def live_fit_report(rows, device):
+    out = ["live grain fitting on %s (tools/mosaic_bench.py --live --fit): HIP events around graph replays after a "
+           "warm-up that fills" % device, "every window and target ring", "",
+           "one StreamingMosaic.replay() per block, grains, k = %d, hop = block = %d, S = 1024, Hann window, gain_max %g, "
+           "VAE(1024, 2048, 256)," % (rows[0]["k"], rows[0]["block"], rows[0]["gain_max"]),
+           "N = %d corpus frames; fitted and unfitted replays alternate in one process, best of three rounds; over = ms - "
+           "unfitted ms" % rows[0]["N"],
+           "%8s %5s %4s %5s %5s %10s %12s %10s %10s %6s" % ("streams", "cont", "lag", "R", "fits", "ms/block", "unfitted ms",
+                                                           "over ms", "block ms", "meets")]
+    for r in rows:
+        out.append("%8d %5g %4d %5d %5d %10.4f %12.4f %10.4f %10.3f %6s" % (
+            r["n_streams"], r["continuity"], r["lag"], r["R"], r["fits_per_block"], r["ms"], r["unfitted_ms"],
+            r["over_ms"], r["block_ms"], "yes" if r["meets"] else "NO"))
+    return "\n".join(out) + "\n"
+
+
 def live_lag_report(rows, device):
     out = ["live mosaicing with a lag on %s (tools/mosaic_bench.py --live --lag): HIP events around graph replays after a "
            "warm-up that fills every window" % device, "",
@@ -357,8 +426,20 @@ def main(argv=None):
     p.add_argument("--out", default=None)
     p.add_argument("--path", action="store_true", help="also time the unit selection beside the search at k = 16")
     p.add_argument("--lag", action="store_true", help="with --live: time the lagged unit selection against lag 0 instead")
-    p.add_argument("--fit", action="store_true", help="time the grain fit beside the search (nothing else is timed)")
+    p.add_argument("--fit", action="store_true", help="time the grain fit beside the search (nothing else is timed); with --live: the live fit")
     a = p.parse_args(argv)
+    if a.fit and a.live:
+        if a.lag:
+            raise ValueError("--lag: --live --fit times lag 0 and lag 8 itself")
+        res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), live_fit=bench_live_fit(a.reps or 30))
+        text = live_fit_report(res["live_fit"], res["device"])
+        print(text, end="")
+        for path, body in ((a.summary, text), (a.out, json.dumps(res, indent=1))):
+            if path:
+                os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+                with open(path, "w") as f:
+                    f.write(body)
+        return res
     if a.fit:
         res = dict(device=torch.cuda.get_device_name(0), host=platform.node(), fit=bench_fit(a.reps or 5))
         text = fit_report(res["fit"], res["device"])
