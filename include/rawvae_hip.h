@@ -683,7 +683,8 @@ typedef struct rv_param_desc {
  * t = *step_counter (1-based).  grad_scale multiplies the summed gradient first
  * (1/world_size after an all-reduce SUM).  `descs` is HOST memory (copied per call).
  * grad_bf16 != NULL: the gradient is taken from that flat bf16 arena (same element offsets as the fp32 arenas; a bf16
- * all-reduce's result) instead of the descriptors' slabs; grad_out must then be NULL. */
+ * all-reduce's result) instead of the descriptors' slabs; grad_out must then be NULL.  The descriptors may be the ones the
+ * slabs were summed with (fp16 slabs included): only offset, shape and shadows are used, and every element is updated. */
 int rv_adam_multi(const rv_param_desc* descs, int n_desc, float* param, float* exp_avg,
                   float* exp_avg_sq, float* grad_out, const void* grad_bf16, float lr, float grad_scale,
                   const long long* step_counter, void* stream);

@@ -137,8 +137,10 @@ __host__ __device__ inline bool adam_wide(const rv_param_desc& d) {
          ((d.cols | d.grad_ld | d.grad_split_stride | d.offset | d.shadow_ld) & 7) == 0 &&
          ((reinterpret_cast<uintptr_t>(d.grad_slabs) & 15) == 0);
 }
-__host__ __device__ inline long adam_groups(const rv_param_desc& d) {   // thread-sized groups of one tensor
-  return adam_wide(d) ? d.rows * (d.cols / 8) : d.rows * ((d.cols + 3) / 4);
+// Thread-sized groups of one tensor.  `flat_grad`: the gradient comes from a flat bf16 arena (rv_adam_multi's grad_bf16),
+// not from the slabs -- adam_block then walks every tensor 4 elements per thread, whatever its slabs look like.
+__host__ __device__ inline long adam_groups(const rv_param_desc& d, const bool flat_grad = false) {
+  return adam_wide(d) && !flat_grad ? d.rows * (d.cols / 8) : d.rows * ((d.cols + 3) / 4);
 }
 
 // The 8-elements-per-thread form of adam_block for fp16-slab tensors (adam_wide): same arithmetic per element (slab
@@ -238,7 +240,9 @@ __device__ __forceinline__ void adam_block(const DescTable& tab, const long vblo
   while (t + 1 < tab.n && vblock >= tab.blk_start[t + 1]) ++t;
   t = __builtin_amdgcn_readfirstlane(t);   // vblock is wave-uniform in every caller
   const rv_param_desc d = tab.d[t];
-  if (adam_wide(d) && !grad_in_bf16) {   // wave-uniform (the descriptor is); a bf16 flat gradient comes with fp32-slab descriptors
+  // wave-uniform (the descriptor is).  With a bf16 flat gradient the slabs are not read and the 4-wide walk below serves
+  // every descriptor: the table was built for it (adam_build_table's flat_grad)
+  if (adam_wide(d) && !grad_in_bf16) {
     adam_block_wide<UPDATE>(d, vblock - tab.blk_start[t], tid, param, m_arena, v_arena, grad_out, lr, grad_scale,
                             step_counter, grad_out_bf16);
     return;
@@ -617,8 +621,10 @@ k_adam(const DescTable tab, float* __restrict__ param, float* __restrict__ m_are
                      step_counter, grad_out_bf16, grad_in_bf16);
 }
 
-// Host side: descriptor table with the first virtual block of every tensor.
-inline int adam_build_table(const rv_param_desc* descs, int n, DescTable* tab) {
+// Host side: descriptor table with the first virtual block of every tensor.  `flat_grad` must say whether the kernel
+// that walks the table is given a flat bf16 gradient: the block layout follows the path adam_block takes (a table sized
+// for 8 elements per thread and walked with 4 updated only the first half of an fp16-slab tensor, silently).
+inline int adam_build_table(const rv_param_desc* descs, int n, DescTable* tab, const bool flat_grad = false) {
   RV_REQUIRE(descs && n > 0 && n <= MAX_DESC, RV_ERR_SHAPE, "param desc count %d out of range", n);
   tab->n = n;
   long blk = 0;
@@ -629,7 +635,7 @@ inline int adam_build_table(const rv_param_desc* descs, int n, DescTable* tab) {
     RV_REQUIRE(descs[i].rows * ((descs[i].cols + 3) / 4) < 0x7fffffffL, RV_ERR_SHAPE, "param desc %d: tensor too large", i);
     tab->blk_start[i] = blk;
     {
-      const long groups = adam_groups(descs[i]);
+      const long groups = adam_groups(descs[i], flat_grad);
       blk += adam_coop(descs[i]) ? (groups + 3) / 4 : (groups + 255) / 256;
     }
   }

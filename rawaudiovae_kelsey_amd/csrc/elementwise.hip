@@ -972,7 +972,7 @@ int rv_adam_multi_guarded(const rv_param_desc* descs, int n_desc, float* param, 
   RV_REQUIRE(param && exp_avg && exp_avg_sq && step_counter, RV_ERR_NULL, "rv_adam_multi: null pointer");
   RV_REQUIRE(!(grad_bf16 && grad_out), RV_ERR_UNSUPPORTED, "rv_adam_multi: grad_out is the sum of the slabs; not with grad_bf16");
   DescTable tab;
-  int rc = adam_build_table(descs, n_desc, &tab);
+  int rc = adam_build_table(descs, n_desc, &tab, grad_bf16 != nullptr);
   if (rc) return rc;
   hipLaunchKernelGGL(k_adam<true>, dim3((unsigned)tab.blk_start[n_desc]), dim3(256), 0,
                      (hipStream_t)stream, tab, param, exp_avg, exp_avg_sq, grad_out, lr, grad_scale,

@@ -23,7 +23,8 @@ import torch
 SENTINEL = 7.0       # what the existing kernel tests fill outputs with
 PACKED_FILL = -3.0   # fill of the packed twin of an output (see above)
 
-_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+_INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32,
+           torch.uint8: torch.uint8}   # (uint8: fp8 images, tests/optimizer_oracle.py)
 
 
 def _round64(n):
