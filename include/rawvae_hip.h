@@ -564,7 +564,47 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
  *   before its add, the sum in ascending j from +0, 1/k applied once; a candidate outside [0, n_rows) or a shifted
  *   grain that would leave src adds nothing.  With shift 0 and gain 1 it is RV_MOSAIC_GATHER_MEAN bit for bit.
  * Both return an RV_ERR_* whose message names the field before anything is launched: R (width), T, k, a null table,
- * frames that overrun n_out, gain_max (lam). */
+ * frames that overrun n_out, gain_max (lam).
+ *
+ * Evaluation (csrc/eval.hip, rawaudiovae_kelsey_amd/evaluate.py): how close a test signal y is
+ * to a reference signal x, frame by frame, and how the KL term spreads over the latent dimensions.
+ * RV_EVAL_FRAMES scores T frame pairs.  Fields:
+ *   T            the frame pairs, 1 <= T < 2^31;  S, hop: frame length and hop (S >= 1, hop >= 1)
+ *   frames, n_out  x, a padded waveform [n_out]: frame t = frames[t hop, t hop + S), (T - 1) hop + S <= n_out
+ *   src, stride, src_len  y: row t = src[t stride, t stride + S), (T - 1) stride + S <= src_len, stride >= 1
+ *                (stride >= S: decoded frames [T, S]; stride = hop: a second waveform whose rows overlap)
+ *   q, c, L      mu and logvar [T, L] fp32; both NULL: no KL column (written as 0); exactly one NULL is an error
+ *   window       [S] fp32, or NULL: the spectral columns 3..5 are not computed (written as 0)
+ *   weight       the twiddle table [S] fp32, required with a window: S / 2 complex pairs, weight[2 j] = cos(2 pi j / S),
+ *                weight[2 j + 1] = -sin(2 pi j / S) for j < S / 2, computed by the caller in float64 and rounded once
+ *   lam          the dynamic range R in dB, 0 < R <= 120
+ *   out, ldo     [T, ldo] fp32, ldo >= 6; only columns 0..5 of rows 0..T-1 are written:
+ *     0  sse = sum_n (y[n] - x[n])^2   the differences in fp32, their squares and the sum in fp64, rounded once
+ *     1  energy = sum_n x[n]^2         likewise
+ *     2  kl = sum_j -0.5 (1 + lv - mu^2 - exp(lv))   every term and the sum in fp64, rounded once
+ *     3  lsd (dB), 4  spec_err = sum_k (sqrt Pa[k] - sqrt Pb[k])^2, 5  spec_ref = sum_k Pa[k]
+ *   The spectral columns need S a power of two, 32 <= S <= 4096 (a window with another S is RV_ERR_SHAPE).
+ *   a[n] = fl32(window[n] x[n]), b[n] = fl32(window[n] y[n]); A, B their S-point DFTs at the K = S / 2 + 1 bins
+ *   k = 0 .. S / 2; Pa = |A|^2, Pb = |B|^2; floor = max(max_k Pa, max_k Pb) * fl32(10^(-R / 10));
+ *   D[k] = 10 log10((Pa[k] + floor) / (Pb[k] + floor)); lsd = sqrt(mean_k D[k]^2).  floor == 0 (both frames silent):
+ *   columns 3..5 are 0.  Each signal is transformed ON ITS OWN (an S/2-point complex radix-2 transform of its even
+ *   and odd samples in LDS and the real-transform post-pass), in fp32 with every product and sum rounded on its own;
+ *   D^2, (sqrt Pa - sqrt Pb)^2 and Pa are fp32 terms added in fp64 and rounded once.
+ *   A sample that is NaN or Inf makes the columns it enters non-finite in that row and touches no other row: 0 and 1
+ *   by the arithmetic above; a power Pa[k] or Pb[k] that is not finite makes 3 and 4 NaN, a Pa[k] also 5.
+ *   A row's six values depend on that row's data, S, L, R, the window and the table only -- not on T, hop, stride, ldo
+ *   or the launch: one workgroup of 256 threads per row, every sum in an order fixed by S and L.  A row scored alone
+ *   is bit-equal to the same row scored among others; identical x and y give sse = lsd = spec_err = +0 exactly.
+ *   One launch; no sync and no read of the device (it may run under capture).
+ * RV_EVAL_DIMS: q, c = mu, logvar [T, L] fp32 (1 <= T < 2^31, 1 <= L <= 2^20) -> cost [L] fp64,
+ *   cost[j] = sum_t -0.5 (1 + lv[t, j] - mu[t, j]^2 - exp(lv[t, j])), every term in fp64.  The rows are taken in blocks
+ *   of 256: block b = rows [256 b, 256 b + 256) is added in ascending t from +0, then the block sums are added in
+ *   ascending b from +0.  ws / ws_bytes: 8 * ceil(T / 256) * L bytes of device scratch when T > 256 (unused, and may
+ *   be NULL / 0, up to 256 rows).  No atomics: bit-identical from run to run.  One launch, two when T > 256.
+ * Both return an RV_ERR_* whose message names the field before anything is launched and without reading a device
+ * pointer: T, S, hop, stride, L out of range; frames that overrun n_out or src_len; ldo < 6; a null frames, src, out
+ * or cost; one of mu / logvar without the other; R (lam) out of range; a window without a table (weight) or with an S
+ * that is no power of two in [32, 4096]; ws_bytes too small. */
 #define RV_MOSAIC_KNN 0
 #define RV_MOSAIC_KNN_WORKSPACE 1
 #define RV_MOSAIC_GATHER_MEAN 2
@@ -581,6 +621,8 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_MOSAIC_LIVE_DRAIN 13
 #define RV_GRAIN_FIT 14
 #define RV_GRAIN_GATHER 15
+#define RV_EVAL_FRAMES 16
+#define RV_EVAL_DIMS 17
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
 struct rv_stream_desc;

@@ -81,6 +81,7 @@ MOSAIC_TRANSITION, MOSAIC_PATH_FORWARD, MOSAIC_PATH_BACKTRACK, MOSAIC_PATH_WORKS
 MOSAIC_KNN_SMALL, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_LIVE, MOSAIC_LIVE_WORKSPACE, MOSAIC_LIVE_RESET = 8, 9, 10, 11, 12
 MOSAIC_LIVE_DRAIN = 13
 GRAIN_FIT, GRAIN_GATHER = 14, 15   # RV_GRAIN_* (rv_mosaic)
+EVAL_FRAMES, EVAL_DIMS = 16, 17    # RV_EVAL_* (rv_mosaic)
 LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.

@@ -1,0 +1,303 @@
+// Held-out evaluation (rawaudiovae_kelsey_amd/evaluate.py): the two scoring ops of rv_mosaic.  The rules: include/
+// rawvae_hip.h, "Evaluation"; the LDS layout, the error model and the measured figures: DESIGN.md section 7.9.
+//   RV_EVAL_FRAMES  per frame pair (x, y): squared error, energy, KL, log-spectral distance and the two sums of the
+//                   spectral convergence: k_eval_frames, one workgroup of 256 threads per pair.  The spectra come from a
+//                   radix-2 transform in LDS, each signal transformed on its own.
+//   RV_EVAL_DIMS    the KL sum of every latent dimension over the rows: k_eval_dims_block (one thread per (block of
+//                   256 rows, dimension)), then k_eval_dims_sum over the blocks.  No atomics.
+#include <limits.h>
+#include <math.h>
+
+#include "common.h"
+#include "internal.h"
+
+using namespace rv;
+
+namespace {
+
+constexpr int EV_THREADS = 256;
+constexpr int EV_SMAX = 4096;            // longest frame with spectral columns
+constexpr int EV_SMIN = 32;
+constexpr int DIMS_ROWS = 256;           // rows of one block of RV_EVAL_DIMS (the header states it)
+constexpr int DIMS_THREADS = 64;
+
+// Sum of one double per thread over the workgroup, in a fixed order: within a wave the xor butterfly (every lane ends
+// with the same bits), then the four wave sums in ascending wave order.  Valid in every thread.
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();   // red may still be read from the call before
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+__device__ __forceinline__ float block_max_f32(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+
+__device__ __forceinline__ double kl_term(float mu, float lv) {
+  const double m = (double)mu, l = (double)lv;
+  return -0.5 * (1.0 + l - m * m - exp(l));
+}
+
+// The spectral arithmetic is plain fp32 with every product and sum rounded on its own (no contraction), so that the
+// float32 restatement of tests/eval_oracle.py states it operation for operation.
+struct cpx {
+  float r, i;
+};
+
+__device__ __forceinline__ cpx cmul(float wr, float wi, float zr, float zi) {
+#pragma clang fp contract(off)
+  cpx o;
+  o.r = wr * zr - wi * zi;
+  o.i = wr * zi + wi * zr;
+  return o;
+}
+
+__device__ __forceinline__ float power(float r, float i) {
+#pragma clang fp contract(off)
+  return r * r + i * i;
+}
+
+// One workgroup per row t.  x = xs + t * hop, y = ys + t * stride, S samples each.
+//
+// Columns 0 / 1: thread u adds the terms n = u, u + 256, ... in ascending n from +0 in fp64, then block_sum_f64.
+// Column 2 likewise over j < L.
+//
+// Spectral columns (SPEC): N = S / 2, lg = log2 N.  The windowed signal a[n] = fl(w[n] x[n]) is read as N complex
+// points z[m] = a[2m] + i a[2m + 1] and stored bit-reversed, z[m] at ar / ai [rev(m)]; b likewise in br / bi.  lg stages
+// of decimation-in-time butterflies in place, h = 1, 2, .., N / 2: butterfly j < N / 2 has p = j mod h,
+// i0 = 2 h (j div h) + p, i1 = i0 + h, W = tw[p * (N / h)] (tw[q] = exp(-2 pi i q / S), S / 2 entries), t = W z[i1],
+// z[i1] = z[i0] - t, z[i0] = z[i0] + t.  Then the real-transform post-pass on the pairs (k, N - k), k = 0 .. N / 2,
+// with Z[N] = Z[0]: E = (Z[k] + conj Z[N - k]) / 2, O = (Z[k] - conj Z[N - k]) / 2i, T = tw[k] O, and the two powers
+// P[k] = |E + T|^2, P[N - k] = |E - T|^2, written over ar[k], ar[N - k] (ar has N + 1 slots) -- every pair is read and
+// written by one thread.  LDS: 4 N + 2 floats of dynamic shared memory (8 200 bytes at S = 1024, 32 776 at S = 4096).
+// The bit-reversed store of the load sends consecutive lanes N / 64 floats apart (16-way bank conflicts at N = 2048,
+// 4-way at N = 512), once per sample; the stages with h < 32 are 2-way conflicted.
+template <bool SPEC>
+__global__ void __launch_bounds__(EV_THREADS)
+k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ ys, long stride, int S,
+              const float* __restrict__ mu, const float* __restrict__ lv, int L, const float* __restrict__ win,
+              const float* __restrict__ tw, float floor_scale, float* __restrict__ out, long ldo) {
+  extern __shared__ float lds[];   // SPEC: 4 N + 2 floats, sized by the launch; none otherwise
+  __shared__ double red[EV_THREADS / 64];
+  __shared__ float redf[EV_THREADS / 64];
+  const long t = blockIdx.x;
+  const float* x = xs + t * hop;
+  const float* y = ys + t * stride;
+  const int N = S >> 1;
+  const int lg = 31 - __clz(N > 0 ? N : 1);
+  float* const ar = lds;               // N + 1
+  float* const ai = ar + N + 1;        // N
+  float* const br = ai + N;            // N + 1
+  float* const bi = br + N + 1;        // N
+
+  double sse = 0.0, en = 0.0;
+  for (int n = threadIdx.x; n < S; n += EV_THREADS) {
+    const float xv = x[n], yv = y[n];
+    const float d = yv - xv;
+    sse += (double)d * (double)d;
+    en += (double)xv * (double)xv;
+    if constexpr (SPEC) {
+      const float w = win[n];
+      const int m = (int)(__brev((unsigned)(n >> 1)) >> (32 - lg));
+      if (n & 1) {
+        ai[m] = w * xv;
+        bi[m] = w * yv;
+      } else {
+        ar[m] = w * xv;
+        br[m] = w * yv;
+      }
+    }
+  }
+  sse = block_sum_f64(sse, red);
+  en = block_sum_f64(en, red);
+  double kl = 0.0;
+  if (mu) {
+    for (int j = threadIdx.x; j < L; j += EV_THREADS) kl += kl_term(mu[t * L + j], lv[t * L + j]);
+    kl = block_sum_f64(kl, red);
+  }
+  float lsd = 0.f, serr = 0.f, sref = 0.f;
+  if constexpr (SPEC) {
+    const int half = N >> 1;
+    for (int h = 1, sh = 0; h < N; h <<= 1, ++sh) {
+      __syncthreads();
+      const int tstep = N >> sh;   // N / h
+      for (int j = threadIdx.x; j < half; j += EV_THREADS) {
+        const int p = j & (h - 1);
+        const int i0 = ((j >> sh) << (sh + 1)) + p, i1 = i0 + h;
+        const float wr = tw[2 * p * tstep], wi = tw[2 * p * tstep + 1];
+        {
+          const cpx tt = cmul(wr, wi, ar[i1], ai[i1]);
+          const float ur = ar[i0], ui = ai[i0];
+          ar[i0] = ur + tt.r;
+          ai[i0] = ui + tt.i;
+          ar[i1] = ur - tt.r;
+          ai[i1] = ui - tt.i;
+        }
+        {
+          const cpx tt = cmul(wr, wi, br[i1], bi[i1]);
+          const float ur = br[i0], ui = bi[i0];
+          br[i0] = ur + tt.r;
+          bi[i0] = ui + tt.i;
+          br[i1] = ur - tt.r;
+          bi[i1] = ui - tt.i;
+        }
+      }
+    }
+    __syncthreads();
+    // the post-pass; the pair (k, N - k) belongs to one thread, so the powers may overwrite the points in place
+    float pmax = 0.f;
+    bool bad_a = false, bad_b = false;
+    for (int k = threadIdx.x; k <= half; k += EV_THREADS) {
+      const int kn = k == 0 ? 0 : N - k;
+      const float wr = tw[2 * k], wi = tw[2 * k + 1];
+      float p0[2], p1[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const float* zr = s ? br : ar;
+        const float* zi = s ? bi : ai;
+        const float er = 0.5f * (zr[k] + zr[kn]), ei = 0.5f * (zi[k] - zi[kn]);
+        const float orr = 0.5f * (zi[k] + zi[kn]), oi = -0.5f * (zr[k] - zr[kn]);
+        const cpx tt = cmul(wr, wi, orr, oi);
+        p0[s] = power(er + tt.r, ei + tt.i);
+        p1[s] = power(er - tt.r, ei - tt.i);
+      }
+      ar[k] = p0[0];
+      br[k] = p0[1];
+      if (N - k != k) {
+        ar[N - k] = p1[0];
+        br[N - k] = p1[1];
+      }
+      // a power that is NaN or +inf: fmaxf would drop a NaN, so it is carried on its own
+      bad_a = bad_a || !(p0[0] < INFINITY) || !(p1[0] < INFINITY);
+      bad_b = bad_b || !(p0[1] < INFINITY) || !(p1[1] < INFINITY);
+      pmax = fmaxf(pmax, fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p1[0], p1[1])));
+    }
+    pmax = block_max_f32(pmax, redf);
+    const int nbad_a = __syncthreads_or(bad_a), nbad_b = __syncthreads_or(bad_b);
+    const float fl = pmax * floor_scale;
+    double d2 = 0.0, se = 0.0, sr = 0.0;
+    for (int k = threadIdx.x; k <= N; k += EV_THREADS) {
+      const float pa = ar[k], pb = br[k];
+      sr += (double)pa;
+      if (fl > 0.f) {
+        const float d = 10.f * log10f((pa + fl) / (pb + fl));
+        const float e = sqrtf(pa) - sqrtf(pb);
+        d2 += (double)(d * d);
+        se += (double)(e * e);
+      }
+    }
+    d2 = block_sum_f64(d2, red);
+    se = block_sum_f64(se, red);
+    sr = block_sum_f64(sr, red);
+    if (fl > 0.f) {
+      lsd = (float)sqrt(d2 / (double)(N + 1));
+      serr = (float)se;
+      sref = (float)sr;
+    }
+    if (nbad_a || nbad_b) lsd = serr = NAN;
+    if (nbad_a) sref = NAN;
+  }
+  if (threadIdx.x == 0) {
+    float* o = out + t * ldo;
+    o[0] = (float)sse;
+    o[1] = (float)en;
+    o[2] = (float)kl;
+    o[3] = lsd;
+    o[4] = serr;
+    o[5] = sref;
+  }
+}
+
+// Grid (blocks of DIMS_ROWS rows, tiles of DIMS_THREADS dimensions): thread (b, j) adds rows [256 b, 256 b + 256) of
+// dimension j in ascending t from +0 into part[b, j] (which is `cost` itself when there is one block).
+__global__ void __launch_bounds__(DIMS_THREADS)
+k_eval_dims_block(const float* __restrict__ mu, const float* __restrict__ lv, long T, long L, double* __restrict__ part) {
+  const long j = (long)blockIdx.y * DIMS_THREADS + threadIdx.x;
+  if (j >= L) return;
+  const long t0 = (long)blockIdx.x * DIMS_ROWS, t1 = t0 + DIMS_ROWS < T ? t0 + DIMS_ROWS : T;
+  double acc = 0.0;
+  for (long t = t0; t < t1; ++t) acc += kl_term(mu[t * L + j], lv[t * L + j]);
+  part[(long)blockIdx.x * L + j] = acc;
+}
+
+// cost[j] = the block sums of dimension j in ascending block order from +0
+__global__ void __launch_bounds__(DIMS_THREADS)
+k_eval_dims_sum(const double* __restrict__ part, long nb, long L, double* __restrict__ cost) {
+  const long j = (long)blockIdx.x * DIMS_THREADS + threadIdx.x;
+  if (j >= L) return;
+  double acc = 0.0;
+  for (long b = 0; b < nb; ++b) acc += part[b * L + j];
+  cost[j] = acc;
+}
+
+}  // namespace
+
+int rv_eval_frames(const rv_mosaic_desc* d, void* stream) {
+  RV_REQUIRE(d->T >= 1 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): T=%ld outside [1, 2^31)", d->T);
+  RV_REQUIRE(d->S >= 1 && d->S < INT_MAX, RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): S=%ld outside [1, 2^31)", d->S);
+  RV_REQUIRE(d->hop >= 1 && d->hop < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): hop=%ld outside [1, 2^31)", d->hop);
+  RV_REQUIRE(d->stride >= 1 && d->stride < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): stride=%ld outside [1, 2^31)",
+             d->stride);
+  RV_REQUIRE(d->frames, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): frames is null");
+  RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): src is null");
+  RV_REQUIRE(d->out, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): out is null");
+  RV_REQUIRE(d->ldo >= 6, RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): ldo=%ld holds no row of 6 scores", d->ldo);
+  RV_REQUIRE(d->n_out >= d->S && (d->T - 1) * d->hop <= d->n_out - d->S, RV_ERR_SHAPE,
+             "rv_mosaic(EVAL_FRAMES): T=%ld frames of S=%ld at hop=%ld overrun n_out=%ld", d->T, d->S, d->hop, d->n_out);
+  RV_REQUIRE(d->src_len >= d->S && (d->T - 1) * d->stride <= d->src_len - d->S, RV_ERR_SHAPE,
+             "rv_mosaic(EVAL_FRAMES): T=%ld rows of S=%ld at stride=%ld overrun src_len=%ld", d->T, d->S, d->stride,
+             d->src_len);
+  RV_REQUIRE(!d->q == !d->c, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): %s is null but %s is not: the KL column needs both",
+             d->q ? "logvar (c)" : "mu (q)", d->q ? "mu (q)" : "logvar (c)");
+  if (d->q)
+    RV_REQUIRE(d->L >= 1 && d->L <= (1L << 20), RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): L=%ld outside [1, 2^20]", d->L);
+  RV_REQUIRE(d->lam > 0.f && d->lam <= 120.f, RV_ERR_SHAPE,
+             "rv_mosaic(EVAL_FRAMES): R (lam)=%g dB must be in (0, 120]", (double)d->lam);
+  if (d->window) {
+    RV_REQUIRE(d->S >= EV_SMIN && d->S <= EV_SMAX && (d->S & (d->S - 1)) == 0, RV_ERR_SHAPE,
+               "rv_mosaic(EVAL_FRAMES): S=%ld: the spectral columns (window given) need a power of two in [%d, %d]",
+               d->S, EV_SMIN, EV_SMAX);
+    RV_REQUIRE(d->weight, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): window given but the twiddle table (weight) is null");
+  }
+  const float floor_scale = (float)pow(10.0, -(double)d->lam / 10.0);
+  const dim3 grid((unsigned)d->T), block(EV_THREADS);
+  const hipStream_t st = (hipStream_t)stream;
+  if (d->window)
+    hipLaunchKernelGGL(k_eval_frames<true>, grid, block, (4 * (d->S / 2) + 2) * sizeof(float), st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->q,
+                       d->c, (int)d->L, d->window, d->weight, floor_scale, d->out, d->ldo);
+  else
+    hipLaunchKernelGGL(k_eval_frames<false>, grid, block, 0, st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->q,
+                       d->c, (int)d->L, (const float*)nullptr, (const float*)nullptr, floor_scale, d->out, d->ldo);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+int rv_eval_dims(const rv_mosaic_desc* d, void* stream) {
+  RV_REQUIRE(d->T >= 1 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): T=%ld outside [1, 2^31)", d->T);
+  RV_REQUIRE(d->L >= 1 && d->L <= (1L << 20), RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): L=%ld outside [1, 2^20]", d->L);
+  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): mu (q) is null");
+  RV_REQUIRE(d->c, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): logvar (c) is null");
+  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): cost is null");
+  const long nb = (d->T + DIMS_ROWS - 1) / DIMS_ROWS;
+  const long need = nb > 1 ? nb * d->L * (long)sizeof(double) : 0;
+  RV_REQUIRE(d->ws_bytes >= need, RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): ws_bytes=%ld, T=%ld rows of L=%ld need %ld", d->ws_bytes,
+             d->T, d->L, need);
+  RV_REQUIRE(need == 0 || d->ws, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): ws is null, T=%ld rows of L=%ld need %ld bytes", d->T,
+             d->L, need);
+  const hipStream_t st = (hipStream_t)stream;
+  const unsigned tiles = (unsigned)((d->L + DIMS_THREADS - 1) / DIMS_THREADS);
+  double* part = nb > 1 ? (double*)d->ws : d->cost;
+  hipLaunchKernelGGL(k_eval_dims_block, dim3((unsigned)nb, tiles), dim3(DIMS_THREADS), 0, st, d->q, d->c, d->T, d->L, part);
+  if (nb > 1)
+    hipLaunchKernelGGL(k_eval_dims_sum, dim3(tiles), dim3(DIMS_THREADS), 0, st, (const double*)d->ws, nb, d->L, d->cost);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}

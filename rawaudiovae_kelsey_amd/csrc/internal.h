@@ -143,3 +143,7 @@ RV_INTERNAL long rv_grain_live_ring(long S, long hop, long block, long lag);
 RV_INTERNAL int rv_grain_live_reset(float* ring, long C, long first, long n, void* stream);
 RV_INTERNAL int rv_grain_live(const rv_mosaic_desc* d, const int* sel, int sel_k, float* ring, const long long* cnt,
                               const long long* tfr, float* frames, void* stream);
+// The two evaluation ops of rv_mosaic (eval.hip): RV_EVAL_FRAMES and RV_EVAL_DIMS on the fields the public header names
+// for them; checks first, then one launch (EVAL_DIMS: two beyond one block of rows), no sync and no read of the device.
+RV_INTERNAL int rv_eval_frames(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_eval_dims(const rv_mosaic_desc* d, void* stream);

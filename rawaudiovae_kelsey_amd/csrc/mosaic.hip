@@ -12,6 +12,7 @@
 //                          the oldest), gather-mean, then the stream's decoder / overlap-add
 //   RV_MOSAIC_LIVE_DRAIN   one block that plays out the frames a lag still holds back: no encoder, no search
 //   RV_GRAIN_FIT / RV_GRAIN_GATHER   shift-and-gain fit of every candidate grain to its target frame: grain.hip
+//   RV_EVAL_FRAMES / RV_EVAL_DIMS    held-out evaluation, per-frame scores and per-dimension KL sums: eval.hip
 // Layout, split and merge, and the measured figures: DESIGN.md sections 7.5, 7.6 and 7.7.
 #include <limits.h>
 
@@ -1395,6 +1396,10 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       return rv_grain_fit(d, stream);
     case RV_GRAIN_GATHER:
       return rv_grain_gather(d, stream);
+    case RV_EVAL_FRAMES:
+      return rv_eval_frames(d, stream);
+    case RV_EVAL_DIMS:
+      return rv_eval_dims(d, stream);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }

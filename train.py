@@ -19,7 +19,13 @@ test_original.wav, test_reconst_%05d.wav}}`), same checkpoint dict keys
   * librosa / soundfile are replaced by scipy wav I/O; TensorBoard is used when importable.
 
 An optional `[mi355x]` section adds `seed`, `loss_ring`, `tensorboard`, `fp8` (fc1 / fc4 forward on e4m3 operands,
-BASELINE configs[4]) and `wgrad_slabs` (`fp32` | `fp16` split-K partial sums) keys.
+BASELINE configs[4]) and `wgrad_slabs` (`fp32` | `fp16` split-K partial sums) keys, and two opt-in keys for validation
+(rawaudiovae_kelsey_amd/evaluate.py): `validate = True` (needs `generate_test`) scores the test set after every epoch,
+deterministically (z = mu), prints `====> Epoch: N - Validation loss: X (mse M, kld K, snr S dB, lsd D dB)`, writes the
+`Loss/validation`, `Validation/snr_db` and `Validation/lsd_db` scalars and stores `validation_loss` (the lowest) and
+`best_validation_epoch` in config.ini's `[training]`; `best_by = validation` (needs `validate`) picks `best_model.pt`
+by the lowest validation loss instead of the training loss (`best_by = train`, the default).  Without them a run prints
+and writes exactly what it did before.
 
 Data-parallel training (no counterpart in the reference, which is single-process): launch with
 `python -m torch.distributed.run --nproc-per-node N train.py --config default.ini`, one process per
@@ -72,6 +78,30 @@ def engine_options(hw):
         raise ValueError("[mi355x] wgrad_slabs = {} (expected fp32 or fp16)".format(slabs))
     kw['slab_dtype'] = slabs
     return kw
+
+
+def validation_options(hw, generate_test, segment_length=None):
+    """(validate, best_by) from the optional [mi355x] section: `validate` (boolean, default False; needs generate_test,
+    and a segment_length the spectral figures take) and `best_by` (`train`, the default, or `validation`, which needs
+    validate).  ValueError naming the key."""
+    raw = str(hw.get('validate', 'False')).lower()
+    if raw not in ('1', 'true', 'yes', 'on', '0', 'false', 'no', 'off'):
+        raise ValueError("[mi355x] validate = {} (expected a boolean)".format(hw.get('validate')))
+    validate = raw in ('1', 'true', 'yes', 'on')
+    if validate and not generate_test:
+        raise ValueError("[mi355x] validate = True needs [dataset] generate_test = True: the test set is what it scores")
+    if validate and segment_length is not None:
+        from rawaudiovae_kelsey_amd.evaluate import check_args
+        try:
+            check_args(segment_length)
+        except ValueError as e:
+            raise ValueError("[mi355x] validate = True: {}".format(e))
+    best_by = str(hw.get('best_by', 'train')).lower()
+    if best_by not in ('train', 'validation'):
+        raise ValueError("[mi355x] best_by = {} (expected train or validation)".format(hw.get('best_by')))
+    if best_by == 'validation' and not validate:
+        raise ValueError("[mi355x] best_by = validation needs validate = True")
+    return validate, best_by
 
 
 def require_gpu(local_rank=0):
@@ -142,6 +172,13 @@ class DataParallel:
         ranks block in a host call with no step in flight and no bound."""
         if self.active:
             self.dist.barrier()
+
+    def solo(self, fn, *args):
+        """fn(*args) on rank 0 alone while the other ranks wait for it at rendezvous(); rank 0's result there, None on
+        the others."""
+        out = fn(*args) if self.main else None
+        self.rendezvous()
+        return out
 
     def check(self):
         """Health of the library-driven step, before results are read back (every rank calls it at the same points).
@@ -309,6 +346,7 @@ def main(argv=None):
     ring = int(hw.get('loss_ring', 256))
     use_tb = str(hw.get('tensorboard', 'True')).lower() in ('1', 'true', 'yes')
     engine_kw = engine_options(hw)
+    validate, best_by = validation_options(hw, generate_test, segment_length)
 
     device = require_gpu(int(os.environ.get("LOCAL_RANK", "0")))
     dp = DataParallel(device)
@@ -378,6 +416,24 @@ def main(argv=None):
         print('Audio examples generated: {}'.format(audio_out))
         writer.add_audio('Reconstructed Audio', pred, epoch, sample_rate=sampling_rate)
 
+    evaluator = None
+    if validate and dp.main:
+        from rawaudiovae_kelsey_amd.evaluate import Evaluator
+        evaluator = Evaluator(model)     # reads the Parameters in place on every call; draws nothing (z = mu)
+    best_validation, best_validation_epoch = float('inf'), -1
+
+    def validation(epoch):
+        """Score the test set (rank 0); returns the validation loss."""
+        evaluator.reset()
+        evaluator.add(test_dataset.audio[:test_dataset.padded], test_audio)
+        r = evaluator.report(kl_beta)
+        print('====> Epoch: {} - Validation loss: {:.9f} (mse {:.9f}, kld {:.6f}, snr {:.3f} dB, lsd {:.3f} dB)'.format(
+            epoch, r['loss'], r['mse'], r['kld'], r['snr_db'], r['lsd_db']))
+        writer.add_scalar('Loss/validation', r['loss'], epoch)
+        writer.add_scalar('Validation/snr_db', r['snr_db'], epoch)
+        writer.add_scalar('Validation/lsd_db', r['lsd_db'], epoch)
+        return r['loss']
+
     best_loss = float('inf')
     final_loss = float('inf')
     train_loss = 0.0
@@ -425,22 +481,32 @@ def main(argv=None):
             for name, param in model.named_parameters():
                 writer.add_histogram(name, param, epoch)
 
+        validation_loss = None
+        if validate:
+            validation_loss = dp.solo(validation, epoch)     # rank 0 scores alone, as it writes checkpoints alone
+            if dp.main and validation_loss < best_validation:
+                best_validation, best_validation_epoch = validation_loss, epoch
+        # what best_model.pt is chosen by: the epoch's training loss, or -- best_by = validation -- its validation loss
+        select_loss = validation_loss if best_by == 'validation' and dp.main else train_loss
+
         if epoch % checkpoint_interval == 0 and epoch != 0 and dp.main:
             print('Checkpoint - Epoch {}'.format(epoch))
             if generate_test:
                 write_reconstruction(epoch, epoch)
             torch.save(checkpoint_state(epoch), checkpoint_dir / 'ckpt_{:05d}'.format(epoch))
-            if train_loss < best_loss and epoch > save_best_model_after:
+            if select_loss < best_loss and epoch > save_best_model_after:
                 save_path = workdir / 'model' / 'best_model.pt'
                 torch.save(model, save_path)
                 print('Epoch {:05d}: Saved {}'.format(epoch, save_path))
                 config['training']['best_epoch'] = str(epoch)
-                best_loss = train_loss
-            elif train_loss > best_loss:
+                best_loss = select_loss
+            elif select_loss > best_loss:
                 print("Loss did not improve.")
         if epoch % checkpoint_interval == 0 and epoch != 0:
             dp.rendezvous()     # every rank: nobody starts the next epoch's steps while rank 0 is still writing
         final_loss = train_loss
+        if best_by == 'validation':
+            final_loss = select_loss
 
     dp.check_replicas(engine)
     if dp.main:
@@ -458,6 +524,9 @@ def main(argv=None):
         torch.save(model, workdir / 'model' / 'last_model.pt')
         print('Training Finished: Saved the last model')
 
+        if validate:
+            config['training']['validation_loss'] = str(best_validation)
+            config['training']['best_validation_epoch'] = str(best_validation_epoch)
         config['extra']['end'] = time.asctime(time.localtime(time.time()))
         config['extra']['time_elapsed'] = str(time.time() - start_time)
         with open(config_path, 'w') as configfile:
