@@ -54,6 +54,34 @@ class MosaicDesc(C.Structure):
                 ("mode", c_long), ("weight", c_void_p), ("which", c_long)]
 
 
+# rv_mosaic_desc reuses some fields under another meaning per op.  Each builder below returns the keyword fields of one
+# such role for MosaicDesc(**fields), so that a call site names the role, not the alias.
+def fitted_fields(shift, gain):
+    # RV_GRAIN_GATHER (include/rawvae_hip.h:562-563): slot [T, k] int32 is the shift, trans [T, k] fp32 the gain
+    return dict(slot=ptr(shift), trans=ptr(gain))
+
+
+def fit_fields(room, R, gain_max, shift, gain, score):
+    # RV_GRAIN_FIT (include/rawvae_hip.h:558-560) and a live fit (529-531): next_of = room [n_rows, 2] int32 (live:
+    # live_fit_table's [3 N]), width = R, lam = gain_max; the outputs slot, trans, cost = shift, gain, score [T, kf]
+    return dict(next_of=ptr(room), width=int(R), lam=float(gain_max), cost=ptr(score), **fitted_fields(shift, gain))
+
+
+def live_fit_table(successors, room):
+    # RV_MOSAIC_LIVE with a fit (include/rawvae_hip.h:530-531) reads ONE next_of table [3 N] int32: the successors [N]
+    # (None: zeros, unread without unit selection), then room [N, 2]
+    import torch
+    if successors is None:
+        successors = torch.zeros(room.shape[0], dtype=torch.int32, device=room.device)
+    return torch.cat([successors, room.reshape(-1)]).contiguous()
+
+
+def eval_fields(mu, logvar, table=None, dynamic_range=0.0):
+    # RV_EVAL_FRAMES (include/rawvae_hip.h:576-580) and RV_EVAL_DIMS (599): q, c = mu, logvar [T, L]; weight = the
+    # twiddle table [S]; lam = the dynamic range in dB (RV_EVAL_DIMS reads neither of the last two)
+    return dict(q=ptr(mu), c=ptr(logvar), weight=ptr(table), lam=float(dynamic_range))
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),

@@ -27,14 +27,15 @@ waveform is to another.
                                         against its target.
   check_args(...)                       the argument rules without a device; ValueError naming the argument.
 
-Every row's scores depend on that row alone, so the result is bit-identical for any max_rows.
+Every row's scores depend on that row alone, so the result is bit-identical for any max_rows.  Framing, encoder and
+decoder are codec.FrameCodec's (`ev.codec`).
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ACT_RELU, ACT_TANH, MosaicDesc, lib, ptr, stream_ptr
-from .interpolate import MAX_GEMM_ROWS, LatentInterpolator, frame_layout
+from ._lib import MosaicDesc, eval_fields, lib, ptr, stream_ptr
+from .codec import MAX_GEMM_ROWS, FrameCodec, frame_layout
 from .som import segment_mean
 from .stream import WINDOWS, window_values
 
@@ -129,8 +130,8 @@ def frame_scores(ref, test, T, segment_length, hop, stride, mu=None, logvar=None
             or out.shape[0] != T or out.shape[1] < 6 or out.stride(1) != 1):
         raise ValueError("out must be a [%d, >= 6] float32 tensor on %s with unit column stride" % (T, ref.device))
     d = MosaicDesc(T=T, S=S, hop=int(hop), frames=ptr(ref), n_out=ref.numel(), src=ptr(test), stride=int(stride),
-                   src_len=test.numel(), q=ptr(mu), c=ptr(logvar), L=L, window=ptr(window), weight=ptr(table),
-                   lam=float(dynamic_range), out=ptr(out), ldo=out.stride(0) if T > 1 else max(out.shape[1], 6))
+                   src_len=test.numel(), L=L, window=ptr(window), out=ptr(out),
+                   ldo=out.stride(0) if T > 1 else max(out.shape[1], 6), **eval_fields(mu, logvar, table, dynamic_range))
     lib().rv_mosaic(_lib.EVAL_FRAMES, _lib.C.byref(d), stream_ptr())
     return out
 
@@ -147,7 +148,7 @@ def kl_dims(mu, logvar):
     nb = -(-T // DIMS_ROWS)
     nbytes = 8 * nb * L if nb > 1 else 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mu.device) if nbytes else None
-    d = MosaicDesc(T=T, L=L, q=ptr(mu), c=ptr(logvar), cost=ptr(cost), ws=ptr(ws), ws_bytes=nbytes)
+    d = MosaicDesc(T=T, L=L, cost=ptr(cost), ws=ptr(ws), ws_bytes=nbytes, **eval_fields(mu, logvar))
     lib().rv_mosaic(_lib.EVAL_DIMS, _lib.C.byref(d), stream_ptr())
     return cost
 
@@ -191,9 +192,9 @@ class Evaluator:
                             % type(model).__name__)
         self.step, self.dynamic_range = check_args(model.segment_length, hop, window, dynamic_range, max_rows,
                                                    active_threshold)
-        self._enc = LatentInterpolator(model, max_rows=int(max_rows))   # RvError for a model that is not on the GPU
-        self.model, self.max_rows, self.device = model, int(max_rows), self._enc.device
-        self.S, self.H, self.L = self._enc.S, self._enc.H, self._enc.L
+        self.codec = c = FrameCodec(model, max_rows=int(max_rows))   # RvError for a model that is not on the GPU
+        self.model, self.max_rows, self.device = model, c.max_rows, c.device
+        self.S, self.H, self.L = c.S, c.H, c.L
         self.hop = None if hop is None else int(hop)
         self.window, self.active_threshold = window, float(active_threshold)
         self._spec = _Spectral(self.S, window, self.device)
@@ -208,9 +209,9 @@ class Evaluator:
         """(scores [T, 6] fp32, kl sums [L] fp64) of one waveform, device tensors (see the module doc)."""
         if eps is not None and seed is not None:
             raise ValueError("eps and seed: give at most one of them")
-        w = self._enc._wave(wave)
-        padded, T = self._enc._padded(w, w.numel(), self.hop)
-        mu, lv = self._enc._encode_padded(padded, T, self.hop)
+        w = self.codec.wave(wave)
+        padded, T = self.codec.pad(w, w.numel(), self.hop)
+        mu, lv = self.codec.encode(padded, T, self.hop)
         if eps is None and seed is None:
             z = mu
         else:
@@ -227,13 +228,10 @@ class Evaluator:
                 lib().rv_reparameterize(ptr(mu), ptr(lv), mu.numel(), None, ptr(drawn), int(seed), 0, ptr(z),
                                         stream_ptr())
         scores = torch.empty((T, 6), dtype=torch.float32, device=self.device)
-        cap = min(self.max_rows, T)
-        h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
-        recon = torch.empty((cap, self.S), dtype=torch.float32, device=self.device)
-        for r0 in range(0, T, self.max_rows):
-            rows = min(self.max_rows, T - r0)
-            self._enc._linear(z.data_ptr() + 4 * r0 * self.L, self.L, rows, "fc3", ACT_RELU, ptr(h), self.H)
-            self._enc._linear(ptr(h), self.H, rows, "fc4", ACT_TANH, ptr(recon), self.S)
+        h = self.codec.hidden(T)
+        recon = torch.empty((min(self.max_rows, T), self.S), dtype=torch.float32, device=self.device)
+        for r0, rows in self.codec.chunks(T):
+            self.codec.decode_chunk(z[r0:r0 + rows], h, recon)
             frame_scores(padded[r0 * self.step:], recon[:rows], rows, self.S, self.step, self.S, mu[r0:r0 + rows],
                          lv[r0:r0 + rows], self._spec.window, self._spec.table, self.dynamic_range,
                          out=scores[r0:r0 + rows])

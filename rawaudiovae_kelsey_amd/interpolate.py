@@ -12,7 +12,8 @@ hop_length 128).  Here each variant is a handful of launches per chunk of frames
 
 Arithmetic follows torch's promotion in the notebook: scalar or fp32 alpha -> fp32 throughout; fp64 alpha or curve
 -> fp64 mix and reparameterisation, z rounded once to fp32 (the notebook's `.float()` before `decode`).  The GEMMs are
-the exact-fp32 inference kernels of `VAE.encode` / `VAE.decode` under `torch.no_grad()`.
+the exact-fp32 inference kernels of `VAE.encode` / `VAE.decode` under `torch.no_grad()`; the framing, the encoder and
+the decoder launches are `codec.FrameCodec`'s, which the SOM, mosaicing and evaluation share.
 
 Memory: mu / logvar of both sources are kept whole ([N, L] fp32 each); per chunk of at most `max_rows` frames one
 h [rows, H] and one z [rows, L] buffer.  Every row's arithmetic is independent of the chunking, so the output is
@@ -21,10 +22,8 @@ bit-identical for any `max_rows`.
 import numpy as np
 import torch
 
-from . import _lib
-from ._lib import ACT_NONE, ACT_RELU, ACT_TANH, ALPHA_CURVE, ALPHA_F32, ALPHA_F64, ALPHA_LIST, lib, ptr, stream_ptr
-
-MAX_GEMM_ROWS = 65535 * 64    # rv_linear_fp32's launch grid
+from ._lib import ALPHA_CURVE, ALPHA_F32, ALPHA_F64, ALPHA_LIST, lib, ptr, stream_ptr
+from .codec import MAX_GEMM_ROWS, FrameCodec, frame_layout  # noqa: F401  (both names are part of this module's surface)
 
 
 def matched_length(n_a, n_b, mode="repeat"):
@@ -37,86 +36,20 @@ def matched_length(n_a, n_b, mode="repeat"):
     raise ValueError("match mode %r: expected 'repeat' or 'crop'" % (mode,))
 
 
-def frame_layout(n_samples, segment_length, hop=None):
-    """(frames, padded length) of a waveform of n_samples.  hop=None: TestDataset (non-overlapping frames, the tail
-    zero-padded to a whole frame, dataset.py:141-160); an int: AudioDataset (padded to a multiple of hop, frame i starts
-    at i * hop, dataset.py:99-121, ValueError when segment_length is not a multiple of hop)."""
-    S = int(segment_length)
-    n = int(n_samples)
-    if hop is None:
-        padded = -(-n // S) * S
-        return padded // S, padded
-    hop = int(hop)
-    if hop <= 0:
-        raise ValueError("hop must be positive, got %d" % hop)
-    if S % hop != 0:
-        raise ValueError("segment_length {} is not a multiple of hop_size {}".format(S, hop))
-    padded = -(-n // hop) * hop
-    return padded // hop - S // hop + 1, padded
-
-
 class LatentInterpolator:
     """Encode two sounds, mix their latent distributions, decode the mix into one waveform (see the module doc).
 
     `model` is a `VAE` on the GPU; its parameters are read, never written (the model's parameters, `_rng_calls` and
     operand shadows stay as they were).  eps is either given ([rows, L] fp32, rows = the output frames) or drawn on
-    the device from `seed` with the Philox stream of `VAE.reparameterize` (offset 0)."""
+    the device from `seed` with the Philox stream of `VAE.reparameterize` (offset 0).  `codec` is the FrameCodec that
+    frames, encodes and decodes."""
 
     def __init__(self, model, max_rows=16384):
-        max_rows = int(max_rows)
-        if not 1 <= max_rows <= MAX_GEMM_ROWS:
-            raise ValueError("max_rows must be in [1, %d], got %d" % (MAX_GEMM_ROWS, max_rows))
-        self.model = model
-        self.max_rows = max_rows
-        self.S, self.H, self.L = int(model.segment_length), int(model.n_units), int(model.latent_dim)
-        self.device = model.fc1.weight.device
-        if self.device.type != "cuda":
-            raise _lib.RvError("LatentInterpolator computes on the GPU only: the model is on %s" % self.device)
+        self.codec = c = FrameCodec(model, max_rows)
+        self.model, self.max_rows, self.device = model, c.max_rows, c.device
+        self.S, self.H, self.L = c.S, c.H, c.L
 
     # -- helpers ---------------------------------------------------------------------------------------------------
-    def _w(self, name):
-        t = getattr(self.model, name)
-        return t.weight.detach().contiguous(), t.bias.detach().contiguous()
-
-    def _wave(self, w):
-        """1-D fp32 device tensor of a waveform given as a device tensor or a numpy array."""
-        if isinstance(w, np.ndarray):
-            w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32))
-        if not torch.is_tensor(w):
-            raise TypeError("waveform must be a torch tensor or a numpy array, got %s" % type(w).__name__)
-        if w.dim() != 1:
-            raise ValueError("waveform must be 1-D, got shape %s" % (tuple(w.shape),))
-        if w.numel() == 0:
-            raise ValueError("empty waveform")
-        return w.to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _padded(self, w, n_valid, hop):
-        """rv_match_pad: w repeated or cropped to n_valid samples, zeros up to the framing's padded length."""
-        n_frames, padded = frame_layout(n_valid, self.S, hop)
-        if n_frames < 1:
-            raise ValueError("%d samples make no frame of %d samples at hop %s" % (n_valid, self.S, hop))
-        dst = torch.empty(padded, dtype=torch.float32, device=self.device)
-        lib().rv_match_pad(ptr(w), w.numel(), n_valid, ptr(dst), padded, stream_ptr())
-        return dst, n_frames
-
-    def _linear(self, x, ldx, rows, name, act, y, ldy):
-        W, b = self._w(name)
-        N, K = W.shape
-        lib().rv_linear_fp32(x, ldx, ptr(W), K, ptr(b), rows, N, K, act, y, ldy, stream_ptr())
-
-    def _encode_padded(self, wave, n_frames, hop):
-        """fc1 -> (fc21, fc22) over the frames of a padded waveform, max_rows frames at a time."""
-        step = self.S if hop is None else int(hop)
-        mu = torch.empty((n_frames, self.L), dtype=torch.float32, device=self.device)
-        lv = torch.empty_like(mu)
-        h = torch.empty((min(self.max_rows, n_frames), self.H), dtype=torch.float32, device=self.device)
-        for f0 in range(0, n_frames, self.max_rows):
-            rows = min(self.max_rows, n_frames - f0)
-            self._linear(wave.data_ptr() + 4 * f0 * step, step, rows, "fc1", ACT_RELU, ptr(h), self.H)
-            self._linear(ptr(h), self.H, rows, "fc21", ACT_NONE, ptr(mu) + 4 * f0 * self.L, self.L)
-            self._linear(ptr(h), self.H, rows, "fc22", ACT_NONE, ptr(lv) + 4 * f0 * self.L, self.L)
-        return mu, lv
-
     def _mix_decode(self, dists, n_frames, mode, alpha, n_alpha, rows_total, eps, seed):
         mu_a, lv_a, mu_b, lv_b = dists
         if eps is not None:
@@ -124,37 +57,35 @@ class LatentInterpolator:
             if eps.numel() != rows_total * self.L:
                 raise ValueError("eps has %d elements, expected [%d, %d]" % (eps.numel(), rows_total, self.L))
         out = torch.empty(rows_total * self.S, dtype=torch.float32, device=self.device)
-        cap = min(self.max_rows, rows_total)
-        z = torch.empty((cap, self.L), dtype=torch.float32, device=self.device)
-        h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
-        for r0 in range(0, rows_total, self.max_rows):
-            rows = min(self.max_rows, rows_total - r0)
+        z = torch.empty((min(self.max_rows, rows_total), self.L), dtype=torch.float32, device=self.device)
+        h = self.codec.hidden(rows_total)
+        for r0, rows in self.codec.chunks(rows_total):
             e = None if eps is None else eps.data_ptr() + 4 * r0 * self.L
             lib().rv_latent_mix(ptr(mu_a), ptr(lv_a), ptr(mu_b), ptr(lv_b), n_frames, self.L, mode, ptr(alpha), n_alpha,
                                 r0, rows, e, None, int(seed), 0, ptr(z), None, None, None, stream_ptr())
-            self._linear(ptr(z), self.L, rows, "fc3", ACT_RELU, ptr(h), self.H)
-            self._linear(ptr(h), self.H, rows, "fc4", ACT_TANH, out.data_ptr() + 4 * r0 * self.S, self.S)
+            self.codec.decode_chunk(z[:rows], h, out[r0 * self.S:])
         return out
 
     def _sources(self, a, b, hop, match):
-        a, b = self._wave(a), self._wave(b)
+        c = self.codec
+        a, b = c.wave(a), c.wave(b)
         n = matched_length(a.numel(), b.numel(), match)
-        (pa, n_frames), (pb, _) = self._padded(a, n, hop), self._padded(b, n, hop)
-        return self._encode_padded(pa, n_frames, hop) + self._encode_padded(pb, n_frames, hop), n_frames
+        (pa, n_frames), (pb, _) = c.pad(a, n, hop), c.pad(b, n, hop)
+        return c.encode(pa, n_frames, hop) + c.encode(pb, n_frames, hop), n_frames
 
     # -- public surface --------------------------------------------------------------------------------------------
     @torch.no_grad()
     def encode_audio(self, wave, hop=None):
         """(mu, logvar) [frames, L] of a waveform framed like TestDataset (hop=None) or AudioDataset (hop=int):
         the notebook's raw_to_z_dist (tutorial.ipynb:456-470) in exact fp32."""
-        w = self._wave(wave)
-        padded, n_frames = self._padded(w, w.numel(), hop)
-        return self._encode_padded(padded, n_frames, hop)
+        w = self.codec.wave(wave)
+        padded, n_frames = self.codec.pad(w, w.numel(), hop)
+        return self.codec.encode(padded, n_frames, hop)
 
     @torch.no_grad()
     def match_length(self, a, b, mode="repeat"):
         """Both waveforms at matched_length(len(a), len(b), mode), as device tensors (rv_match_pad)."""
-        a, b = self._wave(a), self._wave(b)
+        a, b = self.codec.wave(a), self.codec.wave(b)
         n = matched_length(a.numel(), b.numel(), mode)
         out = []
         for w in (a, b):

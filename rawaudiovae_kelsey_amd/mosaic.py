@@ -28,6 +28,8 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
                                           its own and the k fitted grains are averaged; with continuity > 0 the one
                                           chosen frame is fitted.  fit=0, gain_max=0 is the call without them.
   shift_room, fit_grains, gather_fitted   the steps on their own (RV_GRAIN_FIT, RV_GRAIN_GATHER)
+  check_mosaic_args                       the rules for k, mode, continuity, fit and gain_max that index.mosaic and
+                                          check_live_args share, each in its own order
   knn_topk_small(q, c, k)                 knn_topk for at most SMALL_T_MAX query rows by the few-query kernel
                                           (RV_MOSAIC_KNN_SMALL): the same bits
   StreamingMosaic(index, n_streams, block, hop, k, mode, window, continuity, lag)
@@ -51,15 +53,17 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
 
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
-encoder, search, gather and decoder step), so the output is bit-identical for any chunking.
+encoder, search, gather and decoder step), so the output is bit-identical for any chunking.  Framing, encoder and
+decoder are codec.FrameCodec's (`index.codec`); the graphs of the live path are stream.GraphReplay's; the fields of
+rv_mosaic_desc that an op reads under another name are spelled by _lib's fit_fields, fitted_fields and live_fit_table.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import ACT_RELU, ACT_TANH, MosaicDesc, lib, ptr, stream_ptr
-from .interpolate import LatentInterpolator, frame_layout
-from .stream import WINDOWS, check_args, window_norm, window_values
+from ._lib import MosaicDesc, fit_fields, fitted_fields, live_fit_table, lib, ptr, stream_ptr
+from .codec import FrameCodec, frame_layout
+from .stream import WINDOWS, GraphReplay, StreamingVAE, check_args, each_stream, window_values
 
 MODES = ("grains", "decode")
 K_MAX = 16
@@ -247,6 +251,36 @@ def check_fit(fit, gain_max):
     return int(fit), g
 
 
+def check_mosaic_args(k, n_corpus, mode, continuity, fit, gain_max, rules=("fit_mode", "continuity", "mode", "k")):
+    """The argument rules LatentIndex.mosaic and check_live_args share -> (k, continuity, fit, gain_max) as int, float,
+    int, float.  ValueError naming the argument: check_fit's first, then those of `rules` in its order, which is what
+    decides the error of a call that breaks several (the default is LatentIndex.mosaic's order)."""
+    fit, gain_max = check_fit(fit, gain_max)
+    for rule in rules:
+        if rule == "fit_mode":
+            if (fit > 0 or gain_max > 0) and mode == "decode":
+                raise ValueError("fit=%d, gain_max=%g: grains are fitted in mode 'grains' only, mode 'decode' plays no "
+                                 "corpus audio" % (fit, gain_max))
+        elif rule == "continuity":
+            continuity = float(continuity)
+            if not 0 <= continuity < float("inf"):
+                raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
+        elif rule == "mode":
+            if mode not in MODES:
+                raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
+        elif rule == "k":
+            k = int(k)
+            if not 1 <= k <= min(K_MAX, int(n_corpus)):
+                raise ValueError("k=%d must be in [1, %d] and at most the %d corpus frames" % (k, K_MAX, int(n_corpus)))
+    return k, continuity, fit, gain_max
+
+
+def fit_buffers(rows, kf, device, alloc=torch.empty):
+    """(shift int32, gain fp32, score fp64), each [rows, kf], of a grain fit: kf = k fits per row, or 1 where unit
+    selection leaves one frame per row to fit."""
+    return tuple(alloc((rows, kf), dtype=t, device=device) for t in (torch.int32, torch.float32, torch.float64))
+
+
 def shift_room(lengths, segment_length, hop=None):
     """room [N, 2] int32 for the corpus layout of frame_tables: how many samples frame i's start may move back
     (room[i, 0]) and forward (room[i, 1]) while its segment_length samples stay inside its own file's padded
@@ -279,12 +313,9 @@ def fit_grains(target, idx, hop, segment_length, src, row_start, room, fit, gain
             or room.device != idx.device):
         raise ValueError("room must be an int32 device tensor of shape [%d, 2] (shift_room)" % N)
     room = room.contiguous()
-    shift = torch.empty((T, k), dtype=torch.int32, device=idx.device)
-    gain = torch.empty((T, k), dtype=torch.float32, device=idx.device)
-    score = torch.empty((T, k), dtype=torch.float64, device=idx.device)
+    shift, gain, score = fit_buffers(T, k, idx.device)
     _call(_lib.GRAIN_FIT, T=T, k=k, idx=ptr(idx), frames=ptr(target), n_out=target.numel(), hop=hop, S=S, src=ptr(src),
-          src_len=src.numel(), row_start=ptr(row_start), n_rows=N, next_of=ptr(room), width=R, lam=g, slot=ptr(shift),
-          trans=ptr(gain), cost=ptr(score))
+          src_len=src.numel(), row_start=ptr(row_start), n_rows=N, **fit_fields(room, R, g, shift, gain, score))
     return shift, gain, score
 
 
@@ -307,7 +338,7 @@ def gather_fitted(src, idx, shift, gain, width, row_start, out=None, ldo=None):
     if out is None:
         out = torch.empty((T, ldo), dtype=torch.float32, device=src.device)
     _call(_lib.GRAIN_GATHER, T=T, k=k, idx=ptr(idx), src=ptr(src), src_len=src.numel(), row_start=ptr(row_start),
-          n_rows=row_start.numel(), width=width, out=ptr(out), ldo=ldo, slot=ptr(shift), trans=ptr(gain))
+          n_rows=row_start.numel(), width=width, out=ptr(out), ldo=ldo, **fitted_fields(shift, gain))
     return out
 
 
@@ -358,9 +389,9 @@ class LatentIndex:
     `file_of[i]` and `offset_of[i]` (numpy) give the file and the sample offset within the file."""
 
     def __init__(self, model, hop=None, max_rows=16384):
-        self._enc = LatentInterpolator(model, max_rows=max_rows)
-        self.model, self.max_rows, self.device = model, self._enc.max_rows, self._enc.device
-        self.S, self.H, self.L = self._enc.S, self._enc.H, self._enc.L
+        self.codec = c = FrameCodec(model, max_rows=max_rows)
+        self.model, self.max_rows, self.device = model, c.max_rows, c.device
+        self.S, self.H, self.L = c.S, c.H, c.L
         self.hop = None if hop is None else int(hop)
         frame_layout(self.S, self.S, self.hop)   # ValueError for a hop that does not divide segment_length
         self.names = []
@@ -377,13 +408,13 @@ class LatentIndex:
     @torch.no_grad()
     def add(self, wave, name):
         """Frame, encode and append one corpus file.  ValueError naming `name` when it makes no frame."""
-        w = self._enc._wave(wave)
+        w = self.codec.wave(wave)
         n_frames, _ = frame_layout(w.numel(), self.S, self.hop)
         if n_frames < 1:
             raise ValueError("%s: %d samples make no frame of %d samples at hop %s" % (name, w.numel(), self.S,
                                                                                        self.hop))
-        padded, n_frames = self._enc._padded(w, w.numel(), self.hop)
-        mu, _ = self._enc._encode_padded(padded, n_frames, self.hop)
+        padded, n_frames = self.codec.pad(w, w.numel(), self.hop)
+        mu, _ = self.codec.encode(padded, n_frames, self.hop)
         self.names.append(str(name))
         self._lengths.append(w.numel())
         self._waves.append(padded)
@@ -480,84 +511,71 @@ class LatentIndex:
         most R samples and, with gain_max > 0, a gain of at most gain_max (fit_grains) before the overlap-add;
         return_fit then appends (shift, gain, score), each [T, k], or [T, 1] with continuity > 0 (None when nothing
         is fitted)."""
-        fit, gain_max = check_fit(fit, gain_max)
-        fitted = fit > 0 or gain_max > 0
-        if fitted and mode == "decode":
-            raise ValueError("fit=%d, gain_max=%g: grains are fitted in mode 'grains' only, mode 'decode' plays no "
-                             "corpus audio" % (fit, gain_max))
-        continuity = float(continuity)
-        if not 0 <= continuity < float("inf"):
-            raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
-        if mode not in MODES:
-            raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
-        k = int(k)
-        N = len(self)
-        if not 1 <= k <= min(K_MAX, N):
-            raise ValueError("k=%d must be in [1, %d] and at most the %d corpus frames" % (k, K_MAX, N))
+        k, continuity, fit, gain_max = check_mosaic_args(k, len(self), mode, continuity, fit, gain_max)
         hop = self.hop if hop is None else int(hop)
         step = self.S if hop is None else hop
         check_window(self.S, step, window)
         if continuity > 0:
             next_of = self._successor(step / self.step)[1]   # ValueError naming hop unless a whole number of steps
-        w = self._enc._wave(target)
-        n = w.numel()
-        padded, T = self._enc._padded(w, n, hop)
-        mu, _ = self._enc._encode_padded(padded, T, hop)
-        t = self._tables()
-        frames = torch.empty((T, self.S), dtype=torch.float32, device=self.device)
+        w = self.codec.wave(target)
+        padded, T = self.codec.pad(w, w.numel(), hop)
+        mu, _ = self.codec.encode(padded, T, hop)
+        synth = _Synthesis(self, padded, T, step, mode, fit, gain_max, k if continuity == 0 else 1)
         idx = torch.empty((T, k), dtype=torch.int32, device=self.device)
         dist = torch.empty((T, k), dtype=torch.float32, device=self.device)
-        cap = min(self.max_rows, T)
-        if mode == "decode":
-            z = torch.empty((cap, self.L), dtype=torch.float32, device=self.device)
-            h = torch.empty((cap, self.H), dtype=torch.float32, device=self.device)
-
-        fits = None
-        if fitted:
-            room = self._room()[1]
-            kf = k if continuity == 0 else 1
-            fits = (torch.empty((T, kf), dtype=torch.int32, device=self.device),
-                    torch.empty((T, kf), dtype=torch.float32, device=self.device),
-                    torch.empty((T, kf), dtype=torch.float64, device=self.device))
-
-        def synth(i, r0, rows):
-            """frames[r0:r0 + rows] from the corpus frames i [rows, any k]: their mean audio (each fitted to its
-            target frame first when a fit is asked for), or their mean mu decoded"""
-            if fitted:
-                i = i.contiguous()
-                sh, gn, sc = fit_grains(padded[r0 * step:], i, step, self.S, t["audio"], t["row_start"], room, fit,
-                                        gain_max)
-                for dst, part in zip(fits, (sh, gn, sc)):
-                    dst[r0:r0 + rows] = part
-                gather_fitted(t["audio"], i, sh, gn, self.S, t["row_start"], out=frames[r0:r0 + rows])
-            elif mode == "grains":
-                gather_mean(t["audio"], i, self.S, row_start=t["row_start"], out=frames[r0:r0 + rows])
-            else:
-                gather_mean(t["mu"], i, self.L, stride=self.L, n_rows=N, out=z[:rows])
-                self._enc._linear(ptr(z), self.L, rows, "fc3", ACT_RELU, ptr(h), self.H)
-                self._enc._linear(ptr(h), self.H, rows, "fc4", ACT_TANH, frames.data_ptr() + 4 * r0 * self.S, self.S)
-
-        for r0 in range(0, T, self.max_rows):
-            rows = min(self.max_rows, T - r0)
-            i, d = knn_topk(mu[r0:r0 + rows], t["mu"], k)
+        for r0, rows in self.codec.chunks(T):          # search; without unit selection each chunk is synthesised at once
+            i, d = knn_topk(mu[r0:r0 + rows], self.mu, k)
             idx[r0:r0 + rows], dist[r0:r0 + rows] = i, d
             if continuity == 0:
-                synth(i, r0, rows)
+                synth.chunk(i, r0, rows)
         path = None
-        if continuity > 0:
-            path = best_path(idx, dist, t["mu"], next_of, continuity, max_rows=self.max_rows)
+        if continuity > 0:                             # select, then synthesise from the one chosen frame of each row
+            path = best_path(idx, dist, self.mu, next_of, continuity, max_rows=self.max_rows)
             one = path[1].view(T, 1)   # the chosen corpus frame: a gather-mean of one is that frame, bit for bit
-            for r0 in range(0, T, self.max_rows):
-                rows = min(self.max_rows, T - r0)
-                synth(one[r0:r0 + rows], r0, rows)
+            for r0, rows in self.codec.chunks(T):
+                synth.chunk(one[r0:r0 + rows], r0, rows)
         win = None if window is None else torch.from_numpy(window_values(self.S, window)).to(self.device)
-        out = ola(frames, step, n, win)
+        out = ola(synth.frames, step, w.numel(), win)
         res = (out, idx, dist) if return_matches else (out,)
         if return_path:
             res += (path,)
         if return_fit:
-            res += (fits,)
+            res += (synth.fits,)
         return res if len(res) > 1 else out
+
+
+class _Synthesis:
+    """The frames [T, S] of one LatentIndex.mosaic call, `chunk(i, r0, rows)` at a time: rows [r0, r0 + rows) from the
+    corpus frames i [rows, any k] chosen for them -- their mean audio, each fitted to its target frame first when a fit
+    is asked for (`fits`: the (shift, gain, score) of every row, else None), or their mean mu decoded."""
+
+    def __init__(self, index, padded, T, step, mode, fit, gain_max, kf):
+        self.index, self.padded, self.step, self.fit, self.gain_max = index, padded, step, fit, gain_max
+        self.tables = index._tables()
+        self.frames = torch.empty((T, index.S), dtype=torch.float32, device=index.device)
+        self.fits, self.chunk = None, self._mean_grains
+        if fit > 0 or gain_max > 0:
+            self.room, self.fits, self.chunk = index._room()[1], fit_buffers(T, kf, index.device), self._fitted_grains
+        elif mode == "decode":
+            self.z = torch.empty((min(index.max_rows, T), index.L), dtype=torch.float32, device=index.device)
+            self.h, self.chunk = index.codec.hidden(T), self._decoded_mean
+
+    def _fitted_grains(self, i, r0, rows):
+        t, S, i = self.tables, self.index.S, i.contiguous()
+        sh, gn, sc = fit_grains(self.padded[r0 * self.step:], i, self.step, S, t["audio"], t["row_start"], self.room,
+                                self.fit, self.gain_max)
+        for dst, part in zip(self.fits, (sh, gn, sc)):
+            dst[r0:r0 + rows] = part
+        gather_fitted(t["audio"], i, sh, gn, S, t["row_start"], out=self.frames[r0:r0 + rows])
+
+    def _mean_grains(self, i, r0, rows):
+        t = self.tables
+        gather_mean(t["audio"], i, self.index.S, row_start=t["row_start"], out=self.frames[r0:r0 + rows])
+
+    def _decoded_mean(self, i, r0, rows):
+        L = self.index.L
+        gather_mean(self.tables["mu"], i, L, stride=L, n_rows=len(self.index), out=self.z[:rows])
+        self.index.codec.decode_chunk(self.z[:rows], self.h, self.frames[r0:r0 + rows])
 
 
 LAG_MAX = 64       # frames of look-ahead of the live selection at most (csrc/mosaic.hip)
@@ -573,22 +591,13 @@ def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=
         raise ValueError("index: the index is empty, add() corpus files first")
     if int(n_streams) <= 0:
         raise ValueError("n_streams must be positive, got %d" % int(n_streams))
-    if mode not in MODES:
-        raise ValueError("mode %r: expected one of %s" % (mode, ", ".join(MODES)))
-    k = int(k)
-    if not 1 <= k <= min(K_MAX, int(n_corpus)):
-        raise ValueError("k=%d must be in [1, %d] and at most the %d corpus frames" % (k, K_MAX, int(n_corpus)))
-    continuity = float(continuity)
-    if not 0 <= continuity < float("inf"):
-        raise ValueError("continuity=%r must be a finite number >= 0" % (continuity,))
+    _, continuity, _, _ = check_mosaic_args(k, n_corpus, mode, continuity, fit, gain_max, ("mode", "k", "continuity"))
     if isinstance(lag, bool) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) <= LAG_MAX:
         raise ValueError("lag=%r must be an integer in [0, %d]" % (lag, LAG_MAX))
     if int(lag) > 0 and continuity == 0:
         raise ValueError("lag=%d needs continuity > 0: without unit selection there is nothing to look ahead for"
                          % int(lag))
-    if (fit > 0 or gain_max > 0) and mode == "decode":
-        raise ValueError("fit=%d, gain_max=%g: grains are fitted in mode 'grains' only, mode 'decode' plays no "
-                         "corpus audio" % (fit, gain_max))
+    check_mosaic_args(k, n_corpus, mode, continuity, fit, gain_max, ("fit_mode",))
     hop, latency, frames = check_args(S, block, hop, window)   # ValueError naming hop, block or window
     adv = 1
     if continuity > 0:
@@ -599,7 +608,7 @@ def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=
     return hop, latency, frames, adv
 
 
-class StreamingMosaic:
+class StreamingMosaic(GraphReplay):
     """Live mosaicing of `n_streams` streams against a LatentIndex (see the module doc).
 
     `process(x)` -> y [n_streams, block], the input `latency` = S - hop samples late; the concatenated outputs equal
@@ -617,7 +626,6 @@ class StreamingMosaic:
 
     def __init__(self, index, n_streams, block, hop=None, k=1, mode="grains", window=None, continuity=0.0, lag=0,
                  fit=0, gain_max=0.0):
-        from .stream import StreamingVAE
         self.index = index
         N = len(index)
         self.hop, self.latency, self.frames_per_block, adv = check_live_args(
@@ -643,31 +651,23 @@ class StreamingMosaic:
         self._choice = torch.full((M,), -1, dtype=torch.int32, device=self.device)
         self._fit = None
         if self.fitted:
-            # the library reads one table with a fit: the successors [N] (unread without unit selection), then room
-            succ = self._next_of if self.selects else torch.zeros(N, dtype=torch.int32, device=self.device)
-            self._next_of = torch.cat([succ, index._room()[1].reshape(-1)]).contiguous()
-            kf = 1 if self.selects else self.k
-            self._fit = (torch.zeros((M, kf), dtype=torch.int32, device=self.device),
-                         torch.zeros((M, kf), dtype=torch.float32, device=self.device),
-                         torch.zeros((M, kf), dtype=torch.float64, device=self.device))
+            self._next_of = live_fit_table(self._next_of, index._room()[1])
+            self._fit = fit_buffers(M, 1 if self.selects else self.k, self.device, torch.zeros)
         self._ws = None
         nbytes = self._call(_lib.MOSAIC_LIVE_WORKSPACE, None, None).ws_bytes
         self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=self.device)
-        self._graph = self._drain_graph = None
         self._zeros = None
         self.reset()
 
     def _call(self, op, x, y, which=-1, stream=None):
-        sd = self._sv._desc(x, y, None)
+        sd = self._sv.desc(x, y, None)
+        table = (fit_fields(self._next_of, self.fit, self.gain_max, *self._fit) if self.fitted
+                 else dict(next_of=ptr(self._next_of)))
         d = MosaicDesc(k=self.k, idx=ptr(self._idx), dist=ptr(self._dist), c=ptr(self._mu), N=self._mu.shape[0],
                        L=self.L, src=ptr(self._audio), src_len=self._audio.numel(), row_start=ptr(self._row_start),
-                       next_of=ptr(self._next_of), choice=ptr(self._choice), ws=ptr(self._ws),
-                       ws_bytes=0 if self._ws is None else self._ws.numel(), live=_lib.C.pointer(sd),
-                       mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS, weight=ptr(self.weight),
-                       which=int(which), rows=self.lag)
-        if self.fitted:
-            d.width, d.lam = self.fit, self.gain_max
-            d.slot, d.trans, d.cost = (ptr(t) for t in self._fit)
+                       choice=ptr(self._choice), ws=ptr(self._ws), ws_bytes=0 if self._ws is None else self._ws.numel(),
+                       live=_lib.C.pointer(sd), mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS,
+                       weight=ptr(self.weight), which=int(which), rows=self.lag, **table)
         host_only = op == _lib.MOSAIC_LIVE_WORKSPACE
         lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else (stream_ptr() if stream is None else stream))
         return d
@@ -675,7 +675,7 @@ class StreamingMosaic:
     @torch.no_grad()
     def process(self, x):
         """One block: x [n_streams, block] fp32 on the device -> [n_streams, block]."""
-        x = self._sv._input(x)
+        x = self.check_input(x)
         y = torch.empty((self.n_streams, self.block), dtype=torch.float32, device=self.device)
         self._call(_lib.MOSAIC_LIVE, x, y)
         return y
@@ -708,13 +708,7 @@ class StreamingMosaic:
         """Zero the history, the overlap-add tail and the frame counter of `streams` (an index or a list; None = all)
         and forget their last chosen corpus frame and the frames their lag holds back; with a fit their target
         history is silence again."""
-        if streams is None:
-            self._call(_lib.MOSAIC_LIVE_RESET, None, None, -1)
-            return
-        for s in ([streams] if isinstance(streams, int) else list(streams)):
-            s = int(s)
-            if not 0 <= s < self.n_streams:
-                raise ValueError("stream %d of %d" % (s, self.n_streams))
+        for s in each_stream(streams, self.n_streams):
             self._call(_lib.MOSAIC_LIVE_RESET, None, None, s)
 
     def last_matches(self):
@@ -736,54 +730,36 @@ class StreamingMosaic:
         F = self.frames_per_block
         return tuple(t.view(self.n_streams, F, -1) for t in self._fit)
 
+    def last_latents(self):
+        """(mu, logvar) of the last block's frames as views [n_streams, F, L], before `scale` and `offset`."""
+        return self._sv.last_latents()
+
     @torch.no_grad()
     def capture(self):
         """Capture one call as a graph on static buffers `graph_input` / `graph_output` [n_streams, block];
         `replay(x)` then runs one block per call.  With a lag a second graph holds one drain() call for
         `drain_replay()`, writing `graph_output` too.  The graphs hold the Parameters' pointers: replaying after a
         Parameter was replaced raises."""
-        from .engine import Graph
-        self.graph_input = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
-        self.graph_output = torch.zeros_like(self.graph_input)
-        self._held = [(p, p.data_ptr()) for p in self._sv._weights()]
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        g = Graph(side)
-        with g:
-            self._call(_lib.MOSAIC_LIVE, self.graph_input, self.graph_output, stream=side.cuda_stream)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self._graph = g
+        launches = [lambda st: self._call(_lib.MOSAIC_LIVE, self.graph_input, self.graph_output, stream=st)]
         if self.lag > 0:
             zeros = self._zero_block()
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            g = Graph(side)
-            with g:
-                self._call(_lib.MOSAIC_LIVE_DRAIN, zeros, self.graph_output, stream=side.cuda_stream)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            self._drain_graph = g
-        return self
+            launches.append(lambda st: self._call(_lib.MOSAIC_LIVE_DRAIN, zeros, self.graph_output, stream=st))
+        return self._capture(*launches)
 
-    def _check_held(self, what):
-        if self._graph is None:
-            raise _lib.RvError("%s before capture()" % what)
-        now = self._sv._weights()
-        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(now, self._held)):
-            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
+    def parameters(self):
+        return self._sv.parameters()
+
+    def check_input(self, x):
+        return self._sv.check_input(x)
 
     @torch.no_grad()
     def replay(self, x=None):
         """One block through the captured graph on the current stream; x (optional) is copied into `graph_input`
         first.  Returns `graph_output` (overwritten by the next replay)."""
-        self._check_held("replay()")
-        if x is not None:
-            self.graph_input.copy_(self._sv._input(x))
-        self._graph.launch(torch.cuda.current_stream(self.device))
-        return self.graph_output
+        return self._replay(0, "replay()", x)
 
     @torch.no_grad()
     def drain_replay(self):
         """drain() through its captured graph on the current stream.  Returns `graph_output`."""
-        self._zero_block()
-        self._check_held("drain_replay()")
-        self._drain_graph.launch(torch.cuda.current_stream(self.device))
-        return self.graph_output
+        self._zero_block()   # ValueError at lag 0
+        return self._replay(1, "drain_replay()")

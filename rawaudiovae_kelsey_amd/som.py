@@ -19,6 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import lib, ptr, stream_ptr
+from .codec import FrameCodec
 
 
 def sigma_schedule(sigma0, sigma1, epochs):
@@ -168,12 +169,11 @@ class LatentSOM:
 
 class LatentMap:
     """File descriptors for the SOM: the mean encoder mu of each file's frames, framed like TestDataset (hop=None) or
-    AudioDataset (hop=int), through `LatentInterpolator.encode_audio`.  The model is read, never written."""
+    AudioDataset (hop=int), through `codec.FrameCodec`.  The model is read, never written."""
 
     def __init__(self, model, hop=None, max_rows=16384):
-        from .interpolate import LatentInterpolator
         self.hop = None if hop is None else int(hop)
-        self.interp = LatentInterpolator(model, max_rows=max_rows)
+        self.codec = FrameCodec(model, max_rows=max_rows)
 
     @torch.no_grad()
     def describe(self, waves):
@@ -184,7 +184,9 @@ class LatentMap:
         mus, offsets = [], [0]
         for f, w in enumerate(waves):
             try:
-                mu, _ = self.interp.encode_audio(w, hop=self.hop)
+                w = self.codec.wave(w)
+                padded, n_frames = self.codec.pad(w, w.numel(), self.hop)
+                mu, _ = self.codec.encode(padded, n_frames, self.hop)
             except ValueError as e:
                 raise ValueError("waveform %d: %s" % (f, e))
             mus.append(mu)

@@ -18,7 +18,10 @@ themselves (the reference's non-overlapping reconstruction).
 Five launches per call (csrc/stream.hip): fc1 reading its frames from the history and the new block in place, the two
 heads with the controls and the reparameterisation, fc3, fc4, then overlap-add + history update.  Every GEMM is
 `rv_small_linear_f32`'s k-ordered fmaf chain, the arithmetic of the exact-fp32 inference path (`VAE.encode` /
-`decode` under `torch.no_grad()`).  `capture()` / `replay(x)` run the same call as a captured graph.
+`decode` under `torch.no_grad()`).  `capture()` / `replay(x)` run the same call as a captured graph; the capture, the
+check that the model's Parameters are still the captured ones and the replay are `GraphReplay`'s, which live mosaicing
+(mosaic.StreamingMosaic) mixes in too.  What that class needs of a StreamingVAE is public: `desc(x, y, eps)`,
+`check_input(x)`, `parameters()`; `each_stream` is the walk of a `reset(streams)`.
 """
 import numpy as np
 import torch
@@ -74,7 +77,59 @@ def window_norm(w, hop):
     return out
 
 
-class StreamingVAE:
+def each_stream(streams, n_streams):
+    """The stream indices a reset(streams) walks: -1 (all of them at once) for None, else the int or every entry of
+    the iterable, each checked against n_streams as it comes up (ValueError)."""
+    if streams is None:
+        yield -1
+        return
+    for s in ([streams] if isinstance(streams, int) else list(streams)):
+        s = int(s)
+        if not 0 <= s < n_streams:
+            raise ValueError("stream %d of %d" % (s, n_streams))
+        yield s
+
+
+class GraphReplay:
+    """capture() / replay() of a block processor as graphs on static buffers `graph_input` / `graph_output`
+    [n_streams, block].  The class that mixes this in has n_streams, block and device, parameters() (the model
+    Parameters its launches read) and check_input(x).  The graphs hold the Parameters' pointers: replaying after a
+    Parameter was replaced raises."""
+    _graphs = ()
+
+    def _capture(self, *launches):
+        """Allocate the static buffers, note the Parameters' pointers and capture each launch(raw stream) as a graph
+        of its own on a side stream."""
+        from .engine import Graph
+        self.graph_input = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
+        self.graph_output = torch.zeros_like(self.graph_input)
+        self._held = [(p, p.data_ptr()) for p in self.parameters()]
+        side = torch.cuda.Stream(self.device)
+        graphs = []
+        for launch in launches:
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            g = Graph(side)
+            with g:
+                launch(side.cuda_stream)
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            graphs.append(g)
+        self._graphs = graphs
+        return self
+
+    def _replay(self, which, what, x=None):
+        """Graph `which` on the current stream, x (optional) copied into `graph_input` first -> `graph_output`.
+        `what` names the caller in the error raised before capture()."""
+        if not self._graphs:
+            raise _lib.RvError("%s before capture()" % what)
+        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(self.parameters(), self._held)):
+            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
+        if x is not None:
+            self.graph_input.copy_(self.check_input(x))
+        self._graphs[which].launch(torch.cuda.current_stream(self.device))
+        return self.graph_output
+
+
+class StreamingVAE(GraphReplay):
     """Stateful streaming resynthesis of `n_streams` streams through a `VAE` on the GPU (see the module doc).
 
     The model's Parameters are read in place on every eager call.  Control tensors (`scale` [n_streams, L],
@@ -96,7 +151,7 @@ class StreamingVAE:
         self.device = model.fc1.weight.device
         if self.device.type != "cuda":
             raise _lib.RvError("StreamingVAE computes on the GPU only: the model is on %s" % self.device)
-        self._weights()                                  # raises on a non-fp32 / non-contiguous parameter
+        self.parameters()                                # raises on a non-fp32 / non-contiguous parameter
         dev, F, L = self.device, self.frames_per_block, self.L
         w = window_values(self.S, window)
         self._window = torch.from_numpy(w).to(dev)
@@ -110,10 +165,10 @@ class StreamingVAE:
         if nbytes <= 0:
             raise ValueError("rv_stream_workspace_bytes rejected the extents")
         self._ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-        self._graph = None
 
     # -- helpers ---------------------------------------------------------------------------------------------------
-    def _weights(self):
+    def parameters(self):
+        """The model's ten Parameters in the descriptor's order, checked: RvError unless contiguous fp32 on the device."""
         out = []
         for name in _LAYERS:
             layer = getattr(self.model, name)
@@ -123,10 +178,11 @@ class StreamingVAE:
                 out.append(p)
         return out
 
-    def _desc(self, x, y, eps):
+    def desc(self, x, y, eps):
+        """The rv_stream_desc of one call on x, y [n_streams, block] (None: no block, as for a reset) and eps."""
         d = StreamDesc()
         d.S, d.H, d.L, d.n_streams, d.block, d.hop = self.S, self.H, self.L, self.n_streams, self.block, self.hop
-        for (name, p) in zip(("w1", "b1", "w21", "b21", "w22", "b22", "w3", "b3", "w4", "b4"), self._weights()):
+        for (name, p) in zip(("w1", "b1", "w21", "b21", "w22", "b22", "w3", "b3", "w4", "b4"), self.parameters()):
             setattr(d, name, p.data_ptr())
         d.x, d.ld_x = (ptr(x), x.stride(0)) if x is not None else (None, self.block)
         d.y, d.ld_y = (ptr(y), y.stride(0)) if y is not None else (None, self.block)
@@ -145,7 +201,8 @@ class StreamingVAE:
         if tuple(t.shape) != shape:
             raise ValueError("%s has shape %s, expected %s" % (what, tuple(t.shape), shape))
 
-    def _input(self, x):
+    def check_input(self, x):
+        """x as the [n_streams, block] fp32 device tensor a call reads (TypeError, ValueError or RvError otherwise)."""
         if torch.is_tensor(x) and x.dim() == 1 and self.n_streams == 1:
             x = x.view(1, -1)
         self._check(x, (self.n_streams, self.block), "x")
@@ -158,25 +215,19 @@ class StreamingVAE:
     def process(self, x, eps=None):
         """One block: x [n_streams, block] fp32 on the device -> output [n_streams, block] (the input `latency`
         samples late).  eps: None (Philox) or [n_streams, block // hop, L] fp32."""
-        x = self._input(x)
+        x = self.check_input(x)
         if eps is not None:
             self._check(eps, (self.n_streams, self.frames_per_block, self.L), "eps")
             eps = eps.contiguous()
         y = torch.empty((self.n_streams, self.block), dtype=torch.float32, device=self.device)
-        lib().rv_stream_process(self._desc(x, y, eps), stream_ptr())
+        lib().rv_stream_process(self.desc(x, y, eps), stream_ptr())
         return y
 
     @torch.no_grad()
     def reset(self, streams=None):
         """Zero the history, the overlap-add tail and the frame counter of `streams` (an index or a list; None = all)."""
-        d = self._desc(None, None, None)
-        if streams is None:
-            lib().rv_stream_reset(d, -1, stream_ptr())
-            return
-        for s in ([streams] if isinstance(streams, int) else list(streams)):
-            s = int(s)
-            if not 0 <= s < self.n_streams:
-                raise ValueError("stream %d of %d" % (s, self.n_streams))
+        d = self.desc(None, None, None)
+        for s in each_stream(streams, self.n_streams):
             lib().rv_stream_reset(d, s, stream_ptr())
 
     def last_latents(self):
@@ -189,30 +240,10 @@ class StreamingVAE:
         """Capture one call (eps from Philox) as a graph on static buffers `graph_input` / `graph_output`
         [n_streams, block]; `replay(x)` then runs one block per call.  The graph holds the Parameters' pointers:
         replaying after a Parameter was replaced raises."""
-        from .engine import Graph
-        self.graph_input = torch.zeros((self.n_streams, self.block), dtype=torch.float32, device=self.device)
-        self.graph_output = torch.zeros_like(self.graph_input)
-        desc = self._desc(self.graph_input, self.graph_output, None)
-        self._held = [(p, p.data_ptr()) for p in self._weights()]
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        g = Graph(side)
-        with g:
-            lib().rv_stream_process(desc, side.cuda_stream)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        self._graph = g
-        return self
+        return self._capture(lambda st: lib().rv_stream_process(self.desc(self.graph_input, self.graph_output, None), st))
 
     @torch.no_grad()
     def replay(self, x=None):
         """One block through the captured graph on the current stream; x (optional) is copied into `graph_input`
         first.  Returns `graph_output` (overwritten by the next replay)."""
-        if self._graph is None:
-            raise _lib.RvError("replay() before capture()")
-        now = self._weights()
-        if any(p is not q or p.data_ptr() != a for p, (q, a) in zip(now, self._held)):
-            raise _lib.RvError("a Parameter of the model was replaced after capture(): capture again")
-        if x is not None:
-            self.graph_input.copy_(self._input(x))
-        self._graph.launch(torch.cuda.current_stream(self.device))
-        return self.graph_output
+        return self._replay(0, "replay()", x)

@@ -99,8 +99,8 @@ def _decoded(index, rows):
     z = M.gather_mean(index.mu, i, index.L, stride=index.L, n_rows=len(index))
     h = torch.empty((n, index.H), dtype=torch.float32, device="cuda")
     out = torch.empty((n, index.S), dtype=torch.float32, device="cuda")
-    index._enc._linear(ptr(z), index.L, n, "fc3", ACT_RELU, ptr(h), index.H)
-    index._enc._linear(ptr(h), index.H, n, "fc4", ACT_TANH, ptr(out), index.S)
+    index.codec.linear(ptr(z), index.L, n, "fc3", ACT_RELU, ptr(h), index.H)
+    index.codec.linear(ptr(h), index.H, n, "fc4", ACT_TANH, ptr(out), index.S)
     return out.cpu().numpy()
 
 

@@ -299,7 +299,7 @@ def test_graph_replay_equals_eager_and_sees_control_edits():
     b = _run(graph, x, replay=True, before_block=edit(graph))
     assert all(torch.equal(p, q) for p, q in zip(a, b))
     # the offset took effect: the last block's candidates are those of mu * scale + offset with the edited offset
-    mu_last = graph._sv.last_latents()[0]
+    mu_last = graph.last_latents()[0]
     q = (mu_last * graph.scale[:, None, :] + graph.offset[:, None, :]).reshape(-1, index.L)
     assert float(graph.offset[0, 0]) == 0.75 and _same(M.knn_topk(q, index.mu, 4),
                                                        (b[1][:, -2:].reshape(-1, 4), b[2][:, -2:].reshape(-1, 4)))

@@ -42,7 +42,7 @@ def launches(it, a, b, curve, hop, eps):
     z = torch.empty(min(R, N), L, device=dev)
     out = torch.empty(N * S, device=dev)
     c = torch.from_numpy(curve).to(dev)
-    W = {k: it._w(k) for k in ("fc1", "fc21", "fc22", "fc3", "fc4")}
+    W = {k: it.codec.weights(k) for k in ("fc1", "fc21", "fc22", "fc3", "fc4")}
     st = stream_ptr()
     L_ = lib()
 
