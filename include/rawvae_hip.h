@@ -623,6 +623,54 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_GRAIN_GATHER 15
 #define RV_EVAL_FRAMES 16
 #define RV_EVAL_DIMS 17
+/* Latent PCA (csrc/pca.hip, rawaudiovae_kelsey_amd/pca.py): the principal axes of a corpus's
+ * latents and edits along them.  The descriptor gains no field: `centre` below is the field `trans` and `basis` the
+ * field `dist`, each carrying the address of fp64 values (a C caller casts: d.trans = (float*)centre).  All arithmetic is fp64; no op syncs or reads the device, each may run under capture,
+ * and each returns an RV_ERR_* whose message names the field before anything is launched and without reading a device
+ * pointer: T, L, k, mode out of range; a null q, out, centre, basis, cost, choice, weight, c or ws; ldo too small;
+ * ws_bytes too small.
+ * RV_PCA_MOMENTS: q = x [T, L] fp32 (2 <= T < 2^31, 1 <= L <= 512) -> centre [L] fp64 = the column means and
+ *   basis [L, L] fp64 = the sample covariance with ddof = 1 (numpy.cov(x64, rowvar=False)).
+ *   Mean: RV_EVAL_DIMS's order: the rows in blocks of 256, block b = rows [256 b, 256 b + 256) added in ascending t
+ *   from +0 in fp64, the block sums added in ascending b from +0, one division by T.
+ *   Covariance: a second pass over d = (double)x - centre.  T is cut into ranges of 4096 rows; a workgroup owns one
+ *   range and one 64 x 64 tile (I, J >= I) of the matrix, stages 32 rows of d at a time in LDS (columns beyond L and
+ *   rows beyond the range as zeros, in LDS only) and adds them, four rows per v_mfma_f64_16x16x4_f64, in ascending
+ *   row order into its 16 x 16 tiles; 16 x 16 tiles below the diagonal are not computed.  The range's partial tile
+ *   goes to ws; a second launch adds the partials of every element (i, j >= i) in ascending range order from +0,
+ *   divides once by T - 1 and writes basis[i, j] and basis[j, i] from that one value: exactly symmetric.  No atomics; the bits depend on x, T and L only, not on the launch or the device.  Four launches.
+ * RV_PCA_EIG: basis [L, L] symmetric fp64 (1 <= L <= 512), in place -> basis row j = the j-th unit eigenvector,
+ *   cost [L] fp64 = the eigenvalues in descending order (equal values: the lower Jacobi index first), choice [2]
+ *   int32 = {sweeps run, 1 if converged else 0}.  Cyclic two-sided Jacobi in fp64 by ONE workgroup of 1024 threads,
+ *   the matrix in global memory, __syncthreads() between steps.  n = L rounded up to even; a sweep is the n - 1 steps
+ *   of the round-robin (circle) order, step s rotating the n / 2 disjoint pairs {n - 1, s} and
+ *   {(s + m) mod (n - 1), (s - m) mod (n - 1)}, m = 1 .. n / 2 - 1, each as (p < q), at once (a pair with an index
+ *   >= L is skipped).  Rotation of (p, q) with a_pq != 0: theta = (a_qq - a_pp) / (2 a_pq),
+ *   t = sgn(theta) / (|theta| + sqrt(theta^2 + 1)) (sgn(0) = 1), c = 1 / sqrt(t^2 + 1), s = t c; a_pp -= t a_pq,
+ *   a_qq += t a_pq, a_pq = 0; every other 2 x 2 block (pair, pair) gets the rotation of the lower pair number first,
+ *   so the matrix stays bitwise symmetric.  Before every sweep the off-diagonal Frobenius norm is summed directly
+ *   over the off-diagonal entries; the solver stops when it is <= L 2^-52 ||C||_F (||C||_F of the input), or after 40
+ *   sweeps.  Sign: the entry of largest magnitude of each eigenvector is positive (exact ties: the lowest index).
+ *   Negative eigenvalues are reported as computed.  One launch.  ws: 8 L^2 bytes.
+ * RV_PCA_APPLY: mode = RV_PCA_PROJECT / RV_PCA_RECONSTRUCT / RV_PCA_EDIT; 1 <= T < 2^31, 1 <= k <= L <= 512;
+ *   basis [k, L] fp64 = the first k components v_j, centre [L] fp64, cost [k] fp64 = their eigenvalues (read by EDIT
+ *   only).  Rows are independent: a row's bits do not depend on T or on the launch.  Every dot product is one chain
+ *   acc = fma(a, b, acc) in ascending index from +0 in fp64; each output is rounded to fp32 once.
+ *   PROJECT      q = x [T, L] -> out [T, ldo >= k]: y_j = sum_l (x_l - centre_l) v_jl
+ *   RECONSTRUCT  q = y [T, k] -> out [T, ldo >= L]: centre_l + sum_j y_j v_jl
+ *   EDIT         q = x [T, L], weight = gains g [k] fp32, c = shifts h [k] fp32, both on the device -> out [T, ldo >= L]:
+ *                x_l + sum_j ((g_j - 1) y_j + h_j sqrt(max(cost_j, 0))) v_jl with y_j of PROJECT unrounded; where the
+ *                sum is zero the output is x_l itself, so g = 1, h = 0 returns x bit for bit.
+ *   Only columns [0, k) (PROJECT) or [0, L) of out are written.  One launch.
+ * RV_PCA_WORKSPACE: the bytes of ws for RV_PCA_EIG at L and, when T >= 2 (T = 0: EIG only), RV_PCA_MOMENTS at (T, L),
+ *   in d->ws_bytes; launches nothing and touches no device. */
+#define RV_PCA_MOMENTS 18
+#define RV_PCA_EIG 19
+#define RV_PCA_APPLY 20
+#define RV_PCA_WORKSPACE 21
+#define RV_PCA_PROJECT 0
+#define RV_PCA_RECONSTRUCT 1
+#define RV_PCA_EDIT 2
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
 struct rv_stream_desc;

@@ -82,6 +82,14 @@ def eval_fields(mu, logvar, table=None, dynamic_range=0.0):
     return dict(q=ptr(mu), c=ptr(logvar), weight=ptr(table), lam=float(dynamic_range))
 
 
+def pca_fields(centre=None, basis=None, eigenvalues=None, info=None, gains=None, shifts=None):
+    # The RV_PCA_* ops (include/rawvae_hip.h, "Latent PCA"): trans carries centre [L] fp64 and dist carries basis
+    # [L, L] / [k, L] fp64; cost = the eigenvalues fp64, choice = the int32 pair {sweeps, converged} of RV_PCA_EIG, and
+    # RV_PCA_EDIT's weight, c = the gains and shifts [k] fp32
+    return dict(trans=ptr(centre), dist=ptr(basis), cost=ptr(eigenvalues), choice=ptr(info), weight=ptr(gains),
+                c=ptr(shifts))
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),
@@ -110,6 +118,8 @@ MOSAIC_KNN_SMALL, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_LIVE, MOSAIC_LIVE_WORKSPACE
 MOSAIC_LIVE_DRAIN = 13
 GRAIN_FIT, GRAIN_GATHER = 14, 15   # RV_GRAIN_* (rv_mosaic)
 EVAL_FRAMES, EVAL_DIMS = 16, 17    # RV_EVAL_* (rv_mosaic)
+PCA_MOMENTS, PCA_EIG, PCA_APPLY, PCA_WORKSPACE = 18, 19, 20, 21   # RV_PCA_* (rv_mosaic)
+PCA_PROJECT, PCA_RECONSTRUCT, PCA_EDIT = 0, 1, 2   # RV_PCA_APPLY's mode
 LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.

@@ -147,3 +147,10 @@ RV_INTERNAL int rv_grain_live(const rv_mosaic_desc* d, const int* sel, int sel_k
 // for them; checks first, then one launch (EVAL_DIMS: two beyond one block of rows), no sync and no read of the device.
 RV_INTERNAL int rv_eval_frames(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_eval_dims(const rv_mosaic_desc* d, void* stream);
+// The latent-PCA ops of rv_mosaic (pca.hip): RV_PCA_MOMENTS, RV_PCA_EIG and RV_PCA_APPLY on the fields the public header
+// names for them -- checks first, then the launches, no sync and no read of the device -- and RV_PCA_WORKSPACE, which
+// writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_pca_moments(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_pca_eig(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_pca_apply(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_pca_workspace(rv_mosaic_desc* d);

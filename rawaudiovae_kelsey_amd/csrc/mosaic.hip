@@ -1400,6 +1400,14 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       return rv_eval_frames(d, stream);
     case RV_EVAL_DIMS:
       return rv_eval_dims(d, stream);
+    case RV_PCA_MOMENTS:
+      return rv_pca_moments(d, stream);
+    case RV_PCA_EIG:
+      return rv_pca_eig(d, stream);
+    case RV_PCA_APPLY:
+      return rv_pca_apply(d, stream);
+    case RV_PCA_WORKSPACE:
+      return rv_pca_workspace(d);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }

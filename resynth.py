@@ -8,6 +8,9 @@ Streaming resynthesis of one wav through a trained model, block by block, as a l
   --block N          samples per call (a multiple of hop; default segment_length); the output does not depend on it
   --temperature T    scale of eps (0: decode mu' itself)
   --offset file.npy  latent_dim values added to mu
+  --pca pca.npz --pc-shift J:H,...
+                     move mu along principal axis J (1-based) of latent_pca.py's file by H standard deviations of the
+                     corpus; added onto --offset (LatentPCA.offset)
   --seed S           seed of the on-device eps draw
 
 The input is fed in blocks, followed by zeros to flush the latency (segment_length - hop samples); the output is
@@ -37,7 +40,14 @@ def parse_args(argv=None):
     p.add_argument("--temperature", default="1", help="scale of eps")
     p.add_argument("--offset", default=None, help=".npy of latent_dim values added to mu")
     p.add_argument("--seed", default="0", help="seed of the eps draw")
+    p.add_argument("--pca", default=None, help="the .npz written by latent_pca.py fit")
+    p.add_argument("--pc-shift", default=None, help="J:H,...: shift along principal axis J (1-based) by H standard deviations")
     args = p.parse_args(argv)
+    if (args.pca is None) != (args.pc_shift is None):
+        raise ValueError("--%s: --pca and --pc-shift come together" % ("pca" if args.pca is None else "pc-shift"))
+    if args.pc_shift is not None:
+        from latent_pca import parse_axis_values
+        args.pc_shift = parse_axis_values(args.pc_shift, "pc-shift")
     for flag in ("hop", "block", "seed"):
         v = getattr(args, flag)
         if v is None:
@@ -92,6 +102,20 @@ def resynthesize(model, audio, hop, block, window=None, temperature=1.0, offset=
     return out[eng.latency:eng.latency + n].cpu().numpy()
 
 
+def pc_offset(args, cfg, offset, device="cuda"):
+    """--offset's values (or None) plus the shift --pca / --pc-shift ask for -> [latent_dim] fp32 numpy array."""
+    from latent_pca import check_axes
+    from rawaudiovae_kelsey_amd.pca import read_pca
+    if not os.path.exists(args.pca):
+        raise ValueError("--pca %r: no such file" % args.pca)
+    pca, meta = read_pca(args.pca, device)
+    if meta["latent_dim"] != cfg["latent_dim"]:
+        raise ValueError("--pca %r: fitted for latent_dim %d, the model has %d" % (args.pca, meta["latent_dim"],
+                                                                                   cfg["latent_dim"]))
+    shift = pca.offset(check_axes(args.pc_shift, pca.components_.shape[0], "pc-shift")).cpu().numpy()
+    return shift if offset is None else (np.asarray(offset, dtype=np.float32) + shift).astype(np.float32)
+
+
 def main(argv=None):
     args = parse_args(argv)
     from interpolate import load_model, read_model_config
@@ -105,6 +129,8 @@ def main(argv=None):
         if offset.ndim != 1 or offset.size != cfg["latent_dim"]:
             raise ValueError("--offset %r: expected %d values, got shape %s" % (args.offset, cfg["latent_dim"],
                                                                                 offset.shape))
+    if args.pca is not None:
+        offset = pc_offset(args, cfg, offset)
     from rawaudiovae_kelsey_amd import data as D
     model = load_model(args.checkpoint, cfg)
     sr = cfg["sampling_rate"]
