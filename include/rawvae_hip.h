@@ -671,6 +671,63 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_PCA_PROJECT 0
 #define RV_PCA_RECONSTRUCT 1
 #define RV_PCA_EDIT 2
+/* Latent walk (csrc/walk.hip, rawaudiovae_kelsey_amd/walk.py): a first-order linear-Gaussian
+ * model of how a corpus's latents move from one frame to the next, in whitened principal coordinates, and its run as a
+ * generator of new latent rows.  It extends "Latent PCA" above and keeps its conventions: the descriptor gains no field,
+ * fp64 operands travel in float* fields (`centre` = trans, `basis` = dist; the other roles are named per op below and
+ * spelled by _lib.walk_fields), no op syncs or reads a device pointer on the host, each may run under capture, and each
+ * returns an RV_ERR_* whose message names the field before anything is launched.
+ * The model.  x [T, L] fp32 are the corpus's latents in file order, file f owning rows [row_start[f], row_start[f+1]);
+ * c, v_j, lambda_j the centre, components and eigenvalues (ddof = 1) of RV_PCA_MOMENTS / RV_PCA_EIG on x.  The walk
+ * keeps the first k axes, lambda_j > 0 on each.  P [k, L] has rows v_j / sqrt(lambda_j) and R [k, L] rows
+ * sqrt(lambda_j) v_j.  With C1 the lag-1 moment below, A = P C1 P^T [k, k], Q = I - A A^T, Q = U diag(q) U^T and
+ * B = U diag(sqrt(max(q, 0))), so that A A^T + B B^T = I.  C1 is divided by T - 1, the covariance's own divisor: the
+ * Gram matrix of the frames stacked with their successors (zero at file ends) is positive semidefinite with both
+ * diagonal blocks (T - 1) C0, hence ||A||_2 <= 1 and the state w' = A w + B e, e ~ N(0, I), is stable and has I as its
+ * stationary covariance: the latent rows c + R^T w have the corpus's mean and its covariance on the kept axes.
+ * RV_PCA_LAGCOV: q = x [T, L] fp32 (2 <= T < 2^31, 1 <= L <= 512), row_start [n_rows + 1] int64 on the device
+ *   (n_rows = the files, 1 <= n_rows <= T; ascending from 0 to T: the CALLER checks that on its host copy, the library
+ *   never reads the pointer and the kernels only compare its values), centre [L] fp64 -> dist = C1 [L, L] fp64,
+ *   C1[i, j] = (1 / (T - 1)) sum d[t+1, i] d[t, j], d[t] = (double)x[t] - centre, over the pairs (t, t + 1) of one file (a
+ *   file of one row has none).  C1 is the full matrix and is not symmetric.  RV_PCA_MOMENTS' discipline: the T - 1
+ *   pairs are cut into ranges of 4096 in ascending order; a workgroup owns one range and one 64 x 64 tile, stages 32
+ *   pairs at a time in LDS (row t + 1 left, row t right, zero where the pair crosses a file end, where a column is
+ *   beyond L or a pair beyond the range) and adds them, four pairs per v_mfma_f64_16x16x4_f64, in ascending order; the
+ *   range's partial tile goes to ws and a last launch adds the partials of every element in ascending range order from
+ *   +0 and divides once by T - 1.  No atomics; the bits depend on x, row_start, T and L only.  Three launches.
+ * RV_WALK_FIT: the dense fp64 products of the fit; every sum is one chain acc = fma(a, b, acc) in ascending index from
+ *   +0.  1 <= k <= L <= 512.
+ *   mode RV_WALK_DYNAMICS: basis [k, L], cost = lambda [k], src = C1 [L, L] fp64 -> out = fp64 [A (k k) | Q (k k) |
+ *     P (k L) | R (k L)]: P = v / sqrt(lambda), R = sqrt(lambda) v, M = P C1 (in ws, 8 k L bytes), A = M P^T;
+ *     Q[i, j] for i <= j = (i == j ? 1 : 0) - sum_m A[i, m] A[j, m], written to [i, j] and [j, i]: bitwise symmetric.
+ *   mode RV_WALK_NOISE: dist = A [k, k], src = the eigenvectors of Q as RV_PCA_EIG leaves them (row j the j-th) fp64,
+ *     cost = q [k] -> out = fp64 [A^T | B^T] (2 k k), B^T[j, i] = sqrt(max(q_j, 0)) u_j[i]: the layout RV_WALK_STEP
+ *     reads, consecutive lanes at consecutive addresses.
+ *   mode RV_WALK_DIAGONAL: dist = A [k, k] -> out = [A^T | B^T] of the diagonal model: a_jj on the diagonal of the
+ *     first, sqrt(max(fma(-a_jj, a_jj, 1), 0)) on that of the second, zeros elsewhere (|a_jj| <= ||A||_2 <= 1).
+ * RV_WALK_STEP: one block of every stream of *live generated, enqueued without a sync: the step launch, then
+ *   rv_stream_process's fc3, fc4 and overlap-add launches (four in all).  live carries the model's decoder, the block
+ *   output y, window, norm, the stream workspace (frame counters, overlap-add tail), seed, temperature [n_streams],
+ *   offset [n_streams, L] and eps_in; its x must be a readable block (it only feeds the unused input history), and
+ *   scale, mu, logvar are not read.  L = live->L, 1 <= k <= L <= 512; centre [L], dist = R [k, L], src = [A^T | B^T]
+ *   fp64; cost = the state w [n_streams, k] fp64 and choice = the primed flags [n_streams] int32, both read and written.
+ *   One workgroup per stream steps the F = block / hop frames of the call in order.  For stream s, absolute frame f
+ *   (the stream workspace's counter) and axis j: e_j = (double)temperature[s] * (double)eps, eps = eps_in[(s F + frame)
+ *   k + j] (eps_in is [n_streams * F, k] here) or, with eps_in NULL, Philox(seed) at index f k + j, offset s: element
+ *   f k + j of rv_randn(seed, offset = s).  Not primed: w = e and the flag is set.  Otherwise w'_i is ONE chain
+ *   acc = fma(A[i, j], w_j, acc) over ascending j from +0 continued by fma(B[i, j], e_j, acc) over ascending j.
+ *   The latent row: z_l = (float)(centre_l + (double)offset[s, l] + chain_j fma(w_j, R[j, l], .)), written to the stream
+ *   workspace's latent row s F + frame and, when out is not NULL, to out [n_streams * F, ldo >= L].  A stream's bits
+ *   depend on its own state, noise and controls only, not on n_streams or on the block length.
+ * RV_WALK_WORKSPACE: the bytes of ws for RV_WALK_FIT at (k, L) (k = 0: none) and, when T >= 2 (T = 0: none),
+ *   RV_PCA_LAGCOV at (T, L), in d->ws_bytes; launches nothing and touches no device. */
+#define RV_PCA_LAGCOV 22
+#define RV_WALK_FIT 23
+#define RV_WALK_STEP 24
+#define RV_WALK_WORKSPACE 25
+#define RV_WALK_DYNAMICS 0
+#define RV_WALK_NOISE 1
+#define RV_WALK_DIAGONAL 2
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
 struct rv_stream_desc;

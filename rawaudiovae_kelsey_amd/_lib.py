@@ -90,6 +90,16 @@ def pca_fields(centre=None, basis=None, eigenvalues=None, info=None, gains=None,
                 c=ptr(shifts))
 
 
+def walk_fields(centre=None, basis=None, eigenvalues=None, moment=None, result=None, state=None, primed=None):
+    # The latent-walk ops (include/rawvae_hip.h, "Latent walk"), on PCA's roles: trans carries centre [L] fp64, dist the
+    # fp64 matrix an op names `basis` (RV_PCA_LAGCOV: C1 out; RV_WALK_FIT: the components or A; RV_WALK_STEP: R) and cost
+    # the eigenvalues fp64 (RV_WALK_STEP: the state [n_streams, k]); src = the fp64 input matrix (C1, the eigenvectors of
+    # Q, or RV_WALK_STEP's [A^T | B^T]), out = RV_WALK_FIT's fp64 result (RV_WALK_STEP: the fp32 latent rows), choice =
+    # the primed flags [n_streams] int32
+    return dict(trans=ptr(centre), dist=ptr(basis), cost=ptr(state if eigenvalues is None else eigenvalues),
+                src=ptr(moment), out=ptr(result), choice=ptr(primed))
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),
@@ -120,6 +130,8 @@ GRAIN_FIT, GRAIN_GATHER = 14, 15   # RV_GRAIN_* (rv_mosaic)
 EVAL_FRAMES, EVAL_DIMS = 16, 17    # RV_EVAL_* (rv_mosaic)
 PCA_MOMENTS, PCA_EIG, PCA_APPLY, PCA_WORKSPACE = 18, 19, 20, 21   # RV_PCA_* (rv_mosaic)
 PCA_PROJECT, PCA_RECONSTRUCT, PCA_EDIT = 0, 1, 2   # RV_PCA_APPLY's mode
+PCA_LAGCOV, WALK_FIT, WALK_STEP, WALK_WORKSPACE = 22, 23, 24, 25   # the latent walk (rv_mosaic)
+WALK_DYNAMICS, WALK_NOISE, WALK_DIAGONAL = 0, 1, 2   # RV_WALK_FIT's mode
 LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.

@@ -154,3 +154,10 @@ RV_INTERNAL int rv_pca_moments(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_pca_eig(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_pca_apply(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_pca_workspace(rv_mosaic_desc* d);
+// The latent-walk ops of rv_mosaic (walk.hip): RV_PCA_LAGCOV, RV_WALK_FIT and RV_WALK_STEP on the fields the public
+// header names for them -- checks first, then the launches, no sync and no read of the device -- and RV_WALK_WORKSPACE,
+// which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_walk_fit(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_walk_step(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_walk_workspace(rv_mosaic_desc* d);

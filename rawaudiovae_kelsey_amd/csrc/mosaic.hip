@@ -1408,6 +1408,14 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       return rv_pca_apply(d, stream);
     case RV_PCA_WORKSPACE:
       return rv_pca_workspace(d);
+    case RV_PCA_LAGCOV:
+      return rv_pca_lagcov(d, stream);
+    case RV_WALK_FIT:
+      return rv_walk_fit(d, stream);
+    case RV_WALK_STEP:
+      return rv_walk_step(d, stream);
+    case RV_WALK_WORKSPACE:
+      return rv_walk_workspace(d);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }

@@ -1,0 +1,373 @@
+// Latent walk (rawaudiovae_kelsey_amd/walk.py): a first-order linear-Gaussian model of a corpus's latent trajectories in
+// whitened principal coordinates, fitted and run on the device.  Four ops of rv_mosaic; the rules: include/rawvae_hip.h,
+// "Latent walk"; the derivation and the measured figures: DESIGN.md section 7.11.
+//   RV_PCA_LAGCOV     the fp64 lag-1 moment of the centred rows over the pairs (t, t + 1) of one file: k_walk_pairs (which
+//                     pairs count), k_walk_lag (one workgroup per range of 4096 pairs and 64 x 64 tile of the full matrix,
+//                     on v_mfma_f64_16x16x4_f64, pca.hip's staging) and k_walk_lag_sum over the ranges.  No atomics.
+//   RV_WALK_FIT       the small dense fp64 products of the fit, every output one ascending fma chain: k_walk_product
+//                     and three elementwise kernels.  A one-off of at most 2 * 512^3 flops, not tuned.
+//   RV_WALK_STEP      F frames of every stream in one launch, one workgroup per stream, the state in LDS: k_walk_step;
+//                     then rv_stream_synth's fc3, fc4 and overlap-add.
+//   RV_WALK_WORKSPACE the bytes of ws of the first two.
+#include <math.h>
+
+#include "common.h"
+#include "philox.h"
+#include "internal.h"
+
+using namespace rv;
+
+namespace {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int WK_LMAX = 512;
+constexpr int LG_RANGE = 4096;           // pairs of one range (the header states it)
+constexpr int LG_CHUNK = 32;             // pairs staged in LDS at a time
+constexpr int LG_MT = 64;                // the workgroup's tile: 4 x 4 MFMA tiles of 16 x 16, one row of them per wave
+constexpr int LG_LD = 80;                // LDS row pitch in doubles (pca.hip's: rows k .. k + 3 fall into disjoint banks)
+constexpr int LG_THREADS = 256;
+constexpr int ST_THREADS = 256;
+
+long up256(long n) { return (n + 255) / 256 * 256; }
+
+// keep[p] = 1 when rows p and p + 1 lie in one file: p + 1 is none of row_start[0 .. n_files]
+__global__ void __launch_bounds__(256)
+k_walk_pairs(const long long* __restrict__ row_start, long n_files, long n_pairs, unsigned char* __restrict__ keep) {
+  const long p = (long)blockIdx.x * 256 + threadIdx.x;
+  if (p >= n_pairs) return;
+  long lo = 0, hi = n_files + 1;   // the first entry >= p + 1
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (row_start[mid] < p + 1) lo = mid + 1;
+    else hi = mid;
+  }
+  keep[p] = (lo <= n_files && row_start[lo] == p + 1) ? 0 : 1;
+}
+
+// The thread's column of both operands at pairs p, p + 4, ..: row p + 1 for the left operand, row p for the right one
+// and the pair's keep flag; a pair beyond the range is read from the range's last pair (the caller stores zeros).
+template <int PER>
+__device__ __forceinline__ void lag_fetch(const float* __restrict__ xa, const float* __restrict__ xb,
+                                          const unsigned char* __restrict__ keep, long p, long p1, long L,
+                                          float (&fa)[PER], float (&fb)[PER], unsigned char (&fk)[PER]) {
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const long pp = p + 4 * i;
+    const long pr = pp < p1 ? pp : p1 - 1;
+    fa[i] = xa[(pr + 1) * L];
+    fb[i] = xb[pr * L];
+    fk[i] = keep[pr];
+  }
+}
+
+// Grid (ranges of pairs, nI * nI tiles).  Wave w owns the MFMA tiles (w, 0 .. 3) of the 64 x 64 tile (I, J).
+// v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; with
+// A[i][k] = d[p + k + 1][i0 + i] and B[k][j] = keep[p + k] d[p + k][j0 + j] one instruction adds four pairs to the tile.
+// Its result: column l & 15, row (l >> 4) + 4 reg.
+__global__ void __launch_bounds__(LG_THREADS)
+k_walk_lag(const float* __restrict__ x, long n_pairs, int L, const double* __restrict__ centre,
+           const unsigned char* __restrict__ keep, int nI, double* __restrict__ part) {
+  __shared__ double As[LG_CHUNK * LG_LD];
+  __shared__ double Bs[LG_CHUNK * LG_LD];
+  const int I = (int)blockIdx.y / nI, J = (int)blockIdx.y - I * nI;
+  const int lane = threadIdx.x & 63, ti = threadIdx.x >> 6;
+  f64x4 acc[4];
+#pragma unroll
+  for (int tj = 0; tj < 4; ++tj) acc[tj] = f64x4{0.0, 0.0, 0.0, 0.0};
+  const long p0 = (long)blockIdx.x * LG_RANGE, p1 = p0 + LG_RANGE < n_pairs ? p0 + LG_RANGE : n_pairs;
+  constexpr int PER = LG_CHUNK / (LG_THREADS / LG_MT);   // pairs per thread and chunk
+  const int cc = lane;
+  const int ca = I * LG_MT + cc, cb = J * LG_MT + cc;
+  const bool va = ca < L, vb = cb < L;
+  const double ma = va ? centre[ca] : 0.0, mb = vb ? centre[cb] : 0.0;
+  const float* const xa = x + (va ? ca : L - 1);
+  const float* const xb = x + (vb ? cb : L - 1);
+  float fa[PER], fb[PER];
+  unsigned char fk[PER];
+  lag_fetch<PER>(xa, xb, keep, p0 + ti, p1, L, fa, fb, fk);
+  for (long pc = p0; pc < p1; pc += LG_CHUNK) {
+    __syncthreads();   // the MFMAs of the chunk before have read LDS
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int r = ti + 4 * i;
+      const bool vp = pc + r < p1;
+      As[r * LG_LD + cc] = (vp && va) ? (double)fa[i] - ma : 0.0;
+      Bs[r * LG_LD + cc] = (vp && vb && fk[i]) ? (double)fb[i] - mb : 0.0;
+    }
+    __syncthreads();
+    if (pc + LG_CHUNK < p1) lag_fetch<PER>(xa, xb, keep, pc + LG_CHUNK + ti, p1, L, fa, fb, fk);
+#pragma unroll
+    for (int kk = 0; kk < LG_CHUNK; kk += 4) {
+      const int row = (kk + (lane >> 4)) * LG_LD + (lane & 15);
+      const double a = As[row + ti * 16];
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj) {
+        const double b = Bs[row + tj * 16];
+        acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
+      }
+    }
+  }
+  double* const o = part + ((long)blockIdx.x * (nI * nI) + blockIdx.y) * (LG_MT * LG_MT);
+#pragma unroll
+  for (int tj = 0; tj < 4; ++tj)
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+      o[(ti * 16 + (lane >> 4) + 4 * reg) * LG_MT + tj * 16 + (lane & 15)] = acc[tj][reg];
+}
+
+// Grid (tiles of 64 columns, rows): element (i, j) = its partials in ascending range order from +0, over T - 1.
+__global__ void __launch_bounds__(64)
+k_walk_lag_sum(const double* __restrict__ part, long n_ranges, int nI, int L, long T, double* __restrict__ c1) {
+  const int i = (int)blockIdx.y, j = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (j >= L) return;
+  const long at = (long)((i >> 6) * nI + (j >> 6)) * (LG_MT * LG_MT) + (i & 63) * LG_MT + (j & 63);
+  double acc = 0.0;
+  for (long r = 0; r < n_ranges; ++r) acc += part[r * (nI * nI) * (LG_MT * LG_MT) + at];
+  c1[(long)i * L + j] = acc / (double)(T - 1);
+}
+
+// p[j, l] = v[j, l] / sqrt(lam_j) (the whitening rows) and r[j, l] = sqrt(lam_j) v[j, l] (their inverse's)
+__global__ void __launch_bounds__(256)
+k_walk_scale(const double* __restrict__ v, const double* __restrict__ lam, int k, int L, double* __restrict__ p,
+             double* __restrict__ r) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)k * L) return;
+  const double s = sqrt(lam[e / L]);
+  p[e] = v[e] / s;
+  r[e] = s * v[e];
+}
+
+// out[i, j] = sum_l a[i, l] b(l, j) as one chain acc = fma(a, b, acc) in ascending l from +0; b(l, j) = b[j, l] (BT) or
+// b[l, j].  GRAM (a == b, BT, M == N): only i <= j is computed, as (i == j ? 1 : 0) - acc, and written to [i, j] and
+// [j, i] from that one value.
+template <bool BT, bool GRAM>
+__global__ void __launch_bounds__(256)
+k_walk_product(const double* __restrict__ a, const double* __restrict__ b, int M, int N, int K, double* __restrict__ out) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)M * N) return;
+  const int i = (int)(e / N), j = (int)(e - (long)i * N);
+  if (GRAM && i > j) return;
+  double acc = 0.0;
+  for (int l = 0; l < K; ++l) acc = __builtin_fma(a[(long)i * K + l], BT ? b[(long)j * K + l] : b[(long)l * N + j], acc);
+  if (GRAM) {
+    const double v = (i == j ? 1.0 : 0.0) - acc;
+    out[(long)i * N + j] = v;
+    out[(long)j * N + i] = v;
+  } else {
+    out[e] = acc;
+  }
+}
+
+// dyn = [A^T | B^T], B = U diag(sqrt(max(q, 0))): A^T[j, i] = a[i, j]; B^T[j, i] = sqrt(max(q_j, 0)) u[j, i], u's row j
+// being the j-th eigenvector
+__global__ void __launch_bounds__(256)
+k_walk_noise(const double* __restrict__ a, const double* __restrict__ u, const double* __restrict__ q, int k,
+             double* __restrict__ dyn) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)k * k) return;
+  const int j = (int)(e / k), i = (int)(e - (long)j * k);
+  dyn[e] = a[(long)i * k + j];
+  dyn[(long)k * k + e] = sqrt(fmax(q[j], 0.0)) * u[e];
+}
+
+// the diagonal model: A = diag(a_jj), B = diag(sqrt(1 - a_jj^2)), 1 - a^2 rounded once (and clamped at 0)
+__global__ void __launch_bounds__(256)
+k_walk_diagonal(const double* __restrict__ a, int k, double* __restrict__ dyn) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (long)k * k) return;
+  const int j = (int)(e / k), i = (int)(e - (long)j * k);
+  double av = 0.0, bv = 0.0;
+  if (i == j) {
+    av = a[e];
+    bv = sqrt(fmax(__builtin_fma(-av, av, 1.0), 0.0));
+  }
+  dyn[e] = av;
+  dyn[(long)k * k + e] = bv;
+}
+
+__device__ __forceinline__ double noise_of(double temp, float e) {
+#pragma clang fp contract(off)
+  return temp * (double)e;
+}
+
+__device__ __forceinline__ float latent_of(double c, float off, double acc) {
+#pragma clang fp contract(off)
+  return (float)(c + (double)off + acc);
+}
+
+// One workgroup per stream; the F frames of the call one after the other.  LDS: the state w, the frame's noise e and
+// the new state.  Thread i owns coordinate i of the state (A^T and B^T are read along their rows: consecutive lanes,
+// consecutive addresses), then thread l owns latent l (R read along its rows).
+__global__ void __launch_bounds__(ST_THREADS)
+k_walk_step(const double* __restrict__ dyn, const double* __restrict__ R, const double* __restrict__ centre, int k, int L,
+            long F, const long long* __restrict__ cnt, const float* __restrict__ eps, uint64_t seed,
+            const float* __restrict__ temperature, const float* __restrict__ offset, double* __restrict__ state,
+            int* __restrict__ primed, float* __restrict__ z, float* __restrict__ out, long ldo) {
+  __shared__ double sw[WK_LMAX], se[WK_LMAX], sn[WK_LMAX];
+  const long s = blockIdx.x;
+  const int tid = threadIdx.x;
+  const double* const At = dyn;
+  const double* const Bt = dyn + (long)k * k;
+  const long long c0 = cnt[s];
+  bool pr = primed[s] != 0;
+  const double temp = (double)temperature[s];
+  for (int i = tid; i < k; i += ST_THREADS) sw[i] = state[s * k + i];
+  for (long fr = 0; fr < F; ++fr) {
+    const long row = s * F + fr;
+    for (int j = tid; j < k; j += ST_THREADS) {
+      const float e = eps ? eps[row * k + j] : normal1(seed, (uint64_t)((c0 + fr) * k + j), (uint64_t)s);
+      se[j] = noise_of(temp, e);
+    }
+    __syncthreads();   // e and w are written; the latent rows of the frame before have read w
+    for (int i = tid; i < k; i += ST_THREADS) {
+      double acc = se[i];
+      if (pr) {
+        acc = 0.0;
+        for (int j = 0; j < k; ++j) acc = __builtin_fma(At[(long)j * k + i], sw[j], acc);
+        for (int j = 0; j < k; ++j) acc = __builtin_fma(Bt[(long)j * k + i], se[j], acc);
+      }
+      sn[i] = acc;
+    }
+    __syncthreads();
+    for (int i = tid; i < k; i += ST_THREADS) sw[i] = sn[i];
+    __syncthreads();
+    pr = true;
+    for (int l = tid; l < L; l += ST_THREADS) {
+      double acc = 0.0;
+      for (int j = 0; j < k; ++j) acc = __builtin_fma(sw[j], R[(long)j * L + l], acc);
+      const float v = latent_of(centre[l], offset[s * L + l], acc);
+      z[row * L + l] = v;
+      if (out) out[row * ldo + l] = v;
+    }
+  }
+  for (int i = tid; i < k; i += ST_THREADS) state[s * k + i] = sw[i];
+  if (tid == 0) primed[s] = 1;
+}
+
+struct lag_ws {
+  long n_pairs, n_ranges, keep_bytes, bytes;
+  int nI;
+};
+
+lag_ws lag_layout(long T, long L) {
+  lag_ws w;
+  w.n_pairs = T - 1;
+  w.n_ranges = (w.n_pairs + LG_RANGE - 1) / LG_RANGE;
+  w.nI = (int)((L + LG_MT - 1) / LG_MT);
+  w.keep_bytes = up256(w.n_pairs);
+  w.bytes = w.keep_bytes + w.n_ranges * w.nI * w.nI * (long)(LG_MT * LG_MT) * (long)sizeof(double);
+  return w;
+}
+
+long fit_bytes(long k, long L) { return k * L * (long)sizeof(double); }
+
+unsigned blocks256(long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+int rv_walk_workspace(rv_mosaic_desc* d) {
+  RV_REQUIRE(d->T == 0 || (d->T >= 2 && d->T < (1L << 31)), RV_ERR_SHAPE,
+             "rv_mosaic(WALK_WORKSPACE): T=%ld must be 0 (RV_WALK_FIT only) or in [2, 2^31)", d->T);
+  RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(WALK_WORKSPACE): L=%ld outside [1, %d]", d->L, WK_LMAX);
+  RV_REQUIRE(d->k >= 0 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_WORKSPACE): k=%ld outside [0, L=%ld]", d->k, d->L);
+  long need = fit_bytes(d->k, d->L);
+  if (d->T >= 2) {
+    const long m = lag_layout(d->T, d->L).bytes;
+    need = m > need ? m : need;
+  }
+  d->ws_bytes = need;
+  return RV_OK;
+}
+
+int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream) {
+  RV_REQUIRE(d->T >= 2 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): T=%ld outside [2, 2^31)", d->T);
+  RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): L=%ld outside [1, %d]", d->L, WK_LMAX);
+  RV_REQUIRE(d->n_rows >= 1 && d->n_rows <= d->T, RV_ERR_SHAPE,
+             "rv_mosaic(PCA_LAGCOV): n_files (n_rows)=%ld outside [1, T=%ld]", d->n_rows, d->T);
+  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): x (q) is null");
+  RV_REQUIRE(d->row_start, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): row_start is null");
+  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): centre (trans) is null");
+  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): the moment (dist) is null");
+  const lag_ws w = lag_layout(d->T, d->L);
+  RV_REQUIRE(d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): ws_bytes=%ld, T=%ld rows of L=%ld need %ld",
+             d->ws_bytes, d->T, d->L, w.bytes);
+  RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): ws is null, T=%ld rows of L=%ld need %ld bytes", d->T, d->L, w.bytes);
+  const hipStream_t st = (hipStream_t)stream;
+  const int L = (int)d->L;
+  unsigned char* const keep = (unsigned char*)d->ws;
+  double* const part = (double*)(keep + w.keep_bytes);
+  hipLaunchKernelGGL(k_walk_pairs, dim3(blocks256(w.n_pairs)), dim3(256), 0, st, d->row_start, d->n_rows, w.n_pairs, keep);
+  hipLaunchKernelGGL(k_walk_lag, dim3((unsigned)w.n_ranges, (unsigned)(w.nI * w.nI)), dim3(LG_THREADS), 0, st, d->q, w.n_pairs,
+                     L, (const double*)d->trans, (const unsigned char*)keep, w.nI, part);
+  hipLaunchKernelGGL(k_walk_lag_sum, dim3((unsigned)((L + 63) / 64), (unsigned)L), dim3(64), 0, st, (const double*)part,
+                     w.n_ranges, w.nI, L, d->T, (double*)d->dist);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+int rv_walk_fit(const rv_mosaic_desc* d, void* stream) {
+  RV_REQUIRE(d->mode == RV_WALK_DYNAMICS || d->mode == RV_WALK_NOISE || d->mode == RV_WALK_DIAGONAL, RV_ERR_SHAPE,
+             "rv_mosaic(WALK_FIT): mode=%ld is none of RV_WALK_DYNAMICS, RV_WALK_NOISE, RV_WALK_DIAGONAL", d->mode);
+  RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): L=%ld outside [1, %d]", d->L, WK_LMAX);
+  RV_REQUIRE(d->k >= 1 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): k=%ld outside [1, L=%ld]", d->k, d->L);
+  RV_REQUIRE(d->out, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the result (out) is null");
+  const hipStream_t st = (hipStream_t)stream;
+  const int k = (int)d->k, L = (int)d->L;
+  const long kk = (long)k * k, kL = (long)k * L;
+  double* const o = (double*)d->out;
+  if (d->mode != RV_WALK_DYNAMICS) {
+    RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_FIT): A (dist) is null");
+    if (d->mode == RV_WALK_DIAGONAL) {
+      hipLaunchKernelGGL(k_walk_diagonal, dim3(blocks256(kk)), dim3(256), 0, st, (const double*)d->dist, k, o);
+    } else {
+      RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvectors of Q (src) are null");
+      RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues of Q (cost) are null");
+      hipLaunchKernelGGL(k_walk_noise, dim3(blocks256(kk)), dim3(256), 0, st, (const double*)d->dist, (const double*)d->src,
+                         (const double*)d->cost, k, o);
+    }
+    RV_CHECK_LAUNCH();
+    return RV_OK;
+  }
+  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_FIT): basis (dist) is null");
+  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues (cost) are null");
+  RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the lag-1 moment (src) is null");
+  const long need = fit_bytes(k, L);
+  RV_REQUIRE(d->ws_bytes >= need, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): ws_bytes=%ld, k=%ld of L=%ld need %ld", d->ws_bytes, d->k,
+             d->L, need);
+  RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(WALK_FIT): ws is null, k=%ld of L=%ld need %ld bytes", d->k, d->L, need);
+  double *const A = o, *const Q = o + kk, *const P = o + 2 * kk, *const R = P + kL, *const M = (double*)d->ws;
+  hipLaunchKernelGGL(k_walk_scale, dim3(blocks256(kL)), dim3(256), 0, st, (const double*)d->dist, (const double*)d->cost, k, L, P, R);
+  hipLaunchKernelGGL((k_walk_product<false, false>), dim3(blocks256(kL)), dim3(256), 0, st, (const double*)P,
+                     (const double*)d->src, k, L, L, M);
+  hipLaunchKernelGGL((k_walk_product<true, false>), dim3(blocks256(kk)), dim3(256), 0, st, (const double*)M, (const double*)P, k,
+                     k, L, A);
+  hipLaunchKernelGGL((k_walk_product<true, true>), dim3(blocks256(kk)), dim3(256), 0, st, (const double*)A, (const double*)A, k,
+                     k, k, Q);
+  RV_CHECK_LAUNCH();
+  return RV_OK;
+}
+
+int rv_walk_step(const rv_mosaic_desc* d, void* stream) {
+  const rv_stream_desc* sd = d->live;
+  RV_REQUIRE(sd, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the stream (live) is null");
+  RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): L=%ld outside [1, %d]", d->L, WK_LMAX);
+  RV_REQUIRE(d->L == sd->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): L=%ld, the stream's model has L=%ld", d->L, sd->L);
+  RV_REQUIRE(d->k >= 1 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): k=%ld outside [1, L=%ld]", d->k, d->L);
+  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(WALK_STEP): centre (trans) is null");
+  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_STEP): R (dist) is null");
+  RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the dynamics [A^T | B^T] (src) are null");
+  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the state (cost) is null");
+  RV_REQUIRE(d->choice, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the primed flags (choice) are null");
+  RV_REQUIRE(sd->temperature, RV_ERR_NULL, "rv_mosaic(WALK_STEP): live->temperature is null");
+  RV_REQUIRE(!d->out || d->ldo >= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): ldo=%ld holds no row of L=%ld values", d->ldo, d->L);
+  float *z = nullptr, *frames = nullptr;
+  const int rc = rv_stream_encode(sd, nullptr, &z, &frames, stream);   // the stream's own checks; launches nothing
+  if (rc) return rc;
+  hipLaunchKernelGGL(k_walk_step, dim3((unsigned)sd->n_streams), dim3(ST_THREADS), 0, (hipStream_t)stream, (const double*)d->src,
+                     (const double*)d->dist, (const double*)d->trans, (int)d->k, (int)d->L, sd->block / sd->hop,
+                     rv_stream_counters(sd), sd->eps_in, (uint64_t)sd->seed, sd->temperature, sd->offset, d->cost, d->choice, z,
+                     d->out, d->ldo);
+  RV_CHECK_LAUNCH();
+  return rv_stream_synth(sd, 1, stream);
+}
