@@ -184,8 +184,8 @@ int rv_linear_wgrad(const void* dy_bf16, long lddy, const void* x_bf16, long ldx
  *   -> mulv [Bp][2Lp] fp32 (summed, zero in padding), z bf16 [Bp][Lp],
  *      kl_partial[block] = sum over valid (b,l) of 1 + logvar - mu^2 - exp(logvar).
  * eps: explicit [B,L] fp32 when eps_in != NULL (parity runs), otherwise generated
- * on-device (Philox4x32-10 + Box-Muller, keyed by seed and *step_counter) and
- * written to eps_out [B,L].  n_kl_partials = Bp*Lp/1024. */
+ * on-device (Philox4x32-10 + Box-Muller, keyed by seed and *step_counter: the counter layout is stated at rv_randn) and
+ * written to eps_out [B,L].  n_kl_partials = Bp*Lp/1024.  Lp is 64, 128 or 256 (rv_pad_dims), else RV_ERR_SHAPE. */
 int rv_reparam_fwd(const float* mulv_slabs, int splits, long Bp, long Lp, long B, long L,
                    const float* eps_in, float* eps_out, unsigned long long seed,
                    const long long* step_counter, float* mulv, void* z_bf16, float* kl_partial,
@@ -270,8 +270,8 @@ int rv_heads_bwd(const void* dmulv_bf16, const void* wh_bf16, long ldw, const vo
  * dbh_partial [Bp/16][2Lp] (bias grads of fc21|fc22).  One block also finishes the
  * loss: loss_out[0] = sum(mse_partial)/(B S) + kl_beta*(-0.5*sum(kl_partial)/(B L)),
  * loss_out[1] = mse term, loss_out[2] = KL term (pass NULL partials to skip).  When
- * step_counter != NULL and ring > 0, loss_out is a ring of [ring][4] floats and the
- * slot written is (*step_counter - 1) % ring, so graph replays log every step. */
+ * step_counter != NULL and ring > 0, loss_out is a ring of [ring][4] floats and the slot written is (*step_counter - 1)
+ * mod ring in [0, ring) (ring - 1 for a counter of 0), so graph replays log every step.  Lp as for rv_reparam_fwd. */
 /* Gradients that arrive from outside are added in (exact [B, L] fp32, either may be NULL):
  * dmu += dmu_ext, dlv += dlv_ext -- what autograd hands the backward of reparameterize when mu / logvar also feed
  * a loss term directly (the KL half of loss_function, model.py:45).  Pass kl_beta = 0 when the KL gradient is
@@ -800,7 +800,30 @@ int rv_stream_process(const rv_stream_desc* d, void* stream);
 /* Zero the state of stream `which` (-1: every stream) of the workspace laid out for d's extents. */
 int rv_stream_reset(const rv_stream_desc* d, long which, void* stream);
 
-/* Standard normal draws (replaces torch.randn_like, model.py:25). */
+/* Standard normal draws (replaces torch.randn_like, model.py:25).
+ *
+ * THE RANDOM NUMBERS OF THIS LIBRARY, in one place (csrc/philox.h; tests/rng_oracle.py is the same contract in numpy and
+ * tests/test_rng_gpu.py holds every consumer to it bit for bit):
+ *   words    = Philox4x32-10(key, counter), key = (seed & m, seed >> 32), counter = (lo & m, lo >> 32, hi & m, hi >> 32)
+ *              for a 64-bit pair (lo, hi), m = 2^32 - 1
+ *   uniforms = min((float(word) + 0.5f) * 2^-32, 0.99999994f) in fp32, one per word: u_x, u_y, u_z, u_w in [2^-33, 1 - 2^-24]
+ *   normals  = lane 0: r0 cos a0, lane 1: r0 sin a0, lane 2: r1 cos a1, lane 3: r1 sin a1 with r0 = sqrt(-2 ln u_x),
+ *              a0 = 2 pi u_y, r1 = sqrt(-2 ln u_z), a1 = 2 pi u_w (Box-Muller; radii from 3.45e-4 to 6.8)
+ * Two forms of the last step draw the same values from the same words: the accurate one (logf, sincospif; within 7.1e-7 of
+ * the float64 value as measured) and the fast one of the training step (hardware log / sin / cos; within 1.8e-6).  A value depends on
+ * (seed, lo, hi, lane) alone -- never on the launch shape, the kernel form or the batch beside it.  Who uses which counter:
+ *   accurate form, element i of a flat tensor = lane i & 3 of counter (lo = i >> 2, hi = offset):
+ *     rv_randn(n, seed, offset)          i in [0, n)
+ *     rv_reparameterize(seed, offset)    i in [0, n): eps_out is rv_randn's output
+ *     rv_latent_mix(seed, offset)        i = (row0 + r) * L + l for row r of the call
+ *     rv_stream_process (seed)           i = f * L + l, offset = the stream's number s, f the stream's absolute frame number
+ *                                        (counted from its last reset): stream s draws rv_randn(seed, s) laid out [frame][L]
+ *     RV_WALK_STEP (seed)                i = f * k + j, offset = s likewise
+ *   fast form, element (b, l) of the [B, L] eps grid = lane l & 3 of counter (lo = b * (Lp / 4) + l / 4, hi = *step_counter;
+ *   0 when step_counter is NULL), Lp the padded latent width:
+ *     rv_reparam_fwd, rv_heads_reparam_fwd, rv_latent_fwd in each of its forms, and through them rv_plan_step: the cast at
+ *     the head of a step increments *step_counter first, so step t of a run (1-based) draws with hi = t, eagerly and in
+ *     every replay of a captured step. */
 int rv_randn(float* out, long n, unsigned long long seed, unsigned long long offset,
              void* stream);
 

@@ -349,7 +349,7 @@ k_reparam_bwd(const float* __restrict__ dz_slabs, int splits, long Bp, long Lp, 
       if (tid == 0) {
         const float mse = m / ((float)B * (float)S);
         const float kld = -0.5f * k * inv_nk_;
-        if (step_counter && ring > 0) loss_out += 4 * ((*step_counter - 1) % ring);
+        if (step_counter && ring > 0) loss_out += 4 * (((*step_counter - 1) % ring + ring) % ring);   // (slot ring - 1 for a counter of 0)
         loss_out[0] = mse + kl_beta * kld;
         loss_out[1] = mse;
         loss_out[2] = kld;
@@ -762,6 +762,7 @@ int rv_reparam_fwd(const float* slabs, int splits, long Bp, long Lp, long B, lon
                    void* stream) {
   RV_REQUIRE(slabs && mulv && z && kl_partial, RV_ERR_NULL, "rv_reparam_fwd: null pointer");
   RV_REQUIRE(eps_in || eps_out, RV_ERR_NULL, "rv_reparam_fwd: need eps_in or eps_out");
+  RV_REQUIRE(Lp == 64 || Lp == 128 || Lp == 256, RV_ERR_SHAPE, "rv_reparam_fwd: the padded latent width must be 64, 128 or 256 (got %ld)", Lp);
   RV_REQUIRE(splits >= 1 && B <= Bp && L <= Lp && (Bp * Lp) % 1024 == 0 && Bp * Lp < 0x7fffffffL, RV_ERR_SHAPE, "rv_reparam_fwd: bad extents");
   hipLaunchKernelGGL(k_reparam_fwd, dim3((unsigned)(Bp * Lp / 1024)), dim3(256), 0, (hipStream_t)stream,
                      slabs, splits, Bp, Lp, B, L, eps_in, eps_out, (uint64_t)seed, step_counter, mulv,
@@ -776,8 +777,8 @@ int rv_reparam_bwd(const float* dz_slabs, int splits, long Bp, long Lp, long B, 
                        const float* kl_partial, int n_kl, float* loss_out, const long long* step_counter, int ring,
                        void* stream) {
   RV_REQUIRE(dz_slabs && mulv && eps && dmulv, RV_ERR_NULL, "rv_reparam_bwd: null pointer");
-  RV_REQUIRE(splits >= 1 && B <= Bp && L <= Lp && Bp % RB_ROWS == 0 && 256 % Lp == 0, RV_ERR_SHAPE,
-             "rv_reparam_bwd: bad extents (Lp must divide 256)");
+  RV_REQUIRE(Lp == 64 || Lp == 128 || Lp == 256, RV_ERR_SHAPE, "rv_reparam_bwd: the padded latent width must be 64, 128 or 256 (got %ld)", Lp);
+  RV_REQUIRE(splits >= 1 && B <= Bp && L <= Lp && Bp % RB_ROWS == 0, RV_ERR_SHAPE, "rv_reparam_bwd: bad extents");
   hipLaunchKernelGGL(k_reparam_bwd, dim3((unsigned)(Bp / RB_ROWS) + 1), dim3(256), 0,
                      (hipStream_t)stream, dz_slabs, splits, Bp, Lp, B, L, S, mulv, eps, kl_beta,
                      (bf16_t*)dmulv, dbh_partial, mse_partial, n_mse, kl_partial, n_kl, loss_out,

@@ -350,7 +350,7 @@ k_latent_bwd(const bf16_t* __restrict__ dP3, const long lddp, const bf16_t* __re
       if (tid == 0) {
         const float mse = m / ((float)B * (float)S);
         const float kld = -0.5f * k * inv_nk;
-        if (step_counter && ring_n > 0) loss_out += 4 * ((*step_counter - 1) % ring_n);
+        if (step_counter && ring_n > 0) loss_out += 4 * (((*step_counter - 1) % ring_n + ring_n) % ring_n);
         loss_out[0] = mse + kl_beta * kld;
         loss_out[1] = mse;
         loss_out[2] = kld;
@@ -833,7 +833,7 @@ k_dz_reparam_gemm(const GemmArgs dz, const GemmArgs w3grad, const int n_dz, cons
       const float mse = m / ((float)B * (float)S);
       const float inv_nk = 1.0f / ((float)B * (float)L);
       const float kld = -0.5f * k * inv_nk;
-      if (step_counter && ring_n > 0) loss_out += 4 * ((*step_counter - 1) % ring_n);
+      if (step_counter && ring_n > 0) loss_out += 4 * (((*step_counter - 1) % ring_n + ring_n) % ring_n);
       loss_out[0] = mse + kl_beta * kld;
       loss_out[1] = mse;
       loss_out[2] = kld;

@@ -163,6 +163,25 @@ static int launcher_checks() {
                                            n, NULL), RV_ERR_SHAPE, msg);
   }
   fails += ld_checks();
+  // the reparameterisation launchers serve the padded latent widths rv_pad_dims produces (64, 128, 256) and nothing else:
+  // any other width is RV_ERR_SHAPE before the launch (1 and 2 made the kernels divide by Lp / 4 == 0; 4 .. 32 and 512 passed
+  // the old `Bp * Lp % 1024 == 0` / `256 % Lp == 0` rules)
+  float* f = (float*)buf;
+  const long long* ctr = (const long long*)buf;
+  const long bad_lp[] = {1, 2, 3, 4, 8, 16, 32, 96, 192, 512, 0, -64};
+  for (long lp : bad_lp) {
+    const long L = lp < 1 ? 1 : (lp < 3 ? lp : 3);
+    fails += EXPECT(rv_reparam_fwd(f, 1, 1024, lp, 100, L, NULL, f, 1, ctr, f, buf, f, NULL), RV_ERR_SHAPE,
+                    "rv_reparam_fwd: the padded latent width must be 64, 128 or 256");
+    fails += EXPECT(rv_reparam_bwd(f, 1, 1024, lp, 100, L, 512, f, f, 1e-4f, NULL, NULL, buf, f, NULL, 0, NULL, 0, NULL, ctr, 4, NULL),
+                    RV_ERR_SHAPE, "rv_reparam_bwd: the padded latent width must be 64, 128 or 256");
+  }
+  // (the other extent rules still hold at a good width)
+  fails += EXPECT(rv_reparam_fwd(f, 0, 1024, 64, 100, 3, NULL, f, 1, ctr, f, buf, f, NULL), RV_ERR_SHAPE, "rv_reparam_fwd: bad extents");
+  fails += EXPECT(rv_reparam_fwd(f, 1, 1024, 64, 100, 65, NULL, f, 1, ctr, f, buf, f, NULL), RV_ERR_SHAPE, "rv_reparam_fwd: bad extents");
+  fails += EXPECT(rv_reparam_fwd(f, 1, 1000, 64, 100, 3, NULL, f, 1, ctr, f, buf, f, NULL), RV_ERR_SHAPE, "rv_reparam_fwd: bad extents");
+  fails += EXPECT(rv_reparam_bwd(f, 1, 1000, 64, 100, 3, 512, f, f, 1e-4f, NULL, NULL, buf, f, NULL, 0, NULL, 0, NULL, ctr, 4, NULL),
+                  RV_ERR_SHAPE, "rv_reparam_bwd: bad extents");
   return fails;
 }
 

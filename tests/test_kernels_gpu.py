@@ -338,17 +338,59 @@ def _lp_of(Lt):
     return 64 if Lt <= 64 else 128 if Lt <= 128 else 256
 
 
-@pytest.mark.parametrize("B,Lt,H", [(100, 3, 512), (4096, 64, 2048), (300, 40, 900), (200, 64, 1536),
-                                    (4096, 256, 2048), (300, 100, 900), (200, 200, 640), (1000, 129, 1024),
-                                    (16600, 256, 512), (33000, 100, 256), (8300, 64, 512)],   # large batches: 256-row tiles
-                         ids=lambda v: str(v))
-def test_latent_fwd_one_launch_equals_three(L, B, Lt, H):
+def _latent_bwd_tile_rows(L, Bp, Hp, Lt):
+    """What csrc/latent.hip's rv_latent_bwd_tile_rows(Bp, Hp, Lp) says for the shape -- 16: rv_latent_rowlocal, the row-local
+    kernels serve both directions; 64 / 256: the GEMM forms and their dz tile rows -- read off the head biases' descriptors of a
+    host-only plan (one non-zero partial row per that many batch rows; tests/test_host_cpu.py test_large_batch_plan_rules)."""
+    from rawaudiovae_kelsey_amd import _lib
+    plan = C.c_void_p()
+    L.rv_plan_create(C.byref(plan), Bp, 1024, Hp, Lt)
+    base = 0x10000000
+    bufs = _lib.PlanBuffers(param=base, exp_avg=base + 0x4000000, exp_avg_sq=base + 0x8000000, grad=base + 0xc000000,
+                            workspace=base + 0x10000000, step_counter=base + 0x100, loss_ring=base + 0x1000, ring=4)
+    L.rv_plan_bind(plan, C.byref(bufs))
+    arr = (_lib.ParamDesc * 10)()
+    L.rv_plan_descs(plan, arr, 0)
+    rows = Bp // arr[3].grad_splits
+    L.rv_plan_destroy(plan)
+    return rows
+
+
+def _latent_cases(old, new):
+    """Today's cases under today's ids (the padded hidden width is H rounded up to 512), then the added ones: (case, padded
+    hidden width or None, id suffix)."""
+    return ([pytest.param(*c, None, id="-".join(str(v) for v in c)) for c in old] +
+            [pytest.param(*c, hp, id="-".join(str(v) for v in c) + tag) for c, hp, tag in new])
+
+
+# Forms of rv_latent_fwd the cases above the line never launch, and the dz tile rows rv_latent_bwd_tile_rows must report for them
+# (checked in the test: a later change of the thresholds cannot silently move a case back onto a covered form):
+#   (65700, 64, 256)      Bp = 65792 = 257 * 256 > 65536 at Lp = 64: k_heads_reparam_gemm_big, the 256 x 128 EPI_REPARAM tile
+#                         (one KL partial per 16 slots); its backward is the 64-row GEMM form
+#   (300, 40, 600) Hp 640 Lp = 64 with a padded hidden width that is no multiple of 512: not row-local, k_heads_reparam_gemm on
+#                         64 x 128 tiles at a small batch
+LATENT_FWD_NEW = [((65700, 64, 256), None, ""), ((300, 40, 600), 640, "-hp640")]
+LATENT_NEW_ROWS = {(65700, 64, 256): 64, (300, 40, 600): 64, (8300, 64, 512): 64}
+
+
+@pytest.mark.parametrize("B,Lt,H,hp", _latent_cases(
+    [(100, 3, 512), (4096, 64, 2048), (300, 40, 900), (200, 64, 1536),
+     (4096, 256, 2048), (300, 100, 900), (200, 200, 640), (1000, 129, 1024),
+     (16600, 256, 512), (33000, 100, 256), (8300, 64, 512)],   # large batches: 256-row tiles
+    LATENT_FWD_NEW))
+def test_latent_fwd_one_launch_equals_three(L, B, Lt, H, hp):
     """rv_latent_fwd (heads GEMM + reparam + KL partials + fc3, model.py:21-29: one row-local launch at a padded latent
     width of 64, a GEMM with the reparameterisation in its epilogue + fc3's GEMM at 128 / 256 -- the reference's own
     latent_dim = 256, default.ini:18) against the route it replaces (rv_heads_reparam_fwd + rv_linear_fwd) and against
     numpy, on the same bf16 operands and eps."""
     rng = np.random.default_rng(9)
-    Bp, Lp, Hp = -(-B // 128) * 128, _lp_of(Lt), -(-H // 512) * 512
+    Bp, Lp, Hp = -(-B // 128) * 128, _lp_of(Lt), hp or -(-H // 512) * 512
+    rows = _latent_bwd_tile_rows(L, Bp, Hp, Lt)
+    rowlocal = rows == 16
+    if hp or (B, Lt, H) in [c for c, _, _ in LATENT_FWD_NEW]:
+        assert rows == LATENT_NEW_ROWS[(B, Lt, H)] and not rowlocal
+    else:
+        assert rowlocal == (Lp == 64 and Bp <= 8192)          # (today's cases: Hp a multiple of 512 up to 2048)
     h = np.zeros((Bp, Hp), np.float32); h[:B, :H] = np.maximum(rand_bf16(rng, (B, H), 0.5), 0)
     wh = np.zeros((2 * Lp, Hp), np.float32)
     wh[:Lt, :H] = rand_bf16(rng, (Lt, H), 0.05); wh[Lp:Lp + Lt, :H] = rand_bf16(rng, (Lt, H), 0.05)
@@ -386,10 +428,13 @@ def test_latent_fwd_one_launch_equals_three(L, B, Lt, H):
     np.testing.assert_allclose(za, zb, rtol=1e-2, atol=1e-6)
     kl_ref = float(np.sum(1 + lv - mu ** 2 - np.exp(lv)))
     assert abs(float(kl1.double().sum()) - kl_ref) <= 1e-5 * abs(kl_ref) + 1e-4
-    if Lp == 64 and Bp <= 8192:   # (the GEMM forms keep one partial per tile and zeros in the slots beside it)
+    if rowlocal:   # (the GEMM forms keep one partial per tile and zeros in the slots beside it)
         np.testing.assert_allclose(kl1.cpu().numpy(), kl3.cpu().numpy(), rtol=1e-4, atol=1e-4)
     else:
         assert not kl1.cpu().numpy().reshape(-1, 4)[:, 1:].any()   # (the total was checked against float64 above)
+    if (B, Lt, H) == (65700, 64, 256):   # the 256 x 128 tile ran: one partial per 16 slots, every tile holds rows of the batch
+        k16 = kl1.cpu().numpy().reshape(-1, 16)
+        assert k16[:, 0].all() and not k16[:, 1:].any()
     # fc3 on the kernel's own z (bf16) against float64: only the fp32 accumulation and the output rounding differ
     h3ref = np.maximum(za[:B].astype(np.float64) @ w3.astype(np.float64).T + b3, 0)
     np.testing.assert_allclose(h31.float().cpu().numpy()[:B], h3ref, rtol=1e-2, atol=1e-3)
@@ -414,17 +459,33 @@ def test_latent_fwd_one_launch_equals_three(L, B, Lt, H):
                         h31.data_ptr(), Hp, sp())
 
 
-@pytest.mark.parametrize("B,Lt,H,ext", [(100, 3, 512, False), (4096, 64, 2048, False), (300, 40, 900, True), (200, 64, 1536, True),
-                                        (4096, 256, 2048, False), (300, 100, 900, True), (200, 200, 640, True), (1000, 129, 1024, False),
-                                        # large batches: dz and dW3 on 256 x 256 ping-pong tiles at Lp = 256, dz on 256 x 128 at 128
-                                        (16600, 256, 512, True), (33000, 100, 256, False)])
-def test_latent_bwd_one_launch_equals_two(L, B, Lt, H, ext):
+# The GEMM form of rv_latent_bwd at a padded latent width of 64 (k_dz_reparam_gemm<0>: 64 x 64 dz tiles with EPI_REPARAM_BWD, dW3 on
+# the 128 x 64 tiles behind `w3grad.N_valid < 128`; every Lp = 64 case above the line is row-local):
+#   (8300, 64, 512)       Bp = 8320 > 8192, 130 dz tiles
+#   (65700, 64, 256)      Bp = 65792: 1028 dz tiles, still 64 rows each (256-row dz tiles start at Lp = 128)
+#   (300, 40, 600) Hp 640 a padded hidden width that is no multiple of 512, at a small batch
+LATENT_BWD_NEW = [((8300, 64, 512, True), None, ""), ((65700, 64, 256, False), None, ""), ((300, 40, 600, True), 640, "-hp640")]
+
+
+@pytest.mark.parametrize("B,Lt,H,ext,hp", _latent_cases(
+    [(100, 3, 512, False), (4096, 64, 2048, False), (300, 40, 900, True), (200, 64, 1536, True),
+     (4096, 256, 2048, False), (300, 100, 900, True), (200, 200, 640, True), (1000, 129, 1024, False),
+     # large batches: dz and dW3 on 256 x 256 ping-pong tiles at Lp = 256, dz on 256 x 128 at 128
+     (16600, 256, 512, True), (33000, 100, 256, False)],
+    LATENT_BWD_NEW))
+def test_latent_bwd_one_launch_equals_two(L, B, Lt, H, ext, hp):
     """rv_latent_bwd (dz = dP3 W3 over the full contraction + the reparameterisation / KL backward + the loss scalar
     + fc3's weight gradient on extra workgroups, one launch) against the route it replaces (rv_linear_dgrad into fp32 split-K slabs + rv_reparam_bwd) and against
     float64 numpy, on the same bf16 operands.  Stated bound: dz is a 512..2048-term bf16-product sum accumulated in
     fp32 in another order -> 1e-5 relative to the row's term scale; dmulv is rounded to bf16 once (<= 1 ulp apart)."""
     rng = np.random.default_rng(19)
-    Bp, Lp, Hp, S = -(-B // 128) * 128, _lp_of(Lt), -(-H // 512) * 512, 512
+    Bp, Lp, Hp, S = -(-B // 128) * 128, _lp_of(Lt), hp or -(-H // 512) * 512, 512
+    rows = _latent_bwd_tile_rows(L, Bp, Hp, Lt)
+    rowlocal = rows == 16
+    if (B, Lt, H, ext) in [c for c, _, _ in LATENT_BWD_NEW]:
+        assert rows == LATENT_NEW_ROWS[(B, Lt, H)] and not rowlocal and Lp == 64
+    else:
+        assert rowlocal == (Lp == 64)                          # (today's cases: Lp = 64 is row-local, Lp > 64 a GEMM form)
     dp3 = np.zeros((Bp, Hp), np.float32); dp3[:B, :H] = rand_bf16(rng, (B, H), 1e-3)
     w3 = np.zeros((Hp, Lp), np.float32); w3[:H, :Lt] = rand_bf16(rng, (H, Lt), 0.2)
     mulv = np.zeros((Bp, 2 * Lp), np.float32)
@@ -452,7 +513,7 @@ def test_latent_bwd_one_launch_equals_two(L, B, Lt, H, ext):
                     P(xmd), P(xvd), dm1.data_ptr(), db1.data_ptr(), msed.data_ptr(), n_mse, kld.data_ptr(), n_kl,
                     loss1.data_ptr(), ctr.data_ptr(), 4, zd.data_ptr(), Lp, dw3a.data_ptr(), Lp, w3s, sp())
     dm2, db2, loss2 = outs()
-    splits = 4
+    splits = 4 if (Hp // 64) % 4 == 0 else 2   # (split-K divides the K tiles: Hp = 640 has ten)
     slabs = torch.empty(splits, Bp, Lp, device="cuda")
     L.rv_linear_dgrad(dpd.data_ptr(), Hp, w3d.data_ptr(), Lp, Bp, Lp, Hp, None, 0, None, 0, None, slabs.data_ptr(), Lp, splits, sp())
     L.rv_reparam_bwd(slabs.data_ptr(), splits, Bp, Lp, B, Lt, S, mvd.data_ptr(), ed.data_ptr(), kl_beta, P(xmd), P(xvd),
@@ -478,8 +539,9 @@ def test_latent_bwd_one_launch_equals_two(L, B, Lt, H, ext):
     ref_db = np.zeros((Bp, 2 * Lp)); ref_db[:B, :Lt] = dmu; ref_db[:B, Lp:Lp + Lt] = dlv
     ref_db = ref_db.reshape(Bp // 16, 16, 2 * Lp).sum(1)
     d1, d2 = db1.cpu().numpy(), db2.cpu().numpy()
-    if Lp > 64:   # the GEMM form: one partial row per 64-row tile in row 4 t of the table, zeros in rows 4 t + 1 .. + 3
-        g = 16 if (Bp // 64) * (Lp // 64) > 1024 and Bp % 256 == 0 else 4   # (large batches: 256-row tiles, row 16 t)
+    if not rowlocal:   # the GEMM form: one partial row per 64-row tile in row 4 t of the table, zeros in rows 4 t + 1 .. + 3
+        g = 16 if Lp > 64 and (Bp // 64) * (Lp // 64) > 1024 and Bp % 256 == 0 else 4   # (large batches: 256-row tiles, row 16 t)
+        assert rows == 16 * g
         pad = np.zeros((-(-Bp // (16 * g)) * g, 2 * Lp))
         pad[:Bp // 16] = d1
         assert not pad.reshape(-1, g, 2 * Lp)[:, 1:].any()
