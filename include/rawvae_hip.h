@@ -730,6 +730,56 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_WALK_DIAGONAL 2
 #define RV_LIVE_GRAINS 0
 #define RV_LIVE_DECODE 1
+/* Latent alignment (csrc/align.hip, rawaudiovae_kelsey_amd/align.py): a monotone alignment of two
+ * latent trajectories by dynamic time warping, over the whole matrix or a band around the straight line.  The family's
+ * conventions: the descriptor gains no field (the roles are spelled by _lib.align_fields), fp64 values travel in float*
+ * fields, no op syncs or reads a device pointer on the host, each may run under capture, and each returns an RV_ERR_*
+ * whose message names the field before anything is launched: T, N, L, width, mode, lam, a null q / c / dist / ws / slot /
+ * choice / cost / idx, ws_bytes too small.
+ * Notation: a = q [Ta, L] fp32 with Ta = T; b = c [Tb, L] fp32 with Tb = N; rows contiguous; 1 <= L <= 4096; r = width >= 0;
+ * p = lam, the step penalty, finite and >= 0.
+ * The band.  r = 0: the whole matrix, W = Tb, the band-local column of j is j.  r >= 1: centre(i) =
+ * floor(i (Tb - 1) / max(Ta - 1, 1)) in integer arithmetic; cell (i, j) is in the band iff |j - centre(i)| <= r and
+ * 0 <= j < Tb; W = 2 r + 1 and the band-local column of j is j - centre(i) + r.  The band admits a path iff
+ * ceil((Tb - 1) / (Ta - 1)) <= 2 r + 1 for Ta > 1, or Tb - 1 <= r for Ta = 1; a band that does not is RV_ERR_SHAPE naming
+ * width and the least r that would do.  Ta W < 2^31.
+ * RV_ALIGN_COST: q, c, L, T, N, width -> dist = Dm [Ta, W] fp32, Dm[i, col(j)] = D(a_i, b_j), D RV_MOSAIC_KNN's distance
+ *   bit for bit: part = fmaf(d, d, part) in ascending l within tiles of 32, tot += part per tile, from +0.  A band slot
+ *   whose j falls outside [0, Tb) is written +inf; every slot of Dm is written.  One launch over (blocks of 128 rows of
+ *   a, tiles of 64 columns of the block's band), RV_MOSAIC_KNN's register tile; no atomics; the bits depend on a, b, L and
+ *   the band only.
+ * RV_ALIGN_FORWARD: dist = Dm, T, N, width, mode = RV_ALIGN_GLOBAL or RV_ALIGN_SUBSEQUENCE (the latter requires width 0),
+ *   lam, ws.  The accumulated cost C is fp64.  The cell rule: dd = (double)Dm[i, j]; a NaN or +inf makes the cell
+ *   blocked: C = +inf, step = 3.  The candidates in this order: 0 diag: C[i-1, j-1]; 1 up: fl64(C[i-1, j] + (double)p);
+ *   2 left: fl64(C[i, j-1] + (double)p); anything outside the matrix or the band is +inf.  best = +inf, step = 3, then in
+ *   that order `if (cand < best) { best = cand; step = k; }`: ties go diag, up, left, and +inf or NaN never wins.
+ *   C[i, j] = step == 3 ? +inf : fl64(dd + best).  Start cells (C = dd, step 3): GLOBAL: (0, 0) only; SUBSEQUENCE: every
+ *   (0, j), and row 0 takes no left move.  End: GLOBAL: (Ta - 1, Tb - 1); SUBSEQUENCE: the lowest-j argmin of the finite
+ *   C[Ta - 1, .], and when out is not NULL, C[Ta - 1, .] is also written there as [Tb] fp64.  ONE workgroup of 1024
+ *   threads sweeps the anti-diagonals d = i + j in ascending order, a cell per thread (looping when a diagonal is
+ *   longer), a barrier between the diagonals; three rolling diagonals of C in LDS while no diagonal has more than 2048
+ *   cells, in ws otherwise; the step codes go to a back table [Ta, W] uint8 in ws.  One launch, no atomics, no polling.
+ * RV_ALIGN_BACKTRACK: dist = Dm, T, N, width, ws as FORWARD left it -> slot = path [Ta + Tb - 1, 2] int32, the (i, j) pairs
+ *   in ascending order, rows >= P filled with -1; choice [4] int32 = {P, j of the first pair, j of the last pair, reached
+ *   (1 / 0)}; cost [2] fp64 = {C at the end cell, the sum of (double)Dm along the path added in ascending order from +0}:
+ *   with p = 0 the two are the same bits.  Not reached (no finite end cell): P = 0, reached = 0, cost = {+inf, 0}, path all
+ *   -1, choice[1] = choice[2] = -1.  The walk is bounded by Ta + Tb - 1 steps whatever the table holds.  One launch.
+ * RV_ALIGN_WARP: slot = path, choice, T, N, mode = the timeline RV_ALIGN_ON_A, RV_ALIGN_ON_B or RV_ALIGN_ON_PATH ->
+ *   idx [n, 2] int32 = (ia, ib).  ON_A: n = Ta, ia[i] = i, ib[i] = path[m, 1] for the LOWEST m with path[m, 0] = i.  ON_B:
+ *   the mirror image, n = Tb.  ON_PATH: n = Ta + Tb - 1, the path itself, -1 beyond P.  A row the path never visits gets
+ *   (-1, -1).  Every entry of idx is written by exactly one thread.
+ * RV_ALIGN_WORKSPACE: the bytes of ws of FORWARD and BACKTRACK for (T, N, width) in d->ws_bytes; launches nothing and
+ *   touches no device.  ws is 256-byte aligned. */
+#define RV_ALIGN_COST 26
+#define RV_ALIGN_FORWARD 27
+#define RV_ALIGN_BACKTRACK 28
+#define RV_ALIGN_WARP 29
+#define RV_ALIGN_WORKSPACE 30
+#define RV_ALIGN_GLOBAL 0
+#define RV_ALIGN_SUBSEQUENCE 1
+#define RV_ALIGN_ON_A 0
+#define RV_ALIGN_ON_B 1
+#define RV_ALIGN_ON_PATH 2
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   long T, k;                     /* query / output rows, neighbours per row (KNN, GATHER_MEAN) */
@@ -758,7 +808,7 @@ typedef struct rv_mosaic_desc {
   int* choice;                   /* PATH_BACKTRACK [T] */
   double* cost;                  /* PATH_BACKTRACK [2] */
   const struct rv_stream_desc* live; /* LIVE ops: weights, block I/O, scale / offset, window, norm, stream workspace */
-  long mode;                     /* LIVE: RV_LIVE_GRAINS / RV_LIVE_DECODE */
+  long mode;                     /* LIVE: RV_LIVE_GRAINS / RV_LIVE_DECODE; ALIGN_FORWARD: the DP's mode; ALIGN_WARP: the timeline */
   const float* weight;           /* LIVE [n_streams] on the device, or NULL: the mean of the k candidates */
   long which;                    /* LIVE_RESET: the stream, -1 for all */
 } rv_mosaic_desc;

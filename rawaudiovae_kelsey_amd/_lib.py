@@ -100,6 +100,15 @@ def walk_fields(centre=None, basis=None, eigenvalues=None, moment=None, result=N
                 src=ptr(moment), out=ptr(result), choice=ptr(primed))
 
 
+def align_fields(a=None, b=None, local_costs=None, path=None, summary=None, costs=None, table=None, end_costs=None):
+    # The RV_ALIGN_* ops (include/rawvae_hip.h, "Latent alignment"): q, c = the two trajectories a [Ta, L], b [Tb, L]
+    # fp32; dist = the local costs Dm [Ta, W] fp32; slot = the path [Ta + Tb - 1, 2] int32, choice = {P, first j, last j,
+    # reached} int32, cost = the two costs fp64; idx = RV_ALIGN_WARP's table [n, 2] int32; out = the end-cost row [Tb]
+    # fp64 of a subsequence search
+    return dict(q=ptr(a), c=ptr(b), dist=ptr(local_costs), slot=ptr(path), choice=ptr(summary), cost=ptr(costs),
+                idx=ptr(table), out=ptr(end_costs))
+
+
 class CommDesc(C.Structure):
     """rv_comm_desc: everything rv_plan_step_ddp needs from the caller."""
     _fields_ = [("comm", c_void_p), ("world", c_int), ("rank", c_int), ("allreduce", c_void_p),
@@ -133,6 +142,9 @@ PCA_PROJECT, PCA_RECONSTRUCT, PCA_EDIT = 0, 1, 2   # RV_PCA_APPLY's mode
 PCA_LAGCOV, WALK_FIT, WALK_STEP, WALK_WORKSPACE = 22, 23, 24, 25   # the latent walk (rv_mosaic)
 WALK_DYNAMICS, WALK_NOISE, WALK_DIAGONAL = 0, 1, 2   # RV_WALK_FIT's mode
 LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
+ALIGN_COST, ALIGN_FORWARD, ALIGN_BACKTRACK, ALIGN_WARP, ALIGN_WORKSPACE = 26, 27, 28, 29, 30   # RV_ALIGN_* (rv_mosaic)
+ALIGN_GLOBAL, ALIGN_SUBSEQUENCE = 0, 1        # RV_ALIGN_FORWARD's mode
+ALIGN_ON_A, ALIGN_ON_B, ALIGN_ON_PATH = 0, 1, 2   # RV_ALIGN_WARP's mode (the timeline)
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

@@ -161,3 +161,11 @@ RV_INTERNAL int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_walk_fit(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_walk_step(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_walk_workspace(rv_mosaic_desc* d);
+// The alignment ops of rv_mosaic (align.hip): RV_ALIGN_COST, RV_ALIGN_FORWARD, RV_ALIGN_BACKTRACK and RV_ALIGN_WARP on the
+// fields the public header names for them -- checks first, then one launch each, no sync and no read of the device -- and
+// RV_ALIGN_WORKSPACE, which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_align_cost(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_align_forward(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_align_backtrack(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_align_warp(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_align_workspace(rv_mosaic_desc* d);

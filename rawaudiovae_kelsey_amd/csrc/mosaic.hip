@@ -1416,6 +1416,11 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       return rv_walk_step(d, stream);
     case RV_WALK_WORKSPACE:
       return rv_walk_workspace(d);
+    case RV_ALIGN_COST: return rv_align_cost(d, stream);
+    case RV_ALIGN_FORWARD: return rv_align_forward(d, stream);
+    case RV_ALIGN_BACKTRACK: return rv_align_backtrack(d, stream);
+    case RV_ALIGN_WARP: return rv_align_warp(d, stream);
+    case RV_ALIGN_WORKSPACE: return rv_align_workspace(d);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }
