@@ -42,71 +42,33 @@ class StreamDesc(C.Structure):
                    ("workspace", c_void_p)])
 
 
+def _slots(*slots):
+    """(_fields_, _anonymous_) of a struct from (names, ctype) per slot: several space-separated names make the slot an
+    anonymous union of those members, as rv_mosaic_desc declares the roles of a slot that ops read under more than one"""
+    fields, anonymous = [], []
+    for names, ctype in slots:
+        first, *others = names.split()
+        if others:
+            ctype = type("_" + first, (C.Union,), {"_fields_": [(n, ctype) for n in names.split()]})
+            first = "_" + first
+            anonymous.append(first)
+        fields.append((first, ctype))
+    return fields, anonymous
+
+
 class MosaicDesc(C.Structure):
-    """rv_mosaic_desc: one rv_mosaic call (mosaic.py); each op reads the fields the header names for it."""
-    _fields_ = [("T", c_long), ("k", c_long), ("idx", c_void_p), ("q", c_void_p), ("c", c_void_p), ("N", c_long),
-                ("L", c_long), ("splits", c_long), ("dist", c_void_p), ("ws", c_void_p), ("ws_bytes", c_long),
-                ("src", c_void_p), ("src_len", c_long), ("row_start", c_void_p), ("stride", c_long), ("n_rows", c_long),
-                ("width", c_long), ("out", c_void_p), ("ldo", c_long), ("frames", c_void_p), ("F", c_long),
-                ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long), ("next_of", c_void_p),
-                ("row0", c_long), ("rows", c_long), ("trans", c_void_p), ("lam", c_float), ("slot", c_void_p),
-                ("choice", c_void_p), ("cost", c_void_p), ("live", C.POINTER(StreamDesc)),
-                ("mode", c_long), ("weight", c_void_p), ("which", c_long)]
-
-
-# rv_mosaic_desc reuses some fields under another meaning per op.  Each builder below returns the keyword fields of one
-# such role for MosaicDesc(**fields), so that a call site names the role, not the alias.
-def fitted_fields(shift, gain):
-    # RV_GRAIN_GATHER (include/rawvae_hip.h:562-563): slot [T, k] int32 is the shift, trans [T, k] fp32 the gain
-    return dict(slot=ptr(shift), trans=ptr(gain))
-
-
-def fit_fields(room, R, gain_max, shift, gain, score):
-    # RV_GRAIN_FIT (include/rawvae_hip.h:558-560) and a live fit (529-531): next_of = room [n_rows, 2] int32 (live:
-    # live_fit_table's [3 N]), width = R, lam = gain_max; the outputs slot, trans, cost = shift, gain, score [T, kf]
-    return dict(next_of=ptr(room), width=int(R), lam=float(gain_max), cost=ptr(score), **fitted_fields(shift, gain))
-
-
-def live_fit_table(successors, room):
-    # RV_MOSAIC_LIVE with a fit (include/rawvae_hip.h:530-531) reads ONE next_of table [3 N] int32: the successors [N]
-    # (None: zeros, unread without unit selection), then room [N, 2]
-    import torch
-    if successors is None:
-        successors = torch.zeros(room.shape[0], dtype=torch.int32, device=room.device)
-    return torch.cat([successors, room.reshape(-1)]).contiguous()
-
-
-def eval_fields(mu, logvar, table=None, dynamic_range=0.0):
-    # RV_EVAL_FRAMES (include/rawvae_hip.h:576-580) and RV_EVAL_DIMS (599): q, c = mu, logvar [T, L]; weight = the
-    # twiddle table [S]; lam = the dynamic range in dB (RV_EVAL_DIMS reads neither of the last two)
-    return dict(q=ptr(mu), c=ptr(logvar), weight=ptr(table), lam=float(dynamic_range))
-
-
-def pca_fields(centre=None, basis=None, eigenvalues=None, info=None, gains=None, shifts=None):
-    # The RV_PCA_* ops (include/rawvae_hip.h, "Latent PCA"): trans carries centre [L] fp64 and dist carries basis
-    # [L, L] / [k, L] fp64; cost = the eigenvalues fp64, choice = the int32 pair {sweeps, converged} of RV_PCA_EIG, and
-    # RV_PCA_EDIT's weight, c = the gains and shifts [k] fp32
-    return dict(trans=ptr(centre), dist=ptr(basis), cost=ptr(eigenvalues), choice=ptr(info), weight=ptr(gains),
-                c=ptr(shifts))
-
-
-def walk_fields(centre=None, basis=None, eigenvalues=None, moment=None, result=None, state=None, primed=None):
-    # The latent-walk ops (include/rawvae_hip.h, "Latent walk"), on PCA's roles: trans carries centre [L] fp64, dist the
-    # fp64 matrix an op names `basis` (RV_PCA_LAGCOV: C1 out; RV_WALK_FIT: the components or A; RV_WALK_STEP: R) and cost
-    # the eigenvalues fp64 (RV_WALK_STEP: the state [n_streams, k]); src = the fp64 input matrix (C1, the eigenvectors of
-    # Q, or RV_WALK_STEP's [A^T | B^T]), out = RV_WALK_FIT's fp64 result (RV_WALK_STEP: the fp32 latent rows), choice =
-    # the primed flags [n_streams] int32
-    return dict(trans=ptr(centre), dist=ptr(basis), cost=ptr(state if eigenvalues is None else eigenvalues),
-                src=ptr(moment), out=ptr(result), choice=ptr(primed))
-
-
-def align_fields(a=None, b=None, local_costs=None, path=None, summary=None, costs=None, table=None, end_costs=None):
-    # The RV_ALIGN_* ops (include/rawvae_hip.h, "Latent alignment"): q, c = the two trajectories a [Ta, L], b [Tb, L]
-    # fp32; dist = the local costs Dm [Ta, W] fp32; slot = the path [Ta + Tb - 1, 2] int32, choice = {P, first j, last j,
-    # reached} int32, cost = the two costs fp64; idx = RV_ALIGN_WARP's table [n, 2] int32; out = the end-cost row [Tb]
-    # fp64 of a subsequence search
-    return dict(q=ptr(a), c=ptr(b), dist=ptr(local_costs), slot=ptr(path), choice=ptr(summary), cost=ptr(costs),
-                idx=ptr(table), out=ptr(end_costs))
+    """rv_mosaic_desc: one rv_mosaic call; each op reads the members the header names for it.  Every pointer is an
+    address here; the header holds each role's element type."""
+    _fields_, _anonymous_ = _slots(
+        ("T", c_long), ("k", c_long), ("idx warp_table", c_void_p), ("q mu a", c_void_p), ("c logvar b shifts", c_void_p),
+        ("N", c_long), ("L", c_long), ("splits", c_long), ("dist local_costs basis", c_void_p), ("ws", c_void_p),
+        ("ws_bytes", c_long), ("src moment", c_void_p), ("src_len", c_long), ("row_start", c_void_p), ("stride", c_long),
+        ("n_rows", c_long), ("width fit_radius band", c_long), ("out result end_costs", c_void_p), ("ldo", c_long),
+        ("frames", c_void_p), ("F", c_long), ("S", c_long), ("hop", c_long), ("window", c_void_p), ("n_out", c_long),
+        ("next_of room", c_void_p), ("row0", c_long), ("rows lag", c_long), ("trans gain centre", c_void_p),
+        ("lam gain_max dynamic_range penalty", c_float), ("slot shift path", c_void_p),
+        ("choice info primed summary", c_void_p), ("cost score eigenvalues state path_costs", c_void_p),
+        ("live", C.POINTER(StreamDesc)), ("mode", c_long), ("weight gains twiddles", c_void_p), ("which", c_long))
 
 
 class CommDesc(C.Structure):
@@ -145,6 +107,9 @@ LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 ALIGN_COST, ALIGN_FORWARD, ALIGN_BACKTRACK, ALIGN_WARP, ALIGN_WORKSPACE = 26, 27, 28, 29, 30   # RV_ALIGN_* (rv_mosaic)
 ALIGN_GLOBAL, ALIGN_SUBSEQUENCE = 0, 1        # RV_ALIGN_FORWARD's mode
 ALIGN_ON_A, ALIGN_ON_B, ALIGN_ON_PATH = 0, 1, 2   # RV_ALIGN_WARP's mode (the timeline)
+
+_HOST_ONLY_OPS = frozenset((MOSAIC_KNN_WORKSPACE, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_PATH_WORKSPACE, MOSAIC_LIVE_WORKSPACE,
+                            PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE))   # mosaic_call: they launch nothing
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {
@@ -315,6 +280,14 @@ def stream_ptr(stream=None):
         else:
             _raw_stream = lambda: torch.cuda.current_stream().cuda_stream   # noqa: E731
     return _raw_stream() or None
+
+
+def mosaic_call(op, stream=None, **fields):
+    """rv_mosaic(op) on MosaicDesc(**fields), on the raw hipStream_t `stream` (None: the current stream); returns the
+    descriptor.  The *_WORKSPACE ops touch no device and get no stream."""
+    d = MosaicDesc(**fields)
+    lib().rv_mosaic(op, C.byref(d), None if op in _HOST_ONLY_OPS else stream_ptr() if stream is None else stream)
+    return d
 
 
 def _gemm_plan(what, Mp, Np, Kp, splits_in):

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MosaicDesc, RvError, align_fields, lib, ptr, stream_ptr
+from ._lib import RvError, mosaic_call as _call, ptr
 from .codec import FrameCodec
 from .interpolate import LatentInterpolator
 from .stream import GraphReplay, window_values
@@ -52,7 +52,7 @@ def least_band(Ta, Tb):
 
 
 def check_band(Ta, Tb, band, cell_limit=CELL_LIMIT):
-    """`band` (None: the whole matrix) as the library's width for Ta x Tb frames; ValueError naming `band` when it is
+    """`band` (None: the whole matrix) as the library's band for Ta x Tb frames; ValueError naming `band` when it is
     not a non-negative integer, admits no path, or the cells exceed `cell_limit` (then naming the least band that
     admits a path and the widest that fits)."""
     Ta, Tb = int(Ta), int(Tb)
@@ -84,12 +84,6 @@ def check_penalty(penalty):
     return p
 
 
-def _call(op, stream=None, **fields):
-    d = MosaicDesc(**fields)
-    lib().rv_mosaic(op, _lib.C.byref(d), None if op == _lib.ALIGN_WORKSPACE else (stream or stream_ptr()))
-    return d
-
-
 def _rows(x, what):
     if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
         raise ValueError("%s must be a 2-D float32 device tensor, got %s" % (
@@ -103,7 +97,7 @@ def band_slots(Tb, band):
 
 def workspace_bytes(Ta, Tb, band=0):
     """Bytes of device workspace forward and backtrack share for these extents."""
-    return _call(_lib.ALIGN_WORKSPACE, T=int(Ta), N=int(Tb), width=int(band or 0)).ws_bytes
+    return _call(_lib.ALIGN_WORKSPACE, T=int(Ta), N=int(Tb), band=int(band or 0)).ws_bytes
 
 
 def workspace(Ta, Tb, band, device):
@@ -120,7 +114,7 @@ def local_costs(a, b, band=0, out=None, stream=None):
     r = check_band(Ta, Tb, band)
     if out is None:
         out = torch.empty((Ta, band_slots(Tb, r)), dtype=torch.float32, device=a.device)
-    _call(_lib.ALIGN_COST, stream, T=Ta, N=Tb, L=L, width=r, **align_fields(a, b, out))
+    _call(_lib.ALIGN_COST, stream, T=Ta, N=Tb, L=L, band=r, a=ptr(a), b=ptr(b), local_costs=ptr(out))
     return out
 
 
@@ -132,8 +126,8 @@ def forward(dm, Ta, Tb, band=0, mode="global", penalty=0.0, ws=None, end_costs=N
     r = check_band(Ta, Tb, band)
     if ws is None:
         ws = workspace(Ta, Tb, r, dm.device)
-    _call(_lib.ALIGN_FORWARD, stream, T=int(Ta), N=int(Tb), width=r, mode=MODES[mode], lam=check_penalty(penalty),
-          ws=ptr(ws), ws_bytes=ws.numel(), **align_fields(local_costs=dm, end_costs=end_costs))
+    _call(_lib.ALIGN_FORWARD, stream, T=int(Ta), N=int(Tb), band=r, mode=MODES[mode], penalty=check_penalty(penalty),
+          ws=ptr(ws), ws_bytes=ws.numel(), local_costs=ptr(dm), end_costs=ptr(end_costs))
     return ws
 
 
@@ -146,8 +140,8 @@ def backtrack(dm, Ta, Tb, band, ws, out=None, stream=None):
         out = (torch.empty((Ta + Tb - 1, 2), dtype=torch.int32, device=dev), torch.empty(4, dtype=torch.int32, device=dev),
                torch.empty(2, dtype=torch.float64, device=dev))
     path, summary, costs = out
-    _call(_lib.ALIGN_BACKTRACK, stream, T=int(Ta), N=int(Tb), width=r, ws=ptr(ws), ws_bytes=ws.numel(),
-          **align_fields(local_costs=dm, path=path, summary=summary, costs=costs))
+    _call(_lib.ALIGN_BACKTRACK, stream, T=int(Ta), N=int(Tb), band=r, ws=ptr(ws), ws_bytes=ws.numel(),
+          local_costs=ptr(dm), path=ptr(path), summary=ptr(summary), path_costs=ptr(costs))
     return path, summary, costs
 
 
@@ -159,7 +153,7 @@ def warp(path, summary, Ta, Tb, timeline="a", out=None, stream=None):
     if out is None:
         out = torch.empty((n, 2), dtype=torch.int32, device=path.device)
     _call(_lib.ALIGN_WARP, stream, T=int(Ta), N=int(Tb), mode=TIMELINES[timeline],
-          **align_fields(path=path, summary=summary, table=out))
+          path=ptr(path), summary=ptr(summary), warp_table=ptr(out))
     return out
 
 

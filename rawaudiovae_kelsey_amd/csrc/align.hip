@@ -347,15 +347,15 @@ struct align_ws {
   long maxdiag, diag, lastrow, rev, end, bytes;
 };
 
-// the shared checks of (T, N, width) and the band they make
+// the shared checks of (T, N, band) and the band they make
 int align_band(const rv_mosaic_desc* d, const char* op, band* g) {
   RV_REQUIRE(d->T >= 1 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(%s): T=%ld outside [1, 2^31)", op, d->T);
   RV_REQUIRE(d->N >= 1 && d->N < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(%s): N=%ld outside [1, 2^31)", op, d->N);
-  RV_REQUIRE(d->width >= 0 && d->width < (1L << 30), RV_ERR_SHAPE, "rv_mosaic(%s): width=%ld outside [0, 2^30)", op,
-             d->width);
+  RV_REQUIRE(d->band >= 0 && d->band < (1L << 30), RV_ERR_SHAPE, "rv_mosaic(%s): band=%ld outside [0, 2^30)", op,
+             d->band);
   g->Ta = d->T;
   g->Tb = d->N;
-  g->r = d->width;
+  g->r = d->band;
   g->W = g->r ? 2 * g->r + 1 : g->Tb;
   g->num = g->Tb - 1;
   g->den = g->Ta > 1 ? g->Ta - 1 : 1;
@@ -364,11 +364,11 @@ int align_band(const rv_mosaic_desc* d, const char* op, band* g) {
     const long slope = g->Ta > 1 ? (g->num + g->den - 1) / g->den : 0;
     const long least = g->Ta > 1 ? (slope > 3 ? slope / 2 : 1) : g->num;
     RV_REQUIRE(g->Ta > 1 ? slope <= g->W : g->num <= g->r, RV_ERR_SHAPE,
-               "rv_mosaic(%s): width=%ld: the band admits no path through T=%ld by N=%ld; the least width that does is %ld "
-               "(0: the whole matrix)", op, d->width, d->T, d->N, least);
+               "rv_mosaic(%s): band=%ld: the band admits no path through T=%ld by N=%ld; the least band that does is %ld "
+               "(0: the whole matrix)", op, d->band, d->T, d->N, least);
   }
-  RV_REQUIRE(g->Ta * g->W < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(%s): T=%ld rows of %ld band slots (width=%ld) reach 2^31",
-             op, d->T, g->W, d->width);
+  RV_REQUIRE(g->Ta * g->W < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(%s): T=%ld rows of %ld band slots (band=%ld) reach 2^31",
+             op, d->T, g->W, d->band);
   return RV_OK;
 }
 
@@ -385,10 +385,10 @@ align_ws align_layout(const band& g) {
 }
 
 int align_ws_check(const rv_mosaic_desc* d, const char* op, const align_ws& w) {
-  RV_REQUIRE(d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(%s): ws_bytes=%ld, T=%ld by N=%ld at width=%ld need %ld", op,
-             d->ws_bytes, d->T, d->N, d->width, w.bytes);
-  RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(%s): ws is null, T=%ld by N=%ld at width=%ld need %ld bytes", op, d->T, d->N,
-             d->width, w.bytes);
+  RV_REQUIRE(d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(%s): ws_bytes=%ld, T=%ld by N=%ld at band=%ld need %ld", op,
+             d->ws_bytes, d->T, d->N, d->band, w.bytes);
+  RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(%s): ws is null, T=%ld by N=%ld at band=%ld need %ld bytes", op, d->T, d->N,
+             d->band, w.bytes);
   RV_REQUIRE(((unsigned long)d->ws & 255) == 0, RV_ERR_SHAPE, "rv_mosaic(%s): ws is not 256-byte aligned", op);
   return RV_OK;
 }
@@ -408,16 +408,16 @@ int rv_align_cost(const rv_mosaic_desc* d, void* stream) {
   const int rc = align_band(d, "ALIGN_COST", &g);
   if (rc) return rc;
   RV_REQUIRE(d->L >= 1 && d->L <= AL_LMAX, RV_ERR_SHAPE, "rv_mosaic(ALIGN_COST): L=%ld outside [1, %d]", d->L, AL_LMAX);
-  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): a (q) is null");
-  RV_REQUIRE(d->c, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): b (c) is null");
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): the local costs (dist) are null");
+  RV_REQUIRE(d->a, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): a is null");
+  RV_REQUIRE(d->b, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): b is null");
+  RV_REQUIRE(d->local_costs, RV_ERR_NULL, "rv_mosaic(ALIGN_COST): local_costs is null");
   // column tiles of the widest row block: BR - 1 rows move the centre by at most floor((BR - 1) num / den) + 1
   const long span = g.r ? (BR - 1) * g.num / g.den + 1 + g.W : g.Tb;
   const long nt = (span + BN - 1) / BN, nrb = (g.Ta + BR - 1) / BR;
-  RV_REQUIRE(nrb * nt < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(ALIGN_COST): T=%ld by N=%ld at width=%ld make %ld tiles, 2^31 or more",
-             d->T, d->N, d->width, nrb * nt);
-  hipLaunchKernelGGL(k_align_cost, dim3((unsigned)(nrb * nt)), dim3(256), 0, (hipStream_t)stream, d->q, d->c, d->L, g, nt,
-                     d->dist);
+  RV_REQUIRE(nrb * nt < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(ALIGN_COST): T=%ld by N=%ld at band=%ld make %ld tiles, 2^31 or more",
+             d->T, d->N, d->band, nrb * nt);
+  hipLaunchKernelGGL(k_align_cost, dim3((unsigned)(nrb * nt)), dim3(256), 0, (hipStream_t)stream, d->a, d->b, d->L, g, nt,
+                     d->local_costs);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -428,23 +428,23 @@ int rv_align_forward(const rv_mosaic_desc* d, void* stream) {
   if (rc) return rc;
   RV_REQUIRE(d->mode == RV_ALIGN_GLOBAL || d->mode == RV_ALIGN_SUBSEQUENCE, RV_ERR_SHAPE,
              "rv_mosaic(ALIGN_FORWARD): mode=%ld is neither RV_ALIGN_GLOBAL nor RV_ALIGN_SUBSEQUENCE", d->mode);
-  RV_REQUIRE(d->mode == RV_ALIGN_GLOBAL || d->width == 0, RV_ERR_SHAPE,
-             "rv_mosaic(ALIGN_FORWARD): width=%ld: RV_ALIGN_SUBSEQUENCE (mode) runs on the whole matrix, width 0", d->width);
-  RV_REQUIRE(d->lam >= 0.f && d->lam < INFINITY, RV_ERR_SHAPE,
-             "rv_mosaic(ALIGN_FORWARD): the step penalty lam=%g must be finite and not negative", (double)d->lam);
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(ALIGN_FORWARD): the local costs (dist) are null");
+  RV_REQUIRE(d->mode == RV_ALIGN_GLOBAL || d->band == 0, RV_ERR_SHAPE,
+             "rv_mosaic(ALIGN_FORWARD): band=%ld: RV_ALIGN_SUBSEQUENCE (mode) runs on the whole matrix, band 0", d->band);
+  RV_REQUIRE(d->penalty >= 0.f && d->penalty < INFINITY, RV_ERR_SHAPE,
+             "rv_mosaic(ALIGN_FORWARD): penalty=%g must be finite and not negative", (double)d->penalty);
+  RV_REQUIRE(d->local_costs, RV_ERR_NULL, "rv_mosaic(ALIGN_FORWARD): local_costs is null");
   const align_ws w = align_layout(g);
   const int wrc = align_ws_check(d, "ALIGN_FORWARD", w);
   if (wrc) return wrc;
   char* const ws = (char*)d->ws;
   const int subseq = d->mode == RV_ALIGN_SUBSEQUENCE;
   if (w.maxdiag <= FW_DIAG_LDS)
-    hipLaunchKernelGGL(k_align_forward<true>, dim3(1), dim3(FW_THREADS), 0, (hipStream_t)stream, (const float*)d->dist, g, subseq,
-                       (double)d->lam, (double*)nullptr, (unsigned char*)ws, (double*)(ws + w.lastrow), (double*)d->out,
+    hipLaunchKernelGGL(k_align_forward<true>, dim3(1), dim3(FW_THREADS), 0, (hipStream_t)stream, d->local_costs, g, subseq,
+                       (double)d->penalty, (double*)nullptr, (unsigned char*)ws, (double*)(ws + w.lastrow), d->end_costs,
                        (end_rec*)(ws + w.end));
   else
-    hipLaunchKernelGGL(k_align_forward<false>, dim3(1), dim3(FW_THREADS), 0, (hipStream_t)stream, (const float*)d->dist, g, subseq,
-                       (double)d->lam, (double*)(ws + w.diag), (unsigned char*)ws, (double*)(ws + w.lastrow), (double*)d->out,
+    hipLaunchKernelGGL(k_align_forward<false>, dim3(1), dim3(FW_THREADS), 0, (hipStream_t)stream, d->local_costs, g, subseq,
+                       (double)d->penalty, (double*)(ws + w.diag), (unsigned char*)ws, (double*)(ws + w.lastrow), d->end_costs,
                        (end_rec*)(ws + w.end));
   RV_CHECK_LAUNCH();
   return RV_OK;
@@ -454,16 +454,17 @@ int rv_align_backtrack(const rv_mosaic_desc* d, void* stream) {
   band g;
   const int rc = align_band(d, "ALIGN_BACKTRACK", &g);
   if (rc) return rc;
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the local costs (dist) are null");
-  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the path (slot) is null");
-  RV_REQUIRE(d->choice, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the summary (choice) is null");
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the two costs (cost) are null");
+  RV_REQUIRE(d->local_costs, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): local_costs is null");
+  RV_REQUIRE(d->path, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the path is null");
+  RV_REQUIRE(d->summary, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): the summary is null");
+  RV_REQUIRE(d->path_costs, RV_ERR_NULL, "rv_mosaic(ALIGN_BACKTRACK): path_costs is null");
   const align_ws w = align_layout(g);
   const int wrc = align_ws_check(d, "ALIGN_BACKTRACK", w);
   if (wrc) return wrc;
   char* const ws = (char*)d->ws;
-  hipLaunchKernelGGL(k_align_backtrack, dim3(1), dim3(BT_THREADS), 0, (hipStream_t)stream, (const float*)d->dist, g,
-                     (const unsigned char*)ws, (const end_rec*)(ws + w.end), (int*)(ws + w.rev), d->slot, d->choice, d->cost);
+  hipLaunchKernelGGL(k_align_backtrack, dim3(1), dim3(BT_THREADS), 0, (hipStream_t)stream, d->local_costs, g,
+                     (const unsigned char*)ws, (const end_rec*)(ws + w.end), (int*)(ws + w.rev), d->path, d->summary,
+                     d->path_costs);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -473,13 +474,13 @@ int rv_align_warp(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->N >= 1 && d->N < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(ALIGN_WARP): N=%ld outside [1, 2^31)", d->N);
   RV_REQUIRE(d->mode == RV_ALIGN_ON_A || d->mode == RV_ALIGN_ON_B || d->mode == RV_ALIGN_ON_PATH, RV_ERR_SHAPE,
              "rv_mosaic(ALIGN_WARP): mode=%ld is none of RV_ALIGN_ON_A, RV_ALIGN_ON_B, RV_ALIGN_ON_PATH", d->mode);
-  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): the path (slot) is null");
-  RV_REQUIRE(d->choice, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): the summary (choice) is null");
-  RV_REQUIRE(d->idx, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): the index table (idx) is null");
+  RV_REQUIRE(d->path, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): the path is null");
+  RV_REQUIRE(d->summary, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): the summary is null");
+  RV_REQUIRE(d->warp_table, RV_ERR_NULL, "rv_mosaic(ALIGN_WARP): warp_table is null");
   const long cap = d->T + d->N - 1;
   const long n = d->mode == RV_ALIGN_ON_A ? d->T : d->mode == RV_ALIGN_ON_B ? d->N : cap;
-  hipLaunchKernelGGL(k_align_warp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (const int*)d->slot,
-                     (const int*)d->choice, cap, n, (int)d->mode, d->idx);
+  hipLaunchKernelGGL(k_align_warp, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, d->path,
+                     d->summary, cap, n, (int)d->mode, d->warp_table);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

@@ -255,27 +255,27 @@ int rv_eval_frames(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->src_len >= d->S && (d->T - 1) * d->stride <= d->src_len - d->S, RV_ERR_SHAPE,
              "rv_mosaic(EVAL_FRAMES): T=%ld rows of S=%ld at stride=%ld overrun src_len=%ld", d->T, d->S, d->stride,
              d->src_len);
-  RV_REQUIRE(!d->q == !d->c, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): %s is null but %s is not: the KL column needs both",
-             d->q ? "logvar (c)" : "mu (q)", d->q ? "mu (q)" : "logvar (c)");
-  if (d->q)
+  RV_REQUIRE(!d->mu == !d->logvar, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): %s is null but %s is not: the KL column needs both",
+             d->mu ? "logvar" : "mu", d->mu ? "mu" : "logvar");
+  if (d->mu)
     RV_REQUIRE(d->L >= 1 && d->L <= (1L << 20), RV_ERR_SHAPE, "rv_mosaic(EVAL_FRAMES): L=%ld outside [1, 2^20]", d->L);
-  RV_REQUIRE(d->lam > 0.f && d->lam <= 120.f, RV_ERR_SHAPE,
-             "rv_mosaic(EVAL_FRAMES): R (lam)=%g dB must be in (0, 120]", (double)d->lam);
+  RV_REQUIRE(d->dynamic_range > 0.f && d->dynamic_range <= 120.f, RV_ERR_SHAPE,
+             "rv_mosaic(EVAL_FRAMES): dynamic_range=%g dB must be in (0, 120]", (double)d->dynamic_range);
   if (d->window) {
     RV_REQUIRE(d->S >= EV_SMIN && d->S <= EV_SMAX && (d->S & (d->S - 1)) == 0, RV_ERR_SHAPE,
                "rv_mosaic(EVAL_FRAMES): S=%ld: the spectral columns (window given) need a power of two in [%d, %d]",
                d->S, EV_SMIN, EV_SMAX);
-    RV_REQUIRE(d->weight, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): window given but the twiddle table (weight) is null");
+    RV_REQUIRE(d->twiddles, RV_ERR_NULL, "rv_mosaic(EVAL_FRAMES): window given but twiddles is null");
   }
-  const float floor_scale = (float)pow(10.0, -(double)d->lam / 10.0);
+  const float floor_scale = (float)pow(10.0, -(double)d->dynamic_range / 10.0);
   const dim3 grid((unsigned)d->T), block(EV_THREADS);
   const hipStream_t st = (hipStream_t)stream;
   if (d->window)
-    hipLaunchKernelGGL(k_eval_frames<true>, grid, block, (4 * (d->S / 2) + 2) * sizeof(float), st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->q,
-                       d->c, (int)d->L, d->window, d->weight, floor_scale, d->out, d->ldo);
+    hipLaunchKernelGGL(k_eval_frames<true>, grid, block, (4 * (d->S / 2) + 2) * sizeof(float), st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->mu,
+                       d->logvar, (int)d->L, d->window, d->twiddles, floor_scale, d->out, d->ldo);
   else
-    hipLaunchKernelGGL(k_eval_frames<false>, grid, block, 0, st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->q,
-                       d->c, (int)d->L, (const float*)nullptr, (const float*)nullptr, floor_scale, d->out, d->ldo);
+    hipLaunchKernelGGL(k_eval_frames<false>, grid, block, 0, st, d->frames, d->hop, d->src, d->stride, (int)d->S, d->mu,
+                       d->logvar, (int)d->L, (const float*)nullptr, (const float*)nullptr, floor_scale, d->out, d->ldo);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -283,8 +283,8 @@ int rv_eval_frames(const rv_mosaic_desc* d, void* stream) {
 int rv_eval_dims(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->T >= 1 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): T=%ld outside [1, 2^31)", d->T);
   RV_REQUIRE(d->L >= 1 && d->L <= (1L << 20), RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): L=%ld outside [1, 2^20]", d->L);
-  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): mu (q) is null");
-  RV_REQUIRE(d->c, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): logvar (c) is null");
+  RV_REQUIRE(d->mu, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): mu is null");
+  RV_REQUIRE(d->logvar, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): logvar is null");
   RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): cost is null");
   const long nb = (d->T + DIMS_ROWS - 1) / DIMS_ROWS;
   const long need = nb > 1 ? nb * d->L * (long)sizeof(double) : 0;
@@ -295,7 +295,7 @@ int rv_eval_dims(const rv_mosaic_desc* d, void* stream) {
   const hipStream_t st = (hipStream_t)stream;
   const unsigned tiles = (unsigned)((d->L + DIMS_THREADS - 1) / DIMS_THREADS);
   double* part = nb > 1 ? (double*)d->ws : d->cost;
-  hipLaunchKernelGGL(k_eval_dims_block, dim3((unsigned)nb, tiles), dim3(DIMS_THREADS), 0, st, d->q, d->c, d->T, d->L, part);
+  hipLaunchKernelGGL(k_eval_dims_block, dim3((unsigned)nb, tiles), dim3(DIMS_THREADS), 0, st, d->mu, d->logvar, d->T, d->L, part);
   if (nb > 1)
     hipLaunchKernelGGL(k_eval_dims_sum, dim3(tiles), dim3(DIMS_THREADS), 0, st, (const double*)d->ws, nb, d->L, d->cost);
   RV_CHECK_LAUNCH();

@@ -275,18 +275,18 @@ int fit_tk_check(const rv_mosaic_desc* d, const char* op) {
 int rv_grain_fit(const rv_mosaic_desc* d, void* stream) {
   const int rc = fit_tk_check(d, "GRAIN_FIT");
   if (rc) return rc;
-  RV_REQUIRE(d->width >= 0 && d->width <= FIT_RMAX, RV_ERR_SHAPE, "rv_mosaic(GRAIN_FIT): R (width)=%ld outside [0, %d]",
-             d->width, FIT_RMAX);
-  RV_REQUIRE(d->lam >= 0.f && d->lam < INFINITY, RV_ERR_SHAPE,
-             "rv_mosaic(GRAIN_FIT): gain_max (lam)=%g must be finite and not negative", (double)d->lam);
+  RV_REQUIRE(d->fit_radius >= 0 && d->fit_radius <= FIT_RMAX, RV_ERR_SHAPE,
+             "rv_mosaic(GRAIN_FIT): fit_radius=%ld outside [0, %d]", d->fit_radius, FIT_RMAX);
+  RV_REQUIRE(d->gain_max >= 0.f && d->gain_max < INFINITY, RV_ERR_SHAPE,
+             "rv_mosaic(GRAIN_FIT): gain_max=%g must be finite and not negative", (double)d->gain_max);
   RV_REQUIRE(d->idx, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): idx is null");
   RV_REQUIRE(d->frames, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): frames is null");
   RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): src is null");
   RV_REQUIRE(d->row_start, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): row_start is null");
-  RV_REQUIRE(d->next_of, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): room (next_of) is null");
-  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): shift (slot) is null");
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): gain (trans) is null");
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): score (cost) is null");
+  RV_REQUIRE(d->room, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): room is null");
+  RV_REQUIRE(d->shift, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): shift is null");
+  RV_REQUIRE(d->gain, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): gain is null");
+  RV_REQUIRE(d->score, RV_ERR_NULL, "rv_mosaic(GRAIN_FIT): score is null");
   RV_REQUIRE(d->S >= 1 && d->S < INT_MAX && d->hop >= 1 && d->hop < (1L << 20), RV_ERR_SHAPE,
              "rv_mosaic(GRAIN_FIT): bad framing S=%ld hop=%ld", d->S, d->hop);
   RV_REQUIRE(d->n_out >= 1 && d->S <= d->n_out && (d->T - 1) * d->hop <= d->n_out - d->S, RV_ERR_SHAPE,
@@ -297,9 +297,9 @@ int rv_grain_fit(const rv_mosaic_desc* d, void* stream) {
              d->S);
   RV_REQUIRE(d->T * d->k < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(GRAIN_FIT): T=%ld rows of k=%ld too many for one call",
              d->T, d->k);
-  hipLaunchKernelGGL(k_grain_fit<false>, dim3((unsigned)(d->T * d->k)), dim3(fit_threads(d->width)), 0,
+  hipLaunchKernelGGL(k_grain_fit<false>, dim3((unsigned)(d->T * d->k)), dim3(fit_threads(d->fit_radius)), 0,
                      (hipStream_t)stream, d->frames, d->hop, (int)d->S, d->idx, (int)d->k, d->src, d->src_len,
-                     d->row_start, d->n_rows, d->next_of, (int)d->width, d->lam, d->slot, d->trans, d->cost, fit_ring{});
+                     d->row_start, d->n_rows, d->room, (int)d->fit_radius, d->gain_max, d->shift, d->gain, d->score, fit_ring{});
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -310,15 +310,15 @@ int rv_grain_gather(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->idx, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): idx is null");
   RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): src is null");
   RV_REQUIRE(d->out, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): out is null");
-  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): shift (slot) is null");
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): gain (trans) is null");
+  RV_REQUIRE(d->shift, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): shift is null");
+  RV_REQUIRE(d->gain, RV_ERR_NULL, "rv_mosaic(GRAIN_GATHER): gain is null");
   RV_REQUIRE(d->width >= 1 && d->n_rows >= 1 && d->src_len >= d->width && d->ldo >= d->width &&
                  (d->row_start || d->stride >= 0),
              RV_ERR_SHAPE, "rv_mosaic(GRAIN_GATHER): bad extents width=%ld n_rows=%ld src_len=%ld ldo=%ld stride=%ld",
              d->width, d->n_rows, d->src_len, d->ldo, d->stride);
   const long blocks = d->T > 65536 ? 65536 : d->T;
   hipLaunchKernelGGL(k_grain_gather, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, d->src, d->src_len,
-                     d->row_start, d->stride, d->n_rows, d->width, d->idx, d->slot, d->trans, d->T, (int)d->k, d->out,
+                     d->row_start, d->stride, d->n_rows, d->width, d->idx, d->shift, d->gain, d->T, (int)d->k, d->out,
                      d->ldo);
   RV_CHECK_LAUNCH();
   return RV_OK;
@@ -327,14 +327,14 @@ int rv_grain_gather(const rv_mosaic_desc* d, void* stream) {
 long rv_grain_live_ring(long S, long hop, long block, long lag) { return S - hop + 2 * lag * hop + block; }
 
 int rv_grain_live_check(const rv_mosaic_desc* d, const char* op, int run) {
-  RV_REQUIRE(d->width >= 0 && d->width <= FIT_RMAX, RV_ERR_SHAPE, "rv_mosaic(%s): R (width)=%ld outside [0, %d]", op,
-             d->width, FIT_RMAX);
-  RV_REQUIRE(d->lam >= 0.f && d->lam < INFINITY, RV_ERR_SHAPE,
-             "rv_mosaic(%s): gain_max (lam)=%g must be finite and not negative", op, (double)d->lam);
-  if (d->width == 0 && d->lam == 0.f) return RV_OK;
+  RV_REQUIRE(d->fit_radius >= 0 && d->fit_radius <= FIT_RMAX, RV_ERR_SHAPE, "rv_mosaic(%s): fit_radius=%ld outside [0, %d]",
+             op, d->fit_radius, FIT_RMAX);
+  RV_REQUIRE(d->gain_max >= 0.f && d->gain_max < INFINITY, RV_ERR_SHAPE,
+             "rv_mosaic(%s): gain_max=%g must be finite and not negative", op, (double)d->gain_max);
+  if (d->fit_radius == 0 && d->gain_max == 0.f) return RV_OK;
   RV_REQUIRE(d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED,
-             "rv_mosaic(%s): a fit (R (width)=%ld, gain_max (lam)=%g) needs mode RV_LIVE_GRAINS, mode=%ld plays no "
-             "corpus audio", op, d->width, (double)d->lam, d->mode);
+             "rv_mosaic(%s): a fit (fit_radius=%ld, gain_max=%g) needs mode RV_LIVE_GRAINS, mode=%ld plays no "
+             "corpus audio", op, d->fit_radius, (double)d->gain_max, d->mode);
   const rv_stream_desc* sd = d->live;
   RV_REQUIRE(sd->S < INT_MAX && sd->hop < (1L << 20) && sd->n_streams * (sd->block / sd->hop) * d->k < (1L << 31) &&
                  (sd->block + 255) / 256 < (1L << 31) && sd->n_streams <= 65535, RV_ERR_SHAPE,
@@ -343,9 +343,9 @@ int rv_grain_live_check(const rv_mosaic_desc* d, const char* op, int run) {
   if (!run) return RV_OK;
   RV_REQUIRE(d->next_of, RV_ERR_NULL, "rv_mosaic(%s): with a fit next_of [3 N] holds the successors and room: it is null",
              op);
-  RV_REQUIRE(d->slot, RV_ERR_NULL, "rv_mosaic(%s): shift (slot) is null", op);
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(%s): gain (trans) is null", op);
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(%s): score (cost) is null", op);
+  RV_REQUIRE(d->shift, RV_ERR_NULL, "rv_mosaic(%s): shift is null", op);
+  RV_REQUIRE(d->gain, RV_ERR_NULL, "rv_mosaic(%s): gain is null", op);
+  RV_REQUIRE(d->score, RV_ERR_NULL, "rv_mosaic(%s): score is null", op);
   return RV_OK;
 }
 
@@ -361,15 +361,15 @@ int rv_grain_live(const rv_mosaic_desc* d, const int* sel, int sel_k, float* rin
   const rv_stream_desc* sd = d->live;
   const hipStream_t st = (hipStream_t)stream;
   const long F = sd->block / sd->hop, M = sd->n_streams * F;
-  const long C = rv_grain_live_ring(sd->S, sd->hop, sd->block, d->rows);
+  const long C = rv_grain_live_ring(sd->S, sd->hop, sd->block, d->lag);
   hipLaunchKernelGGL(k_live_target, dim3((unsigned)((sd->block + 255) / 256), (unsigned)sd->n_streams), dim3(256), 0, st,
                      sd->x, sd->ld_x, sd->block, sd->hop, C, cnt, ring);
-  const fit_ring fr{cnt, tfr, F, C, sd->S - sd->hop, 2 * d->rows};
-  hipLaunchKernelGGL(k_grain_fit<true>, dim3((unsigned)(M * sel_k)), dim3(fit_threads(d->width)), 0, st, ring, sd->hop,
-                     (int)sd->S, sel, sel_k, d->src, d->src_len, d->row_start, d->N, d->next_of + d->N, (int)d->width,
-                     d->lam, d->slot, d->trans, d->cost, fr);
+  const fit_ring fr{cnt, tfr, F, C, sd->S - sd->hop, 2 * d->lag};
+  hipLaunchKernelGGL(k_grain_fit<true>, dim3((unsigned)(M * sel_k)), dim3(fit_threads(d->fit_radius)), 0, st, ring,
+                     sd->hop, (int)sd->S, sel, sel_k, d->src, d->src_len, d->row_start, d->N, d->next_of + d->N,
+                     (int)d->fit_radius, d->gain_max, d->shift, d->gain, d->score, fr);
   hipLaunchKernelGGL(k_grain_gather, dim3((unsigned)(M > 65536 ? 65536 : M)), dim3(256), 0, st, d->src, d->src_len,
-                     d->row_start, 0L, d->N, sd->S, sel, d->slot, d->trans, M, sel_k, frames, sd->S);
+                     d->row_start, 0L, d->N, sd->S, sel, d->shift, d->gain, M, sel_k, frames, sd->S);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

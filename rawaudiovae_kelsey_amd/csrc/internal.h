@@ -132,7 +132,7 @@ RV_INTERNAL const long long* rv_stream_counters(const rv_stream_desc* d);
 RV_INTERNAL int rv_grain_fit(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_grain_gather(const rv_mosaic_desc* d, void* stream);
 // The live mosaic's grain fit (grain.hip; the rule: the public header, "Live grain fitting"), on the fields the header
-// names: width = R, lam = gain_max, slot / trans / cost [M, sel_k], next_of [3 N] = successors then room.
+// names: fit_radius, gain_max, shift / gain / score [M, sel_k], next_of [3 N] = successors then room.
 // rv_grain_live_check: the fit's argument checks for op `op` (d->live is not null); run: also the tables and outputs.
 // rv_grain_live_ring: floats of one stream's target ring.  rv_grain_live_reset: silence in the rings of n streams from
 // `first`.  rv_grain_live: the block into the rings, the fit of sel [M, sel_k] against the target frames the rows stand

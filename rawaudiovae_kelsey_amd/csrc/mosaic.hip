@@ -1140,9 +1140,9 @@ int run_knn(const rv_mosaic_desc* d, bool small, hipStream_t st) {
 }
 
 // RV_MOSAIC_LIVE's workspace: prev [n_streams] int32, the query rows [M, L] fp32, the search's partials; with a lag of
-// D = d->rows > 0 frames then the lagged selection's state: (head, count) [n_streams, 2] int32 and the rings of
+// D = d->lag > 0 frames then the lagged selection's state: (head, count) [n_streams, 2] int32 and the rings of
 // R = D + 1 rows per stream, idx [n_streams, R, k] int32, dist [n_streams, R, k] fp32, trans [n_streams, R, k, k] fp32.
-// With a grain fit (d->width > 0 or d->lam > 0) then the TARGET RINGS [n_streams, C] fp32, C = P + 2 D hop + block:
+// With a grain fit (d->fit_radius > 0 or d->gain_max > 0) then the TARGET RINGS [n_streams, C] fp32, C = P + 2 D hop + block:
 // input sample a of a stream (counted from its last reset) at ring[a mod C], silence before the reset; the block is
 // written at the stream's frame count before the fit reads it, so the ring holds the block and the P + 2 D hop samples
 // before it (a row that drains interleave with blocks can wait up to 2 D frames).  With a lag also the pending rows'
@@ -1164,10 +1164,10 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w, bool run = 
              sd->block, sd->hop, sd->S);
   RV_REQUIRE(d->L == sd->L, RV_ERR_SHAPE, "rv_mosaic(%s): corpus rows of L=%ld, the model's latent has %ld", op, d->L,
              sd->L);
-  RV_REQUIRE(d->rows >= 0 && d->rows <= LAG_MAX, RV_ERR_SHAPE, "rv_mosaic(%s): lag (rows)=%ld outside [0, %d]", op,
-             d->rows, LAG_MAX);
-  RV_REQUIRE(d->rows == 0 || d->weight, RV_ERR_NULL,
-             "rv_mosaic(%s): lag (rows)=%ld needs unit selection: weight is null", op, d->rows);
+  RV_REQUIRE(d->lag >= 0 && d->lag <= LAG_MAX, RV_ERR_SHAPE, "rv_mosaic(%s): lag=%ld outside [0, %d]", op, d->lag,
+             LAG_MAX);
+  RV_REQUIRE(d->lag == 0 || d->weight, RV_ERR_NULL, "rv_mosaic(%s): lag=%ld needs unit selection: weight is null", op,
+             d->lag);
   const int frc = rv_grain_live_check(d, op, run);
   if (frc) return frc;
   w->M = sd->n_streams * (sd->block / sd->hop);
@@ -1182,7 +1182,7 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w, bool run = 
   w->knn = w->q + up(w->M * d->L * 4);
   w->knn_bytes = knn_ws_bytes(w->M, d->k, n_splits);
   w->bytes = w->knn + up(w->knn_bytes);
-  w->lag = d->rows;
+  w->lag = d->lag;
   if (w->lag > 0) {
     const long rows = sd->n_streams * (w->lag + 1);
     w->state = w->bytes;
@@ -1191,7 +1191,7 @@ int live_layout(const rv_mosaic_desc* d, const char* op, live_ws* w, bool run = 
     w->rtrans = w->rdist + up(rows * d->k * 4);
     w->bytes = w->rtrans + up(rows * d->k * d->k * 4);
   }
-  w->fit = d->width > 0 || d->lam > 0.f;
+  w->fit = d->fit_radius > 0 || d->gain_max > 0.f;
   if (w->fit) {
     w->C = rv_grain_live_ring(sd->S, sd->hop, sd->block, w->lag);
     w->ring = w->bytes;
@@ -1332,15 +1332,15 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       const rv_stream_desc* sd = d->live;
       const bool decode = d->mode == RV_LIVE_DECODE;
       RV_REQUIRE(decode || d->mode == RV_LIVE_GRAINS, RV_ERR_UNSUPPORTED, "rv_mosaic(%s): mode %ld", who, d->mode);
-      RV_REQUIRE(!drain || w.lag > 0, RV_ERR_SHAPE, "rv_mosaic(LIVE_DRAIN): lag (rows)=%ld: nothing is pending without a lag",
-                 d->rows);
+      RV_REQUIRE(!drain || w.lag > 0, RV_ERR_SHAPE, "rv_mosaic(LIVE_DRAIN): lag=%ld: nothing is pending without a lag",
+                 d->lag);
       RV_REQUIRE(d->c && d->idx && d->dist && d->ws && (decode || (d->src && d->row_start)) &&
                      (!d->weight || (d->next_of && d->choice)), RV_ERR_NULL,
-                 "rv_mosaic(%s): null pointer (lag (rows)=%ld; unit selection needs weight, next_of and choice)", who,
-                 d->rows);
+                 "rv_mosaic(%s): null pointer (lag=%ld; unit selection needs weight, next_of and choice)", who,
+                 d->lag);
       RV_REQUIRE(d->ws_bytes >= w.bytes && ((unsigned long)d->ws & 255) == 0, RV_ERR_SHAPE,
-                 "rv_mosaic(%s): workspace of %ld bytes (256-byte aligned), %ld needed at lag (rows)=%ld", who, d->ws_bytes,
-                 w.bytes, d->rows);
+                 "rv_mosaic(%s): workspace of %ld bytes (256-byte aligned), %ld needed at lag=%ld", who, d->ws_bytes,
+                 w.bytes, d->lag);
       RV_REQUIRE(d->N < INT_MAX && (decode || d->src_len >= sd->S), RV_ERR_SHAPE,
                  "rv_mosaic(%s): bad extents N=%ld src_len=%ld", who, d->N, d->src_len);
       char* ws = (char*)d->ws;

@@ -427,10 +427,6 @@ moments_ws moments_layout(long T, long L) {
 
 long eig_bytes(long L) { return L * L * (long)sizeof(double); }
 
-// The two fp64 operands travel in float* fields of the descriptor (the header says so): centre in trans, basis in dist.
-double* centre_of(const rv_mosaic_desc* d) { return (double*)d->trans; }
-double* basis_of(const rv_mosaic_desc* d) { return (double*)d->dist; }
-
 }  // namespace
 
 int rv_pca_workspace(rv_mosaic_desc* d) {
@@ -449,9 +445,9 @@ int rv_pca_workspace(rv_mosaic_desc* d) {
 int rv_pca_moments(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->T >= 2 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(PCA_MOMENTS): T=%ld outside [2, 2^31)", d->T);
   RV_REQUIRE(d->L >= 1 && d->L <= PCA_LMAX, RV_ERR_SHAPE, "rv_mosaic(PCA_MOMENTS): L=%ld outside [1, %d]", d->L, PCA_LMAX);
-  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): x (q) is null");
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): centre (trans) is null");
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): basis (dist) is null");
+  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): q is null");
+  RV_REQUIRE(d->centre, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): centre is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(PCA_MOMENTS): basis is null");
   const moments_ws w = moments_layout(d->T, d->L);
   RV_REQUIRE(d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(PCA_MOMENTS): ws_bytes=%ld, T=%ld rows of L=%ld need %ld",
              d->ws_bytes, d->T, d->L, w.bytes);
@@ -463,25 +459,25 @@ int rv_pca_moments(const rv_mosaic_desc* d, void* stream) {
   const unsigned col_tiles = (unsigned)((L + MEAN_THREADS - 1) / MEAN_THREADS);
   hipLaunchKernelGGL(k_pca_mean_block, dim3((unsigned)w.nb, col_tiles), dim3(MEAN_THREADS), 0, st, d->q, d->T, d->L, mean_part);
   hipLaunchKernelGGL(k_pca_mean_sum, dim3(col_tiles), dim3(MEAN_THREADS), 0, st, (const double*)mean_part, w.nb, d->L, d->T,
-                     centre_of(d));
+                     d->centre);
   hipLaunchKernelGGL(k_pca_cov, dim3((unsigned)w.n_ranges, (unsigned)w.n_tiles), dim3(CV_THREADS), 0, st, d->q, d->T, L,
-                     (const double*)centre_of(d), w.nI, w.n_tiles, cov_part);
+                     d->centre, w.nI, w.n_tiles, cov_part);
   hipLaunchKernelGGL(k_pca_cov_sum, dim3((unsigned)((L + 63) / 64), (unsigned)L), dim3(64), 0, st, (const double*)cov_part,
-                     w.n_ranges, w.n_tiles, w.nI, L, d->T, basis_of(d));
+                     w.n_ranges, w.n_tiles, w.nI, L, d->T, d->basis);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
 
 int rv_pca_eig(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->L >= 1 && d->L <= PCA_LMAX, RV_ERR_SHAPE, "rv_mosaic(PCA_EIG): L=%ld outside [1, %d]", d->L, PCA_LMAX);
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(PCA_EIG): basis (dist) is null");
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(PCA_EIG): the eigenvalues (cost) are null");
-  RV_REQUIRE(d->choice, RV_ERR_NULL, "rv_mosaic(PCA_EIG): the info pair (choice) is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(PCA_EIG): basis is null");
+  RV_REQUIRE(d->eigenvalues, RV_ERR_NULL, "rv_mosaic(PCA_EIG): the eigenvalues are null");
+  RV_REQUIRE(d->info, RV_ERR_NULL, "rv_mosaic(PCA_EIG): info is null");
   const long need = eig_bytes(d->L);
   RV_REQUIRE(d->ws_bytes >= need, RV_ERR_SHAPE, "rv_mosaic(PCA_EIG): ws_bytes=%ld, L=%ld needs %ld", d->ws_bytes, d->L, need);
   RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(PCA_EIG): ws is null, L=%ld needs %ld bytes", d->L, need);
-  hipLaunchKernelGGL(k_pca_eig, dim3(1), dim3(EG_THREADS), 0, (hipStream_t)stream, basis_of(d), (int)d->L, (double*)d->ws, d->cost,
-                     d->choice);
+  hipLaunchKernelGGL(k_pca_eig, dim3(1), dim3(EG_THREADS), 0, (hipStream_t)stream, d->basis, (int)d->L, (double*)d->ws,
+                     d->eigenvalues, d->info);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -492,16 +488,16 @@ int rv_pca_apply(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->T >= 1 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(PCA_APPLY): T=%ld outside [1, 2^31)", d->T);
   RV_REQUIRE(d->L >= 1 && d->L <= PCA_LMAX, RV_ERR_SHAPE, "rv_mosaic(PCA_APPLY): L=%ld outside [1, %d]", d->L, PCA_LMAX);
   RV_REQUIRE(d->k >= 1 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(PCA_APPLY): k=%ld outside [1, L=%ld]", d->k, d->L);
-  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the input rows (q) are null");
+  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): q is null");
   RV_REQUIRE(d->out, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): out is null");
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): centre (trans) is null");
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): basis (dist) is null");
+  RV_REQUIRE(d->centre, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): centre is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): basis is null");
   const long width = d->mode == RV_PCA_PROJECT ? d->k : d->L;
   RV_REQUIRE(d->ldo >= width, RV_ERR_SHAPE, "rv_mosaic(PCA_APPLY): ldo=%ld holds no row of %ld values", d->ldo, width);
   if (d->mode == RV_PCA_EDIT) {
-    RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the eigenvalues (cost) are null");
-    RV_REQUIRE(d->weight, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the gains (weight) are null");
-    RV_REQUIRE(d->c, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the shifts (c) are null");
+    RV_REQUIRE(d->eigenvalues, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the eigenvalues are null");
+    RV_REQUIRE(d->gains, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the gains are null");
+    RV_REQUIRE(d->shifts, RV_ERR_NULL, "rv_mosaic(PCA_APPLY): the shifts are null");
   }
   const hipStream_t st = (hipStream_t)stream;
   const int L = (int)d->L, k = (int)d->k;
@@ -509,14 +505,12 @@ int rv_pca_apply(const rv_mosaic_desc* d, void* stream) {
     constexpr int RT = 8;
     const size_t lds = ((size_t)RT * (L + k) + AP_THREADS * AP_VLD) * sizeof(double);
     hipLaunchKernelGGL(k_pca_apply<RT>, dim3((unsigned)((d->T + RT - 1) / RT)), dim3(AP_THREADS), lds, st, (int)d->mode, d->q,
-                       d->T, L, k, (const double*)centre_of(d), (const double*)basis_of(d), (const double*)d->cost, d->weight, d->c,
-                       d->out, d->ldo);
+                       d->T, L, k, d->centre, d->basis, d->eigenvalues, d->gains, d->shifts, d->out, d->ldo);
   } else {
     constexpr int RT = 4;
     const size_t lds = ((size_t)RT * (L + k) + AP_THREADS * AP_VLD) * sizeof(double);
     hipLaunchKernelGGL(k_pca_apply<RT>, dim3((unsigned)((d->T + RT - 1) / RT)), dim3(AP_THREADS), lds, st, (int)d->mode, d->q,
-                       d->T, L, k, (const double*)centre_of(d), (const double*)basis_of(d), (const double*)d->cost, d->weight, d->c,
-                       d->out, d->ldo);
+                       d->T, L, k, d->centre, d->basis, d->eigenvalues, d->gains, d->shifts, d->out, d->ldo);
   }
   RV_CHECK_LAUNCH();
   return RV_OK;

@@ -284,11 +284,11 @@ int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->T >= 2 && d->T < (1L << 31), RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): T=%ld outside [2, 2^31)", d->T);
   RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): L=%ld outside [1, %d]", d->L, WK_LMAX);
   RV_REQUIRE(d->n_rows >= 1 && d->n_rows <= d->T, RV_ERR_SHAPE,
-             "rv_mosaic(PCA_LAGCOV): n_files (n_rows)=%ld outside [1, T=%ld]", d->n_rows, d->T);
-  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): x (q) is null");
+             "rv_mosaic(PCA_LAGCOV): n_rows=%ld (the files) outside [1, T=%ld]", d->n_rows, d->T);
+  RV_REQUIRE(d->q, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): q is null");
   RV_REQUIRE(d->row_start, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): row_start is null");
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): centre (trans) is null");
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): the moment (dist) is null");
+  RV_REQUIRE(d->centre, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): centre is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(PCA_LAGCOV): basis (the moment C1) is null");
   const lag_ws w = lag_layout(d->T, d->L);
   RV_REQUIRE(d->ws_bytes >= w.bytes, RV_ERR_SHAPE, "rv_mosaic(PCA_LAGCOV): ws_bytes=%ld, T=%ld rows of L=%ld need %ld",
              d->ws_bytes, d->T, d->L, w.bytes);
@@ -299,9 +299,9 @@ int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream) {
   double* const part = (double*)(keep + w.keep_bytes);
   hipLaunchKernelGGL(k_walk_pairs, dim3(blocks256(w.n_pairs)), dim3(256), 0, st, d->row_start, d->n_rows, w.n_pairs, keep);
   hipLaunchKernelGGL(k_walk_lag, dim3((unsigned)w.n_ranges, (unsigned)(w.nI * w.nI)), dim3(LG_THREADS), 0, st, d->q, w.n_pairs,
-                     L, (const double*)d->trans, (const unsigned char*)keep, w.nI, part);
+                     L, d->centre, (const unsigned char*)keep, w.nI, part);
   hipLaunchKernelGGL(k_walk_lag_sum, dim3((unsigned)((L + 63) / 64), (unsigned)L), dim3(64), 0, st, (const double*)part,
-                     w.n_ranges, w.nI, L, d->T, (double*)d->dist);
+                     w.n_ranges, w.nI, L, d->T, d->basis);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -311,35 +311,35 @@ int rv_walk_fit(const rv_mosaic_desc* d, void* stream) {
              "rv_mosaic(WALK_FIT): mode=%ld is none of RV_WALK_DYNAMICS, RV_WALK_NOISE, RV_WALK_DIAGONAL", d->mode);
   RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): L=%ld outside [1, %d]", d->L, WK_LMAX);
   RV_REQUIRE(d->k >= 1 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): k=%ld outside [1, L=%ld]", d->k, d->L);
-  RV_REQUIRE(d->out, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the result (out) is null");
+  RV_REQUIRE(d->result, RV_ERR_NULL, "rv_mosaic(WALK_FIT): result is null");
   const hipStream_t st = (hipStream_t)stream;
   const int k = (int)d->k, L = (int)d->L;
   const long kk = (long)k * k, kL = (long)k * L;
-  double* const o = (double*)d->out;
+  double* const o = d->result;
   if (d->mode != RV_WALK_DYNAMICS) {
-    RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_FIT): A (dist) is null");
+    RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(WALK_FIT): basis (A) is null");
     if (d->mode == RV_WALK_DIAGONAL) {
-      hipLaunchKernelGGL(k_walk_diagonal, dim3(blocks256(kk)), dim3(256), 0, st, (const double*)d->dist, k, o);
+      hipLaunchKernelGGL(k_walk_diagonal, dim3(blocks256(kk)), dim3(256), 0, st, d->basis, k, o);
     } else {
-      RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvectors of Q (src) are null");
-      RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues of Q (cost) are null");
-      hipLaunchKernelGGL(k_walk_noise, dim3(blocks256(kk)), dim3(256), 0, st, (const double*)d->dist, (const double*)d->src,
-                         (const double*)d->cost, k, o);
+      RV_REQUIRE(d->moment, RV_ERR_NULL, "rv_mosaic(WALK_FIT): moment (the eigenvectors of Q) is null");
+      RV_REQUIRE(d->eigenvalues, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues of Q are null");
+      hipLaunchKernelGGL(k_walk_noise, dim3(blocks256(kk)), dim3(256), 0, st, d->basis, d->moment, d->eigenvalues, k,
+                         o);
     }
     RV_CHECK_LAUNCH();
     return RV_OK;
   }
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_FIT): basis (dist) is null");
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues (cost) are null");
-  RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the lag-1 moment (src) is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(WALK_FIT): basis is null");
+  RV_REQUIRE(d->eigenvalues, RV_ERR_NULL, "rv_mosaic(WALK_FIT): the eigenvalues are null");
+  RV_REQUIRE(d->moment, RV_ERR_NULL, "rv_mosaic(WALK_FIT): moment (the lag-1 moment) is null");
   const long need = fit_bytes(k, L);
   RV_REQUIRE(d->ws_bytes >= need, RV_ERR_SHAPE, "rv_mosaic(WALK_FIT): ws_bytes=%ld, k=%ld of L=%ld need %ld", d->ws_bytes, d->k,
              d->L, need);
   RV_REQUIRE(d->ws, RV_ERR_NULL, "rv_mosaic(WALK_FIT): ws is null, k=%ld of L=%ld need %ld bytes", d->k, d->L, need);
   double *const A = o, *const Q = o + kk, *const P = o + 2 * kk, *const R = P + kL, *const M = (double*)d->ws;
-  hipLaunchKernelGGL(k_walk_scale, dim3(blocks256(kL)), dim3(256), 0, st, (const double*)d->dist, (const double*)d->cost, k, L, P, R);
+  hipLaunchKernelGGL(k_walk_scale, dim3(blocks256(kL)), dim3(256), 0, st, d->basis, d->eigenvalues, k, L, P, R);
   hipLaunchKernelGGL((k_walk_product<false, false>), dim3(blocks256(kL)), dim3(256), 0, st, (const double*)P,
-                     (const double*)d->src, k, L, L, M);
+                     d->moment, k, L, L, M);
   hipLaunchKernelGGL((k_walk_product<true, false>), dim3(blocks256(kk)), dim3(256), 0, st, (const double*)M, (const double*)P, k,
                      k, L, A);
   hipLaunchKernelGGL((k_walk_product<true, true>), dim3(blocks256(kk)), dim3(256), 0, st, (const double*)A, (const double*)A, k,
@@ -354,19 +354,19 @@ int rv_walk_step(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->L >= 1 && d->L <= WK_LMAX, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): L=%ld outside [1, %d]", d->L, WK_LMAX);
   RV_REQUIRE(d->L == sd->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): L=%ld, the stream's model has L=%ld", d->L, sd->L);
   RV_REQUIRE(d->k >= 1 && d->k <= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): k=%ld outside [1, L=%ld]", d->k, d->L);
-  RV_REQUIRE(d->trans, RV_ERR_NULL, "rv_mosaic(WALK_STEP): centre (trans) is null");
-  RV_REQUIRE(d->dist, RV_ERR_NULL, "rv_mosaic(WALK_STEP): R (dist) is null");
-  RV_REQUIRE(d->src, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the dynamics [A^T | B^T] (src) are null");
-  RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the state (cost) is null");
-  RV_REQUIRE(d->choice, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the primed flags (choice) are null");
+  RV_REQUIRE(d->centre, RV_ERR_NULL, "rv_mosaic(WALK_STEP): centre is null");
+  RV_REQUIRE(d->basis, RV_ERR_NULL, "rv_mosaic(WALK_STEP): basis (R) is null");
+  RV_REQUIRE(d->moment, RV_ERR_NULL, "rv_mosaic(WALK_STEP): moment (the dynamics [A^T | B^T]) is null");
+  RV_REQUIRE(d->state, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the state is null");
+  RV_REQUIRE(d->primed, RV_ERR_NULL, "rv_mosaic(WALK_STEP): the primed flags are null");
   RV_REQUIRE(sd->temperature, RV_ERR_NULL, "rv_mosaic(WALK_STEP): live->temperature is null");
   RV_REQUIRE(!d->out || d->ldo >= d->L, RV_ERR_SHAPE, "rv_mosaic(WALK_STEP): ldo=%ld holds no row of L=%ld values", d->ldo, d->L);
   float *z = nullptr, *frames = nullptr;
   const int rc = rv_stream_encode(sd, nullptr, &z, &frames, stream);   // the stream's own checks; launches nothing
   if (rc) return rc;
-  hipLaunchKernelGGL(k_walk_step, dim3((unsigned)sd->n_streams), dim3(ST_THREADS), 0, (hipStream_t)stream, (const double*)d->src,
-                     (const double*)d->dist, (const double*)d->trans, (int)d->k, (int)d->L, sd->block / sd->hop,
-                     rv_stream_counters(sd), sd->eps_in, (uint64_t)sd->seed, sd->temperature, sd->offset, d->cost, d->choice, z,
+  hipLaunchKernelGGL(k_walk_step, dim3((unsigned)sd->n_streams), dim3(ST_THREADS), 0, (hipStream_t)stream, d->moment,
+                     d->basis, d->centre, (int)d->k, (int)d->L, sd->block / sd->hop,
+                     rv_stream_counters(sd), sd->eps_in, (uint64_t)sd->seed, sd->temperature, sd->offset, d->state, d->primed, z,
                      d->out, d->ldo);
   RV_CHECK_LAUNCH();
   return rv_stream_synth(sd, 1, stream);

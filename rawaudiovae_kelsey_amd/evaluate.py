@@ -34,7 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MosaicDesc, eval_fields, lib, ptr, stream_ptr
+from ._lib import lib, mosaic_call, ptr, stream_ptr
 from .codec import MAX_GEMM_ROWS, FrameCodec, frame_layout
 from .som import segment_mean
 from .stream import WINDOWS, window_values
@@ -129,10 +129,10 @@ def frame_scores(ref, test, T, segment_length, hop, stride, mu=None, logvar=None
     if (not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != ref.device or out.dim() != 2
             or out.shape[0] != T or out.shape[1] < 6 or out.stride(1) != 1):
         raise ValueError("out must be a [%d, >= 6] float32 tensor on %s with unit column stride" % (T, ref.device))
-    d = MosaicDesc(T=T, S=S, hop=int(hop), frames=ptr(ref), n_out=ref.numel(), src=ptr(test), stride=int(stride),
-                   src_len=test.numel(), L=L, window=ptr(window), out=ptr(out),
-                   ldo=out.stride(0) if T > 1 else max(out.shape[1], 6), **eval_fields(mu, logvar, table, dynamic_range))
-    lib().rv_mosaic(_lib.EVAL_FRAMES, _lib.C.byref(d), stream_ptr())
+    mosaic_call(_lib.EVAL_FRAMES, T=T, S=S, hop=int(hop), frames=ptr(ref), n_out=ref.numel(), src=ptr(test),
+                stride=int(stride), src_len=test.numel(), L=L, window=ptr(window), out=ptr(out),
+                ldo=out.stride(0) if T > 1 else max(out.shape[1], 6), mu=ptr(mu), logvar=ptr(logvar), twiddles=ptr(table),
+                dynamic_range=float(dynamic_range))
     return out
 
 
@@ -148,8 +148,7 @@ def kl_dims(mu, logvar):
     nb = -(-T // DIMS_ROWS)
     nbytes = 8 * nb * L if nb > 1 else 0
     ws = torch.empty(nbytes, dtype=torch.uint8, device=mu.device) if nbytes else None
-    d = MosaicDesc(T=T, L=L, cost=ptr(cost), ws=ptr(ws), ws_bytes=nbytes, **eval_fields(mu, logvar))
-    lib().rv_mosaic(_lib.EVAL_DIMS, _lib.C.byref(d), stream_ptr())
+    mosaic_call(_lib.EVAL_DIMS, T=T, L=L, cost=ptr(cost), ws=ptr(ws), ws_bytes=nbytes, mu=ptr(mu), logvar=ptr(logvar))
     return cost
 
 

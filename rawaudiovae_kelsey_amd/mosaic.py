@@ -54,14 +54,14 @@ space (corpus-based concatenative synthesis with the VAE's encoder as the descri
 The kNN distance is rv_som_bmu's direct fp32 form (identical frames are at distance exactly 0), ties go to the lower
 corpus index and NaN never wins.  Every row's arithmetic is independent of `max_rows` (the chunk of target frames per
 encoder, search, gather and decoder step), so the output is bit-identical for any chunking.  Framing, encoder and
-decoder are codec.FrameCodec's (`index.codec`); the graphs of the live path are stream.GraphReplay's; the fields of
-rv_mosaic_desc that an op reads under another name are spelled by _lib's fit_fields, fitted_fields and live_fit_table.
+decoder are codec.FrameCodec's (`index.codec`); the graphs of the live path are stream.GraphReplay's; every rv_mosaic
+call passes the member names rv_mosaic_desc declares for the op's roles (_lib.mosaic_call).
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MosaicDesc, fit_fields, fitted_fields, live_fit_table, lib, ptr, stream_ptr
+from ._lib import mosaic_call as _call, ptr
 from .codec import FrameCodec, frame_layout
 from .stream import WINDOWS, GraphReplay, StreamingVAE, check_args, each_stream, window_values
 
@@ -71,12 +71,12 @@ FIT_MAX = 1024     # samples a grain may be shifted at most (csrc/grain.hip)
 SMALL_T_MAX = 64   # query rows of knn_topk_small (csrc/mosaic.hip)
 
 
-def _call(op, **fields):
-    d = MosaicDesc(**fields)
-    host_only = op in (_lib.MOSAIC_KNN_WORKSPACE, _lib.MOSAIC_PATH_WORKSPACE, _lib.MOSAIC_KNN_SMALL_WORKSPACE,
-                       _lib.MOSAIC_LIVE_WORKSPACE)
-    lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else stream_ptr())
-    return d
+def live_fit_table(successors, room):
+    """RV_MOSAIC_LIVE with a fit reads ONE next_of table [3 N] int32: the successors [N] (None: zeros, unread without
+    unit selection), then room [N, 2]"""
+    if successors is None:
+        successors = torch.zeros(room.shape[0], dtype=torch.int32, device=room.device)
+    return torch.cat([successors, room.reshape(-1)]).contiguous()
 
 
 def _rows(x, what):
@@ -315,7 +315,8 @@ def fit_grains(target, idx, hop, segment_length, src, row_start, room, fit, gain
     room = room.contiguous()
     shift, gain, score = fit_buffers(T, k, idx.device)
     _call(_lib.GRAIN_FIT, T=T, k=k, idx=ptr(idx), frames=ptr(target), n_out=target.numel(), hop=hop, S=S, src=ptr(src),
-          src_len=src.numel(), row_start=ptr(row_start), n_rows=N, **fit_fields(room, R, g, shift, gain, score))
+          src_len=src.numel(), row_start=ptr(row_start), n_rows=N, room=ptr(room), fit_radius=R, gain_max=g,
+          shift=ptr(shift), gain=ptr(gain), score=ptr(score))
     return shift, gain, score
 
 
@@ -338,7 +339,7 @@ def gather_fitted(src, idx, shift, gain, width, row_start, out=None, ldo=None):
     if out is None:
         out = torch.empty((T, ldo), dtype=torch.float32, device=src.device)
     _call(_lib.GRAIN_GATHER, T=T, k=k, idx=ptr(idx), src=ptr(src), src_len=src.numel(), row_start=ptr(row_start),
-          n_rows=row_start.numel(), width=width, out=ptr(out), ldo=ldo, **fitted_fields(shift, gain))
+          n_rows=row_start.numel(), width=width, out=ptr(out), ldo=ldo, shift=ptr(shift), gain=ptr(gain))
     return out
 
 
@@ -661,16 +662,13 @@ class StreamingMosaic(GraphReplay):
 
     def _call(self, op, x, y, which=-1, stream=None):
         sd = self._sv.desc(x, y, None)
-        table = (fit_fields(self._next_of, self.fit, self.gain_max, *self._fit) if self.fitted
-                 else dict(next_of=ptr(self._next_of)))
-        d = MosaicDesc(k=self.k, idx=ptr(self._idx), dist=ptr(self._dist), c=ptr(self._mu), N=self._mu.shape[0],
-                       L=self.L, src=ptr(self._audio), src_len=self._audio.numel(), row_start=ptr(self._row_start),
-                       choice=ptr(self._choice), ws=ptr(self._ws), ws_bytes=0 if self._ws is None else self._ws.numel(),
-                       live=_lib.C.pointer(sd), mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS,
-                       weight=ptr(self.weight), which=int(which), rows=self.lag, **table)
-        host_only = op == _lib.MOSAIC_LIVE_WORKSPACE
-        lib().rv_mosaic(op, _lib.C.byref(d), None if host_only else (stream_ptr() if stream is None else stream))
-        return d
+        shift, gain, score = self._fit or (None, None, None)
+        return _call(op, stream, k=self.k, idx=ptr(self._idx), dist=ptr(self._dist), c=ptr(self._mu), N=self._mu.shape[0],
+                     L=self.L, src=ptr(self._audio), src_len=self._audio.numel(), row_start=ptr(self._row_start),
+                     choice=ptr(self._choice), ws=ptr(self._ws), ws_bytes=0 if self._ws is None else self._ws.numel(),
+                     live=_lib.C.pointer(sd), mode=_lib.LIVE_DECODE if self.mode == "decode" else _lib.LIVE_GRAINS,
+                     weight=ptr(self.weight), which=int(which), lag=self.lag, next_of=ptr(self._next_of),
+                     fit_radius=self.fit, gain_max=self.gain_max, shift=ptr(shift), gain=ptr(gain), score=ptr(score))
 
     @torch.no_grad()
     def process(self, x):

@@ -13,23 +13,16 @@ include/rawvae_hip.h, "Latent PCA").
   write_pca(path, pca, ...) / read_pca(path)   one .npz of fp64 arrays and the framing they were fitted at
 
 Everything is computed by the library's kernels in fp64; nothing syncs, and the three apply forms may be captured in a
-graph (the gains and shifts are device tensors, so a replay sees their updates).  The field roles of rv_mosaic_desc are
-spelled by _lib.pca_fields.
+graph (the gains and shifts are device tensors, so a replay sees their updates).
 """
 import numpy as np
 import torch
 
 from . import _lib
-from ._lib import MosaicDesc, RvError, lib, pca_fields, ptr, stream_ptr
+from ._lib import RvError, mosaic_call as _call, ptr
 from .codec import FrameCodec
 
 L_MAX = 512     # csrc/pca.hip
-
-
-def _call(op, **fields):
-    d = MosaicDesc(**fields)
-    lib().rv_mosaic(op, _lib.C.byref(d), None if op == _lib.PCA_WORKSPACE else stream_ptr())
-    return d
 
 
 def _rows(x, what="x", dtype=torch.float32, cols=None):
@@ -72,7 +65,7 @@ def moments(x):
     centre = torch.empty(L, dtype=torch.float64, device=x.device)
     cov = torch.empty((L, L), dtype=torch.float64, device=x.device)
     ws, n = _workspace(N, L, x.device)
-    _call(_lib.PCA_MOMENTS, T=N, L=L, q=ptr(x), ws=ptr(ws), ws_bytes=n, **pca_fields(centre, cov))
+    _call(_lib.PCA_MOMENTS, T=N, L=L, q=ptr(x), ws=ptr(ws), ws_bytes=n, centre=ptr(centre), basis=ptr(cov))
     return centre, cov
 
 
@@ -87,7 +80,7 @@ def eig(cov):
     lam = torch.empty(L, dtype=torch.float64, device=cov.device)
     info = torch.empty(2, dtype=torch.int32, device=cov.device)
     ws, n = _workspace(0, L, cov.device)
-    _call(_lib.PCA_EIG, L=L, ws=ptr(ws), ws_bytes=n, **pca_fields(None, comp, lam, info))
+    _call(_lib.PCA_EIG, L=L, ws=ptr(ws), ws_bytes=n, basis=ptr(comp), eigenvalues=ptr(lam), info=ptr(info))
     sweeps, converged = (int(v) for v in info.cpu())
     return lam, comp, sweeps, bool(converged)
 
@@ -116,8 +109,7 @@ def _apply(mode, x, width, k, L, out, ldo, **roles):
             raise ValueError("out must be a float32 device tensor of %d rows of at least %d contiguous values" % (T, width))
         ldo = out.stride(0) if T > 1 else out.shape[1]
     _call(_lib.PCA_APPLY, mode=mode, T=T, L=L, k=k, q=ptr(x), out=ptr(out), ldo=ldo,
-          **pca_fields(roles["centre"], roles["basis"], roles.get("eigenvalues"), None, roles.get("gains"),
-                       roles.get("shifts")))
+          **{role: ptr(t) for role, t in roles.items()})
     return out
 
 

@@ -33,7 +33,7 @@ import torch
 
 from . import _lib
 from . import pca as P_
-from ._lib import MosaicDesc, RvError, lib, ptr, stream_ptr, walk_fields
+from ._lib import RvError, mosaic_call as _call, ptr
 from .codec import FrameCodec
 from .pca import L_MAX, LatentPCA, _rows, _vector
 from .stream import GraphReplay, StreamingVAE, each_stream
@@ -74,12 +74,6 @@ def check_components(k, rank):
     return int(k)
 
 
-def _call(op, **fields):
-    d = MosaicDesc(**fields)
-    lib().rv_mosaic(op, C.byref(d), None if op == _lib.WALK_WORKSPACE else stream_ptr())
-    return d
-
-
 def _workspace(T, k, L, device):
     n = _call(_lib.WALK_WORKSPACE, T=int(T), k=int(k), L=int(L)).ws_bytes
     return torch.empty(max(n, 1), dtype=torch.uint8, device=device), n
@@ -98,7 +92,7 @@ def lagcov(x, row_start, centre):
     c1 = torch.empty((L, L), dtype=torch.float64, device=x.device)
     ws, n = _workspace(T, 0, L, x.device)
     _call(_lib.PCA_LAGCOV, T=T, L=L, n_rows=rs.size - 1, q=ptr(x), row_start=ptr(rs_dev), ws=ptr(ws), ws_bytes=n,
-          **walk_fields(centre, c1))
+          centre=ptr(centre), basis=ptr(c1))
     return c1
 
 
@@ -156,19 +150,20 @@ class LatentWalk:
         dev = x.device
         res = torch.empty(2 * k * k + 2 * k * L, dtype=torch.float64, device=dev)
         ws, n = _workspace(0, k, L, dev)
-        _call(_lib.WALK_FIT, mode=_lib.WALK_DYNAMICS, k=k, L=L, ws=ptr(ws), ws_bytes=n,
-              **walk_fields(None, comp, lam, c1, res))
+        _call(_lib.WALK_FIT, mode=_lib.WALK_DYNAMICS, k=k, L=L, ws=ptr(ws), ws_bytes=n, basis=ptr(comp),
+              eigenvalues=ptr(lam), moment=ptr(c1), result=ptr(res))
         A, Q = res[:k * k].view(k, k), res[k * k:2 * k * k].view(k, k)
         Pm, R = res[2 * k * k:2 * k * k + k * L].view(k, L), res[2 * k * k + k * L:].view(k, L)
         dyn = torch.empty((2, k, k), dtype=torch.float64, device=dev)
         if self.mode == "diagonal":
-            _call(_lib.WALK_FIT, mode=_lib.WALK_DIAGONAL, k=k, L=L, **walk_fields(None, A, result=dyn))
+            _call(_lib.WALK_FIT, mode=_lib.WALK_DIAGONAL, k=k, L=L, basis=ptr(A), result=ptr(dyn))
             Q = None
         else:
             q, U, sweeps, converged = P_.eig(Q)
             if not converged:
                 raise RvError("LatentWalk.fit: the Jacobi eigensolver did not converge on Q in %d sweeps" % sweeps)
-            _call(_lib.WALK_FIT, mode=_lib.WALK_NOISE, k=k, L=L, **walk_fields(None, A, q, U, dyn))
+            _call(_lib.WALK_FIT, mode=_lib.WALK_NOISE, k=k, L=L, basis=ptr(A), eigenvalues=ptr(q), moment=ptr(U),
+                  result=ptr(dyn))
         self.lagcov_ = c1
         return self._set(pca.mean_, comp, lam, dyn, Pm.clone(), R.clone(), rank, T, rs.size - 1,
                          None if Q is None else Q.clone())
@@ -295,9 +290,8 @@ class StreamingWalk(GraphReplay):
     def _step(self, x, y, eps, stream):
         sd = self.stream.desc(x, y, eps)
         w = self.walk
-        d = MosaicDesc(live=C.pointer(sd), k=self.k, L=self.L, ldo=self.L,
-                       **walk_fields(w.mean_, w.R_, None, w.dyn_, self._z, self._state, self._primed))
-        lib().rv_mosaic(_lib.WALK_STEP, C.byref(d), stream)
+        _call(_lib.WALK_STEP, stream, live=C.pointer(sd), k=self.k, L=self.L, ldo=self.L, centre=ptr(w.mean_),
+              basis=ptr(w.R_), moment=ptr(w.dyn_), out=ptr(self._z), state=ptr(self._state), primed=ptr(self._primed))
 
     @torch.no_grad()
     def generate(self, eps=None):
@@ -312,7 +306,7 @@ class StreamingWalk(GraphReplay):
                     shape, self.device))
             eps = eps.contiguous()
         y = torch.empty((self.n_streams, self.block), dtype=torch.float32, device=self.device)
-        self._step(self._silence, y, eps, stream_ptr())
+        self._step(self._silence, y, eps, None)
         return y
 
     @torch.no_grad()

@@ -11,6 +11,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from conftest import REPO  # noqa: E402
+import abi_slots  # noqa: E402
 import align_oracle as O  # noqa: E402
 
 FAKE = 0x7000_0000_0000      # a non-null, 256-byte aligned address no check dereferences
@@ -155,11 +156,9 @@ def test_op_codes_and_field_roles_follow_the_header():
     # the ops before them keep their numbers, the descriptor its 37 eight-byte slots, the library its version
     assert (_lib.MOSAIC_KNN, _lib.EVAL_DIMS, _lib.PCA_WORKSPACE, _lib.WALK_WORKSPACE) == (0, 17, 21, 25)
     assert re.search(r"#define RV_WALK_WORKSPACE 25\b", text) and re.search(r"#define RV_MOSAIC_KNN 0\b", text)
-    assert len(_lib.MosaicDesc._fields_) == 37 and _lib.C.sizeof(_lib.MosaicDesc) == 37 * 8
+    assert len(abi_slots.check_layout()) == 37 and _lib.C.sizeof(_lib.MosaicDesc) == 37 * 8
     assert _lib.lib().rv_version() == 100
-    f = _lib.align_fields()
-    assert sorted(f) == ["c", "choice", "cost", "dist", "idx", "out", "q", "slot"] and not any(f.values())
-    _lib.MosaicDesc(**f)
+    # the roles' slots and element types: the table of test_audio_tools_cpu.py
 
 
 def _err(op, text, **fields):
@@ -180,11 +179,11 @@ def test_workspace_query_and_every_argument_error_names_its_field():
     assert A.workspace_bytes(2049, 2049) == up(2049 * 2049) + up(3 * 8 * 2049) + up(8 * 2049) + up(8 * 4097) + 256
     assert A.workspace_bytes(5000, 5000, 1024) == up(5000 * 2049) + up(3 * 8 * 5000) + up(8 * 5000) + up(8 * 9999) + 256
     shape = (("T", dict(T=0), "T=0 outside [1, 2^31)"), ("T", dict(T=1 << 31), "T=2147483648"),
-             ("N", dict(N=0), "N=0 outside [1, 2^31)"), ("width", dict(width=-1), "width=-1 outside"),
-             ("width", dict(T=5, N=40, width=3), "width=3: the band admits no path through T=5 by N=40; the least width "
+             ("N", dict(N=0), "N=0 outside [1, 2^31)"), ("width", dict(width=-1), "band=-1 outside"),
+             ("width", dict(T=5, N=40, width=3), "band=3: the band admits no path through T=5 by N=40; the least band "
                                                  "that does is 5"),
-             ("width", dict(T=1, N=9, width=2), "width=2: the band admits no path through T=1 by N=9; the least width that does is 8"),
-             ("cells", dict(T=1 << 20, N=1 << 20, width=0), "T=1048576 rows of 1048576 band slots (width=0) reach 2^31"))
+             ("width", dict(T=1, N=9, width=2), "band=2: the band admits no path through T=1 by N=9; the least band that does is 8"),
+             ("cells", dict(T=1 << 20, N=1 << 20, width=0), "T=1048576 rows of 1048576 band slots (band=0) reach 2^31"))
     for op, name in ((_lib.ALIGN_WORKSPACE, "ALIGN_WORKSPACE"), (_lib.ALIGN_COST, "ALIGN_COST"),
                      (_lib.ALIGN_FORWARD, "ALIGN_FORWARD"), (_lib.ALIGN_BACKTRACK, "ALIGN_BACKTRACK")):
         ok = dict(T=20, N=30, L=8, width=4, q=FAKE, c=FAKE, dist=FAKE, ws=FAKE, ws_bytes=1 << 30, slot=FAKE, choice=FAKE,
@@ -193,27 +192,27 @@ def test_workspace_query_and_every_argument_error_names_its_field():
             _err(op, "rv_mosaic(%s): %s" % (name, what), **dict(ok, **change))
     ok = dict(T=20, N=30, L=8, width=4, q=FAKE, c=FAKE, dist=FAKE)
     for change, what in ((dict(L=0), "L=0 outside [1, 4096]"), (dict(L=4097), "L=4097 outside [1, 4096]"),
-                         (dict(q=None), "a (q) is null"), (dict(c=None), "b (c) is null"),
-                         (dict(dist=None), "the local costs (dist) are null")):
+                         (dict(q=None), "a is null"), (dict(c=None), "b is null"),
+                         (dict(dist=None), "local_costs is null")):
         _err(_lib.ALIGN_COST, "rv_mosaic(ALIGN_COST): " + what, **dict(ok, **change))
     need = A.workspace_bytes(20, 30, 4)
     ok = dict(T=20, N=30, width=4, dist=FAKE, ws=FAKE, ws_bytes=need, mode=_lib.ALIGN_GLOBAL, lam=0.5)
     for change, what in ((dict(mode=2), "mode=2 is neither"), (dict(mode=-1), "mode=-1"),
-                         (dict(mode=_lib.ALIGN_SUBSEQUENCE), "width=4: RV_ALIGN_SUBSEQUENCE (mode) runs on the whole matrix"),
-                         (dict(lam=-1.0), "the step penalty lam=-1 must be finite and not negative"), (dict(lam=float("inf")), "the step penalty lam=inf"),
-                         (dict(lam=float("nan")), "the step penalty lam=nan"), (dict(dist=None), "the local costs (dist) are null"),
+                         (dict(mode=_lib.ALIGN_SUBSEQUENCE), "band=4: RV_ALIGN_SUBSEQUENCE (mode) runs on the whole matrix"),
+                         (dict(lam=-1.0), "penalty=-1 must be finite and not negative"), (dict(lam=float("inf")), "penalty=inf"),
+                         (dict(lam=float("nan")), "penalty=nan"), (dict(dist=None), "local_costs is null"),
                          (dict(ws=None), "ws is null"), (dict(ws=FAKE + 8), "ws is not 256-byte aligned"),
-                         (dict(ws_bytes=need - 1), "ws_bytes=%d, T=20 by N=30 at width=4 need %d" % (need - 1, need))):
+                         (dict(ws_bytes=need - 1), "ws_bytes=%d, T=20 by N=30 at band=4 need %d" % (need - 1, need))):
         _err(_lib.ALIGN_FORWARD, "rv_mosaic(ALIGN_FORWARD): " + what, **dict(ok, **change))
     ok = dict(T=20, N=30, width=4, dist=FAKE, ws=FAKE, ws_bytes=need, slot=FAKE, choice=FAKE, cost=FAKE)
-    for change, what in ((dict(dist=None), "the local costs (dist) are null"), (dict(slot=None), "the path (slot) is null"),
-                         (dict(choice=None), "the summary (choice) is null"), (dict(cost=None), "the two costs (cost) are null"),
+    for change, what in ((dict(dist=None), "local_costs is null"), (dict(slot=None), "the path is null"),
+                         (dict(choice=None), "the summary is null"), (dict(cost=None), "path_costs is null"),
                          (dict(ws=None), "ws is null"), (dict(ws_bytes=need - 1), "ws_bytes=%d" % (need - 1))):
         _err(_lib.ALIGN_BACKTRACK, "rv_mosaic(ALIGN_BACKTRACK): " + what, **dict(ok, **change))
     ok = dict(T=20, N=30, slot=FAKE, choice=FAKE, idx=FAKE, mode=_lib.ALIGN_ON_B)
     for change, what in ((dict(T=0), "T=0"), (dict(N=0), "N=0"), (dict(mode=3), "mode=3 is none of"),
-                         (dict(slot=None), "the path (slot) is null"), (dict(choice=None), "the summary (choice) is null"),
-                         (dict(idx=None), "the index table (idx) is null")):
+                         (dict(slot=None), "the path is null"), (dict(choice=None), "the summary is null"),
+                         (dict(idx=None), "warp_table is null")):
         _err(_lib.ALIGN_WARP, "rv_mosaic(ALIGN_WARP): " + what, **dict(ok, **change))
 
 

@@ -279,19 +279,19 @@ def test_every_error_names_its_field_and_leaves_the_outputs_untouched():
     wrp = dict(T=Ta, N=Tb, slot=gp.ptr, choice=gs.ptr, idx=gi.ptr, mode=_lib.ALIGN_ON_B)
     bad = [(_lib.ALIGN_COST, cost, dict(T=0), "T=0"), (_lib.ALIGN_COST, cost, dict(N=0), "N=0"),
            (_lib.ALIGN_COST, cost, dict(L=0), "L=0"), (_lib.ALIGN_COST, cost, dict(L=4097), "L=4097"),
-           (_lib.ALIGN_COST, cost, dict(width=-1), "width=-1"), (_lib.ALIGN_COST, cost, dict(T=3, N=40, width=2), "width=2"),
-           (_lib.ALIGN_COST, cost, dict(q=None), "a (q) is null"), (_lib.ALIGN_COST, cost, dict(c=None), "b (c) is null"),
-           (_lib.ALIGN_COST, cost, dict(dist=None), "(dist) are null"),
-           (_lib.ALIGN_FORWARD, fwd, dict(mode=5), "mode=5"), (_lib.ALIGN_FORWARD, fwd, dict(mode=1), "width=4"),
-           (_lib.ALIGN_FORWARD, fwd, dict(lam=-1.0), "lam=-1"), (_lib.ALIGN_FORWARD, fwd, dict(lam=float("nan")), "lam=nan"),
-           (_lib.ALIGN_FORWARD, fwd, dict(dist=None), "(dist) are null"), (_lib.ALIGN_FORWARD, fwd, dict(ws=None), "ws is null"),
+           (_lib.ALIGN_COST, cost, dict(width=-1), "band=-1"), (_lib.ALIGN_COST, cost, dict(T=3, N=40, width=2), "band=2"),
+           (_lib.ALIGN_COST, cost, dict(q=None), "a is null"), (_lib.ALIGN_COST, cost, dict(c=None), "b is null"),
+           (_lib.ALIGN_COST, cost, dict(dist=None), "local_costs is null"),
+           (_lib.ALIGN_FORWARD, fwd, dict(mode=5), "mode=5"), (_lib.ALIGN_FORWARD, fwd, dict(mode=1), "band=4"),
+           (_lib.ALIGN_FORWARD, fwd, dict(lam=-1.0), "penalty=-1"), (_lib.ALIGN_FORWARD, fwd, dict(lam=float("nan")), "penalty=nan"),
+           (_lib.ALIGN_FORWARD, fwd, dict(dist=None), "local_costs is null"), (_lib.ALIGN_FORWARD, fwd, dict(ws=None), "ws is null"),
            (_lib.ALIGN_FORWARD, fwd, dict(ws_bytes=ws.numel() - 1), "ws_bytes=%d" % (ws.numel() - 1)),
-           (_lib.ALIGN_BACKTRACK, back, dict(slot=None), "(slot) is null"),
-           (_lib.ALIGN_BACKTRACK, back, dict(choice=None), "(choice) is null"),
-           (_lib.ALIGN_BACKTRACK, back, dict(cost=None), "(cost) are null"),
+           (_lib.ALIGN_BACKTRACK, back, dict(slot=None), "the path is null"),
+           (_lib.ALIGN_BACKTRACK, back, dict(choice=None), "the summary is null"),
+           (_lib.ALIGN_BACKTRACK, back, dict(cost=None), "path_costs is null"),
            (_lib.ALIGN_BACKTRACK, back, dict(ws_bytes=16), "ws_bytes=16"), (_lib.ALIGN_BACKTRACK, back, dict(T=-2), "T=-2"),
-           (_lib.ALIGN_WARP, wrp, dict(mode=3), "mode=3"), (_lib.ALIGN_WARP, wrp, dict(idx=None), "(idx) is null"),
-           (_lib.ALIGN_WARP, wrp, dict(slot=None), "(slot) is null"), (_lib.ALIGN_WARP, wrp, dict(N=0), "N=0")]
+           (_lib.ALIGN_WARP, wrp, dict(mode=3), "mode=3"), (_lib.ALIGN_WARP, wrp, dict(idx=None), "warp_table is null"),
+           (_lib.ALIGN_WARP, wrp, dict(slot=None), "the path is null"), (_lib.ALIGN_WARP, wrp, dict(N=0), "N=0")]
     for op, ok, change, what in bad:
         with pytest.raises(_lib.RvError) as e:
             _lib.lib().rv_mosaic(op, _lib.C.byref(_lib.MosaicDesc(**dict(ok, **change))), _lib.stream_ptr())

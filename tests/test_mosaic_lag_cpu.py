@@ -14,6 +14,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from conftest import REPO  # noqa: E402
+import abi_slots  # noqa: E402
 import live_lag_oracle as G  # noqa: E402
 import live_mosaic_oracle as LO  # noqa: E402
 import mosaic_oracle as O  # noqa: E402
@@ -146,7 +147,7 @@ def test_header_adds_the_drain_op_and_nothing_else(tmp_path):
         assert re.search(r"#define RV_MOSAIC_%s %d\b" % (name, num), src), name
         assert getattr(_lib, "MOSAIC_" + name) == num
     assert len(re.findall(r"#define RV_MOSAIC_[A-Z_]+ \d+", src)) == len(OPS)
-    assert len(_lib.MosaicDesc._fields_) == 37 and C.sizeof(_lib.MosaicDesc) == 37 * 8
+    assert len(abi_slots.check_layout()) == 37 and C.sizeof(_lib.MosaicDesc) == 37 * 8
     c = tmp_path / "c.c"
     c.write_text('#include "rawvae_hip.h"\nint main(void) { rv_stream_desc s = {0}; rv_mosaic_desc d = {0}; d.live = &s; '
                  'd.rows = 8; return rv_mosaic(RV_MOSAIC_LIVE_DRAIN, &d, 0) + (int)sizeof(d) - 37 * 8; }\n')

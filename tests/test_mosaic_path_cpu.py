@@ -13,6 +13,7 @@ import pytest
 torch = pytest.importorskip("torch")
 
 from conftest import REPO  # noqa: E402
+import abi_slots  # noqa: E402
 import mosaic_oracle as O  # noqa: E402
 import mosaic_path_oracle as P  # noqa: E402
 
@@ -118,14 +119,7 @@ def test_header_adds_ops_and_fields_but_no_entry_point(tmp_path):
     for name in ("KNN", "KNN_WORKSPACE", "GATHER_MEAN", "OLA", "TRANSITION", "PATH_FORWARD", "PATH_BACKTRACK",
                  "PATH_WORKSPACE"):
         assert int(re.search(r"#define RV_MOSAIC_%s (\d+)" % name, src).group(1)) == getattr(_lib, "MOSAIC_" + name)
-    body = re.search(r"typedef struct rv_mosaic_desc \{(.*?)\} rv_mosaic_desc;", src, flags=re.S).group(1)
-    fields = []
-    for decl in body.split(";"):
-        decl = decl.strip()
-        if decl:
-            first, *rest = decl.split(",")
-            fields += [re.findall(r"\w+", first)[-1]] + [r.strip() for r in rest]
-    assert fields == [n for n, _ in _lib.MosaicDesc._fields_]
+    fields = abi_slots.check_layout()    # the slots' first names, the same in the header and in _lib
     assert fields[:25] == ["T", "k", "idx", "q", "c", "N", "L", "splits", "dist", "ws", "ws_bytes", "src", "src_len",
                            "row_start", "stride", "n_rows", "width", "out", "ldo", "frames", "F", "S", "hop", "window",
                            "n_out"]                                      # the existing fields stay where they were

@@ -350,7 +350,7 @@ def test_graph_replay_equals_eager_and_sees_the_controls():
 def test_argument_errors_name_the_field_and_touch_nothing():
     from rawaudiovae_kelsey_amd import _lib
     from rawaudiovae_kelsey_amd import walk as W
-    from rawaudiovae_kelsey_amd._lib import MosaicDesc, RvError, lib, ptr, stream_ptr, walk_fields
+    from rawaudiovae_kelsey_amd._lib import MosaicDesc, RvError, lib, ptr, stream_ptr
     model, walk = _setup(17)
     g = W.StreamingWalk(model, walk, 2, 16, 8, "hann", 1)
     g.generate()
@@ -362,15 +362,15 @@ def test_argument_errors_name_the_field_and_touch_nothing():
         sd = g.stream.desc(g._silence, y, None)
         for name in [n for n in change if n.startswith("live_")]:
             setattr(sd, name[5:], change.pop(name))
-        f = dict(live=C.pointer(sd), k=16, L=17, ldo=17,
-                 **walk_fields(walk.mean_, walk.R_, None, walk.dyn_, g._z, g._state, g._primed))
+        f = dict(live=C.pointer(sd), k=16, L=17, ldo=17, centre=ptr(walk.mean_), basis=ptr(walk.R_), moment=ptr(walk.dyn_),
+                 out=ptr(g._z), state=ptr(g._state), primed=ptr(g._primed))
         f.update(change)
         lib().rv_mosaic(_lib.WALK_STEP, C.byref(MosaicDesc(**f)), stream_ptr())
 
     for change, msg in ((dict(k=0), "k=0 outside"), (dict(k=18), "k=18 outside"), (dict(L=16), "L=16, the stream's model has L=17"),
-                        (dict(L=513), "L=513 outside"), (dict(trans=None), "centre \\(trans\\) is null"),
-                        (dict(dist=None), "R \\(dist\\) is null"), (dict(src=None), "\\(src\\) are null"),
-                        (dict(cost=None), "the state \\(cost\\) is null"), (dict(choice=None), "\\(choice\\) are null"),
+                        (dict(L=513), "L=513 outside"), (dict(centre=None), "centre is null"),
+                        (dict(basis=None), "basis \\(R\\) is null"), (dict(moment=None), "moment .* is null"),
+                        (dict(state=None), "the state is null"), (dict(primed=None), "the primed flags are null"),
                         (dict(ldo=16), "ldo=16 holds no row"), (dict(live=None), "\\(live\\) is null"),
                         (dict(live_temperature=None), "live->temperature is null"), (dict(live_y=None), "null buffer")):
         with pytest.raises(RvError, match=msg):
@@ -387,17 +387,17 @@ def test_argument_errors_name_the_field_and_touch_nothing():
     c1 = torch.full((17, 17), 7.0, dtype=torch.float64, device="cuda")
     ws = torch.zeros(W._workspace(257, 16, 17, "cuda")[1], dtype=torch.uint8, device="cuda")
     good = dict(T=257, L=17, n_rows=3, q=ptr(xd), row_start=ptr(rsd), ws=ptr(ws), ws_bytes=ws.numel(),
-                **walk_fields(pca.mean_, c1))
-    for change, msg in ((dict(T=1), "T=1 outside"), (dict(L=513), "L=513 outside"), (dict(n_rows=0), "n_files \\(n_rows\\)=0"),
-                        (dict(q=None), "x \\(q\\) is null"), (dict(row_start=None), "row_start is null"),
-                        (dict(trans=None), "centre \\(trans\\) is null"), (dict(dist=None), "\\(dist\\) is null"),
+                centre=ptr(pca.mean_), basis=ptr(c1))
+    for change, msg in ((dict(T=1), "T=1 outside"), (dict(L=513), "L=513 outside"), (dict(n_rows=0), "n_rows=0"),
+                        (dict(q=None), "q is null"), (dict(row_start=None), "row_start is null"),
+                        (dict(centre=None), "centre is null"), (dict(basis=None), "basis .* is null"),
                         (dict(ws_bytes=8), "ws_bytes=8"), (dict(ws=None), "ws is null")):
         with pytest.raises(RvError, match="PCA_LAGCOV.*" + msg):
             lib().rv_mosaic(_lib.PCA_LAGCOV, C.byref(MosaicDesc(**dict(good, **change))), stream_ptr())
-    for change, msg in ((dict(mode=3), "mode=3"), (dict(k=0), "k=0 outside"), (dict(out=None), "\\(out\\) is null"),
-                        (dict(src=None), "\\(src\\) is null"), (dict(ws_bytes=0), "ws_bytes=0")):
-        f = dict(mode=_lib.WALK_DYNAMICS, k=16, L=17, ws=ptr(ws), ws_bytes=ws.numel(),
-                 **walk_fields(None, pca.components_, pca.explained_variance_, c1, c1))
+    for change, msg in ((dict(mode=3), "mode=3"), (dict(k=0), "k=0 outside"), (dict(result=None), "result is null"),
+                        (dict(moment=None), "moment .* is null"), (dict(ws_bytes=0), "ws_bytes=0")):
+        f = dict(mode=_lib.WALK_DYNAMICS, k=16, L=17, ws=ptr(ws), ws_bytes=ws.numel(), basis=ptr(pca.components_),
+                 eigenvalues=ptr(pca.explained_variance_), moment=ptr(c1), result=ptr(c1))
         with pytest.raises(RvError, match="WALK_FIT.*" + msg):
             lib().rv_mosaic(_lib.WALK_FIT, C.byref(MosaicDesc(**dict(f, **change))), stream_ptr())
     with pytest.raises(RvError, match="WALK_WORKSPACE.*T=1 "):
