@@ -777,6 +777,47 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_ALIGN_ON_A 0
 #define RV_ALIGN_ON_B 1
 #define RV_ALIGN_ON_PATH 2
+/* Latent structure (csrc/structure.hip, rawaudiovae_kelsey_amd/structure.py): where a latent
+ * trajectory changes.  A novelty curve from the banded self-distance matrix of the trajectory, and the boundaries picked
+ * from it.  The family's conventions: no op syncs or reads a device pointer on the host, each may run under capture, and
+ * each returns an RV_ERR_* whose message names the field before anything is launched: T, band, k, lag, width, lam, a null
+ * local_costs / moment / result / path / summary / ws, ws_bytes too small.
+ * The matrix.  RV_ALIGN_COST with a = b = mu [T, L] and N = T writes Dm [T, W] fp32: centre(i) = i, so band = 0 is the
+ * whole matrix (W = T, the column of j is j) and band = r >= 1 keeps |j - i| <= r (W = 2 r + 1, the column of j is
+ * j - i + r).  T W < 2^31.
+ * RV_STRUCT_NOVELTY: T >= 1, local_costs = Dm, band = 0 or r >= 2 R - 1 (a narrower band is RV_ERR_SHAPE naming band and
+ *   2 R - 1, the least that holds the window), k = R, the half-width of the kernel in frames, 1 <= R <= 512,
+ *   moment = the taper w [2 R] fp64 on the device -> result = nov [T] fp64.  For frame t the offsets u, v run over
+ *   [-R, R), i = t + u, j = t + v; a term whose i or j is outside [0, T) is skipped, by index (the +inf of such a band
+ *   slot is never read).  c(u, v) = fl64(w[u + R] * w[v + R]), d = (double)Dm[i, col(j)]; a term is CROSS when
+ *   (u < 0) != (v < 0), WITHIN otherwise.  Row u has four fp64 chains over ascending v, each from +0:
+ *   cross_u += fl64(c * d) and wc_u += c over its cross terms, within_u += fl64(c * d) and ww_u += c over its within
+ *   terms: every product is rounded before it is added, nothing is contracted into an fma.  The four row results are
+ *   added over ascending u from +0 into Cross, Wc, Within, Ww, and nov[t] = Cross / Wc - Within / Ww when Wc > 0 and
+ *   Ww > 0, +0 otherwise (t = 0 has no past: +0).  A NaN in Dm makes NaN exactly the nov[t] whose window holds it.  A
+ *   thread per (frame t, row u), 1024 threads to a workgroup: it takes floor(1024 / 2R) consecutive frames and stages
+ *   the window they share once, through LDS in chunks of 32 columns, the chains carried across the chunks in
+ *   ascending v; the row results go through LDS and one lane per (frame, chain) adds them in ascending u.  One launch,
+ *   no atomics; the bits depend on Dm, T, R and w only, not on the band or on the launch: the whole matrix and any
+ *   admissible band give the same bits.
+ * RV_STRUCT_PEAKS: T >= 1, moment = nov [T] fp64, lag = g, the minimum gap in frames, 0 <= g <= 65536, width = m, the
+ *   radius of the local mean, 0 <= m <= 65536, lam = delta, finite and >= 0, ws / ws_bytes -> path = offsets [T + 1]
+ *   int32, summary [4] int32.  G = the mean of |nov[t]| over the finite entries: RV_EVAL_DIMS's order (blocks of 256 rows
+ *   added in ascending t from +0, the block sums added in ascending order from +0), one division by their count, 0 when
+ *   there is none.  m[t] = the mean of the finite nov[t'], t' in [max(0, t - m), min(T - 1, t + m)], added in ascending
+ *   t' from +0 and divided once by their count.  With ge = max(g, 1), frame t is a boundary iff ge <= t <= T - ge and
+ *   t < T; nov[t] is finite; nov[t] > fl64(m[t] + fl64((double)delta * G)); nov[t] > nov[t'] for every finite t' in
+ *   [t - g, t); nov[t] >= nov[t'] for every finite t' in (t, t + g].  Ties go to the earlier frame; a NaN never wins
+ *   and is never compared.  Two boundaries are more than g frames apart and every segment is non-empty.
+ *   path[0] = 0, then the boundaries in ascending order, path[F] = T, then -1 up to path[T]; F >= 1 is the number of
+ *   segments; summary = {F, the number of finite entries of nov, 0, 0}.  Every entry of path and summary is written, each
+ *   by one thread; the compaction is a scan in ascending t (per 256 frames, then over the blocks), no atomics.  Five
+ *   launches.
+ * RV_STRUCT_WORKSPACE: the bytes of ws of RV_STRUCT_PEAKS for T in d->ws_bytes; launches nothing and touches no device.
+ *   ws is 256-byte aligned. */
+#define RV_STRUCT_NOVELTY 31
+#define RV_STRUCT_PEAKS 32
+#define RV_STRUCT_WORKSPACE 33
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the

@@ -107,9 +107,10 @@ LIVE_GRAINS, LIVE_DECODE = 0, 1   # RV_LIVE_*
 ALIGN_COST, ALIGN_FORWARD, ALIGN_BACKTRACK, ALIGN_WARP, ALIGN_WORKSPACE = 26, 27, 28, 29, 30   # RV_ALIGN_* (rv_mosaic)
 ALIGN_GLOBAL, ALIGN_SUBSEQUENCE = 0, 1        # RV_ALIGN_FORWARD's mode
 ALIGN_ON_A, ALIGN_ON_B, ALIGN_ON_PATH = 0, 1, 2   # RV_ALIGN_WARP's mode (the timeline)
+STRUCT_NOVELTY, STRUCT_PEAKS, STRUCT_WORKSPACE = 31, 32, 33   # RV_STRUCT_* (rv_mosaic)
 
 _HOST_ONLY_OPS = frozenset((MOSAIC_KNN_WORKSPACE, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_PATH_WORKSPACE, MOSAIC_LIVE_WORKSPACE,
-                            PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE))   # mosaic_call: they launch nothing
+                            PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE, STRUCT_WORKSPACE))   # mosaic_call: they launch nothing
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

@@ -169,3 +169,9 @@ RV_INTERNAL int rv_align_forward(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_align_backtrack(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_align_warp(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_align_workspace(rv_mosaic_desc* d);
+// The structure ops of rv_mosaic (structure.hip): RV_STRUCT_NOVELTY and RV_STRUCT_PEAKS on the fields the public header
+// names for them -- checks first, then the launches, no sync and no read of the device -- and RV_STRUCT_WORKSPACE, which
+// writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_struct_novelty(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_struct_peaks(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_struct_workspace(rv_mosaic_desc* d);

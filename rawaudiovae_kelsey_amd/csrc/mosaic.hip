@@ -1421,6 +1421,9 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
     case RV_ALIGN_BACKTRACK: return rv_align_backtrack(d, stream);
     case RV_ALIGN_WARP: return rv_align_warp(d, stream);
     case RV_ALIGN_WORKSPACE: return rv_align_workspace(d);
+    case RV_STRUCT_NOVELTY: return rv_struct_novelty(d, stream);
+    case RV_STRUCT_PEAKS: return rv_struct_peaks(d, stream);
+    case RV_STRUCT_WORKSPACE: return rv_struct_workspace(d);
     default:
       RV_REQUIRE(false, RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
   }
