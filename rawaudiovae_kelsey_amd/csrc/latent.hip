@@ -43,6 +43,34 @@ __device__ __forceinline__ void dma16(const bf16_t* g, lds_char* l) {
   __builtin_amdgcn_global_load_lds((glb_cptr)g, (__attribute__((address_space(3))) void*)l, 16, 0, 0);
 }
 
+// load_frag<ROWS, false> (gemm_bf16.h: the MN-major image's transposing reads) for loops that keep LDS-DMA in flight
+// ACROSS the reads.  The compiler cannot tell which LDS bytes a global_load_lds in flight will write, so in front of
+// every ds_read_b64_tr_b16 of its own (the builtin carries no memory operand to compare; plain ds_read_b128 / _b64 of
+// the same images get no such wait) it waits for all of them (s_waitcnt vmcnt(0)), and a loop's counted vmcnt waits
+// are moot: each step then also waits for the slots requested one and two steps ahead.  Reads issued from inline assembly
+// leave the waiting to the loop: the caller waits for vmcnt itself BEFORE the reads, and passes the fragments through
+// lds_landed() (behind its own s_waitcnt lgkmcnt(0)) before their first use: volatile asm statements keep their
+// order, so no use can be scheduled ahead of that wait.
+struct frag_mn {
+  v2i32_ lo, hi;
+};
+template <int ROWS>
+__device__ __forceinline__ frag_mn load_frag_mn_async(const lds_char* lds, int row0, int kk, int lane) {
+  constexpr int RB = ROWS * 2;
+  const int k = kk * 32 + 8 * (lane >> 4) + ((lane & 15) >> 2);
+  const int c32 = (row0 >> 4) ^ swz_mn<ROWS>(k);
+  const lds_char* a = lds + k * RB + c32 * 32 + (lane & 3) * 8;
+  frag_mn f;
+  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(f.hi) : "v"(a), "i"(4 * RB) : "memory");
+  return f;
+}
+__device__ __forceinline__ void lds_landed(frag_mn& f) { asm volatile("" : "+v"(f.lo), "+v"(f.hi)); }
+__device__ __forceinline__ bf16x8 frag_bits(const frag_mn& f) {
+  const v4i32_ v = {f.lo[0], f.lo[1], f.hi[0], f.hi[1]};
+  return __builtin_bit_cast(bf16x8, v);
+}
+
 // `rows` (a multiple of 8) rows of 64 bf16 starting at g (row stride ld) -> K-major LDS image at sl
 template <int ROWS>
 __device__ __forceinline__ void stage_rows(const bf16_t* g, long ld, lds_char* sl, int lane) {
@@ -319,6 +347,14 @@ __device__ __forceinline__ void stage_rows_mn64(const bf16_t* g, long ld, lds_ch
 // split-K GEMM on 64 x 64 tiles (gemm_bf16.h's body, same 256 threads): it needs nothing this launch produces, and with
 // 80 KiB of LDS per workgroup a dz block and a dW3 block share every CU, so the second read of dP3 fills the bubbles of
 // the first instead of lengthening another launch.  The last block finishes the loss scalar.
+// Bytes in flight.  A wave has two steps of its ring outstanding (2 x (2 KiB dP3 + 8 KiB W3)): 16 KiB of first-touch dP3
+// per workgroup out of the 64 KiB its 16 rows need.  Until the transposing reads moved into assembly (load_frag_mn_async)
+// the compiler put s_waitcnt vmcnt(0) in front of them, so step s also waited for step s + 1 and the vmcnt(10) below
+// decided nothing.  Tried on top of that and REMOVED: the wave's whole dP3 slice requested before the ring starts, into
+// registers in fragment layout (16 x 16-byte loads per lane at Hp = 2048, 184 VGPRs, no scratch, still two workgroups per
+// CU; predicted 11.5 -> 7-8 us from 2-3 us of HBM latency on 16 KiB in flight).  Measured: no gain, the step 178.7-180.2
+// us against 178.6-179.6 for the parent and 176.6-177.4 for the assembly reads alone (four interleaved rounds, one box;
+// profiles/latent_bwd_burst_ab.txt).  The dP3 stream is not what this launch waits for.
 constexpr int LB_WAVES = 4;
 constexpr int LB_LDS = LB_WAVES * L_RING;   // 80 KiB: two workgroups per CU
 
@@ -409,19 +445,26 @@ k_latent_bwd(const bf16_t* __restrict__ dP3, const long lddp, const bf16_t* __re
     if (s + 1 < NU) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const lds_char* ws = (s & 1) ? W1 : W0;
-    bf16x8 x[2], w[4][2];
+    bf16x8 x[2];
+    frag_mn w[4][2];   // (transposing reads from assembly: see load_frag_mn_async -- the vmcnt(10) above is the loop's only wait)
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) x[kk] = load_frag<16, true>(ring + LX_OFF + (s & 1) * LX_SLOT, 0, kk, lane);
 #pragma unroll
     for (int cb = 0; cb < 4; ++cb)
 #pragma unroll
-      for (int kk = 0; kk < 2; ++kk) w[cb][kk] = load_frag<64, false>(ws, cb * 16, kk, lane);
+      for (int kk = 0; kk < 2; ++kk) w[cb][kk] = load_frag_mn_async<64>(ws, cb * 16, kk, lane);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // fragments are in registers: both slots may be refilled
+#pragma unroll
+    for (int cb = 0; cb < 4; ++cb)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) lds_landed(w[cb][kk]);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) asm volatile("" : "+v"(x[kk]));   // (x too is read before its slot is requested again)
     if (s + 2 < NU) issue(s + 2);
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[cb][kk], x[kk], acc[cb], 0, 0, 0);
+      for (int cb = 0; cb < 4; ++cb) acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_bits(w[cb][kk]), x[kk], acc[cb], 0, 0, 0);
   }
   // lane (q, j) holds partial dz[j][16 cb + 4 q + e]: park the wave's 16 x 64 partial sums in its weight slot 0 (256-byte
   // rows: the 16-byte quad index XOR j & 7 spreads the eight lanes of a store group over the banks, as in k_latent_fwd)
@@ -484,6 +527,16 @@ k_latent_bwd(const bf16_t* __restrict__ dP3, const long lddp, const bf16_t* __re
 // the next tile's loads fly while this tile's dP1 is stored.  dWh accumulates in registers over the 8 tiles and leaves
 // as one fp32 slab per 512-row group (the split-K partials rv_adam_multi sums), the column sums of dP1 (fc1's bias
 // gradient) as one partial row per group.
+// Bytes in flight.  With three stages and tile t + 2 requested behind tile t's barrier, two tiles are outstanding per CU:
+// 16 KiB of first-touch h1 (out of the workgroup's 64 KiB) and 64 KiB of dmulv, which every column strip re-reads from L2.
+// The loop's transposing LDS reads are issued from assembly (load_frag_mn_async): as compiler reads they had a full
+// s_waitcnt vmcnt(0) in front of them, BEHIND issue_stage(t + 2), so every tile waited for the stage it had just
+// requested and wait_vm_exact decided nothing: 14.1 -> 12.9 us in the step.  Tried on top of that and REMOVED: all 64
+// KiB of h1 requested in the prologue into 8 resident tile images, dmulv alone ringing through three 32 KiB stages (the
+// third recycled from the Wh slice and the h1 images of tiles 0 and 1; 144 KiB; predicted 14.3 -> 9-10 us from 2-3 us of
+// HBM latency on 16 KiB in flight).  Measured: 14.7 us in the step, the step 178.7-182.3 us against 178.6-179.6 for the
+// parent and 176.6-177.4 for the assembly reads alone (four interleaved rounds, one box;
+// profiles/latent_bwd_burst_ab.txt).  The first-touch stream's latency is not what bounds this kernel either.
 constexpr int HB_TR = 64;                       // rows per tile
 constexpr int HB_RG = 512;                      // rows per workgroup
 constexpr int HB_AK = 2 * 8192;                 // dmulv tile, K-major (rows x 128 k as two 64-k images): dgrad's operand
@@ -600,13 +653,26 @@ k_heads_bwd(const bf16_t* __restrict__ dmulv, const bf16_t* __restrict__ Wh, con
     __builtin_amdgcn_s_barrier();         // ... and so has everybody else's -- and every wave has finished tile t - 1:
     asm volatile("" ::: "memory");        // ITS stage is free, and takes tile t + 2 (ONE barrier per tile, three stages)
     if (t + 2 < NT) issue_stage(t + 2, (t + 2) % HB_NS);
+    // (the transposing reads below come from assembly -- see load_frag_mn_async: with the compiler's reads, a full
+    // vmcnt(0) stood in front of them, BEHIND issue_stage(t + 2), and every tile waited for the stage it had just requested)
     if (t == 0) {
+      frag_mn f[2][2][2];
 #pragma unroll
       for (int half = 0; half < 2; ++half)
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
-          for (int c = 0; c < 2; ++c) wf[half][kk][c] = load_frag<64, false>(whI + half * 8192, (2 * cp + c) * 16, kk, lane);
+          for (int c = 0; c < 2; ++c) f[half][kk][c] = load_frag_mn_async<64>(whI + half * 8192, (2 * cp + c) * 16, kk, lane);
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+      for (int half = 0; half < 2; ++half)
+#pragma unroll
+        for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+          for (int c = 0; c < 2; ++c) {
+            lds_landed(f[half][kk][c]);
+            wf[half][kk][c] = frag_bits(f[half][kk][c]);
+          }
     }
     // ---- dgrad: rows 16 rb + j, columns 32 cp .. +31, K = 128
     f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -621,15 +687,25 @@ k_heads_bwd(const bf16_t* __restrict__ dmulv, const bf16_t* __restrict__ Wh, con
     // ---- dWh += dmulv_tile^T h1_tile: row block `wave` of l, contraction over the tile's 64 rows
     const lds_char* am = st + HB_AK;
     const lds_char* hm = st + HB_AK + HB_AM;
+    frag_mn xa[2], hb[2][4];
 #pragma unroll
     for (int kk = 0; kk < 2; ++kk) {
-      const bf16x8 xa = load_frag<128, false>(am, wave * 16, kk, lane);
+      xa[kk] = load_frag_mn_async<128>(am, wave * 16, kk, lane);
 #pragma unroll
-      for (int cb = 0; cb < 4; ++cb) {
-        const bf16x8 hb = load_frag<64, false>(hm, cb * 16, kk, lane);
-        acc2[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(hb, xa, acc2[cb], 0, 0, 0);
-      }
+      for (int cb = 0; cb < 4; ++cb) hb[kk][cb] = load_frag_mn_async<64>(hm, cb * 16, kk, lane);
     }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      lds_landed(xa[kk]);
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb) lds_landed(hb[kk][cb]);
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int cb = 0; cb < 4; ++cb)
+        acc2[cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_bits(hb[kk][cb]), frag_bits(xa[kk]), acc2[cb], 0, 0, 0);
     // ---- ReLU mask from the same h1 tile (element (row r, column c) of the MN-major image), column sums
     const int r = 16 * rb + j;
     float v[2][4];
