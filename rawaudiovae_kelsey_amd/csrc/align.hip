@@ -1,8 +1,8 @@
 // Time alignment of two latent trajectories (rawaudiovae_kelsey_amd/align.py): banded dynamic time warping over the
 // encoder's mu rows.  Five ops of rv_mosaic; the rules: include/rawvae_hip.h, "Latent alignment"; the design and the
 // measured figures: DESIGN.md section 7.12.
-//   RV_ALIGN_COST       the local costs of the band, the search's distance bit for bit: k_align_cost, k_knn_topk's
-//                       128 x 64 register tile over (row block, column tile of the block's band); the finished tile
+//   RV_ALIGN_COST       the local costs of the band, the search's distance bit for bit: k_align_cost, sqdist.h's
+//                       register tile over (row block, column tile of the block's band); the finished tile
 //                       goes through LDS and out in rows of 64 consecutive band slots.  No atomics, one launch.
 //   RV_ALIGN_FORWARD    the DP in fp64: k_align_forward, ONE workgroup of 1024 threads over the anti-diagonals, three
 //                       rolling diagonals of C in LDS (or in ws beyond FW_DIAG_LDS cells), a __syncthreads() between
@@ -16,15 +16,13 @@
 
 #include "common.h"
 #include "internal.h"
+#include "sqdist.h"
 
 using namespace rv;
+using namespace rv::sqd;
 
 namespace {
 
-// k_knn_topk's tile (mosaic.hip): every distance is its arithmetic bit for bit
-constexpr int BR = 128, BN = 64, KT = 32, TR = 8, TN = 4, PAD = 4, DPAD = 1;
-constexpr int STAGE_FLOATS = KT * (BR + PAD) + KT * (BN + PAD), DIST_FLOATS = BR * (BN + DPAD);
-constexpr int SMEM_FLOATS = STAGE_FLOATS > DIST_FLOATS ? STAGE_FLOATS : DIST_FLOATS;
 constexpr int AL_LMAX = 4096;
 constexpr int FW_THREADS = 1024;
 constexpr int FW_DIAG_LDS = 2048;   // cells of the longest diagonal up to which the rolling diagonals live in LDS
@@ -66,55 +64,10 @@ k_align_cost(const float* __restrict__ a, const float* __restrict__ b, long L, b
   const long m0 = jfirst + BN * t;
   if (m0 > jlast) return;   // the band of these rows has fewer tiles than the widest row block
   const bool inside = m0 + BN > 0 && m0 < g.Tb;
-  float tot[TR][TN];
-#pragma unroll
-  for (int i = 0; i < TR; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) tot[i][j] = 0.f;
-  if (inside) {
-    for (long k0 = 0; k0 < L; k0 += KT) {
-      // out-of-range rows and k are zeros: (0 - 0)^2 adds an exact 0
-#pragma unroll
-      for (int s = 0; s < KT * BR / 256; ++s) {
-        const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-        const long gk = k0 + kk, gr = r0 + rr;
-        Xs[kk][rr] = (gr < g.Ta && gk < L) ? a[gr * L + gk] : 0.f;
-      }
-#pragma unroll
-      for (int s = 0; s < KT * BN / 256; ++s) {
-        const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-        const long gk = k0 + kk, gm = m0 + rr;
-        Ws[kk][rr] = (gm >= 0 && gm < g.Tb && gk < L) ? b[gm * L + gk] : 0.f;
-      }
-      __syncthreads();
-      // this K tile's sum of (x - c)^2, each term one fma in ascending k; then tot += part (k_knn_topk's two levels)
-      float part[TR][TN];
-#pragma unroll
-      for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) part[i][j] = 0.f;
-#pragma unroll 4
-      for (int kk = 0; kk < KT; ++kk) {
-        const f32x4 xa = *reinterpret_cast<const f32x4*>(&Xs[kk][tr * TR]);
-        const f32x4 xb = *reinterpret_cast<const f32x4*>(&Xs[kk][tr * TR + 4]);
-        const f32x4 wa = *reinterpret_cast<const f32x4*>(&Ws[kk][tn * TN]);
-        const float xv[TR] = {xa[0], xa[1], xa[2], xa[3], xb[0], xb[1], xb[2], xb[3]};
-        const float wv[TN] = {wa[0], wa[1], wa[2], wa[3]};
-#pragma unroll
-        for (int i = 0; i < TR; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float d = xv[i] - wv[j];
-            part[i][j] = __builtin_fmaf(d, d, part[i][j]);
-          }
-      }
-#pragma unroll
-      for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) tot[i][j] += part[i][j];
-      __syncthreads();
-    }
-  }
+  float tot[TR][TN] = {};
+  if (inside)
+    tile_sq_dist(Xs, Ws, a, b, r0, m0, L, [&](long gr) { return gr < g.Ta; },
+                 [&](long gm) { return gm >= 0 && gm < g.Tb; }, tot);
 #pragma unroll
   for (int i = 0; i < TR; ++i)
 #pragma unroll

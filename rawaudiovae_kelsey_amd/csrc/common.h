@@ -95,6 +95,9 @@ __device__ __forceinline__ float fast_tanh(float y) {
   return 1.0f - 2.0f * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// blocks of a grid-stride launch over n items: at least one, at most cap
+inline unsigned blocks_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n > cap ? cap : n)); }
+
 }  // namespace rv
 
 // Slots of the fp8 state block (workspace buffer "fp8_state"; the layout is documented under RV_OPT_FP8 in the public

@@ -18,25 +18,19 @@
 
 #include "common.h"
 #include "internal.h"
+#include "sqdist.h"
 
 using namespace rv;
+using namespace rv::sqd;
 
 namespace {
 
-// k_knn_topk tile: rv_som_bmu's (BR query rows x BN corpus rows per step, KT latent elements per LDS stage, 16 x 16
-// threads each owning an 8 x 4 register tile), so every distance is its arithmetic bit for bit.  The finished
-// BR x BN distance tile goes through LDS and is scanned by two lanes per query row, each keeping a sorted top-KM
-// list in registers over its half of the corpus rows: 2 KM VGPRs per lane instead of 8 rows x 2 KM.
-constexpr int BR = 128, BN = 64, KT = 32, TR = 8, TN = 4, PAD = 4, DPAD = 1;
-constexpr int STAGE_FLOATS = KT * (BR + PAD) + KT * (BN + PAD), DIST_FLOATS = BR * (BN + DPAD);
-constexpr int SMEM_FLOATS = STAGE_FLOATS > DIST_FLOATS ? STAGE_FLOATS : DIST_FLOATS;
+// k_knn_topk: sqdist.h's tile over BR query rows x BN corpus rows per step.  The finished BR x BN distance tile goes
+// through LDS and is scanned by two lanes per query row, each keeping a sorted top-KM list in registers over its half
+// of the corpus rows: 2 KM VGPRs per lane instead of 8 rows x 2 KM.
 constexpr int KMAX = 16;
 constexpr long TARGET_BLOCKS = 1024;   // 4 workgroups per CU of a 256-CU MI355X
 constexpr long MIN_SPLIT_TILES = 4;    // corpus tiles per split before a search is split further
-
-// (d, i) < (e, j) in the order "smaller distance, then lower index" (rv_som_bmu's): a total order on the candidates of
-// one query row (corpus indices are distinct), so the top k do not depend on the visiting order.  NaN never wins.
-__device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
 
 // sorted insert by a compare-and-swap cascade over static indices (selects only): the list stays in registers
 template <int KM>
@@ -79,52 +73,7 @@ k_knn_topk(const float* __restrict__ q, long T, const float* __restrict__ c, lon
   for (int s = 0; s < KM; ++s) { bd[s] = INFINITY; bi[s] = INT_MAX; }
   for (long m0 = n_lo; m0 < n_hi; m0 += BN) {
     float tot[TR][TN];
-#pragma unroll
-    for (int i = 0; i < TR; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) tot[i][j] = 0.f;
-    for (long k0 = 0; k0 < L; k0 += KT) {
-      // out-of-range rows and k are zeros: (0 - 0)^2 adds an exact 0
-#pragma unroll
-      for (int s = 0; s < KT * BR / 256; ++s) {
-        const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-        const long gk = k0 + kk, gr = r0 + rr;
-        Xs[kk][rr] = (gr < T && gk < L) ? q[gr * L + gk] : 0.f;
-      }
-#pragma unroll
-      for (int s = 0; s < KT * BN / 256; ++s) {
-        const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-        const long gk = k0 + kk, gm = m0 + rr;
-        Ws[kk][rr] = (gm < n_hi && gk < L) ? c[gm * L + gk] : 0.f;
-      }
-      __syncthreads();
-      // this K tile's sum of (x - c)^2, each term one fma in ascending k; then tot += part (rv_som_bmu's two levels)
-      float part[TR][TN];
-#pragma unroll
-      for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) part[i][j] = 0.f;
-#pragma unroll 4
-      for (int kk = 0; kk < KT; ++kk) {
-        const f32x4 xa = *reinterpret_cast<const f32x4*>(&Xs[kk][tr * TR]);
-        const f32x4 xb = *reinterpret_cast<const f32x4*>(&Xs[kk][tr * TR + 4]);
-        const f32x4 wa = *reinterpret_cast<const f32x4*>(&Ws[kk][tn * TN]);
-        const float xv[TR] = {xa[0], xa[1], xa[2], xa[3], xb[0], xb[1], xb[2], xb[3]};
-        const float wv[TN] = {wa[0], wa[1], wa[2], wa[3]};
-#pragma unroll
-        for (int i = 0; i < TR; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float d = xv[i] - wv[j];
-            part[i][j] = __builtin_fmaf(d, d, part[i][j]);
-          }
-      }
-#pragma unroll
-      for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) tot[i][j] += part[i][j];
-      __syncthreads();
-    }
+    tile_sq_dist(Xs, Ws, q, c, r0, m0, L, [&](long gr) { return gr < T; }, [&](long gm) { return gm < n_hi; }, tot);
 #pragma unroll
     for (int i = 0; i < TR; ++i)
 #pragma unroll
@@ -218,11 +167,10 @@ k_knn_merge(const float* __restrict__ ws_d, const int* __restrict__ ws_i, long T
 // k_knn_topk pads its queries to tiles of BR = 128 rows; a live block has 1..16.  Here one thread owns one corpus row
 // of a run of SRUN, a block walks the runs of its split, and a pass covers up to SQ query rows, so the corpus is read
 // once per pass.  Each KT-wide slice of the run goes through LDS (16-byte global loads, eight lanes per row, one slice
-// ahead in registers; row stride KT + 4 floats, so the b128 reads of 16 consecutive rows cover all 64 banks).  The
-// query values are wave-uniform and come through the scalar cache.  A pair's arithmetic is k_knn_topk's: fmaf(d, d,
-// part) in ascending l within the slice, tot += part per slice from +0.  The run's TQ x SRUN distances go through LDS
-// to SRUN / TQ lanes per query row, each with a sorted top-KM list; at the end one wave per query row merges them.
-constexpr int SQ = 16, SRUN = 256, SROW = KT + 4, SLD4 = SRUN * (KT / 4) / 256;
+// ahead in registers; row stride SLICE_ROW).  The query values are wave-uniform and come through the scalar cache.  A
+// pair's arithmetic is sqdist.h's, a slice being a tile.  The run's TQ x SRUN distances go through LDS to SRUN / TQ
+// lanes per query row, each with a sorted top-KM list; at the end one wave per query row merges them.
+constexpr int SQ = 16, SRUN = 256, SLD4 = SRUN * (KT / 4) / 256;
 // Query rows RV_MOSAIC_KNN_SMALL accepts, and up to which RV_MOSAIC_LIVE searches with it: measured faster than
 // k_knn_topk at every T up to here (1.4-1.9x at 64 rows, 4-10x at 16 and fewer against 1.24 M corpus rows; section 7.6)
 constexpr int SMALL_T_MAX = 4 * SQ;
@@ -245,8 +193,9 @@ template <int KM, int TQ, bool VEC>
 __global__ void __launch_bounds__(256)
 k_knn_small(const float* __restrict__ q, int T, const float* __restrict__ c, long N, long L, int k, long per_split,
             int n_splits, int* __restrict__ idx, float* __restrict__ dist, float* __restrict__ ws_d) {
-  static_assert(SRUN * SROW >= 2 * 256 * KM && SRUN * SROW >= TQ * SRUN, "the lists and the distances fit the stage");
-  __shared__ __attribute__((aligned(16))) float smem[SRUN * SROW];
+  static_assert(SRUN * SLICE_ROW >= 2 * 256 * KM && SRUN * SLICE_ROW >= TQ * SRUN,
+                "the lists and the distances fit the stage");
+  __shared__ __attribute__((aligned(16))) float smem[SRUN * SLICE_ROW];
   constexpr int LPQ = SRUN / TQ;   // lanes per query row in the scan
   const int tid = threadIdx.x, srow = tid / LPQ, ssub = tid % LPQ;
   const int t0 = blockIdx.x * SQ, split = blockIdx.y;
@@ -265,21 +214,10 @@ k_knn_small(const float* __restrict__ q, int T, const float* __restrict__ c, lon
     for (int u = 0; u < SLD4; ++u) {
       const int e = tid + 256 * u;
       const long gm = m0 + (e >> 3), gk = k0 + (e & 7) * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (gm < n_hi) {
-        const float* p = c + gm * L + gk;
-        if constexpr (VEC) {
-          if (gk < L) v = *reinterpret_cast<const f32x4*>(p);   // L % 4 == 0: the whole vector is inside the row
-        } else {
-#pragma unroll
-          for (int x = 0; x < 4; ++x)
-            if (gk + x < L) v[x] = p[x];
-        }
-      }
-      pre[u] = v;
+      pre[u] = gm < n_hi ? slice_fetch4(c + gm * L, gk, L, VEC) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   };
-  const float* crow = smem + tid * SROW;
+  const float* crow = smem + tid * SLICE_ROW;
   fetch(n_lo, 0);
   for (long m0 = n_lo; m0 < n_hi; m0 += SRUN) {
     float tot[TQ];
@@ -289,7 +227,7 @@ k_knn_small(const float* __restrict__ q, int T, const float* __restrict__ c, lon
 #pragma unroll
       for (int u = 0; u < SLD4; ++u) {
         const int e = tid + 256 * u;
-        *reinterpret_cast<f32x4*>(smem + (e >> 3) * SROW + (e & 7) * 4) = pre[u];
+        *reinterpret_cast<f32x4*>(smem + (e >> 3) * SLICE_ROW + (e & 7) * 4) = pre[u];
       }
       __syncthreads();
       const bool wrap = k0 + KT >= L;
@@ -413,48 +351,9 @@ k_ola(const float* __restrict__ frames, long F, long S, long hop, const float* _
 
 // ---- Unit selection over the candidates ("Continuity") ----
 
-// The search's distance, shared by every kernel of the unit selection (k_transition, k_live_select, k_live_lag) so that
-// their costs are k_knn_topk's bit for bit: part = fmaf(d, d, part) in ascending l within tiles of KT, tot += part per
-// tile, from +0.
-__device__ __forceinline__ void sq_acc4(float& part, const f32x4& a, const f32x4& b) {
-#pragma unroll
-  for (int x = 0; x < 4; ++x) {
-    const float d = a[x] - b[x];
-    part = __builtin_fmaf(d, d, part);
-  }
-}
-
-// D(a, b) of two latent rows in global memory, element by element
-__device__ __forceinline__ float row_sq_dist(const float* __restrict__ a, const float* __restrict__ b, long L) {
-  float tot = 0.f;
-  for (long k0 = 0; k0 < L; k0 += KT) {
-    const int n = L - k0 < KT ? (int)(L - k0) : KT;
-    float part = 0.f;
-    for (int kk = 0; kk < n; ++kk) {
-      const float d = a[k0 + kk] - b[k0 + kk];
-      part = __builtin_fmaf(d, d, part);
-    }
-    tot += part;
-  }
-  return tot;
-}
-
-// the same by 16-byte loads: L % 4 == 0 and rows on 16-byte boundaries
-__device__ __forceinline__ float row_sq_dist4(const float* __restrict__ a, const float* __restrict__ b, long L) {
-  float tot = 0.f;
-  for (long k0 = 0; k0 < L; k0 += KT) {
-    const int n = L - k0 < KT ? (int)(L - k0) : KT;
-    float part = 0.f;
-    for (int kk = 0; kk < n; kk += 4)
-      sq_acc4(part, *reinterpret_cast<const f32x4*>(a + k0 + kk), *reinterpret_cast<const f32x4*>(b + k0 + kk));
-    tot += part;
-  }
-  return tot;
-}
-
-// k_transition stages latent rows in LDS tile by tile (KT elements); a row stride of KT + 4 floats keeps rows 16-byte
-// aligned and spreads the 16 candidate rows a wave reads with b128 over all 64 banks.
-constexpr int TROW = KT + 4;
+// Every kernel of the unit selection (k_transition, k_live_select, k_live_lag) takes its costs from sqdist.h's pair
+// form, so that they are k_knn_topk's bit for bit.  k_transition stages latent rows in LDS tile by tile (KT elements,
+// row stride SLICE_ROW).
 constexpr int TRB_MAX = 32;   // rows of T per workgroup at most
 
 // KP = k rounded up to a power of two: a workgroup covers RB rows of T, one thread per (row, i, j) pair, and stages
@@ -467,16 +366,15 @@ struct trans_cfg {
   static constexpr int LD4 = (NR * (KT / 4) + 255) / 256;   // 16-byte loads per thread and tile
 };
 
-// trans[t - row0, i, j] = D(mu[next_of[idx[t-1, i]]], mu[idx[t, j]]), D being k_knn_topk's arithmetic: fmaf(d, d, part)
-// in ascending l within tiles of KT, tot += part per tile.  Missing candidates (and indices outside [0, N)) stage
-// zeros and give +inf; columns past L stage zeros, whose terms add an exact 0.  The next tile's rows are loaded into
-// registers while this one is summed.
+// trans[t - row0, i, j] = D(mu[next_of[idx[t-1, i]]], mu[idx[t, j]]), D being sqdist.h's.  Missing candidates (and
+// indices outside [0, N)) stage zeros and give +inf.  The next tile's rows are loaded into registers while this one is
+// summed.
 template <int KP>
 __global__ void __launch_bounds__(256)
 k_transition(const float* __restrict__ mu, long N, long L, const int* __restrict__ next_of,
              const int* __restrict__ idx, int k, long row0, long rows, int vec, float* __restrict__ trans) {
   using C = trans_cfg<KP>;
-  __shared__ __attribute__((aligned(16))) float V[C::NR][TROW];
+  __shared__ __attribute__((aligned(16))) float V[C::NR][SLICE_ROW];
   __shared__ int src[C::NR];
   const int tid = threadIdx.x;
   const long tb = row0 + (long)blockIdx.x * C::RB, t_end = row0 + rows;
@@ -503,19 +401,8 @@ k_transition(const float* __restrict__ mu, long N, long L, const int* __restrict
 #pragma unroll
     for (int u = 0; u < C::LD4; ++u) {
       const int e = tid + 256 * u, row = e >> 3, c = (e & 7) * 4;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
       const int s = e < C::NR * (KT / 4) ? src[row] : -1;
-      if (s >= 0) {
-        const float* p = mu + (long)s * L + k0 + c;
-        if (vec) {
-          if (k0 + c < L) v = *reinterpret_cast<const f32x4*>(p);   // L % 4 == 0: the whole vector is inside the row
-        } else {
-#pragma unroll
-          for (int x = 0; x < 4; ++x)
-            if (k0 + c + x < L) v[x] = p[x];
-        }
-      }
-      pre[u] = v;
+      pre[u] = s >= 0 ? slice_fetch4(mu + (long)s * L, k0 + c, L, vec) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
   };
   const int r = tid / C::PP, pr = tid % C::PP, i = pr / KP, j = pr % KP;
@@ -1020,8 +907,6 @@ __global__ void __launch_bounds__(256) k_live_clear(int* __restrict__ prev, long
   if (i < n) prev[i] = -1;
 }
 
-unsigned blocks_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n > cap ? cap : n)); }
-
 // corpus rows per split (a multiple of BN) and the number of splits: enough (query tile, split) blocks to fill the
 // chip, at least MIN_SPLIT_TILES corpus tiles per split; `forced` > 0 asks for that many splits instead
 void knn_split(long T, long N, long forced, long* per_split, long* n_splits) {
@@ -1060,7 +945,7 @@ void knn_small_split(long T, long N, long forced, long* per_split, long* n_split
 template <int KM, int TQ>
 void launch_knn_small_q(const rv_mosaic_desc* d, long per_split, long n_splits, float* ws_d, int* ws_i, hipStream_t st) {
   const dim3 grid((unsigned)((d->T + SQ - 1) / SQ), (unsigned)n_splits);
-  if (d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0)   // 16-byte loads of corpus rows
+  if (rows_vec16(d->c, d->L))
     hipLaunchKernelGGL((k_knn_small<KM, TQ, true>), grid, dim3(256), 0, st, d->q, (int)d->T, d->c, d->N, d->L, (int)d->k,
                        per_split, (int)n_splits, d->idx, d->dist, ws_d);
   else
@@ -1250,7 +1135,7 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
                  d->N, d->L);
       RV_REQUIRE((d->rows + trans_cfg<16>::RB - 1) / trans_cfg<16>::RB < (1L << 31), RV_ERR_SHAPE,
                  "rv_mosaic(TRANSITION): rows=%ld too many for one call", d->rows);
-      const int vec = d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0;   // 16-byte loads of latent rows
+      const int vec = rows_vec16(d->c, d->L);
       if (d->k <= 1) launch_transition<1>(d, vec, st);
       else if (d->k <= 2) launch_transition<2>(d, vec, st);
       else if (d->k <= 4) launch_transition<4>(d, vec, st);
@@ -1367,7 +1252,7 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
       }
       if (d->weight) {
         if (w.lag > 0) {
-          const int vec = d->L % 4 == 0 && ((unsigned long)d->c & 15) == 0;   // 16-byte loads of latent rows
+          const int vec = rows_vec16(d->c, d->L);
           hipLaunchKernelGGL(k_live_lag, dim3((unsigned)sd->n_streams), dim3(256), 0, st, d->c, d->N, d->L, d->next_of,
                              d->idx, d->dist, (int)d->k, sd->block / sd->hop, drain ? 0 : 1, (int)w.lag + 1, vec, d->weight,
                              (int*)ws, (int*)(ws + w.state), (int*)(ws + w.ridx), (float*)(ws + w.rdist),

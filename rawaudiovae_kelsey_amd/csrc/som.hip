@@ -7,19 +7,13 @@
 #include <limits.h>
 
 #include "common.h"
+#include "sqdist.h"
 #include "../../include/rawvae_hip.h"
 
 using namespace rv;
+using namespace rv::sqd;
 
 namespace {
-
-// rv_som_bmu tile: BR rows x BN nodes per block, KT latent elements per LDS stage; 256 threads as 16 (rows) x 16
-// (nodes), each owning an 8 x 4 register tile (8 x 8 with both accumulator levels spills past 256 VGPRs).
-constexpr int BR = 128, BN = 64, KT = 32, TR = 8, TN = 4, PAD = 4;
-
-// (d, i) < (e, j) in the order "smaller distance, then lower index": a total order on the candidates of one row (node
-// indices are distinct), so the top two of a set do not depend on the order it is visited in.  NaN never wins.
-__device__ __forceinline__ bool cand_less(float d, int i, float e, int j) { return d < e || (d == e && i < j); }
 
 // branch-free (selects), so the per-row state stays in registers
 __device__ __forceinline__ void top2_insert(float d, int i, float& b1, int& i1, float& b2, int& i2) {
@@ -33,7 +27,8 @@ __device__ __forceinline__ void top2_insert(float d, int i, float& b1, int& i1, 
 __global__ void __launch_bounds__(256)
 k_som_bmu(const float* __restrict__ x, long N, const float* __restrict__ w, int M, long L, int* __restrict__ best,
           int* __restrict__ second, float* __restrict__ d_best, float* __restrict__ d_second) {
-  __shared__ __attribute__((aligned(16))) float Xs[KT][BR + PAD];   // k-major: a thread's 8 rows are one 32-byte run
+  // the stages of sqdist.h's tile; the top twos stay in registers, so no distance tile shares LDS with them
+  __shared__ __attribute__((aligned(16))) float Xs[KT][BR + PAD];
   __shared__ __attribute__((aligned(16))) float Ws[KT][BN + PAD];
   const int tid = threadIdx.x, tn = tid & 15, tr = tid >> 4;
   const long n_tiles = (N + BR - 1) / BR;
@@ -45,53 +40,8 @@ k_som_bmu(const float* __restrict__ x, long N, const float* __restrict__ w, int 
     for (int i = 0; i < TR; ++i) { b1[i] = b2[i] = INFINITY; i1[i] = i2[i] = INT_MAX; }
     for (int m0 = 0; m0 < M; m0 += BN) {
       float tot[TR][TN];
-#pragma unroll
-      for (int i = 0; i < TR; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j) tot[i][j] = 0.f;
-      for (long k0 = 0; k0 < L; k0 += KT) {
-        // stage x[r0 : r0 + BR, k0 : k0 + KT] and w[m0 : m0 + BN, k0 : k0 + KT]; 32 lanes read 128 contiguous bytes of
-        // one row.  Out-of-range rows, nodes and k are zeros: (0 - 0)^2 adds an exact 0.
-#pragma unroll
-        for (int s = 0; s < KT * BR / 256; ++s) {
-          const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-          const long gk = k0 + kk, gr = r0 + rr;
-          Xs[kk][rr] = (gr < N && gk < L) ? x[gr * L + gk] : 0.f;
-        }
-#pragma unroll
-        for (int s = 0; s < KT * BN / 256; ++s) {
-          const int e = tid + 256 * s, kk = e & (KT - 1), rr = e / KT;
-          const long gk = k0 + kk, gm = (long)m0 + rr;
-          Ws[kk][rr] = (gm < M && gk < L) ? w[gm * L + gk] : 0.f;
-        }
-        __syncthreads();
-        // part: this K tile's sum of (x - w)^2, each term by one fma in ascending k; then tot += part (two levels)
-        float part[TR][TN];
-#pragma unroll
-        for (int i = 0; i < TR; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) part[i][j] = 0.f;
-#pragma unroll 4
-        for (int k = 0; k < KT; ++k) {
-          const f32x4 xa = *reinterpret_cast<const f32x4*>(&Xs[k][tr * TR]);
-          const f32x4 xb = *reinterpret_cast<const f32x4*>(&Xs[k][tr * TR + 4]);
-          const f32x4 wa = *reinterpret_cast<const f32x4*>(&Ws[k][tn * TN]);
-          const float xv[TR] = {xa[0], xa[1], xa[2], xa[3], xb[0], xb[1], xb[2], xb[3]};
-          const float wv[TN] = {wa[0], wa[1], wa[2], wa[3]};
-#pragma unroll
-          for (int i = 0; i < TR; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-              const float d = xv[i] - wv[j];
-              part[i][j] = __builtin_fmaf(d, d, part[i][j]);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < TR; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j) tot[i][j] += part[i][j];
-        __syncthreads();
-      }
+      // node indices fit an int (M < INT_MAX - BN): the node predicate stays a 32-bit compare
+      tile_sq_dist(Xs, Ws, x, w, r0, m0, L, [&](long gr) { return gr < N; }, [&](long gm) { return (int)gm < M; }, tot);
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int m = m0 + tn * TN + j;
@@ -243,8 +193,6 @@ k_som_update(const double* __restrict__ sums, const long long* __restrict__ coun
     }
   }
 }
-
-unsigned blocks_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n > cap ? cap : n)); }
 
 }  // namespace
 

@@ -73,7 +73,9 @@ def test_knn_pads_rows_with_fewer_finite_candidates():
         assert np.all(gi[:, 3:] == -1) and np.all(np.isinf(gd[:, 3:]))
 
 
-@pytest.mark.parametrize("N,M,L", [(1000, 700, 64), (300, 5000, 33), (5, 2, 256)])
+@pytest.mark.parametrize("N,M,L", [(1000, 700, 64), (300, 5000, 33), (5, 2, 256),
+                                   (129, 65, 33),     # one past a row block, a column tile and a K tile at once
+                                   (128, 64, 32)])    # exactly one full tile: no padding path at all
 def test_knn_k_le_2_is_som_bmu_bit_for_bit(N, M, L):
     from rawaudiovae_kelsey_amd import som
     rng = np.random.default_rng(N + M)
