@@ -15,16 +15,31 @@ allocation the test owns:
     neither call wrote differs, and an element only one of them skipped differs unless the value the other one wrote IS
     the fill, i.e. the skipped store would have changed nothing;
   - an INPUT (fill = an array [rows, cols]) has NaN in its guards and gap columns: any read of them poisons the result
-    and fails the value check.
+    and fails the value check;
+  - an INPUT with `guard` = an array of rows has those rows, flattened and repeated, in its guards and gap columns
+    instead of NaN.  The back guard's copy starts at its first element and the front guard's ends at its last, so with
+    ld == cols == the guard rows' width the view's row `rows + i` IS guard row i (mod their number) and row -1 the
+    last one.  Two uses.  An ATTRACTIVE guard: in a nearest-neighbour search NaN never wins, so a corpus or node row
+    read past the end would lose silently behind NaN guards; with copies of the query rows there it is at distance 0,
+    wins, and the exact comparison with the oracle fails on an index >= rows.  And integer inputs, which have no NaN:
+    their guards hold values the kernel must not act on (indices past the table, for instance).
+
+Dtypes: the 16- and 32-bit floats and uint8 of the GEMM tests, and float64, int32 and int64 (sums, counts, indices).
+An integer or fp64 output is checked like any other: its guards against the bits of the fill.  INT_FILL is a fill for
+index outputs that no kernel writes (-1 is "no candidate", 7 a valid index).
 """
 import numpy as np
 import torch
 
 SENTINEL = 7.0       # what the existing kernel tests fill outputs with
 PACKED_FILL = -3.0   # fill of the packed twin of an output (see above)
+INT_FILL = -77       # fill of an int32 / int64 output
 
 _INT_OF = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32,
-           torch.uint8: torch.uint8}   # (uint8: fp8 images, tests/optimizer_oracle.py)
+           torch.uint8: torch.uint8,   # (uint8: fp8 images, tests/optimizer_oracle.py)
+           torch.float64: torch.int64, torch.int32: torch.int32, torch.int64: torch.int64}
+# what an input array is staged as on the host: float32 (then cast on the device) unless that would lose bits
+_STAGE_OF = {torch.float64: np.float64, torch.int32: np.int32, torch.int64: np.int64}
 
 
 def _round64(n):
@@ -32,20 +47,31 @@ def _round64(n):
 
 
 class Guarded:
-    def __init__(self, rows, cols, ld, dtype, fill):
+    def __init__(self, rows, cols, ld, dtype, fill, guard=None):
         assert ld >= cols and rows >= 1 and cols >= 1
         self.rows, self.cols, self.ld, self.dtype = rows, cols, ld, dtype
         self.front = _round64(max(ld, 64))
         self.back = _round64(rows * ld) + 64
         n = self.front + rows * ld + self.back
         self.is_output = np.isscalar(fill)
+        stage = _STAGE_OF.get(dtype, np.float32)
         if self.is_output:
-            self.fill = float(fill)
+            assert guard is None
+            self.fill = fill if dtype in (torch.int32, torch.int64) else float(fill)
             self.flat = torch.full((n,), self.fill, dtype=dtype, device="cuda")
         else:
-            a = np.ascontiguousarray(fill, dtype=np.float32)
+            a = np.array(fill, dtype=stage, order="C")               # a copy: the caller's array may be read-only
             assert a.shape == (rows, cols), (a.shape, rows, cols)
-            self.flat = torch.full((n,), float("nan"), dtype=dtype, device="cuda")
+            if guard is None:
+                assert dtype.is_floating_point or dtype == torch.uint8, "an integer input needs a guard fill"
+                self.flat = torch.full((n,), float("nan"), dtype=dtype, device="cuda")
+            else:
+                g = np.ascontiguousarray(guard, dtype=stage).reshape(-1)
+                assert g.size >= 1
+                body = np.resize(g, rows * ld)                           # gap columns; the payload is written below
+                front = np.resize(g, -(-self.front // g.size) * g.size)[-self.front:]   # ends on the pattern's end
+                host = np.concatenate([front, body, np.resize(g, self.back)])
+                self.flat = torch.from_numpy(host).cuda().to(dtype)
             self._body()[:, :cols] = torch.from_numpy(a).cuda().to(dtype)
         self.view = torch.as_strided(self.flat, (rows, cols), (ld, 1), self.front)
         assert self.view.data_ptr() % 16 == 0
@@ -80,10 +106,11 @@ class Guarded:
                 name, bad, region, self.rows, self.cols, self.ld)
 
 
-def guarded(rows, cols, ld, dtype, fill=SENTINEL):
-    return Guarded(rows, cols, ld, dtype, fill)
+def guarded(rows, cols, ld, dtype, fill=SENTINEL, guard=None):
+    return Guarded(rows, cols, ld, dtype, fill, guard)
 
 
-def guarded_flat(n, dtype, fill=SENTINEL):
+def guarded_flat(n, dtype, fill=SENTINEL, guard=None):
     """An output (or input) without a leading dimension: n packed elements between two guards."""
-    return Guarded(1, n, n, dtype, fill if np.isscalar(fill) else np.asarray(fill, dtype=np.float32).reshape(1, n))
+    stage = _STAGE_OF.get(dtype, np.float32)
+    return Guarded(1, n, n, dtype, fill if np.isscalar(fill) else np.asarray(fill, dtype=stage).reshape(1, n), guard)

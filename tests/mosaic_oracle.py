@@ -65,17 +65,23 @@ def knn(q, c, k, chunk_elems=1 << 22):
     return idx, dist
 
 
-def gather_mean(src, starts, idx, width):
-    """[T, width] fp32: (1/k) sum_j src[starts[idx[t, j]] : + width] in ascending j from +0; idx -1 adds nothing."""
-    src = np.asarray(src, np.float32)
+def gather_mean(src, starts, idx, width, src_len=None, n_rows=None):
+    """[T, width] fp32: (1/k) sum_j src[starts[idx[t, j]] : + width] in ascending j from +0.  What the kernel skips adds
+    nothing and leaves the divisor at k: an index outside [0, n_rows) (-1: no neighbour) and a row that does not lie
+    inside src[0 : src_len].  src_len and n_rows default to all of src and of starts."""
+    src = np.asarray(src, np.float32).reshape(-1)
     idx = np.asarray(idx)
+    starts = np.asarray(starts)
+    src_len = src.size if src_len is None else int(src_len)
+    n_rows = starts.size if n_rows is None else int(n_rows)
     T, k = idx.shape
     acc = np.zeros((T, width), np.float32)
     for j in range(k):
         i = idx[:, j]
-        ok = i >= 0
+        ok = (i >= 0) & (i < n_rows)
+        st = starts[np.where(ok, i, 0)]
+        ok &= (st >= 0) & (st + width <= src_len)
         rows = np.zeros((T, width), np.float32)
-        st = np.asarray(starts)[np.where(ok, i, 0)]
         rows[ok] = src[st[ok][:, None] + np.arange(width)[None, :]]
         acc = np.where(ok[:, None], acc + rows, acc).astype(np.float32)
     return (acc * (np.float32(1.0) / np.float32(k))).astype(np.float32)

@@ -3,6 +3,8 @@
 Plain restatement of the algorithm in LatentSOM's doc, with every quantity in float64 and no tiling."""
 import numpy as np
 
+import mosaic_oracle
+
 
 def sq_dists(x, w, chunk=4096):
     """[N, M] float64 squared distances, exact-ish: sum over l of (x - w)^2, chunked over rows."""
@@ -42,19 +44,47 @@ def bmu(x, w, chunk=4096):
     return best, second, direct_dist(x, w, best), direct_dist(x, w, second)
 
 
+def bmu_exact(x, w):
+    """(best int32, second int32, d_best fp32, d_second fp32) as rv_som_bmu writes them, to the bit: the search's fp32
+    distance (mosaic_oracle.sq_dist, csrc/sqdist.h) and the first two nodes in (distance, index) order.  A node whose
+    distance is NaN is never taken; where fewer than two remain the slot is -1 / +inf."""
+    idx, dist = mosaic_oracle.knn(x, w, 2)
+    return idx[:, 0].astype(np.int32), idx[:, 1].astype(np.int32), dist[:, 0].copy(), dist[:, 1].copy()
+
+
 def node_sums(x, best, M):
+    """(sums [M, L] float64, counts [M] int64).  np.add.at is unbuffered: it adds the rows one by one in ascending row
+    order, each node's sum starting from +0 -- k_som_node_sums's order, so the sums are the kernel's bit for bit.  Rows
+    whose entry lies outside [0, M) belong to no node."""
     x = np.asarray(x, np.float64)
+    best = np.asarray(best).astype(np.int64)
+    ok = (best >= 0) & (best < M)
     sums = np.zeros((M, x.shape[1]))
-    np.add.at(sums, np.asarray(best), x)
-    counts = np.bincount(np.asarray(best), minlength=M).astype(np.int64)
+    np.add.at(sums, best[ok], x[ok])
+    counts = np.bincount(best[ok], minlength=M).astype(np.int64)
     return sums, counts
+
+
+def segment_mean(x, offsets):
+    """[F, L] float32 as rv_segment_mean writes it: per segment the float64 sum of its rows in ascending order from +0,
+    divided by their number, rounded to float32 once."""
+    x = np.asarray(x, np.float32)
+    offsets = np.asarray(offsets, np.int64)
+    out = np.empty((offsets.size - 1, x.shape[1]), np.float32)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        for f in range(offsets.size - 1):
+            s = np.zeros(x.shape[1], np.float64)
+            for r in range(int(offsets[f]), int(offsets[f + 1])):
+                s = s + x[r].astype(np.float64)
+            out[f] = (s / np.float64(offsets[f + 1] - offsets[f])).astype(np.float32)
+    return out
 
 
 def neighbourhood(rows, cols, sigma):
     m = np.arange(rows * cols)
     r, c = m // cols, m % cols
     d2 = (r[:, None] - r[None, :]) ** 2 + (c[:, None] - c[None, :]) ** 2
-    with np.errstate(divide="ignore", over="ignore", under="ignore"):
+    with np.errstate(divide="ignore", over="ignore", under="ignore", invalid="ignore"):   # 0 / 0 at d2 = 0: masked
         return np.where(d2 == 0, 1.0, np.exp(-d2 / (2.0 * sigma * sigma)))
 
 

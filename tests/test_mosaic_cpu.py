@@ -165,3 +165,23 @@ def test_cli_help_and_bad_flags(tmp_path):
     (corpus / "c.wav").write_bytes(b"not a wav")
     with pytest.raises(ValueError, match="c.wav"):
         cli.main(base + ["--corpus", str(corpus)])
+
+
+def test_gather_mean_oracle_skips_what_the_kernel_skips_and_defaults_to_the_old_result():
+    rng = np.random.default_rng(31)
+    src = rng.standard_normal(500).astype(np.float32)
+    starts = np.array([0, 100, 484, 485, 250], np.int64)          # 484 + 16 = 500 is inside, 485 + 16 is not
+    idx = np.array([[0, 1, -1], [2, 2, 2], [4, 0, 1]], np.int32)
+    old = O.gather_mean(src, starts, idx, 16)
+    assert np.array_equal(old, O.gather_mean(src, starts, idx, 16, src_len=500, n_rows=5))
+    third = np.float32(1.0) / np.float32(3)
+    assert np.array_equal(old[0], ((src[0:16] + src[100:116]) * third).astype(np.float32))     # the divisor stays k
+    assert np.array_equal(old[1], ((src[484:500] + src[484:500] + src[484:500]) * third).astype(np.float32))
+    wide = np.array([[0, 1, 7], [2, 3, 5], [4, 0, 1], [3, 3, 3]], np.int32)
+    got = O.gather_mean(src, starts, wide, 16)
+    assert np.array_equal(got[0], old[0])                         # 7 >= n_rows adds nothing
+    assert np.array_equal(got[1], (src[484:500] * third).astype(np.float32))                    # 3 ends past src, 5 >= n_rows
+    assert np.array_equal(got[3], np.zeros(16, np.float32))
+    cut = O.gather_mean(src, starts, wide, 16, src_len=499, n_rows=4)
+    assert np.array_equal(cut[1], np.zeros(16, np.float32))       # now row 2 ends past src_len too
+    assert np.array_equal(cut[2], ((src[0:16] + src[100:116]) * third).astype(np.float32))      # and 4 >= n_rows

@@ -201,3 +201,66 @@ def test_som_header_entries_compile_as_c(tmp_path):
     subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-c", "-I", os.path.join(REPO, "include"), str(src), "-o",
                     str(tmp_path / "som.o")], check=True)
     assert {"rv_segment_mean", "rv_som_bmu", "rv_som_node_sums", "rv_som_update"} <= set(_lib.EXPORTED)
+
+
+def test_node_sums_oracle_adds_in_ascending_row_order_bit_for_bit():
+    rng = np.random.default_rng(21)
+    N, L, M = 97, 5, 6
+    x = (rng.standard_normal((N, L)) * 10.0 ** rng.integers(-6, 7, (N, L))).astype(np.float32)   # order matters
+    best = rng.integers(-1, M + 2, N).astype(np.int32)           # -1, M and M + 1 belong to no node
+    best[best == 3] = 2                                           # node 3 stays empty
+    sums, counts = O.node_sums(x, best, M)
+    ref = np.zeros((M, L), np.float64)
+    n = [0] * M
+    for r in range(N):
+        if 0 <= best[r] < M:
+            for l in range(L):
+                ref[best[r], l] = ref[best[r], l] + float(x[r, l])
+            n[best[r]] += 1
+    assert np.array_equal(sums.view(np.int64), ref.view(np.int64)) and counts.tolist() == n and counts.dtype == np.int64
+    assert n[3] == 0 and np.array_equal(sums[3].view(np.int64), np.zeros(L, np.int64))          # +0, not -0
+    rev = np.zeros((M, L), np.float64)
+    for r in range(N - 1, -1, -1):
+        if 0 <= best[r] < M:
+            rev[best[r]] += x[r].astype(np.float64)
+    assert not np.array_equal(rev, ref)                           # the case does tell the orders apart
+    inside = (best >= 0) & (best < M)                             # entries inside [0, M) alone: the result from before
+    s2, c2 = O.node_sums(x[inside], best[inside], M)
+    assert np.array_equal(s2.view(np.int64), sums.view(np.int64)) and np.array_equal(c2, counts)
+
+
+def test_bmu_exact_agrees_with_the_float64_bmu_where_the_margin_is_clear():
+    rng = np.random.default_rng(22)
+    x = rng.standard_normal((200, 33)).astype(np.float32)
+    w = rng.standard_normal((65, 33)).astype(np.float32)
+    w[40] = w[7]                                                  # an exact tie: the lower index is best
+    x[:2] = w[7]
+    best, second, d1, d2 = O.bmu_exact(x, w)
+    ob, os_, od1, od2 = O.bmu(x, w)
+    assert best.dtype == second.dtype == np.int32 and d1.dtype == d2.dtype == np.float32
+    assert best[0] == 7 and second[0] == 40 and d1[0] == 0 and d2[0] == 0
+    # fp32 sums of 33 squares: each distance within 33 * 2^-24 relative of the float64 one
+    clear = (od2 - od1) > 1e-5 * od2
+    assert clear.sum() > 150 and np.array_equal(best[clear], ob[clear])
+    np.testing.assert_allclose(d1, od1, rtol=1e-5, atol=0)
+    np.testing.assert_allclose(d2, O.direct_dist(x, w, second), rtol=1e-5, atol=0)
+    assert np.all(d1 <= d2) and np.all(best != second)
+    wn, xn = w[:2].copy(), x[:5].copy()
+    wn[1] = np.nan
+    xn[3] = np.nan
+    best, second, d1, d2 = O.bmu_exact(xn, wn)
+    assert best.tolist() == [0, 0, 0, -1, 0] and second.tolist() == [-1] * 5
+    assert np.isinf(d2).all() and np.isinf(d1[3]) and np.isfinite(np.delete(d1, 3)).all()
+
+
+def test_segment_mean_oracle_is_the_float64_mean_rounded_once():
+    rng = np.random.default_rng(23)
+    lens = [1, 5, 1, 30, 2]
+    x = (rng.standard_normal((sum(lens), 7)) * 10 + 3).astype(np.float32)
+    off = np.concatenate([[0], np.cumsum(lens)])
+    got = O.segment_mean(x, off)
+    assert got.dtype == np.float32 and got.shape == (5, 7)
+    assert np.array_equal(got[0], x[0]) and np.array_equal(got[2], x[6])
+    for f in range(5):
+        s = [sum((float(v) for v in x[off[f]:off[f + 1], l]), 0.0) for l in range(7)]            # ascending, from +0
+        assert np.array_equal(got[f], (np.array(s) / lens[f]).astype(np.float32))
