@@ -420,7 +420,7 @@ int rv_som_node_sums(const float* x, long N, long L, const int* bmu, long M, dou
 int rv_som_update(const double* sums, const long long* counts, const float* w_old, long rows, long cols, long L,
                   double sigma, float* w_new, void* stream);
 
-/* ---- Latent audio mosaicing (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py) ----
+/* ---- Latent audio mosaicing (csrc/mosaic*.hip, rawaudiovae_kelsey_amd/mosaic.py) ----
  * rv_mosaic(op, d, stream): one entry point for the operations below, each reading the fields of *d its op names.
  *
  * RV_MOSAIC_KNN (rv_knn_topk): for each query row of q [T, L] fp32 the k nearest rows of c [N, L] fp32 under the

@@ -294,8 +294,6 @@ k_align_warp(const int* __restrict__ path, const int* __restrict__ choice, long 
   idx[2 * x + 1] = ib;
 }
 
-long up256(long n) { return (n + 255) / 256 * 256; }
-
 struct align_ws {
   long maxdiag, diag, lastrow, rev, end, bytes;
 };

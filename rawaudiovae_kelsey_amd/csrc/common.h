@@ -98,6 +98,9 @@ __device__ __forceinline__ float fast_tanh(float y) {
 // blocks of a grid-stride launch over n items: at least one, at most cap
 inline unsigned blocks_for(long n, long cap) { return (unsigned)(n < 1 ? 1 : (n > cap ? cap : n)); }
 
+// n >= 0 bytes rounded up to the 256-byte boundary on which every part of a workspace starts
+inline long up256(long n) { return (n + 255) / 256 * 256; }
+
 }  // namespace rv
 
 // Slots of the fp8 state block (workspace buffer "fp8_state"; the layout is documented under RV_OPT_FP8 in the public

@@ -4,7 +4,7 @@
 //   RV_GRAIN_FIT     per (target frame, candidate) the shift in [-R, R] and the gain of the least-squares fit of the
 //                    shifted grain to the frame: k_grain_fit, one workgroup per pair
 //   RV_GRAIN_GATHER  RV_MOSAIC_GATHER_MEAN with a shift and a gain per candidate: k_grain_gather
-// and the live path's use of both (RV_MOSAIC_LIVE / LIVE_DRAIN with a fit, mosaic.hip): rv_grain_live_* keep the
+// and the live path's use of both (RV_MOSAIC_LIVE / LIVE_DRAIN with a fit, mosaic_live.hip): rv_grain_live_* keep the
 // streams' input in a TARGET RING (k_live_target), fit the frames a block is about to play against the target frames
 // they stand for (k_grain_fit reading its frame from the ring) and gather them into the stream's frame buffer.
 #include <limits.h>
@@ -22,7 +22,6 @@ constexpr int FIT_CH = 1024;       // samples of a frame staged at a time; a lon
 constexpr int FIT_NS = 4;          // adjacent shifts per thread: one 16-byte LDS read of the grain feeds 32 fmas
 constexpr int FIT_THREADS = 256;
 constexpr int FIT_SPAN = FIT_CH + 2 * FIT_RMAX + 8;   // floats of the staged grain span: 12 320 bytes, 16 KB with x
-constexpr int KMAX = 16;
 
 // a before b in the order of the choice: greater score, then smaller |delta|, then the negative delta.  Scores are
 // never NaN (a NaN sum scores 0) and the deltas of one pair are distinct, so the order is total and the winner does

@@ -1,4 +1,4 @@
-// Launchers that only the step plan (plan.hip) and the live mosaic (mosaic.hip) call: forms of public entry points with extra operands (fp8 copies,
+// Launchers that only the step plan (plan.hip) and the live mosaic (mosaic_live.hip) call: forms of public entry points with extra operands (fp8 copies,
 // per-block maxima, frames read in place).  Not part of the C ABI (include/rawvae_hip.h) and not exported.
 #pragma once
 #include "../../include/rawvae_hip.h"
@@ -127,6 +127,36 @@ RV_INTERNAL int rv_stream_synth(const rv_stream_desc* d, int decode, void* strea
 // the streams' frame counters [n_streams] int64 in the stream workspace (frames since the stream's last reset; moved on
 // by the overlap-add at the end of a block call)
 RV_INTERNAL const long long* rv_stream_counters(const rv_stream_desc* d);
+// Candidates per row at most, of every rv_mosaic op that takes k (mosaic*.hip, grain.hip)
+constexpr int KMAX = 16;
+// Query rows RV_MOSAIC_KNN_SMALL accepts, and up to which RV_MOSAIC_LIVE searches with it: measured faster than
+// k_knn_topk at every T up to here (1.4-1.9x at 64 rows, 4-10x at 16 and fewer against 1.24 M corpus rows)
+constexpr int SMALL_T_MAX = 64;
+// The kNN search of rv_mosaic (mosaic_knn.hip), small != 0 being its few-query form: RV_MOSAIC_KNN / _KNN_SMALL -- checks
+// first, then the search and its merge, no sync and no read of the device -- and RV_MOSAIC_KNN_WORKSPACE /
+// _KNN_SMALL_WORKSPACE, which runs the checks, writes d->ws_bytes and launches nothing (the live block's layout calls
+// it on a copy of its descriptor with T = its query rows).
+RV_INTERNAL int rv_knn_search(const rv_mosaic_desc* d, int small, void* stream);
+RV_INTERNAL int rv_knn_workspace(rv_mosaic_desc* d, int small);
+// RV_MOSAIC_GATHER_MEAN and RV_MOSAIC_OLA (mosaic.hip): checks first, then one launch each.  rv_gather_mean_launch is
+// the former's launch on explicit operands, without the op's checks: the live block gathers latent rows or grains
+// with it.
+RV_INTERNAL int rv_gather_mean(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_gather_mean_launch(const float* src, long src_len, const long long* row_start, long stride, long n_rows,
+                                      long width, const int* idx, long T, int k, float* out, long ldo, void* stream);
+RV_INTERNAL int rv_ola(const rv_mosaic_desc* d, void* stream);
+// The offline unit selection of rv_mosaic (mosaic_path.hip): RV_MOSAIC_TRANSITION, RV_MOSAIC_PATH_FORWARD and
+// RV_MOSAIC_PATH_BACKTRACK -- checks first, then one launch each, no sync and no read of the device -- and
+// RV_MOSAIC_PATH_WORKSPACE, which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_path_transition(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_path_forward(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_path_backtrack(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_path_workspace(rv_mosaic_desc* d);
+// The live block of rv_mosaic (mosaic_live.hip): RV_MOSAIC_LIVE_WORKSPACE, which writes d->ws_bytes and launches
+// nothing; RV_MOSAIC_LIVE_RESET; and rv_live_block: RV_MOSAIC_LIVE, or -- drain != 0 -- RV_MOSAIC_LIVE_DRAIN.
+RV_INTERNAL int rv_live_workspace(rv_mosaic_desc* d);
+RV_INTERNAL int rv_live_reset(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_live_block(const rv_mosaic_desc* d, int drain, void* stream);
 // The two grain-fitting ops of rv_mosaic (grain.hip): RV_GRAIN_FIT and RV_GRAIN_GATHER on the fields the public header
 // names for them; checks first, then one launch each, no sync and no read of the device.
 RV_INTERNAL int rv_grain_fit(const rv_mosaic_desc* d, void* stream);

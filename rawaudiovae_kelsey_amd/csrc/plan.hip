@@ -22,8 +22,6 @@ struct Buf {
   long off;
 };
 
-long align256(long b) { return (b + 255) / 256 * 256; }
-
 int splits_of(long Mp, long Np, long Kp) {
   int s = 1;
   rv_gemm_pick(Mp, Np, Kp, 16, nullptr, nullptr, &s);
@@ -151,7 +149,7 @@ struct rv_plan {
   }
   void add(const char* name, long bytes) {
     bufs.push_back({name, bytes, ws_bytes});
-    ws_bytes += align256(bytes);
+    ws_bytes += rv::up256(bytes);
   }
 };
 

@@ -1,6 +1,6 @@
 // The distance between two latent rows, and the order among candidates, of the whole latent search family: rv_som_bmu
-// (som.hip), the kNN search, its few-query form and the unit selection (mosaic.hip), the alignment's local costs
-// (align.hip).  Defined here once, down to the bit:
+// (som.hip), the kNN search and its few-query form (mosaic_knn.hip), the unit selection (mosaic_path.hip,
+// mosaic_live.hip), the alignment's local costs (align.hip).  Defined here once, down to the bit:
 //   D(x, w) = tot, where per tile of KT latent elements  part = fmaf(d, d, part), d = x[l] - w[l], in ascending l from
 //   +0, then tot += part, the tiles in ascending order from +0.
 //   Out-of-range rows, columns and k stage zeros: (0 - 0)^2 adds an exact 0.

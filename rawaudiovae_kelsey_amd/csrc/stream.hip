@@ -8,7 +8,7 @@
 //                         heads + latent controls + reparameterisation, fc3, fc4, then overlap-add + history update.
 //   rv_stream_reset     : zero one stream's state (or every stream's).
 //   rv_stream_encode / rv_stream_synth (internal.h): the two ends of rv_stream_process for the live mosaic
-//                         (mosaic.hip), which puts a corpus search between them.
+//                         (mosaic_live.hip), which puts a corpus search between them.
 #include "common.h"
 #include "philox.h"
 #include "internal.h"
@@ -303,15 +303,13 @@ struct Ws {
   float *h1, *h3, *z, *dec, *carry, *tail;
 };
 
-long round256(long n) { return (n + 255) / 256 * 256; }
-
 long ws_layout(long S, long H, long L, long NS, long block, long hop, char* base, Ws* w) {
   const long M = NS * (block / hop), P = S - hop;
   const long sizes[7] = {NS * 8, M * H * 4, M * H * 4, M * L * 4, M * S * 4, 2 * NS * P * 4, 2 * NS * P * 4};
   long off[7], o = 0;
   for (int i = 0; i < 7; ++i) {
     off[i] = o;
-    o += round256(sizes[i]);
+    o += up256(sizes[i]);
   }
   if (w) {
     w->cnt = (long long*)(base + off[0]);

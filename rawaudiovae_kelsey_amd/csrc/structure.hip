@@ -243,8 +243,6 @@ k_peaks_write(const int* __restrict__ rank, const int* __restrict__ boff, const 
   }
 }
 
-long up256(long n) { return (n + 255) / 256 * 256; }
-
 struct peaks_ws {
   long nb, bsum, bcnt, tot, rank, bflag, boff, bytes;
 };

@@ -29,8 +29,6 @@ constexpr int LG_LD = 80;                // LDS row pitch in doubles (pca.hip's:
 constexpr int LG_THREADS = 256;
 constexpr int ST_THREADS = 256;
 
-long up256(long n) { return (n + 255) / 256 * 256; }
-
 // keep[p] = 1 when rows p and p + 1 lie in one file: p + 1 is none of row_start[0 .. n_files]
 __global__ void __launch_bounds__(256)
 k_walk_pairs(const long long* __restrict__ row_start, long n_files, long n_pairs, unsigned char* __restrict__ keep) {

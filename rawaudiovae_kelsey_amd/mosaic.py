@@ -68,7 +68,7 @@ from .stream import WINDOWS, GraphReplay, StreamingVAE, check_args, each_stream,
 MODES = ("grains", "decode")
 K_MAX = 16
 FIT_MAX = 1024     # samples a grain may be shifted at most (csrc/grain.hip)
-SMALL_T_MAX = 64   # query rows of knn_topk_small (csrc/mosaic.hip)
+SMALL_T_MAX = 64   # query rows of knn_topk_small (csrc/internal.h, csrc/mosaic_knn.hip)
 
 
 def live_fit_table(successors, room):
@@ -579,7 +579,7 @@ class _Synthesis:
         self.index.codec.decode_chunk(self.z[:rows], self.h, self.frames[r0:r0 + rows])
 
 
-LAG_MAX = 64       # frames of look-ahead of the live selection at most (csrc/mosaic.hip)
+LAG_MAX = 64       # frames of look-ahead of the live selection at most (csrc/mosaic_live.hip)
 
 
 def check_live_args(segment_length, index_step, n_corpus, n_streams, block, hop=None, k=1, mode="grains", window=None,

@@ -1,5 +1,5 @@
 """Numpy statement of live grain fitting (RV_MOSAIC_LIVE / LIVE_DRAIN with width = R or lam = gain_max in
-csrc/mosaic.hip and csrc/grain.hip, StreamingMosaic(fit=R, gain_max=g) in rawaudiovae_kelsey_amd/mosaic.py) for the
+csrc/mosaic_live.hip and csrc/grain.hip, StreamingMosaic(fit=R, gain_max=g) in rawaudiovae_kelsey_amd/mosaic.py) for the
 tests, built from the other oracles: live_mosaic_oracle.greedy / live_lag_oracle.fixed_lag choose, grain_fit_oracle.fit
 and .gather fit and scale the grains, live_lag_oracle.play overlap-adds them.
 

@@ -1,5 +1,5 @@
-"""Numpy statement of live mosaicing with a lag (k_live_lag in csrc/mosaic.hip, StreamingMosaic(lag=D) and drain() in
-rawaudiovae_kelsey_amd/mosaic.py) for the tests, built on mosaic_oracle (the distance, the overlap-add),
+"""Numpy statement of live mosaicing with a lag (k_live_lag in csrc/mosaic_live.hip, StreamingMosaic(lag=D) and drain()
+in rawaudiovae_kelsey_amd/mosaic.py) for the tests, built on mosaic_oracle (the distance, the overlap-add),
 mosaic_path_oracle (transitions, the forward rule, the backtrack) and live_mosaic_oracle (the weight rule).
 
 The rule.  Frames arrive in order and wait as PENDING rows, at most lag + 1 of them.  A window solve commits the oldest

@@ -1,5 +1,5 @@
-"""Numpy statement of live mosaicing (RV_MOSAIC_LIVE in csrc/mosaic.hip, rawaudiovae_kelsey_amd.mosaic.StreamingMosaic)
-for the tests.
+"""Numpy statement of live mosaicing (RV_MOSAIC_LIVE in csrc/mosaic_live.hip,
+rawaudiovae_kelsey_amd.mosaic.StreamingMosaic) for the tests.
 
 greedy: the lag-0 selection rule.  Per frame, in order, with prev = the last chosen corpus frame (-1 at the start):
 prev < 0, or next_of[prev] outside [0, N): the lowest j whose candidate is a corpus row.  Otherwise the argmin over

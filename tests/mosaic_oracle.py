@@ -1,4 +1,4 @@
-"""Numpy restatement of the mosaicing kernels (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py) for the tests.
+"""Numpy restatement of the mosaicing kernels (csrc/mosaic*.hip, rawaudiovae_kelsey_amd/mosaic.py) for the tests.
 
 knn: the direct-form fp32 distance bit for bit -- each term fmaf(d, d, part) in ascending l within tiles of 32, the
 tile sums added in order from +0 -- then the first k candidates in (distance, index) order, NaN excluded.

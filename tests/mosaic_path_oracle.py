@@ -1,4 +1,4 @@
-"""Numpy statement of continuity-aware mosaicing (RV_MOSAIC_TRANSITION / RV_MOSAIC_PATH_* in csrc/mosaic.hip,
+"""Numpy statement of continuity-aware mosaicing (RV_MOSAIC_TRANSITION / RV_MOSAIC_PATH_* in csrc/mosaic_path.hip,
 rawaudiovae_kelsey_amd.mosaic.best_path) for the tests.
 
 Inputs: candidates idx [T, k] and dist [T, k] as the kNN search writes them (ascending, -1 / +inf for missing), corpus

@@ -1,4 +1,4 @@
-"""The loop edges of the rv_mosaic ops from before the guard-band habit (csrc/mosaic.hip: KNN, KNN_SMALL and their merge,
+"""The loop edges of the rv_mosaic ops from before the guard-band habit (csrc/mosaic*.hip: KNN, KNN_SMALL and their merge,
 GATHER_MEAN, OLA, TRANSITION, PATH_*, LIVE without a fit), exactly and between guards: rv_mosaic calls (_lib.mosaic_call)
 on pointers cut from tests/guarded.py buffers, against mosaic_oracle and mosaic_path_oracle bit for bit.
 

@@ -1,4 +1,4 @@
-"""Latent mosaicing on the GPU (csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py, mosaic.py) against the numpy
+"""Latent mosaicing on the GPU (csrc/mosaic*.hip, rawaudiovae_kelsey_amd/mosaic.py, mosaic.py) against the numpy
 restatement in tests/mosaic_oracle.py."""
 import csv
 import os

@@ -1,6 +1,7 @@
-"""Live mosaicing with a lag on the GPU (k_live_lag / RV_MOSAIC_LIVE_DRAIN in csrc/mosaic.hip, StreamingMosaic(lag=D),
-drain(), mosaic.py --lag).  The committed choices are checked bit for bit against tests/live_lag_oracle.py on the
-device's own candidates, the audio against the oracle's block player, lag 0 against the default construction."""
+"""Live mosaicing with a lag on the GPU (k_live_lag / RV_MOSAIC_LIVE_DRAIN in csrc/mosaic_live.hip,
+StreamingMosaic(lag=D), drain(), mosaic.py --lag).  The committed choices are checked bit for bit against
+tests/live_lag_oracle.py on the device's own candidates, the audio against the oracle's block player, lag 0
+against the default construction."""
 import os
 import subprocess
 import sys

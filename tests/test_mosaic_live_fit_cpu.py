@@ -1,6 +1,6 @@
 """Live grain fitting without a GPU: the numpy oracle on planted cases, the header's text, the workspace query, the
 host-side checks, the device-free validator and the command line's flags (tests/live_fit_oracle.py,
-include/rawvae_hip.h, csrc/mosaic.hip, rawaudiovae_kelsey_amd/mosaic.py, mosaic.py)."""
+include/rawvae_hip.h, csrc/mosaic_live.hip, rawaudiovae_kelsey_amd/mosaic.py, mosaic.py)."""
 import ctypes as C
 import os
 import re

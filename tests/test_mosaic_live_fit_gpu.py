@@ -1,4 +1,4 @@
-"""Live grain fitting on the GPU (RV_MOSAIC_LIVE / LIVE_DRAIN with a fit in csrc/mosaic.hip and csrc/grain.hip,
+"""Live grain fitting on the GPU (RV_MOSAIC_LIVE / LIVE_DRAIN with a fit in csrc/mosaic_live.hip and csrc/grain.hip,
 StreamingMosaic(fit=R, gain_max=g), mosaic.py --live-fit / --live-gain-max).  Everything is compared bit for bit: the
 audio and the gains as int32 views, the scores as int64 views.  Without unit selection and at lag 0 the reference is
 the offline mosaic of the zero-prefixed input; with a lag, drains and resets it is tests/live_fit_oracle.py on the

@@ -1,6 +1,7 @@
-"""Live mosaicing on the GPU (RV_MOSAIC_KNN_SMALL / RV_MOSAIC_LIVE in csrc/mosaic.hip, rawaudiovae_kelsey_amd.mosaic.
-StreamingMosaic, mosaic.py --live-block).  The offline path (LatentIndex.mosaic, knn_topk) is the oracle of the live
-one: the two must agree bit for bit; the greedy selection is checked against tests/live_mosaic_oracle.py."""
+"""Live mosaicing on the GPU (RV_MOSAIC_KNN_SMALL in csrc/mosaic_knn.hip, RV_MOSAIC_LIVE in csrc/mosaic_live.hip,
+rawaudiovae_kelsey_amd.mosaic.StreamingMosaic, mosaic.py --live-block).  The offline path (LatentIndex.mosaic, knn_topk)
+is the oracle of the live one: the two must agree bit for bit; the greedy selection is checked against
+tests/live_mosaic_oracle.py."""
 import os
 import subprocess
 import sys

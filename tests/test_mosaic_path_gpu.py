@@ -1,4 +1,4 @@
-"""Continuity-aware mosaicing on the GPU (RV_MOSAIC_TRANSITION / RV_MOSAIC_PATH_* in csrc/mosaic.hip,
+"""Continuity-aware mosaicing on the GPU (RV_MOSAIC_TRANSITION / RV_MOSAIC_PATH_* in csrc/mosaic_path.hip,
 rawaudiovae_kelsey_amd/mosaic.py, mosaic.py) against the numpy statement in tests/mosaic_path_oracle.py."""
 import csv
 import os

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the mosaicing kNN search (rv_mosaic RV_MOSAIC_KNN, csrc/mosaic.hip) and one whole LatentIndex.mosaic() call.
+"""Time the mosaicing kNN search (rv_mosaic RV_MOSAIC_KNN, csrc/mosaic_knn.hip) and one whole LatentIndex.mosaic() call.
 
     python tools/mosaic_bench.py [--reps 5] [--path] [--out build/mosaic_bench.json]
     python tools/mosaic_bench.py --live [--reps 30] [--summary profiles/mosaic_live_summary.txt]
