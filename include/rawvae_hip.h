@@ -1231,7 +1231,15 @@ typedef struct rv_comm_desc {
 int rv_plan_attach_comm(rv_plan*, const rv_comm_desc*);
 int rv_plan_step_ddp(rv_plan*, const float* x, const float* eps, float* recon_out, float kl_beta,
                      float lr, unsigned long long seed, void* stream);
-/* Device pointers into the workspace for tests (name: "mulv","z","h1","h3","dP4",...). */
+/* Device pointer to (and, if n_bytes is given, size of) one buffer of the bound workspace, for tests and tools.  NULL for an
+ * unknown or NULL name and for an unbound plan.  The names, in layout order:
+ *   bf16 operands and padded biases   "xb" "W1b" "Whb" "W3b" "W4b" "b1p" "bhp" "b3p" "b4p"
+ *   forward                           "h1" "mulv_slabs" "mulv" "eps" "z" "h3"
+ *   backward                          "dP4" "dP3" "dz_slabs" "dmulv" "dP1"
+ *   weight-gradient slabs, fp16 scales "dW1" "dWh" "dWh_us" "dW3" "dW4" "dW1_us" "dW4_us"
+ *   bias-gradient partial rows        "db1p" "dbhp" "db3p" "db4p"
+ *   fp8 images and state              "xq" "W1q" "W4q" "h3q" "dP4q" "dP1q" "fp8_state" "h3_amax"
+ *   data-parallel flags, loss partials "ddp_flags" "mse_part" "kl_part" */
 void* rv_plan_buffer(rv_plan*, const char* name, long* n_bytes);
 
 /* ---- hipGraph capture of any sequence of the calls above on one stream ---- */

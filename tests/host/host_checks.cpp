@@ -185,6 +185,58 @@ static int launcher_checks() {
   return fails;
 }
 
+// The plan's tables on fake base addresses (nothing is dereferenced): every named buffer lies inside the workspace, 256-byte
+// aligned and in layout order; the lookups that must give NULL do; every option that edits the descriptor tables, then both
+// tables read back, with and without a gradient arena.
+static int plan_checks() {
+  static const char* names[] = {
+      "xb", "W1b", "Whb", "W3b", "W4b", "b1p", "bhp", "b3p", "b4p", "h1", "mulv_slabs", "mulv", "eps", "z", "h3", "dP4", "dP3",
+      "dz_slabs", "dmulv", "dP1", "dW1", "dWh", "dWh_us", "dW3", "dW4", "dW1_us", "dW4_us", "db1p", "dbhp", "db3p", "db4p", "xq",
+      "W1q", "W4q", "h3q", "dP4q", "dP1q", "fp8_state", "h3_amax", "ddp_flags", "mse_part", "kl_part"};
+  int fails = 0;
+  char* const base = (char*)0x10000000000;
+  for (int with_grad = 0; with_grad < 2; ++with_grad) {
+    rv_plan* pl = NULL;
+    fails += rv_plan_create(&pl, 4096, 1024, 2048, 64) != 0;
+    fails += rv_plan_buffer(pl, "xb", NULL) != NULL;                     // not bound yet
+    const long ws_bytes = rv_plan_workspace_bytes(pl);
+    rv_plan_buffers b;
+    memset(&b, 0, sizeof b);
+    b.param = (float*)(base + 0x100000000); b.exp_avg = (float*)(base + 0x200000000);
+    b.exp_avg_sq = (float*)(base + 0x300000000); b.grad = with_grad ? (float*)(base + 0x400000000) : NULL;
+    b.workspace = base; b.step_counter = (long long*)(base + 0x500000000); b.loss_ring = (float*)(base + 0x500001000);
+    b.ring = 4;
+    fails += rv_plan_bind(pl, &b) != 0;
+    long end = 0;
+    for (const char* name : names) {
+      long n = -1;
+      char* ptr = (char*)rv_plan_buffer(pl, name, &n);
+      fails += !(ptr && ptr - base == end && n > 0 && end % 256 == 0);
+      end = (ptr - base) + (n + 255) / 256 * 256;
+    }
+    fails += end != ws_bytes;
+    fails += rv_plan_buffer(pl, "no_such_buffer", NULL) != NULL;
+    fails += rv_plan_buffer(pl, NULL, NULL) != NULL;
+    fails += rv_plan_buffer(NULL, "xb", NULL) != NULL;
+    rv_param_desc slab[10], flat[10];
+    const int opts[][2] = {{RV_OPT_FP8, 1}, {RV_OPT_FP8, 2}, {RV_OPT_FP8, 0}, {RV_OPT_SLAB_DTYPE, RV_SLAB_F32},
+                           {RV_OPT_SLAB_DTYPE, RV_SLAB_F16}, {RV_OPT_LATENT_FUSED, 0}, {RV_OPT_LATENT_FUSED, 1}};
+    for (const auto& o : opts) {
+      fails += rv_plan_set_option(pl, o[0], o[1]) != 0;
+      fails += rv_plan_descs(pl, slab, 0) != 0;
+      fails += rv_plan_descs(pl, flat, 1) != 0;
+      for (int i = 0; i < 10; ++i) {
+        fails += !(flat[i].offset == slab[i].offset && flat[i].shadow_fp8 == slab[i].shadow_fp8);
+        if (with_grad) fails += !(flat[i].grad_slabs == b.grad + slab[i].offset && flat[i].grad_splits == 1 && !flat[i].grad_half);
+        else fails += !(flat[i].grad_slabs == slab[i].grad_slabs && flat[i].grad_splits == slab[i].grad_splits);
+      }
+    }
+    fails += EXPECT(rv_plan_set_option(pl, RV_OPT_FP8, 3), RV_ERR_UNSUPPORTED, "rv_plan_set_option: RV_OPT_FP8 takes 0, 1 or 2");
+    rv_plan_destroy(pl);
+  }
+  return fails;
+}
+
 int main() {
   long Bp, Sp, Hp, Lp; int bm, bn, sp, paired;
   int fails = 0;
@@ -221,6 +273,7 @@ int main() {
   fails += rv_gemm_plan(7, 256, 256, 256, 1, &bm, &bn, &sp, &paired) == 0;   // unknown query
   rv_plan_destroy(pl);
   fails += launcher_checks();
+  fails += plan_checks();
   printf("host checks: %d failures; last error: %s\n", fails, rv_last_error());
   return fails != 0;
 }

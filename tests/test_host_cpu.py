@@ -264,6 +264,39 @@ def test_large_batch_plan_rules():
             assert -(-blocks // 256) == want[1] and bm == 256
 
 
+def test_plan_tables_match_the_recorded_layout():
+    """Host-only: the workspace layout (size, offset and bytes of all 42 named buffers, NULL for an unknown name), all
+    twenty parameter descriptors field by field and the rider range, for seven shapes, with and without a gradient arena,
+    in every combination of RV_OPT_FP8 x RV_OPT_SLAB_DTYPE x RV_OPT_LATENT_FUSED and along two round trips (fused
+    1 -> 0 -> 1, fp8 0 -> 1 -> 0), equal what tests/golden/plan_tables.npz holds: recorded by tools/plan_tables.py from the
+    commit before the plan's tables got typed ids and d_flat one derivation."""
+    import sys
+    sys.path.insert(0, os.path.join(REPO, "tools"))
+    import plan_tables as T
+    want = np.load(os.path.join(GOLDEN, "plan_tables.npz"))
+    got = T.tables()
+    assert sorted(want.files) == sorted(got)
+    states, fields = T.state_labels(), T.desc_fields()
+    for shape in T.SHAPES:
+        w, g = want[T.key(shape, "ws")], got[T.key(shape, "ws")]
+        assert w.shape == g.shape == (2 + 2 * len(T.NAMES),) and w[-1] == g[-1] == 1, shape
+        assert g[0] == w[0], "shape %s: workspace bytes %d, recorded %d" % (shape, g[0], w[0])
+        for i, name in enumerate(T.NAMES):
+            assert tuple(g[1 + 2 * i:3 + 2 * i]) == tuple(w[1 + 2 * i:3 + 2 * i]), \
+                "shape %s, buffer %s: (offset, bytes) %s, recorded %s" % (shape, name, g[1 + 2 * i:3 + 2 * i], w[1 + 2 * i:3 + 2 * i])
+        w, g = want[T.key(shape, "descs")], got[T.key(shape, "descs")]
+        assert w.shape == g.shape == (2, len(states), 2, 10, len(fields))
+        for arena, si, flat, t, fi in np.argwhere(w != g)[:1]:
+            raise AssertionError("shape %s, %s grad arena, state '%s', %s table, %s.%s: %d, recorded %d" % (
+                shape, "with" if arena else "without", states[si], "d_flat" if flat else "d_slab", T.TENSORS[t], fields[fi],
+                g[arena, si, flat, t, fi], w[arena, si, flat, t, fi]))
+        w, g = want[T.key(shape, "riders")], got[T.key(shape, "riders")]
+        assert w.shape == g.shape
+        for arena, si in np.argwhere((w != g).any(axis=-1))[:1]:
+            raise AssertionError("shape %s, %s grad arena, state '%s': riders %s, recorded %s" % (
+                shape, "with" if arena else "without", states[si], g[arena, si], w[arena, si]))
+
+
 def test_private_torch_entry_points_are_feature_tested_with_public_fallbacks(monkeypatch):
     """The drop-in loop's host path leans on three torch entry points outside the documented API
     (`torch.autograd.graph.increment_version`, `torch._foreach_add_`, `torch._C._cuda_getCurrentRawStream`).  Each is
