@@ -818,6 +818,69 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_STRUCT_NOVELTY 31
 #define RV_STRUCT_PEAKS 32
 #define RV_STRUCT_WORKSPACE 33
+/* Latent restoration (csrc/smooth.hip, rawaudiovae_kelsey_amd/smooth.py): inference with the model
+ * of "Latent walk" above, w' = A w + B e with A A^T + B B^T = I: a Kalman filter and a fixed-interval smoother over
+ * sequences of latent rows whose frames are partly missing, and the splice of a resynthesis into the original.  The
+ * family's conventions: no op syncs or reads a device pointer on the host, each may run under capture, and each returns
+ * an RV_ERR_* whose message names the field before anything is launched: mode, T, L, k, n_rows, lam, a null q / row_start /
+ * centre / basis / moment / ws / out / src / frames / room, ws_bytes too small, ws not 256-byte aligned, ldo, n_out, width.
+ * The model, per sequence.  q = x [T, L] fp32 (1 <= T < 2^31); sequence s owns rows [row_start[s], row_start[s+1]),
+ * row_start [n_rows + 1] int64 on the device, ascending from 0 to T (the CALLER checks that on its host copy; the kernels
+ * clamp what they read to [0, T]).  centre = c [L], P, R [k, L] and moment = dyn = [A^T | B^T] [2, k, k] fp64 are the fitted
+ * walk's arrays.  Qn = B B^T, element (i, j), i <= j, one chain fma(B[i, m], B[j, m], .) in ascending m from +0, written to
+ * [i, j] and [j, i].  The observation of frame t is y_t = P (x_t - c): y_j = chain fma(P[j, l], (double)x[t, l] - c[l], .) in
+ * ascending l from +0 (fp64 from the fp32 row, not RV_PCA_APPLY's rounded output).  Its noise is r_t I, r = lam (finite,
+ * 1e-8 <= r <= 1e8), r_t = fl64((double)r / (double)weight[t]).  Frame t is OBSERVED iff weight[t] > 0 (weight [T] fp32;
+ * NaN, 0 and negative: missing); weight NULL: every frame observed with weight 1.  The row x_t of a missing frame is never
+ * read and may hold NaN.
+ * dot4: every inner product below is four chains of fmas over the indices m mod 4 = 0 .. 3, each in ascending m from +0,
+ * added as (a0 + a1) + (a2 + a3).
+ * mode RV_SMOOTH_DENSE: 1 <= k <= 64 (more is RV_ERR_SHAPE naming k and the limit), k <= L <= 512.  mode
+ * RV_SMOOTH_DIAGONAL: the caller asserts that A^T and B^T are diagonal, only their diagonals are read, k independent
+ * scalar filters, 1 <= k <= L <= 512, ws is O(k) per frame.
+ * RV_SMOOTH_FILTER: q, weight, lam, centre, basis = P, moment = dyn, T, L, k, n_rows, row_start, mode, ws, ws_bytes ->
+ *   result [T, ldo >= k + 2] fp64 or NULL.  Per sequence in ascending t.  First frame: w- = 0, P- = I (the walk's
+ *   stationary law).  Later: w- = A w+, M = A P+, P-[i, j] = dot4(M[i, .], A[j, .]) + Qn[i, j] for i <= j, mirrored.
+ *   Missing frame: w+ = w-, P+ = P-.  Observed: S = P- + r_t I = G G^T, v = y_t - w-, and with base = [S; P-; v^T]
+ *   (2 k + 1 rows) every row r obeys, column after column, Y[r, j] = (base[r, j] - dot4(Y[r, :j], G[j, :j])) / G[j, j],
+ *   G[j, j] = sqrt(S[j, j] - dot4(G[j, :j], G[j, :j])): rows [0, k) are G (Cholesky-Crout), rows [k, 2 k) W^T = P- G^-T
+ *   and the last a = G^-1 v, the forward solves folded into the factorisation.  w+ = w- + W^T a (= w- + P- u with
+ *   u = S^-1 v = G^-T a); P+[i, j] = P-[i, j] - dot4(W^T[i, .], W^T[j, .]) for i <= j, mirrored.  P- <= I always, so
+ *   cond(S) <= (1 + r_t) / r_t: why r has a floor and no inverse of P- appears.  A row of result: [0, k) w+; column k
+ *   the normalised innovation squared v^T u = a^T a (missing: -1); column k + 1 log det S = 2 sum log G[j, j] in ascending
+ *   j (missing: 0).  ws receives y, w-, a, diag G and the tile [P- upper triangle | G strict lower triangle] of every frame.
+ *   DIAGONAL, axis j with a = A[j, j], q = B[j, j]^2: w- = a w+, P- = fma(a P+, a, q); S = P- + r_t, u = v / S,
+ *   w+ = fma(P-, u, w-), P+ = P- r_t / S; the columns k and k + 1 are sum_j v_j u_j and sum_j log S_j in ascending j from
+ *   +0.  One workgroup per sequence (dense: A, the covariance and Y in 132.5 KB of LDS at k = 64, opted in by launch
+ *   attribute; diagonal: a thread per axis, no barrier) behind the launches of Qn and y: three launches (diagonal with
+ *   result: also three).
+ * RV_SMOOTH_BACKWARD: the modified Bryson-Frazier recursion, which needs S^-1 only.  q, weight, lam, centre, basis = R,
+ *   moment = dyn and ws as FILTER left it for the same (T, L, k, n_rows, row_start, mode) -> out [T, ldo >= L] fp32 (only
+ *   columns [0, L) are written) and state [T, k] fp64 or NULL.  Per sequence in descending t from lambda = 0.  Observed:
+ *   lambda-hat = lambda + G^-T (a - G^-1 (P- lambda)) (= u + lambda - S^-1 P- lambda), two substitutions with the
+ *   reciprocals of diag G; missing: lambda-hat = lambda.  w-hat_t = w-_t + P-_t lambda-hat; lambda <- A^T lambda-hat.
+ *   DIAGONAL: lambda-hat = u + lambda - P- lambda / S, w-hat = fma(P-, lambda-hat, w-), lambda <- a lambda-hat.
+ *   The latent row: z_l = (float)(c_l + chain_j fma(w-hat_j, R[j, l], .) + g_t rho_l), rho_l = (double)x[t, l] - c_l -
+ *   chain_j fma(y_j, R[j, l], .), the part of an observed row outside the kept axes; g_t = 1 observed, 0 missing (rho is
+ *   then not computed): a frame the model does not touch keeps what the walk cannot see.  Two launches.  BACKWARD
+ *   leaves FILTER's part of ws as it was (w-hat has its own place) and may be repeated.
+ *   A sequence's bits depend on its own rows, weights and the model only, not on n_rows, on where it lies in x or on
+ *   the launch; w+[t] depends on the frames up to t only.  No atomics, no polling.
+ * RV_SMOOTH_SPLICE: src = the original [n_out] fp32, frames = the resynthesis [n_out] fp32, room [n_rows, 2] int32 on
+ *   the device = the damaged sample ranges [s, e), ascending and disjoint (the CALLER checks that), 1 <= n_rows,
+ *   width = F >= 0 fade samples, 1 <= n_out < 2^31 -> out [n_out], out[n] = (float)((1 - g) (double)src[n] + g
+ *   (double)frames[n]), both products rounded.  d = the distance from n to the nearest range (0 inside);
+ *   g = 1 for d = 0, g = 0.5 + 0.5 cos(pi d / (F + 1)) for 1 <= d <= F (the maximum over the ranges where ramps meet),
+ *   g = 0 beyond.  Where g = 0 the output is src[n] bit for bit, where g = 1 frames[n] bit for bit.  One launch, every
+ *   sample written by one thread.
+ * RV_SMOOTH_WORKSPACE: the bytes of ws for (T, L, k, mode) in d->ws_bytes; launches nothing and touches no device.  ws is
+ *   256-byte aligned.  Dense: 8 (k^2 rounded up to 256 bytes + T k (k + 5)); diagonal: 64 T k. */
+#define RV_SMOOTH_FILTER 34
+#define RV_SMOOTH_BACKWARD 35
+#define RV_SMOOTH_SPLICE 36
+#define RV_SMOOTH_WORKSPACE 37
+#define RV_SMOOTH_DENSE 0
+#define RV_SMOOTH_DIAGONAL 1
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the

@@ -205,3 +205,10 @@ RV_INTERNAL int rv_align_workspace(rv_mosaic_desc* d);
 RV_INTERNAL int rv_struct_novelty(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_struct_peaks(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_struct_workspace(rv_mosaic_desc* d);
+// The restoration ops of rv_mosaic (smooth.hip): RV_SMOOTH_FILTER, RV_SMOOTH_BACKWARD and RV_SMOOTH_SPLICE on the fields the
+// public header names for them -- checks first, then the launches, no sync and no read of the device -- and
+// RV_SMOOTH_WORKSPACE, which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_smooth_filter(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_smooth_backward(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_smooth_splice(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_smooth_workspace(rv_mosaic_desc* d);
