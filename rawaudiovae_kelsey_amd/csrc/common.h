@@ -52,6 +52,20 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return r;
 }
 
+// Sum over the block's NW waves; result valid in thread 0.  `red` = NW floats of LDS.
+template <int NW>
+__device__ __forceinline__ float block_sum(float v, float* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) red[w] = v;
+  __syncthreads();
+  float r = 0.f;
+  if (threadIdx.x == 0)
+    for (int i = 0; i < NW; ++i) r += red[i];
+  __syncthreads();
+  return r;
+}
+
 // 16-byte WRITE-THROUGH store (global_store_dwordx4 ... sc0 sc1): the line goes to memory as the store retires instead
 // of staying dirty in the XCD's L2 until the end-of-kernel release writes everything back at once.  Every kernel of
 // the step ends with a burst of output stores (8-34 MB) that nothing in the same launch reads again, and the next

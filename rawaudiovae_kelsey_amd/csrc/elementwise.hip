@@ -5,6 +5,7 @@
 #include "common.h"
 #include "adam.h"
 #include "philox.h"
+#include "reparam.h"
 #include "../../include/rawvae_hip.h"
 #include "internal.h"
 
@@ -298,9 +299,7 @@ k_reparam_fwd(const float* __restrict__ slabs, int splits, long Bp, long Lp, lon
             e = ev[j];
             eps_out[b * L + l + j] = e;
           }
-          const float sd = __expf(0.5f * lva[j]);
-          zz[j] = mua[j] + e * sd;
-          kl += 1.f + lva[j] - mua[j] * mua[j] - sd * sd;
+          reparam_fwd(mua[j], lva[j], e, zz[j], kl);
         } else {
           mua[j] = 0.f;
           lva[j] = 0.f;
@@ -336,32 +335,19 @@ k_reparam_bwd(const float* __restrict__ dz_slabs, int splits, long Bp, long Lp, 
   __shared__ float sh[2 * 256 * 4];
   const int tid = threadIdx.x;
   const long L2p = 2 * Lp;
-  const float inv_nk_ = 1.0f / ((float)B * (float)L);
+  const float inv_nk = 1.0f / ((float)B * (float)L);   // (up here: the loss block forms it too, and the launch keeps one division)
   // ONE EXTRA block (the grid has Bp / RB_ROWS + 1) finishes the loss scalar and does nothing else: as an epilogue of
   // the last row block it added a second dependent round trip to memory to the block the whole launch waits for
   if (blockIdx.x == gridDim.x - 1) {
-    if (loss_out && mse_partial && kl_partial) {
-      float m = 0.f, k = 0.f;
-      for (int i = tid; i < n_mse; i += 256) m += mse_partial[i];
-      for (int i = tid; i < n_kl; i += 256) k += kl_partial[i];
-      m = block_sum_256(m, sh);
-      k = block_sum_256(k, sh);
-      if (tid == 0) {
-        const float mse = m / ((float)B * (float)S);
-        const float kld = -0.5f * k * inv_nk_;
-        if (step_counter && ring > 0) loss_out += 4 * (((*step_counter - 1) % ring + ring) % ring);   // (slot ring - 1 for a counter of 0)
-        loss_out[0] = mse + kl_beta * kld;
-        loss_out[1] = mse;
-        loss_out[2] = kld;
-      }
-    }
+    if (loss_out && mse_partial && kl_partial)
+      loss_finish<4>(mse_partial, n_mse, kl_partial, n_kl, B, S, L, kl_beta, loss_out, step_counter, ring,
+                     [&](float v) { return block_sum_256(v, sh); });
     return;
   }
   const int lq = (int)(Lp / 4);             // column groups per row (16, 32 or 64)
   const int rows_par = 256 / lq;            // rows covered per pass (16, 8 or 4)
   const int cg = tid % lq, r0 = tid / lq;
   const long l = (long)cg * 4;
-  const float inv_nk = 1.0f / ((float)B * (float)L);
   float cs_mu[4] = {0.f, 0.f, 0.f, 0.f}, cs_lv[4] = {0.f, 0.f, 0.f, 0.f};
   for (int r = r0; r < RB_ROWS; r += rows_par) {
     const long b = (long)blockIdx.x * RB_ROWS + r;
@@ -380,10 +366,7 @@ k_reparam_bwd(const float* __restrict__ dz_slabs, int splits, long Bp, long Lp, 
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         if (l + j < L) {
-          const float e = eps[b * L + l + j];
-          const float sd = __expf(0.5f * lva[j]);
-          dmu[j] = dza[j] + kl_beta * mua[j] * inv_nk;
-          dlv[j] = dza[j] * e * 0.5f * sd + kl_beta * 0.5f * (sd * sd - 1.f) * inv_nk;
+          reparam_bwd(dza[j], mua[j], lva[j], eps[b * L + l + j], kl_beta, inv_nk, dmu[j], dlv[j]);
           if (dmu_ext) dmu[j] += dmu_ext[b * L + l + j];   // gradients arriving from outside (autograd)
           if (dlv_ext) dlv[j] += dlv_ext[b * L + l + j];
         }
@@ -509,7 +492,7 @@ k_reparameterize(const float* __restrict__ mu, const float* __restrict__ lv, lon
       e = normal1(seed, (uint64_t)i, offset);
       if (eps_out) eps_out[i] = e;
     }
-    z[i] = mu[i] + e * __expf(0.5f * lv[i]);
+    z[i] = reparam_z(mu[i], lv[i], e);
   }
 }
 
@@ -788,25 +771,14 @@ int rv_reparam_bwd(const float* dz_slabs, int splits, long Bp, long Lp, long B, 
 }
 
 // The loss scalar from the partial sums a forward phase left (mse_partial of the fc4 forward's epilogue, kl_partial of the
-// reparameterisation): what the extra block of k_reparam_bwd / k_latent_bwd computes during the backward, in the same
-// summation order, as a launch of its own -- for a caller that wants the value before (or without) a backward.
+// reparameterisation): what the extra block of k_reparam_bwd / k_latent_bwd computes during the backward (reparam.h's
+// loss_finish), as a launch of its own -- for a caller that wants the value before (or without) a backward.
 __global__ void __launch_bounds__(256)
 k_loss_from_partials(const float* __restrict__ mse_partial, int n_mse, const float* __restrict__ kl_partial, int n_kl,
                      long B, long S, long L, float kl_beta, float* __restrict__ out) {
   __shared__ float sh[4];
-  const int tid = threadIdx.x;
-  float m = 0.f, k = 0.f;
-  for (int i = tid; i < n_mse; i += 256) m += mse_partial[i];
-  for (int i = tid; i < n_kl; i += 256) k += kl_partial[i];
-  m = block_sum_256(m, sh);
-  k = block_sum_256(k, sh);
-  if (tid == 0) {
-    const float mse = m / ((float)B * (float)S);
-    const float kld = -0.5f * k * (1.0f / ((float)B * (float)L));
-    out[0] = mse + kl_beta * kld;
-    out[1] = mse;
-    out[2] = kld;
-  }
+  loss_finish<4>(mse_partial, n_mse, kl_partial, n_kl, B, S, L, kl_beta, out, nullptr, 0,
+                 [&](float v) { return block_sum_256(v, sh); });
 }
 int rv_loss_from_partials(const float* mse_partial, int n_mse, const float* kl_partial, int n_kl, long B, long S, long L,
                           float kl_beta, float* out3, void* stream) {

@@ -27,6 +27,7 @@
 
 #include "common.h"
 #include "philox.h"
+#include "reparam.h"
 
 namespace rv {
 
@@ -323,20 +324,6 @@ __device__ __forceinline__ void wait_tiles_in_flight(int tiles) {
   else if (tiles == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * GL) : "memory");
   else if (tiles == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(GL) : "memory");
   else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-
-// Sum over the block's NW waves; result valid in thread 0.  `red` = NW floats of LDS.
-template <int NW>
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) red[w] = v;
-  __syncthreads();
-  float r = 0.f;
-  if (threadIdx.x == 0)
-    for (int i = 0; i < NW; ++i) r += red[i];
-  __syncthreads();
-  return r;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -953,9 +940,8 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, char
     // The B tile's rows were gathered head-interleaved (above), so fragment (mi, 0) of this wave holds mu and fragment
     // (mi, 1) logvar of the SAME (row, latent) pairs: lane (q, j) owns row mi * 16 + j of the wave tile and the four
     // consecutive latents l .. l + 3.  No pairing swap, no hand-over between lanes: bias, eps, exp, z and the KL term
-    // straight on the accumulators (k_reparam_fwd's arithmetic and eps draws -- counter = the (row, 4-latent group) index
-    // over the padded [Mp, lat_lp / 4] grid --, elementwise.hip), 16-byte fp32 / 8-byte bf16 stores, 64 bytes per row
-    // and store instruction.
+    // straight on the accumulators (reparam.h's forward rule and eps counter), 16-byte fp32 / 8-byte bf16 stores, 64 bytes
+    // per row and store instruction.
     static_assert(NI % 2 == 0, "reparameterisation epilogue: (mu, logvar) fragment pairs");
     const int q = lane >> 4, j = lane & 15;
     const long Lp_ = p.lat_lp, L2p_ = 2 * Lp_, L_ = p.lat_l;
@@ -1002,9 +988,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, char
               }
               mua[e_] = acc[mi][2 * pr][e_] + bm[e_];
               lva[e_] = acc[mi][2 * pr + 1][e_] + bv[e_];
-              const float sd = __expf(0.5f * lva[e_]);
-              zz[e_] = mua[e_] + e * sd;
-              kl += 1.f + lva[e_] - mua[e_] * mua[e_] - sd * sd;
+              reparam_fwd(mua[e_], lva[e_], e, zz[e_], kl);
             }
           }
         }
@@ -1253,7 +1237,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, char
         }
       }
     } else if constexpr (EPI == EPI_REPARAM_BWD) {
-      // v = dz of (row, 8 consecutive latents): k_reparam_bwd's arithmetic (elementwise.hip) on the accumulators
+      // v = dz of (row, 8 consecutive latents): reparam.h's backward rule on the accumulators
       const long Lp_ = p.lat_lp, L2p_ = 2 * Lp_, L_ = p.lat_l;
       // (64-row tiles: mu | logvar and, where 16-byte loads were possible, eps of these items were fetched before the main
       // loop; the 256-row tiles of large batches fetch them here, chunk by chunk)
@@ -1282,9 +1266,7 @@ __device__ __forceinline__ void gemm_body(const GemmArgs& p, const int bid, char
           if (b < p.M_valid && l + e < L_) {
             const float ee = rb_vec[it] ? rb_e[it][e >> 2][e & 3] : p.eps[b * L_ + l + e];
             const float mu_ = rb_m[it][e >> 2][e & 3], lv_ = rb_l[it][e >> 2][e & 3];
-            const float sd = __expf(0.5f * lv_);
-            dmu = v[it][e] + p.kl_beta * mu_ * p.inv_nk;
-            dlv = v[it][e] * ee * 0.5f * sd + p.kl_beta * 0.5f * (sd * sd - 1.f) * p.inv_nk;
+            reparam_bwd(v[it][e], mu_, lv_, ee, p.kl_beta, p.inv_nk, dmu, dlv);
             if (p.dmu_ext) dmu += p.dmu_ext[b * L_ + l + e];
             if (p.dlv_ext) dlv += p.dlv_ext[b * L_ + l + e];
           }

@@ -189,7 +189,7 @@ k_latent_fwd(const bf16_t* __restrict__ h1, const long ldh, const bf16_t* __rest
   asm volatile("" ::: "memory");
 
   // ---- reduce the 8 partial sums (fixed order), bias, reparameterise: threads 0..255 take the 256 four-column
-  // groups of the block in k_reparam_fwd's order (same eps draws, same KL partial granularity)
+  // groups of the block in k_reparam_fwd's order (reparam.h's forward rule and eps counter, one KL partial per 1024 elements)
   float kl = 0.f;
   if (tid < 256) {
     const int rr = tid >> 4;
@@ -220,9 +220,7 @@ k_latent_fwd(const bf16_t* __restrict__ h1, const long ldh, const bf16_t* __rest
           }
           mua[e_] = (((pm[0][e_] + pm[1][e_]) + (pm[2][e_] + pm[3][e_])) + ((pm[4][e_] + pm[5][e_]) + (pm[6][e_] + pm[7][e_]))) + bm[e_];
           lva[e_] = (((pv[0][e_] + pv[1][e_]) + (pv[2][e_] + pv[3][e_])) + ((pv[4][e_] + pv[5][e_]) + (pv[6][e_] + pv[7][e_]))) + bv[e_];
-          const float sd = __expf(0.5f * lva[e_]);
-          zz[e_] = mua[e_] + e * sd;
-          kl += 1.f + lva[e_] - mua[e_] * mua[e_] - sd * sd;
+          reparam_fwd(mua[e_], lva[e_], e, zz[e_], kl);
         }
       }
     }
@@ -340,7 +338,7 @@ __device__ __forceinline__ void stage_rows_mn64(const bf16_t* g, long ld, lds_ch
 
 // The backward mirror of k_latent_fwd's first two steps: dz = dP3 W3 (autograd of fc3, model.py:29) for 16 batch rows
 // per workgroup over the FULL contraction (K = Hp cut over the 4 waves, private LDS-DMA rings, no barrier in the
-// streaming loop), then the backward of reparameterize + KL (k_reparam_bwd's arithmetic, elementwise.hip) on the
+// streaming loop), then the backward of reparameterize + KL (reparam.h's backward rule) on the
 // block's 16 x 64 dz while it is still in LDS: no dz slabs in HBM, no second launch.  Streams W3 (Hp x 64) + 16 rows
 // of dP3 through every CU: 320 KB at C2, and the CU's L2 -> LDS port is the bound again.
 // The launch has two more roles.  Blocks [n_rows, n_rows + n_w3): fc3's weight gradient dW3 = dP3^T z as an ordinary
@@ -376,22 +374,9 @@ k_latent_bwd(const bf16_t* __restrict__ dP3, const long lddp, const bf16_t* __re
       gemm_body<64, 64, 2, 2, false, false, EPI_F32, 2>(w3grad, (int)blockIdx.x - n_rows, smem_dyn);
       return;
     }
-    if (loss_out && mse_partial && kl_partial) {   // the loss scalar (k_reparam_bwd's extra block, same summation order)
-      float* red = (float*)smem_dyn;
-      float m = 0.f, k = 0.f;
-      for (int i = tid; i < n_mse; i += 256) m += mse_partial[i];
-      for (int i = tid; i < n_kl; i += 256) k += kl_partial[i];
-      m = block_sum_256(m, red);
-      k = block_sum_256(k, red);
-      if (tid == 0) {
-        const float mse = m / ((float)B * (float)S);
-        const float kld = -0.5f * k * inv_nk;
-        if (step_counter && ring_n > 0) loss_out += 4 * (((*step_counter - 1) % ring_n + ring_n) % ring_n);
-        loss_out[0] = mse + kl_beta * kld;
-        loss_out[1] = mse;
-        loss_out[2] = kld;
-      }
-    }
+    if (loss_out && mse_partial && kl_partial)   // the loss scalar
+      loss_finish<4>(mse_partial, n_mse, kl_partial, n_kl, B, S, L, kl_beta, loss_out, step_counter, ring_n,
+                     [&](float v) { return block_sum_256(v, (float*)smem_dyn); });
     return;
   }
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -484,9 +469,7 @@ k_latent_bwd(const bf16_t* __restrict__ dP3, const long lddp, const bf16_t* __re
     for (int e = 0; e < 4; ++e) {
       if (l + e < L) {
         const float dz = (pz[0][e] + pz[1][e]) + (pz[2][e] + pz[3][e]);
-        const float sd = __expf(0.5f * lva[e]);
-        dmu[e] = dz + kl_beta * mua[e] * inv_nk;
-        dlv[e] = dz * ev[e] * 0.5f * sd + kl_beta * 0.5f * (sd * sd - 1.f) * inv_nk;
+        reparam_bwd(dz, mua[e], lva[e], ev[e], kl_beta, inv_nk, dmu[e], dlv[e]);
         if (dmu_ext) dmu[e] += xm[e];   // gradients arriving from outside (autograd)
         if (dlv_ext) dlv[e] += xv[e];
       }
@@ -848,6 +831,7 @@ __global__ void __launch_bounds__(512) k_heads_reparam_gemm(const GemmArgs p) {
 // rows).  The row-local kernels of Lp = 64 hand over to these forms there too: they re-stream every weight for each 16 rows,
 // 0.06-0.08 of the MFMA peak at B = 131072 (profiles/r06_batch_sweep.jsonl).
 constexpr int LG_BIG_TILES = 1024;                       // (Bp / 64) (Lp / 64) above which the 256-row forms run
+bool large_batch(long Bp, long Lp) { return (Bp / 64) * (Lp / 64) > LG_BIG_TILES && Bp % 256 == 0; }   // both directions ask here
 constexpr int HGB_STAGES = 3;
 constexpr int HGB_LDS = HGB_STAGES * (256 + 128) * 128;  // 144 KiB
 __global__ void __launch_bounds__(512) k_heads_reparam_gemm_big(const GemmArgs p) {
@@ -878,7 +862,7 @@ k_dz_reparam_gemm(const GemmArgs dz, const GemmArgs w3grad, const int n_dz, cons
                   const float* __restrict__ kl_partial, const int n_kl, float* __restrict__ loss_out,
                   const long long* __restrict__ step_counter, const int ring_n) {
   extern __shared__ __attribute__((aligned(16))) char smem_dyn[];
-  const int bid = (int)blockIdx.x, tid = threadIdx.x;
+  const int bid = (int)blockIdx.x;
   // the weight-gradient blocks come FIRST in dispatch order: each contracts over a slice of the whole batch and is the
   // launch's longest block by far at large batches (behind the dz blocks they started when those were done: 413 us at
   // B = 131072, L = 64)
@@ -895,26 +879,9 @@ k_dz_reparam_gemm(const GemmArgs dz, const GemmArgs w3grad, const int n_dz, cons
     else gemm_body<64, 64, 4, 2, true, false, EPI_REPARAM_BWD, DZ_STAGES>(dz, bid - n_w3, smem_dyn);
     return;
   }
-  if (loss_out && mse_partial && kl_partial) {   // the loss scalar (k_reparam_bwd's extra block, same summation order)
-    float* red = (float*)smem_dyn;
-    float m = 0.f, k = 0.f;
-    // (threads 0..255 only: k_reparam_bwd's extra block has 256 threads, and the sums must come out bit-equal to its)
-    if (tid < 256) {
-      for (int i = tid; i < n_mse; i += 256) m += mse_partial[i];
-      for (int i = tid; i < n_kl; i += 256) k += kl_partial[i];
-    }
-    m = block_sum<8>(m, red);
-    k = block_sum<8>(k, red);
-    if (tid == 0) {
-      const float mse = m / ((float)B * (float)S);
-      const float inv_nk = 1.0f / ((float)B * (float)L);
-      const float kld = -0.5f * k * inv_nk;
-      if (step_counter && ring_n > 0) loss_out += 4 * (((*step_counter - 1) % ring_n + ring_n) % ring_n);
-      loss_out[0] = mse + kl_beta * kld;
-      loss_out[1] = mse;
-      loss_out[2] = kld;
-    }
-  }
+  if (loss_out && mse_partial && kl_partial)   // the loss scalar (512 threads here: the first 256 sum the partials)
+    loss_finish<8>(mse_partial, n_mse, kl_partial, n_kl, B, S, L, kl_beta, loss_out, step_counter, ring_n,
+                   [&](float v) { return block_sum<8>(v, (float*)smem_dyn); });
 }
 
 // host side of the two (called by rv_latent_fwd_ex / rv_latent_bwd for Lp > 64; arguments checked there)
@@ -924,7 +891,7 @@ int heads_reparam_gemm(const void* h, long ldh, const void* wh, long ldwh, const
   GemmArgs a{};
   a.A = (const bf16_t*)h; a.lda = ldh; a.B = (const bf16_t*)wh; a.ldb = ldwh;
   a.k_tiles = (int)(Hp / 64); a.M_valid = (int)B; a.N_valid = (int)(2 * Lp);
-  const bool big = (Bp / 64) * (Lp / 64) > LG_BIG_TILES && Bp % 256 == 0;
+  const bool big = large_batch(Bp, Lp);
   const bool pp = big && Lp >= 128;   // (Hp / 64 is even: the GEMM forms require Hp % 128 == 0)
   a.tiles_m = (int)(Bp / (big ? 256 : 64)); a.tiles_n = (int)(Lp / (pp ? 128 : 64)); a.splits = 1;
   a.bias = bias_heads; a.lat_lp = Lp; a.lat_l = L; a.eps_in = eps_in; a.eps_out = eps_out; a.seed = seed;
@@ -936,9 +903,9 @@ int heads_reparam_gemm(const void* h, long ldh, const void* wh, long ldwh, const
   lds_opt_in((const void*)k_heads_reparam_gemm_big, HGB_LDS, attr_done1);
   static std::atomic<unsigned long long> attr_done2{0};
   lds_opt_in((const void*)k_heads_reparam_gemm_pp, PP_LDS, attr_done2);
-  if (pp) hipLaunchKernelGGL(k_heads_reparam_gemm_pp, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(512), PP_LDS, st, a);
-  else if (big) hipLaunchKernelGGL(k_heads_reparam_gemm_big, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(512), HGB_LDS, st, a);
-  else hipLaunchKernelGGL(k_heads_reparam_gemm, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(512), HG_LDS, st, a);
+  void (*const kern)(GemmArgs) = pp ? k_heads_reparam_gemm_pp : big ? k_heads_reparam_gemm_big : k_heads_reparam_gemm;
+  const int lds = pp ? PP_LDS : big ? HGB_LDS : HG_LDS;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(512), lds, st, a);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }
@@ -956,13 +923,13 @@ int rv_latent_rowlocal(long Bp, long Hp, long Lp) { return Lp == 64 && Hp % 512 
 // zeros): 16 for the row-local kernel, the dz tile's rows for the GEMM forms.  The plan's optimizer descriptors skip the zeros.
 int rv_latent_bwd_tile_rows(long Bp, long Hp, long Lp) {
   if (rv_latent_rowlocal(Bp, Hp, Lp)) return 16;
-  return (Lp >= 128 && (Bp / 64) * (Lp / 64) > LG_BIG_TILES && Bp % 256 == 0) ? 256 : 64;
+  return (Lp >= 128 && large_batch(Bp, Lp)) ? 256 : 64;
 }
 
 // The latent backward's ping-pong form (k_dz_reparam_gemm<2>): a large batch at a padded latent width of 256.  Its dW3 blocks are
 // 256 x 256 tiles over Hp / 256 row tiles, so the plan splits K until they fill the chip once (even K tiles per block).
 int rv_latent_bwd_pp(long Bp, long Hp, long Lp) {
-  return Lp == 256 && Hp % 256 == 0 && (Bp / 64) * (Lp / 64) > LG_BIG_TILES && Bp % 256 == 0;
+  return Lp == 256 && Hp % 256 == 0 && large_batch(Bp, Lp);
 }
 
 int rv_latent_fwd(const void* h_bf16, long ldh, const void* wh_bf16, long ldwh, const float* bias_heads,
@@ -1071,15 +1038,10 @@ int rv_latent_bwd(const void* dp3_bf16, long lddp, const void* w3_bf16, long ldw
     lds_opt_in((const void*)k_dz_reparam_gemm<1>, HGB_LDS, attr_gemm1);
     static std::atomic<unsigned long long> attr_gemm2{0};
     lds_opt_in((const void*)k_dz_reparam_gemm<2>, PP_LDS, attr_gemm2);
-    if (pp)
-      hipLaunchKernelGGL(k_dz_reparam_gemm<2>, dim3((unsigned)(n_dz + n_w3 + 1)), dim3(512), PP_LDS, (hipStream_t)stream, d, g,
-                         n_dz, n_w3, B, L, S, kl_beta, mse_partial, n_mse, kl_partial, n_kl, loss_out, step_counter, ring);
-    else if (big)
-      hipLaunchKernelGGL(k_dz_reparam_gemm<1>, dim3((unsigned)(n_dz + n_w3 + 1)), dim3(512), HGB_LDS, (hipStream_t)stream, d, g,
-                         n_dz, n_w3, B, L, S, kl_beta, mse_partial, n_mse, kl_partial, n_kl, loss_out, step_counter, ring);
-    else
-      hipLaunchKernelGGL(k_dz_reparam_gemm<0>, dim3((unsigned)(n_dz + n_w3 + 1)), dim3(512), DZ_LDS, (hipStream_t)stream, d, g,
-                         n_dz, n_w3, B, L, S, kl_beta, mse_partial, n_mse, kl_partial, n_kl, loss_out, step_counter, ring);
+    const auto kern = pp ? k_dz_reparam_gemm<2> : big ? k_dz_reparam_gemm<1> : k_dz_reparam_gemm<0>;
+    const int lds = pp ? PP_LDS : big ? HGB_LDS : DZ_LDS;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(n_dz + n_w3 + 1)), dim3(512), lds, (hipStream_t)stream, d, g, n_dz, n_w3, B, L, S,
+                       kl_beta, mse_partial, n_mse, kl_partial, n_kl, loss_out, step_counter, ring);
     RV_CHECK_LAUNCH();
     return RV_OK;
   }

@@ -7,6 +7,7 @@
 //                   (scipy.interpolate.interp1d evaluated at numpy.linspace).
 #include "common.h"
 #include "philox.h"
+#include "reparam.h"
 #include "../../include/rawvae_hip.h"
 
 using namespace rv;
@@ -95,7 +96,7 @@ k_latent_mix(const float* __restrict__ mu_a, const float* __restrict__ lv_a, con
       }
       const float m = mix_f32(mu_a[src], wa, mu_b[src], wb);
       const float lv = mix_f32(lv_a[src], wa, lv_b[src], wb);
-      z[i] = m + e * __expf(0.5f * lv);   // k_reparameterize's expression (elementwise.hip), same flags: bit-equal
+      z[i] = reparam_z(m, lv, e);
       if (mu_out) mu_out[i] = m;
       if (lv_out) lv_out[i] = lv;
       if (alpha_out && l == 0) alpha_out[i / L] = (double)wb;

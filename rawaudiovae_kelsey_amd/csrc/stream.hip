@@ -11,6 +11,7 @@
 //                         (mosaic_live.hip), which puts a corpus search between them.
 #include "common.h"
 #include "philox.h"
+#include "reparam.h"
 #include "internal.h"
 
 using namespace rv;
@@ -189,8 +190,7 @@ k_stream_heads(const float* __restrict__ h1, long H, const float* __restrict__ w
     const float mc = latent_ctl(m, scale[s * L + l], offset[s * L + l]);
     if constexpr (REPARAM) {
       const float e = eps_in ? eps_in[r * L + l] : normal1(seed, (uint64_t)(f * L + l), (uint64_t)s);
-      const float te = temperature[s] * e;
-      z[r * L + l] = mc + te * __expf(0.5f * v);   // k_reparameterize's expression (elementwise.hip), same flags
+      z[r * L + l] = reparam_z(mc, v, temperature[s] * e);
     } else {
       z[r * L + l] = mc;
     }

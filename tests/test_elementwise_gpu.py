@@ -246,3 +246,47 @@ def test_loss_ring_slot(L, route, counter, slot):
     kld_ = -0.5 * klp.astype(np.float64).sum() / (B * Lt)
     np.testing.assert_allclose(got[slot, :3], [mse + kl_beta * kld_, mse, kld_], rtol=1e-5)
     assert int(ctr.item()) == counter
+
+
+def test_loss_finish_is_one_rule(L):
+    """The three backward routes finish the loss scalar by one rule (csrc/reparam.h, loss_finish): on the same partial
+    sums the three words they write to the ring's slot are equal as bits -- rv_reparam_bwd's extra block, the row-local
+    rv_latent_bwd (Hp = 512) and its GEMM form (Hp = 128, the 512-thread k_dz_reparam_gemm<0>), at a counter of 0 (slot
+    ring - 1) and of 5 (slot 0).  The guards around the ring and its other slots stay untouched."""
+    rng = np.random.default_rng(5)
+    B, Lt, Lp, Bp, S, ring, kl_beta = 100, 3, 64, 128, 512, 4, 1e-2
+    mulv = np.zeros((Bp, 2 * Lp), np.float32)
+    mulv[:B, :Lt] = rng.standard_normal((B, Lt)) * 0.5; mulv[:B, Lp:Lp + Lt] = rng.standard_normal((B, Lt)) * 0.3
+    eps = rng.standard_normal((B, Lt)).astype(np.float32)
+    n_mse, n_kl = 37, Bp // 16
+    msep, klp = rng.random(n_mse).astype(np.float32), -rng.random(n_kl).astype(np.float32)
+    mvd, ed, msed, kld = dev(mulv), dev(eps), dev(msep), dev(klp)
+    slabs = dev((rng.standard_normal((1, Bp, Lp)) * 1e-3).astype(np.float32))
+    dmulv = torch.empty(Bp, 2 * Lp, device="cuda", dtype=torch.bfloat16)
+    dbh = torch.zeros(Bp // 16, 2 * Lp, device="cuda")
+
+    def run(route, counter):
+        ctr = torch.tensor([counter], dtype=torch.int64, device="cuda")
+        loss = guarded_flat(4 * ring, torch.float32)
+        if route == "reparam_bwd":
+            L.rv_reparam_bwd(slabs.data_ptr(), 1, Bp, Lp, B, Lt, S, mvd.data_ptr(), ed.data_ptr(), kl_beta, None, None,
+                             dmulv.data_ptr(), dbh.data_ptr(), msed.data_ptr(), n_mse, kld.data_ptr(), n_kl, loss.ptr,
+                             ctr.data_ptr(), ring, sp())
+        else:
+            Hp = 512 if route == "latent_bwd_rowlocal" else 128
+            dp3 = dev((rng.standard_normal((Bp, Hp)) * 1e-3).astype(np.float32), torch.bfloat16)
+            w3 = dev((rng.standard_normal((Hp, Lp)) * 0.2).astype(np.float32), torch.bfloat16)
+            L.rv_latent_bwd(dp3.data_ptr(), Hp, w3.data_ptr(), Lp, Bp, Hp, Lp, B, Lt, S, mvd.data_ptr(), ed.data_ptr(), kl_beta,
+                            None, None, dmulv.data_ptr(), dbh.data_ptr(), msed.data_ptr(), n_mse, kld.data_ptr(), n_kl, loss.ptr,
+                            ctr.data_ptr(), ring, None, 0, None, 0, 0, sp())
+        loss.assert_untouched("loss_out (%s, counter %d)" % (route, counter))
+        return got_of(loss).reshape(ring, 4)
+
+    for counter, slot in ((0, 3), (5, 0)):
+        got = {r: run(r, counter) for r in ("reparam_bwd", "latent_bwd_rowlocal", "latent_bwd_gemm")}
+        first = got["reparam_bwd"]
+        assert (first[slot, :3] != SENTINEL).all()
+        for r, g in got.items():
+            others = [s for s in range(ring) if s != slot]
+            assert (g[others] == SENTINEL).all() and g[slot, 3] == SENTINEL, r
+            np.testing.assert_array_equal(bits(g[slot, :3]), bits(first[slot, :3]), err_msg="%s, counter %d" % (r, counter))
