@@ -881,6 +881,43 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_SMOOTH_WORKSPACE 37
 #define RV_SMOOTH_DENSE 0
 #define RV_SMOOTH_DIAGONAL 1
+/* Latent recurrence (csrc/recur.hip, rawaudiovae_kelsey_amd/recur.py): what repeats in a latent
+ * trajectory.  The matrix profile of a distance matrix: for every window of m consecutive frames the nearest other
+ * window under the sum of the frame distances along a diagonal.  The family's conventions: no op syncs or reads a device
+ * pointer on the host, each may run under capture, and each returns an RV_ERR_* whose message names the field before
+ * anything is launched: k, T, N, splits, n_rows, stride, row0, lag, width, mode, a null local_costs / result / idx / ws,
+ * ws_bytes too small, ws not 256-byte aligned.  No atomics, no polling.  The op codes 38 and 39 are unassigned: rv_mosaic
+ * answers them as unknown ops.
+ * RV_RECUR_PROFILE: local_costs = Dm fp32, n_rows rows of N columns with a row pitch of stride >= N elements,
+ *   Dm[r, j] = D(a[row0 + r], b[j]): what RV_ALIGN_COST with band 0 writes for a slab of a's rows (stride = N).  k = m,
+ *   the window in frames, 1 <= m <= 256.  T = n_rows - m + 1 >= 1, the windows of the slab: a T that disagrees is
+ *   RV_ERR_SHAPE naming T and n_rows.  N >= m; window j exists for 0 <= j <= N - m.  n_rows stride < 2^31.  row0 >= 0,
+ *   the slab's first row in the whole recording.  lag = lo and width = hi, lo <= hi, any sign, |lo|, |hi| < 2^31.
+ *   mode = 0 or RV_RECUR_MIRROR.
+ *   Admission.  With g = row0 + i, window j is admitted for row i iff lo <= j - g <= hi, and under RV_RECUR_MIRROR also
+ *   iff lo <= g - j <= hi.  A self-join with an exclusion zone of e frames: lo = e, hi = 2^31 - 1, MIRROR.  Loop
+ *   candidates: lo = the shortest loop, hi = the longest, no mirror.  A join against another recording: the full range.
+ *   The window sum W(i, j) is ONE fp64 chain: s = +0, then s += (double)Dm[i + u, j + u] for u = 0 .. m - 1 in ascending
+ *   u.  A direct sum for every cell, neither a sliding update nor a difference of prefix sums: the bits depend on Dm, m,
+ *   i and j only, not on the slab, the tiling, splits or the launch.
+ *   -> result = P [T] fp64 and idx = I [T] int32: over the admitted j whose W is finite, (P[i], I[i]) is the least (W, j),
+ *   ordered by the smaller W, then the lower j.  NaN and +inf never win; with no such j, P[i] = +inf and I[i] = -1.  Every
+ *   entry of P and I is written by exactly one thread.  Cells outside the matrix are skipped by index, the padding
+ *   between N and stride is never read, and a cell of Dm is read only for an admitted diagonal.
+ *   splits = the workgroups the columns of a block of 16 rows are divided among, 0 <= splits <= 1024; 0 = the library's
+ *   choice, which fills the chip for any T.  With more than one split the partial (W, j) pairs go to ws (ws_bytes) and a
+ *   second launch takes their least; the order is total, so the result is the same bits for every split count.  With
+ *   one split ws is not read.
+ *   A workgroup takes 16 rows and walks its share of the diagonals j - i in tiles of 256, a thread per diagonal: the 16
+ *   windows of a diagonal share all but 15 of their cells, so the thread reads each cell once (a wave reads consecutive
+ *   columns of one row) and adds it to the chain of every window that holds it, each chain in its own ascending u.  It
+ *   keeps the best pair of every row in registers across the tiles; a wave reduction and a cross-wave reduction under
+ *   the (W, j) order close the rows.
+ * RV_RECUR_WORKSPACE: the bytes of ws of RV_RECUR_PROFILE for (T, N, k, splits) in d->ws_bytes (0 with one split);
+ *   launches nothing and touches no device.  ws is 256-byte aligned. */
+#define RV_RECUR_PROFILE 40
+#define RV_RECUR_WORKSPACE 41
+#define RV_RECUR_MIRROR 1
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the
@@ -919,9 +956,9 @@ typedef struct rv_mosaic_desc {
   long n_out;
   union { const int* next_of;    /* TRANSITION [N]; LIVE with a fit: [3 N], successors then room */
           const int* room; };    /* GRAIN_FIT [n_rows, 2] */
-  long row0;                     /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T */
+  long row0;                     /* TRANSITION, PATH_FORWARD: rows [row0, row0 + rows) of T; RECUR_PROFILE: the slab's first row */
   union { long rows;
-          long lag; };           /* LIVE ops: D */
+          long lag; };           /* LIVE ops: D; RECUR_PROFILE: lo (width: hi) */
   union { float* trans;          /* [rows, k, k]: TRANSITION output, PATH_FORWARD input */
           float* gain;           /* GRAIN ops, LIVE with a fit */
           double* centre; };     /* PCA and walk ops [L] */

@@ -110,9 +110,12 @@ ALIGN_ON_A, ALIGN_ON_B, ALIGN_ON_PATH = 0, 1, 2   # RV_ALIGN_WARP's mode (the ti
 STRUCT_NOVELTY, STRUCT_PEAKS, STRUCT_WORKSPACE = 31, 32, 33   # RV_STRUCT_* (rv_mosaic)
 SMOOTH_FILTER, SMOOTH_BACKWARD, SMOOTH_SPLICE, SMOOTH_WORKSPACE = 34, 35, 36, 37   # RV_SMOOTH_* (rv_mosaic)
 SMOOTH_DENSE, SMOOTH_DIAGONAL = 0, 1   # RV_SMOOTH_FILTER's and _BACKWARD's mode
+RECUR_PROFILE, RECUR_WORKSPACE = 40, 41   # RV_RECUR_* (rv_mosaic); 38 and 39 are unassigned
+RECUR_MIRROR = 1   # RV_RECUR_PROFILE's mode
 
 _HOST_ONLY_OPS = frozenset((MOSAIC_KNN_WORKSPACE, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_PATH_WORKSPACE, MOSAIC_LIVE_WORKSPACE,
-                            PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE, STRUCT_WORKSPACE, SMOOTH_WORKSPACE))   # mosaic_call: they launch nothing
+                            PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE, STRUCT_WORKSPACE, SMOOTH_WORKSPACE,
+                            RECUR_WORKSPACE))   # mosaic_call: they launch nothing
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

@@ -212,3 +212,8 @@ RV_INTERNAL int rv_smooth_filter(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_smooth_backward(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_smooth_splice(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_smooth_workspace(rv_mosaic_desc* d);
+// The recurrence ops of rv_mosaic (recur.hip): RV_RECUR_PROFILE on the fields the public header names for it -- checks
+// first, then the launches, no sync and no read of the device -- and RV_RECUR_WORKSPACE, which writes d->ws_bytes and
+// launches nothing.
+RV_INTERNAL int rv_recur_profile(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_recur_workspace(rv_mosaic_desc* d);

@@ -1,5 +1,6 @@
-// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 38 ops.  Each family keeps
-// its kernels, checks and launches in its own file and hands rv_mosaic one function per op (internal.h):
+// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 40 ops (codes 0 .. 37, 40 and
+// 41; 38 and 39 are unassigned and answer as unknown ops).  Each family keeps its kernels, checks and launches in its own
+// file and hands rv_mosaic one function per op (internal.h):
 //    0, 1, 8, 9   RV_MOSAIC_KNN, _KNN_WORKSPACE, _KNN_SMALL, _KNN_SMALL_WORKSPACE        mosaic_knn.hip
 //    2, 3         RV_MOSAIC_GATHER_MEAN, RV_MOSAIC_OLA                                   this file
 //    4 .. 7       RV_MOSAIC_TRANSITION, _PATH_FORWARD, _PATH_BACKTRACK, _PATH_WORKSPACE  mosaic_path.hip
@@ -11,6 +12,7 @@
 //   26 .. 30      RV_ALIGN_COST, _FORWARD, _BACKTRACK, _WARP, _WORKSPACE                 align.hip
 //   31 .. 33      RV_STRUCT_NOVELTY, _PEAKS, _WORKSPACE                                  structure.hip
 //   34 .. 37      RV_SMOOTH_FILTER, _BACKWARD, _SPLICE, _WORKSPACE                       smooth.hip
+//   40, 41        RV_RECUR_PROFILE, _WORKSPACE                                           recur.hip
 // Here also the two synthesis ops of the offline mosaic (rawaudiovae_kelsey_amd/mosaic.py):
 //   RV_MOSAIC_GATHER_MEAN  out[t] = (1/k) sum_j src[start(idx[t, j]) : + width] (grains or latent rows)
 //   RV_MOSAIC_OLA          offline weighted overlap-add normalised by the window sum
@@ -137,6 +139,8 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
     case RV_SMOOTH_BACKWARD: return rv_smooth_backward(d, stream);
     case RV_SMOOTH_SPLICE: return rv_smooth_splice(d, stream);
     case RV_SMOOTH_WORKSPACE: return rv_smooth_workspace(d);
+    case RV_RECUR_PROFILE: return rv_recur_profile(d, stream);
+    case RV_RECUR_WORKSPACE: return rv_recur_workspace(d);
   }
   return rv_fail(RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
 }
