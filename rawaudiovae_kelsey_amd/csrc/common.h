@@ -66,6 +66,23 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   return r;
 }
 
+// Sum of one double per thread over the block's WAVES waves in a fixed order: the xor butterfly within a wave (every
+// lane ends with the same bits), then red[0] + red[1] + .. left to right.  Valid in every thread.  `red` = WAVES doubles
+// of LDS.  Starting from red[0] and from +0.0 differ in bits only when every addend is -0.0; k_pca_eig's sums of
+// fma(a, a, part) from +0.0 never are.
+template <int WAVES>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();   // red may still be read from the call before
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s += red[w];
+  return s;
+}
+
 // 16-byte WRITE-THROUGH store (global_store_dwordx4 ... sc0 sc1): the line goes to memory as the store retires instead
 // of staying dirty in the XCD's L2 until the end-of-kernel release writes everything back at once.  Every kernel of
 // the step ends with a burst of output stores (8-34 MB) that nothing in the same launch reads again, and the next

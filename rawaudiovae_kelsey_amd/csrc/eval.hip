@@ -4,12 +4,14 @@
 //                   spectral convergence: k_eval_frames, one workgroup of 256 threads per pair.  The spectra come from a
 //                   radix-2 transform in LDS, each signal transformed on its own.
 //   RV_EVAL_DIMS    the KL sum of every latent dimension over the rows: k_eval_dims_block (one thread per (block of
-//                   256 rows, dimension)), then k_eval_dims_sum over the blocks.  No atomics.
+//                   256 rows, dimension)), then k_eval_dims_sum over the blocks: moment.h's blocked column sum, which
+//                   RV_PCA_MOMENTS' mean shares.  No atomics.
 #include <limits.h>
 #include <math.h>
 
 #include "common.h"
 #include "internal.h"
+#include "moment.h"
 
 using namespace rv;
 
@@ -18,19 +20,6 @@ namespace {
 constexpr int EV_THREADS = 256;
 constexpr int EV_SMAX = 4096;            // longest frame with spectral columns
 constexpr int EV_SMIN = 32;
-constexpr int DIMS_ROWS = 256;           // rows of one block of RV_EVAL_DIMS (the header states it)
-constexpr int DIMS_THREADS = 64;
-
-// Sum of one double per thread over the workgroup, in a fixed order: within a wave the xor butterfly (every lane ends
-// with the same bits), then the four wave sums in ascending wave order.  Valid in every thread.
-__device__ __forceinline__ double block_sum_f64(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();   // red may still be read from the call before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((red[0] + red[1]) + red[2]) + red[3];
-}
 
 __device__ __forceinline__ float block_max_f32(float v, float* red) {
 #pragma unroll
@@ -116,12 +105,12 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
       }
     }
   }
-  sse = block_sum_f64(sse, red);
-  en = block_sum_f64(en, red);
+  sse = block_sum_f64<EV_THREADS / 64>(sse, red);
+  en = block_sum_f64<EV_THREADS / 64>(en, red);
   double kl = 0.0;
   if (mu) {
     for (int j = threadIdx.x; j < L; j += EV_THREADS) kl += kl_term(mu[t * L + j], lv[t * L + j]);
-    kl = block_sum_f64(kl, red);
+    kl = block_sum_f64<EV_THREADS / 64>(kl, red);
   }
   float lsd = 0.f, serr = 0.f, sref = 0.f;
   if constexpr (SPEC) {
@@ -194,9 +183,9 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
         se += (double)(e * e);
       }
     }
-    d2 = block_sum_f64(d2, red);
-    se = block_sum_f64(se, red);
-    sr = block_sum_f64(sr, red);
+    d2 = block_sum_f64<EV_THREADS / 64>(d2, red);
+    se = block_sum_f64<EV_THREADS / 64>(se, red);
+    sr = block_sum_f64<EV_THREADS / 64>(sr, red);
     if (fl > 0.f) {
       lsd = (float)sqrt(d2 / (double)(N + 1));
       serr = (float)se;
@@ -216,26 +205,20 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
   }
 }
 
-// Grid (blocks of DIMS_ROWS rows, tiles of DIMS_THREADS dimensions): thread (b, j) adds rows [256 b, 256 b + 256) of
-// dimension j in ascending t from +0 into part[b, j] (which is `cost` itself when there is one block).
-__global__ void __launch_bounds__(DIMS_THREADS)
+// Grid (blocks of 256 rows, tiles of 64 dimensions), moment.h's blocked column sum: thread (b, j) adds rows
+// [256 b, 256 b + 256) of dimension j in ascending t from +0 into part[b, j] (which is `cost` itself when there is one
+// block).
+__global__ void __launch_bounds__(mom::THREADS)
 k_eval_dims_block(const float* __restrict__ mu, const float* __restrict__ lv, long T, long L, double* __restrict__ part) {
-  const long j = (long)blockIdx.y * DIMS_THREADS + threadIdx.x;
-  if (j >= L) return;
-  const long t0 = (long)blockIdx.x * DIMS_ROWS, t1 = t0 + DIMS_ROWS < T ? t0 + DIMS_ROWS : T;
-  double acc = 0.0;
-  for (long t = t0; t < t1; ++t) acc += kl_term(mu[t * L + j], lv[t * L + j]);
-  part[(long)blockIdx.x * L + j] = acc;
+  mom::colsum_block([=](long t, long j) { return kl_term(mu[t * L + j], lv[t * L + j]); }, T, L, part);
 }
 
 // cost[j] = the block sums of dimension j in ascending block order from +0
-__global__ void __launch_bounds__(DIMS_THREADS)
+__global__ void __launch_bounds__(mom::THREADS)
 k_eval_dims_sum(const double* __restrict__ part, long nb, long L, double* __restrict__ cost) {
-  const long j = (long)blockIdx.x * DIMS_THREADS + threadIdx.x;
+  const long j = (long)blockIdx.x * mom::THREADS + threadIdx.x;
   if (j >= L) return;
-  double acc = 0.0;
-  for (long b = 0; b < nb; ++b) acc += part[b * L + j];
-  cost[j] = acc;
+  cost[j] = mom::colsum_total(part, nb, L, j);
 }
 
 }  // namespace
@@ -286,18 +269,18 @@ int rv_eval_dims(const rv_mosaic_desc* d, void* stream) {
   RV_REQUIRE(d->mu, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): mu is null");
   RV_REQUIRE(d->logvar, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): logvar is null");
   RV_REQUIRE(d->cost, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): cost is null");
-  const long nb = (d->T + DIMS_ROWS - 1) / DIMS_ROWS;
+  const long nb = (d->T + mom::ROWS - 1) / mom::ROWS;
   const long need = nb > 1 ? nb * d->L * (long)sizeof(double) : 0;
   RV_REQUIRE(d->ws_bytes >= need, RV_ERR_SHAPE, "rv_mosaic(EVAL_DIMS): ws_bytes=%ld, T=%ld rows of L=%ld need %ld", d->ws_bytes,
              d->T, d->L, need);
   RV_REQUIRE(need == 0 || d->ws, RV_ERR_NULL, "rv_mosaic(EVAL_DIMS): ws is null, T=%ld rows of L=%ld need %ld bytes", d->T,
              d->L, need);
   const hipStream_t st = (hipStream_t)stream;
-  const unsigned tiles = (unsigned)((d->L + DIMS_THREADS - 1) / DIMS_THREADS);
+  const unsigned tiles = (unsigned)((d->L + mom::THREADS - 1) / mom::THREADS);
   double* part = nb > 1 ? (double*)d->ws : d->cost;
-  hipLaunchKernelGGL(k_eval_dims_block, dim3((unsigned)nb, tiles), dim3(DIMS_THREADS), 0, st, d->mu, d->logvar, d->T, d->L, part);
+  hipLaunchKernelGGL(k_eval_dims_block, dim3((unsigned)nb, tiles), dim3(mom::THREADS), 0, st, d->mu, d->logvar, d->T, d->L, part);
   if (nb > 1)
-    hipLaunchKernelGGL(k_eval_dims_sum, dim3(tiles), dim3(DIMS_THREADS), 0, st, (const double*)d->ws, nb, d->L, d->cost);
+    hipLaunchKernelGGL(k_eval_dims_sum, dim3(tiles), dim3(mom::THREADS), 0, st, (const double*)d->ws, nb, d->L, d->cost);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

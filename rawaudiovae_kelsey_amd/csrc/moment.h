@@ -1,0 +1,174 @@
+// The fp64 corpus statistics of the audio tools: the second moments of RV_PCA_MOMENTS (pca.hip, the covariance) and
+// RV_PCA_LAGCOV (walk.hip, the lag-1 moment), and the blocked column sums of RV_PCA_MOMENTS (the mean) and RV_EVAL_DIMS
+// (eval.hip, the KL sums).  Defined here once, down to the order of every add; no atomics anywhere, so the bits depend
+// on the data and its shape alone.
+//   Second moment.  d[t][c] = (double)x[t][c] - centre[c].  Element (i, j) of the range of RANGE rows from t0 is
+//   sum_t a[t][i] b[t][j], with a = b = d (covariance, t a row) or a[t] = d[t + 1], b[t] = keep[t] d[t] (lag-1, t a
+//   pair): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
+//   four rows to the element.  Rows and columns beyond the data stage zeros.  Then the ranges' partials of an element
+//   in ascending range order from +0 (range_sum), and the caller's one division.
+//   Column sum.  Blocks of ROWS rows: a block's terms in ascending t from +0 (colsum_block), then the block sums in
+//   ascending block order from +0 (colsum_total).
+// The tiling and the measured figures: DESIGN.md sections 7.9 to 7.11.
+#pragma once
+#include "common.h"
+
+namespace rv {
+namespace mom {
+
+typedef double f64x4 __attribute__((ext_vector_type(4)));
+
+constexpr int RANGE = 4096;        // rows (pairs) of one range (the public header states it)
+constexpr int CHUNK = 32;          // rows staged in LDS at a time
+constexpr int MT = 64;             // the workgroup's tile: 4 x 4 MFMA tiles of 16 x 16, one row of them per wave
+constexpr int LD = 80;             // LDS row pitch in doubles: rows k .. k + 3 of an operand fall into disjoint banks
+constexpr int TILE_THREADS = 256;
+constexpr int STAGE = CHUNK * LD;  // doubles of one operand's LDS stage
+constexpr int TILE = MT * MT;      // doubles of one partial tile
+constexpr int ROWS = 256;          // rows of one block of a column sum (the public header states it)
+constexpr int THREADS = 64;        // a column per thread
+
+// Number of the 64 x 64 tile (I, J) within a range: among the tiles on or above the diagonal, row by row (J >= I, the
+// covariance), or in the full square (the lag-1 moment).
+__host__ __device__ __forceinline__ int tile_number(int I, int J, int nI) { return I * nI - I * (I - 1) / 2 + (J - I); }
+__host__ __device__ __forceinline__ int square_number(int I, int J, int nI) { return I * nI + J; }
+
+// The partial tiles of `rows` rows (pairs) of L columns in ws
+struct tiles {
+  long n_ranges, doubles;
+  int nI, n_tiles;   // tiles along a side, tiles per range
+};
+
+inline tiles tile_layout(long rows, long L, bool lag) {
+  tiles w;
+  w.n_ranges = (rows + RANGE - 1) / RANGE;
+  w.nI = (int)((L + MT - 1) / MT);
+  w.n_tiles = lag ? w.nI * w.nI : w.nI * (w.nI + 1) / 2;
+  w.doubles = w.n_ranges * w.n_tiles * (long)TILE;
+  return w;
+}
+
+// The thread's column of both operands at rows t, t + 4, ..: row t + 1 for the left operand and the pair's keep flag
+// when LAG.  A row beyond the range is read from the range's last row (the caller stores a zero in its place).
+template <bool LAG, int PER>
+__device__ __forceinline__ void fetch(const float* __restrict__ xa, const float* __restrict__ xb,
+                                      const unsigned char* __restrict__ keep, long t, long t1, long L, bool diag,
+                                      float (&fa)[PER], float (&fb)[PER], unsigned char (&fk)[PER]) {
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    const long tt = t + 4 * i;
+    const long tr = tt < t1 ? tt : t1 - 1;
+    if constexpr (LAG) {
+      fa[i] = xa[(tr + 1) * L];
+      fb[i] = xb[tr * L];
+      fk[i] = keep[tr];
+    } else {
+      fa[i] = xa[tr * L];
+      fb[i] = diag ? 0.f : xb[tr * L];
+    }
+  }
+}
+
+// One range (blockIdx.x) of the n rows (pairs) and the tile (I, J), which is number blockIdx.y of the n_tiles of a
+// range in part.  TILE_THREADS threads; As and Bs are STAGE doubles of LDS each.  Wave w owns the MFMA tiles (w, 0 .. 3) of the tile; on a diagonal
+// tile of the covariance those left of the diagonal are skipped (and not written) and B is read from As.
+// v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; with
+// A[i][k] = a[t + k][i0 + i] and B[k][j] = b[t + k][j0 + j] one instruction adds four rows to the tile.  Its result:
+// column l & 15, row (l >> 4) + 4 reg.
+template <bool LAG>
+__device__ __forceinline__ void moment_tile(double* As, double* Bs, const float* __restrict__ x, long n, int L,
+                                            const double* __restrict__ centre, const unsigned char* __restrict__ keep,
+                                            int I, int J, int n_tiles, double* __restrict__ part) {
+  const bool diag = !LAG && I == J;
+  const int lane = threadIdx.x & 63, ti = threadIdx.x >> 6;
+  const double* const Bsrc = diag ? As : Bs;
+  f64x4 acc[4];
+#pragma unroll
+  for (int tj = 0; tj < 4; ++tj) acc[tj] = f64x4{0.0, 0.0, 0.0, 0.0};
+  const long t0 = (long)blockIdx.x * RANGE, t1 = t0 + RANGE < n ? t0 + RANGE : n;
+  // Staging: thread (cc = lane, ti) carries column cc of both operands for the rows ti, ti + 4, .. of a chunk.  The
+  // loads of the next chunk are issued before the MFMAs of this one; a row or column beyond the data is read from a
+  // clamped address and replaced by zero on its way into LDS.
+  constexpr int PER = CHUNK / (TILE_THREADS / MT);   // rows per thread and chunk
+  const int cc = lane;
+  const int ca = I * MT + cc, cb = J * MT + cc;
+  const bool va = ca < L, vb = cb < L;
+  const double ma = va ? centre[ca] : 0.0, mb = vb ? centre[cb] : 0.0;
+  const float* const xa = x + (va ? ca : L - 1);
+  const float* const xb = x + (vb ? cb : L - 1);
+  float fa[PER], fb[PER];
+  unsigned char fk[PER];
+  fetch<LAG, PER>(xa, xb, keep, t0 + ti, t1, L, diag, fa, fb, fk);
+  for (long tc = t0; tc < t1; tc += CHUNK) {
+    __syncthreads();   // the MFMAs of the chunk before have read LDS
+#pragma unroll
+    for (int i = 0; i < PER; ++i) {
+      const int r = ti + 4 * i;
+      const bool vt = tc + r < t1;
+      As[r * LD + cc] = (vt && va) ? (double)fa[i] - ma : 0.0;
+      if constexpr (LAG) Bs[r * LD + cc] = (vt && vb && fk[i]) ? (double)fb[i] - mb : 0.0;
+      else if (!diag) Bs[r * LD + cc] = (vt && vb) ? (double)fb[i] - mb : 0.0;
+    }
+    __syncthreads();
+    if (tc + CHUNK < t1) fetch<LAG, PER>(xa, xb, keep, tc + CHUNK + ti, t1, L, diag, fa, fb, fk);
+#pragma unroll
+    for (int kk = 0; kk < CHUNK; kk += 4) {
+      const int row = (kk + (lane >> 4)) * LD + (lane & 15);
+      const double a = As[row + ti * 16];
+#pragma unroll
+      for (int tj = 0; tj < 4; ++tj) {
+        if (diag && tj < ti) continue;   // wave-uniform
+        const double b = Bsrc[row + tj * 16];
+        acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
+      }
+    }
+  }
+  double* const part_tile = part + ((long)blockIdx.x * n_tiles + blockIdx.y) * TILE;
+#pragma unroll
+  for (int tj = 0; tj < 4; ++tj) {
+    if (diag && tj < ti) continue;
+#pragma unroll
+    for (int reg = 0; reg < 4; ++reg)
+      part_tile[(ti * 16 + (lane >> 4) + 4 * reg) * MT + tj * 16 + (lane & 15)] = acc[tj][reg];
+  }
+}
+
+// Element (i, j) of the matrix: its partials in ascending range order from +0.  `tile` is the number of the element's
+// tile within a range, of n_tiles.
+__device__ __forceinline__ double range_sum(const double* __restrict__ part, long n_ranges, int n_tiles, int tile, int i,
+                                            int j) {
+  const long at = (long)tile * TILE + (i & 63) * MT + (j & 63);
+  double acc = 0.0;
+  for (long r = 0; r < n_ranges; ++r) acc += part[r * n_tiles * TILE + at];
+  return acc;
+}
+
+// Grid (blocks of ROWS rows, tiles of THREADS columns): part[b, j] = term(t, j) over the rows [256 b, 256 b + 256) of
+// column j, added in ascending t from +0.
+template <class Term>
+__device__ __forceinline__ void colsum_block(Term term, long T, long L, double* __restrict__ part) {
+  const long j = (long)blockIdx.y * THREADS + threadIdx.x;
+  if (j >= L) return;
+  const long t0 = (long)blockIdx.x * ROWS, t1 = t0 + ROWS < T ? t0 + ROWS : T;
+  double acc = 0.0;
+  for (long t = t0; t < t1; ++t) acc += term(t, j);
+  part[(long)blockIdx.x * L + j] = acc;
+}
+
+// The nb block sums of column j in ascending block order from +0
+__device__ __forceinline__ double colsum_total(const double* __restrict__ part, long nb, long L, long j) {
+  double acc = 0.0;
+  long b = 0;
+  for (; b + 8 <= nb; b += 8) {   // eight loads in flight, added in ascending order all the same
+    double v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) v[i] = part[(b + i) * L + j];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc += v[i];
+  }
+  for (; b < nb; ++b) acc += part[b * L + j];
+  return acc;
+}
+
+}  // namespace mom
+}  // namespace rv

@@ -1,8 +1,8 @@
 // Latent PCA (rawaudiovae_kelsey_amd/pca.py): four ops of rv_mosaic.  The rules: include/rawvae_hip.h, "Latent PCA";
 // the tiling, the error model and the measured figures: DESIGN.md section 7.10.
-//   RV_PCA_MOMENTS   fp64 column means (k_pca_mean_block / k_pca_mean_sum, RV_EVAL_DIMS's order of adding) and the
+//   RV_PCA_MOMENTS   fp64 column means (k_pca_mean_block / k_pca_mean_sum, moment.h's blocked column sum) and the
 //                    fp64 sample covariance: k_pca_cov, one workgroup per (range of 4096 rows, 64 x 64 tile on or
-//                    above the diagonal) on v_mfma_f64_16x16x4_f64, then k_pca_cov_sum over the ranges.  No atomics.
+//                    above the diagonal) on moment.h's MFMA tile, then k_pca_cov_sum over the ranges.  No atomics.
 //   RV_PCA_EIG       cyclic two-sided Jacobi in fp64: k_pca_eig, ONE workgroup, the matrix in global memory, a
 //                    __syncthreads() between the steps; nothing waits on another workgroup.
 //   RV_PCA_APPLY     projection, reconstruction and edits along the components: k_pca_apply, a tile of rows per
@@ -13,21 +13,13 @@
 
 #include "common.h"
 #include "internal.h"
+#include "moment.h"
 
 using namespace rv;
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int PCA_LMAX = 512;
-constexpr int MEAN_ROWS = 256;           // rows of one block of the mean (the header states it)
-constexpr int MEAN_THREADS = 64;
-constexpr int CV_RANGE = 4096;           // rows of one range of the covariance (the header states it)
-constexpr int CV_CHUNK = 32;             // rows staged in LDS at a time
-constexpr int CV_MT = 64;                // the workgroup's tile: 4 x 4 MFMA tiles of 16 x 16, one row of them per wave
-constexpr int CV_LD = 80;                // LDS row pitch in doubles: rows k .. k + 3 of an operand fall into disjoint banks
-constexpr int CV_THREADS = 256;
 constexpr int EG_THREADS = 1024;
 constexpr int EG_SWEEPS = 40;
 constexpr int AP_THREADS = 256;
@@ -35,116 +27,32 @@ constexpr int AP_VC = 8;                 // columns of the component tile staged
 constexpr int AP_VLD = AP_VC + 1;
 
 // part[b, j] = rows [256 b, 256 b + 256) of column j added in ascending t from +0
-__global__ void __launch_bounds__(MEAN_THREADS)
+__global__ void __launch_bounds__(mom::THREADS)
 k_pca_mean_block(const float* __restrict__ x, long T, long L, double* __restrict__ part) {
-  const long j = (long)blockIdx.y * MEAN_THREADS + threadIdx.x;
-  if (j >= L) return;
-  const long t0 = (long)blockIdx.x * MEAN_ROWS, t1 = t0 + MEAN_ROWS < T ? t0 + MEAN_ROWS : T;
-  double acc = 0.0;
-  for (long t = t0; t < t1; ++t) acc += (double)x[t * L + j];
-  part[(long)blockIdx.x * L + j] = acc;
+  mom::colsum_block([=](long t, long j) { return (double)x[t * L + j]; }, T, L, part);
 }
 
 // centre[j] = (the block sums of column j in ascending block order from +0) / T
-__global__ void __launch_bounds__(MEAN_THREADS)
+__global__ void __launch_bounds__(mom::THREADS)
 k_pca_mean_sum(const double* __restrict__ part, long nb, long L, long T, double* __restrict__ centre) {
-  const long j = (long)blockIdx.x * MEAN_THREADS + threadIdx.x;
+  const long j = (long)blockIdx.x * mom::THREADS + threadIdx.x;
   if (j >= L) return;
-  double acc = 0.0;
-  long b = 0;
-  for (; b + 8 <= nb; b += 8) {   // eight loads in flight, added in ascending order all the same
-    double v[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = part[(b + i) * L + j];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc += v[i];
-  }
-  for (; b < nb; ++b) acc += part[b * L + j];
-  centre[j] = acc / (double)T;
+  centre[j] = mom::colsum_total(part, nb, L, j) / (double)T;
 }
 
-// number of the 64 x 64 tile (I, J >= I) among the tiles on or above the diagonal, row by row
-__host__ __device__ __forceinline__ int tile_number(int I, int J, int nI) { return I * nI - I * (I - 1) / 2 + (J - I); }
-
-// The thread's column of both operands at rows t, t + 4, ..; a row beyond the range is read from the range's last row
-// (the caller stores a zero in its place).
-template <int PER>
-__device__ __forceinline__ void cov_fetch(const float* __restrict__ xa, const float* __restrict__ xb, long t, long t1, long L,
-                                          bool diag, float (&fa)[PER], float (&fb)[PER]) {
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const long tt = t + 4 * i;
-    const long tr = (tt < t1 ? tt : t1 - 1) * L;
-    fa[i] = xa[tr];
-    fb[i] = diag ? 0.f : xb[tr];
-  }
-}
-
-// Grid (ranges, tiles on or above the diagonal).  Wave w owns the MFMA tiles (w, 0 .. 3) of the 64 x 64 tile; on a
-// diagonal tile those left of the diagonal are skipped.  v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4]
-// and B[k = l >> 4][j = l & 15]; with A[i][k] = d[t + k][i0 + i] and B[k][j] = d[t + k][j0 + j] one instruction adds
-// four rows of d to the tile.  Its result: column l & 15, row (l >> 4) + 4 reg.
-__global__ void __launch_bounds__(CV_THREADS)
+// Grid (ranges, tiles on or above the diagonal): moment.h's tile in its symmetric form, A[i][k] = d[t + k][i0 + i]
+// and B[k][j] = d[t + k][j0 + j].
+__global__ void __launch_bounds__(mom::TILE_THREADS)
 k_pca_cov(const float* __restrict__ x, long T, int L, const double* __restrict__ centre, int nI, int n_tiles,
           double* __restrict__ part) {
-  __shared__ double As[CV_CHUNK * CV_LD];
-  __shared__ double Bs[CV_CHUNK * CV_LD];
+  __shared__ double As[mom::STAGE];
+  __shared__ double Bs[mom::STAGE];
   int I = 0, rem = (int)blockIdx.y;
   while (rem >= nI - I) {
     rem -= nI - I;
     ++I;
   }
-  const int J = I + rem;
-  const bool diag = I == J;
-  const int lane = threadIdx.x & 63, ti = threadIdx.x >> 6;
-  const double* const Bsrc = diag ? As : Bs;
-  f64x4 acc[4];
-#pragma unroll
-  for (int tj = 0; tj < 4; ++tj) acc[tj] = f64x4{0.0, 0.0, 0.0, 0.0};
-  const long t0 = (long)blockIdx.x * CV_RANGE, t1 = t0 + CV_RANGE < T ? t0 + CV_RANGE : T;
-  // Staging: thread (cc = lane, ti) carries column cc of both operands for the rows ti, ti + 4, .. of a chunk.  The
-  // loads of the next chunk are issued before the MFMAs of this one; a row or column beyond the data is read from a
-  // clamped address and replaced by zero on its way into LDS.
-  constexpr int PER = CV_CHUNK / (CV_THREADS / CV_MT);   // rows per thread and chunk
-  const int cc = lane;
-  const int ca = I * CV_MT + cc, cb = J * CV_MT + cc;
-  const bool va = ca < L, vb = cb < L;
-  const double ma = va ? centre[ca] : 0.0, mb = vb ? centre[cb] : 0.0;
-  const float* const xa = x + (va ? ca : L - 1);
-  const float* const xb = x + (vb ? cb : L - 1);
-  float fa[PER], fb[PER];
-  cov_fetch<PER>(xa, xb, t0 + ti, t1, L, diag, fa, fb);
-  for (long tc = t0; tc < t1; tc += CV_CHUNK) {
-    __syncthreads();   // the MFMAs of the chunk before have read LDS
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int r = ti + 4 * i;
-      const bool vt = tc + r < t1;
-      As[r * CV_LD + cc] = (vt && va) ? (double)fa[i] - ma : 0.0;
-      if (!diag) Bs[r * CV_LD + cc] = (vt && vb) ? (double)fb[i] - mb : 0.0;
-    }
-    __syncthreads();
-    if (tc + CV_CHUNK < t1) cov_fetch<PER>(xa, xb, tc + CV_CHUNK + ti, t1, L, diag, fa, fb);
-#pragma unroll
-    for (int kk = 0; kk < CV_CHUNK; kk += 4) {
-      const int row = (kk + (lane >> 4)) * CV_LD + (lane & 15);
-      const double a = As[row + ti * 16];
-#pragma unroll
-      for (int tj = 0; tj < 4; ++tj) {
-        if (diag && tj < ti) continue;   // wave-uniform
-        const double b = Bsrc[row + tj * 16];
-        acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
-      }
-    }
-  }
-  double* const o = part + ((long)blockIdx.x * n_tiles + blockIdx.y) * (CV_MT * CV_MT);
-#pragma unroll
-  for (int tj = 0; tj < 4; ++tj) {
-    if (diag && tj < ti) continue;
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
-      o[(ti * 16 + (lane >> 4) + 4 * reg) * CV_MT + tj * 16 + (lane & 15)] = acc[tj][reg];
-  }
+  mom::moment_tile<false>(As, Bs, x, T, L, centre, nullptr, I, I + rem, n_tiles, part);
 }
 
 // Grid (tiles of 64 columns, rows): element (i, j >= i) = its partials in ascending range order from +0, over T - 1,
@@ -153,26 +61,10 @@ __global__ void __launch_bounds__(64)
 k_pca_cov_sum(const double* __restrict__ part, long n_ranges, int n_tiles, int nI, int L, long T, double* __restrict__ cov) {
   const int i = (int)blockIdx.y, j = (int)blockIdx.x * 64 + (int)threadIdx.x;
   if (j >= L || j < i) return;
-  const long at = (long)tile_number(i >> 6, j >> 6, nI) * (CV_MT * CV_MT) + (i & 63) * CV_MT + (j & 63);
-  double acc = 0.0;
-  for (long r = 0; r < n_ranges; ++r) acc += part[r * n_tiles * (CV_MT * CV_MT) + at];
+  const double acc = mom::range_sum(part, n_ranges, n_tiles, mom::tile_number(i >> 6, j >> 6, nI), i, j);
   const double v = acc / (double)(T - 1);
   cov[(long)i * L + j] = v;
   cov[(long)j * L + i] = v;
-}
-
-// Sum of one double per thread over the 1024 threads in a fixed order: the xor butterfly within a wave, then the 16
-// wave sums in ascending wave order.  Valid in every thread.
-__device__ __forceinline__ double eig_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();   // red may still be read from the call before
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < EG_THREADS / 64; ++w) s += red[w];
-  return s;
 }
 
 // A 2 x 2 block x[a][b] whose axis 0 carries the pair of the lower pair number: that pair's rotation (c0, s0) along
@@ -209,7 +101,7 @@ k_pca_eig(double* A, int L, double* Vt, double* lam_out, int* info) {
     part = __builtin_fma(a, a, part);
     Vt[e] = (e / L == e % L) ? 1.0 : 0.0;
   }
-  const double thr = (double)L * 0x1p-52 * sqrt(eig_block_sum(part, red));
+  const double thr = (double)L * 0x1p-52 * sqrt(block_sum_f64<EG_THREADS / 64>(part, red));
 
   int sweeps = 0, converged = 0;
   for (int sweep = 0; sweep <= EG_SWEEPS; ++sweep) {
@@ -218,7 +110,7 @@ k_pca_eig(double* A, int L, double* Vt, double* lam_out, int* info) {
       const double a = A[e];
       if (e / L != e % L) part = __builtin_fma(a, a, part);
     }
-    const double off = sqrt(eig_block_sum(part, red));   // the same bits in every thread
+    const double off = sqrt(block_sum_f64<EG_THREADS / 64>(part, red));   // the same bits in every thread
     if (off <= thr) {
       converged = 1;
       break;
@@ -410,18 +302,16 @@ k_pca_apply(int mode, const float* __restrict__ q, long T, int L, int k, const d
 }
 
 struct moments_ws {
-  long nb, n_ranges, mean_doubles, bytes;
-  int nI, n_tiles;
+  long nb, mean_doubles, bytes;
+  mom::tiles cov;
 };
 
 moments_ws moments_layout(long T, long L) {
   moments_ws w;
-  w.nb = (T + MEAN_ROWS - 1) / MEAN_ROWS;
-  w.n_ranges = (T + CV_RANGE - 1) / CV_RANGE;
-  w.nI = (int)((L + CV_MT - 1) / CV_MT);
-  w.n_tiles = w.nI * (w.nI + 1) / 2;
+  w.nb = (T + mom::ROWS - 1) / mom::ROWS;
   w.mean_doubles = w.nb * L;
-  w.bytes = (w.mean_doubles + w.n_ranges * w.n_tiles * (long)(CV_MT * CV_MT)) * (long)sizeof(double);
+  w.cov = mom::tile_layout(T, L, false);
+  w.bytes = (w.mean_doubles + w.cov.doubles) * (long)sizeof(double);
   return w;
 }
 
@@ -456,14 +346,14 @@ int rv_pca_moments(const rv_mosaic_desc* d, void* stream) {
   const int L = (int)d->L;
   double* const mean_part = (double*)d->ws;
   double* const cov_part = mean_part + w.mean_doubles;
-  const unsigned col_tiles = (unsigned)((L + MEAN_THREADS - 1) / MEAN_THREADS);
-  hipLaunchKernelGGL(k_pca_mean_block, dim3((unsigned)w.nb, col_tiles), dim3(MEAN_THREADS), 0, st, d->q, d->T, d->L, mean_part);
-  hipLaunchKernelGGL(k_pca_mean_sum, dim3(col_tiles), dim3(MEAN_THREADS), 0, st, (const double*)mean_part, w.nb, d->L, d->T,
+  const unsigned col_tiles = (unsigned)((L + mom::THREADS - 1) / mom::THREADS);
+  hipLaunchKernelGGL(k_pca_mean_block, dim3((unsigned)w.nb, col_tiles), dim3(mom::THREADS), 0, st, d->q, d->T, d->L, mean_part);
+  hipLaunchKernelGGL(k_pca_mean_sum, dim3(col_tiles), dim3(mom::THREADS), 0, st, (const double*)mean_part, w.nb, d->L, d->T,
                      d->centre);
-  hipLaunchKernelGGL(k_pca_cov, dim3((unsigned)w.n_ranges, (unsigned)w.n_tiles), dim3(CV_THREADS), 0, st, d->q, d->T, L,
-                     d->centre, w.nI, w.n_tiles, cov_part);
+  hipLaunchKernelGGL(k_pca_cov, dim3((unsigned)w.cov.n_ranges, (unsigned)w.cov.n_tiles), dim3(mom::TILE_THREADS), 0, st, d->q,
+                     d->T, L, d->centre, w.cov.nI, w.cov.n_tiles, cov_part);
   hipLaunchKernelGGL(k_pca_cov_sum, dim3((unsigned)((L + 63) / 64), (unsigned)L), dim3(64), 0, st, (const double*)cov_part,
-                     w.n_ranges, w.n_tiles, w.nI, L, d->T, d->basis);
+                     w.cov.n_ranges, w.cov.n_tiles, w.cov.nI, L, d->T, d->basis);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

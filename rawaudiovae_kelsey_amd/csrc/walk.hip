@@ -3,7 +3,7 @@
 // "Latent walk"; the derivation and the measured figures: DESIGN.md section 7.11.
 //   RV_PCA_LAGCOV     the fp64 lag-1 moment of the centred rows over the pairs (t, t + 1) of one file: k_walk_pairs (which
 //                     pairs count), k_walk_lag (one workgroup per range of 4096 pairs and 64 x 64 tile of the full matrix,
-//                     on v_mfma_f64_16x16x4_f64, pca.hip's staging) and k_walk_lag_sum over the ranges.  No atomics.
+//                     on moment.h's MFMA tile, which k_pca_cov shares) and k_walk_lag_sum over the ranges.  No atomics.
 //   RV_WALK_FIT       the small dense fp64 products of the fit, every output one ascending fma chain: k_walk_product
 //                     and three elementwise kernels.  A one-off of at most 2 * 512^3 flops, not tuned.
 //   RV_WALK_STEP      F frames of every stream in one launch, one workgroup per stream, the state in LDS: k_walk_step;
@@ -14,19 +14,13 @@
 #include "common.h"
 #include "philox.h"
 #include "internal.h"
+#include "moment.h"
 
 using namespace rv;
 
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WK_LMAX = 512;
-constexpr int LG_RANGE = 4096;           // pairs of one range (the header states it)
-constexpr int LG_CHUNK = 32;             // pairs staged in LDS at a time
-constexpr int LG_MT = 64;                // the workgroup's tile: 4 x 4 MFMA tiles of 16 x 16, one row of them per wave
-constexpr int LG_LD = 80;                // LDS row pitch in doubles (pca.hip's: rows k .. k + 3 fall into disjoint banks)
-constexpr int LG_THREADS = 256;
 constexpr int ST_THREADS = 256;
 
 // keep[p] = 1 when rows p and p + 1 lie in one file: p + 1 is none of row_start[0 .. n_files]
@@ -43,75 +37,15 @@ k_walk_pairs(const long long* __restrict__ row_start, long n_files, long n_pairs
   keep[p] = (lo <= n_files && row_start[lo] == p + 1) ? 0 : 1;
 }
 
-// The thread's column of both operands at pairs p, p + 4, ..: row p + 1 for the left operand, row p for the right one
-// and the pair's keep flag; a pair beyond the range is read from the range's last pair (the caller stores zeros).
-template <int PER>
-__device__ __forceinline__ void lag_fetch(const float* __restrict__ xa, const float* __restrict__ xb,
-                                          const unsigned char* __restrict__ keep, long p, long p1, long L,
-                                          float (&fa)[PER], float (&fb)[PER], unsigned char (&fk)[PER]) {
-#pragma unroll
-  for (int i = 0; i < PER; ++i) {
-    const long pp = p + 4 * i;
-    const long pr = pp < p1 ? pp : p1 - 1;
-    fa[i] = xa[(pr + 1) * L];
-    fb[i] = xb[pr * L];
-    fk[i] = keep[pr];
-  }
-}
-
-// Grid (ranges of pairs, nI * nI tiles).  Wave w owns the MFMA tiles (w, 0 .. 3) of the 64 x 64 tile (I, J).
-// v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; with
-// A[i][k] = d[p + k + 1][i0 + i] and B[k][j] = keep[p + k] d[p + k][j0 + j] one instruction adds four pairs to the tile.
-// Its result: column l & 15, row (l >> 4) + 4 reg.
-__global__ void __launch_bounds__(LG_THREADS)
+// Grid (ranges of pairs, nI * nI tiles): moment.h's tile in its lag-1 form, A[i][k] = d[p + k + 1][i0 + i] and
+// B[k][j] = keep[p + k] d[p + k][j0 + j].
+__global__ void __launch_bounds__(mom::TILE_THREADS)
 k_walk_lag(const float* __restrict__ x, long n_pairs, int L, const double* __restrict__ centre,
            const unsigned char* __restrict__ keep, int nI, double* __restrict__ part) {
-  __shared__ double As[LG_CHUNK * LG_LD];
-  __shared__ double Bs[LG_CHUNK * LG_LD];
+  __shared__ double As[mom::STAGE];
+  __shared__ double Bs[mom::STAGE];
   const int I = (int)blockIdx.y / nI, J = (int)blockIdx.y - I * nI;
-  const int lane = threadIdx.x & 63, ti = threadIdx.x >> 6;
-  f64x4 acc[4];
-#pragma unroll
-  for (int tj = 0; tj < 4; ++tj) acc[tj] = f64x4{0.0, 0.0, 0.0, 0.0};
-  const long p0 = (long)blockIdx.x * LG_RANGE, p1 = p0 + LG_RANGE < n_pairs ? p0 + LG_RANGE : n_pairs;
-  constexpr int PER = LG_CHUNK / (LG_THREADS / LG_MT);   // pairs per thread and chunk
-  const int cc = lane;
-  const int ca = I * LG_MT + cc, cb = J * LG_MT + cc;
-  const bool va = ca < L, vb = cb < L;
-  const double ma = va ? centre[ca] : 0.0, mb = vb ? centre[cb] : 0.0;
-  const float* const xa = x + (va ? ca : L - 1);
-  const float* const xb = x + (vb ? cb : L - 1);
-  float fa[PER], fb[PER];
-  unsigned char fk[PER];
-  lag_fetch<PER>(xa, xb, keep, p0 + ti, p1, L, fa, fb, fk);
-  for (long pc = p0; pc < p1; pc += LG_CHUNK) {
-    __syncthreads();   // the MFMAs of the chunk before have read LDS
-#pragma unroll
-    for (int i = 0; i < PER; ++i) {
-      const int r = ti + 4 * i;
-      const bool vp = pc + r < p1;
-      As[r * LG_LD + cc] = (vp && va) ? (double)fa[i] - ma : 0.0;
-      Bs[r * LG_LD + cc] = (vp && vb && fk[i]) ? (double)fb[i] - mb : 0.0;
-    }
-    __syncthreads();
-    if (pc + LG_CHUNK < p1) lag_fetch<PER>(xa, xb, keep, pc + LG_CHUNK + ti, p1, L, fa, fb, fk);
-#pragma unroll
-    for (int kk = 0; kk < LG_CHUNK; kk += 4) {
-      const int row = (kk + (lane >> 4)) * LG_LD + (lane & 15);
-      const double a = As[row + ti * 16];
-#pragma unroll
-      for (int tj = 0; tj < 4; ++tj) {
-        const double b = Bs[row + tj * 16];
-        acc[tj] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[tj], 0, 0, 0);
-      }
-    }
-  }
-  double* const o = part + ((long)blockIdx.x * (nI * nI) + blockIdx.y) * (LG_MT * LG_MT);
-#pragma unroll
-  for (int tj = 0; tj < 4; ++tj)
-#pragma unroll
-    for (int reg = 0; reg < 4; ++reg)
-      o[(ti * 16 + (lane >> 4) + 4 * reg) * LG_MT + tj * 16 + (lane & 15)] = acc[tj][reg];
+  mom::moment_tile<true>(As, Bs, x, n_pairs, L, centre, keep, I, J, nI * nI, part);
 }
 
 // Grid (tiles of 64 columns, rows): element (i, j) = its partials in ascending range order from +0, over T - 1.
@@ -119,9 +53,7 @@ __global__ void __launch_bounds__(64)
 k_walk_lag_sum(const double* __restrict__ part, long n_ranges, int nI, int L, long T, double* __restrict__ c1) {
   const int i = (int)blockIdx.y, j = (int)blockIdx.x * 64 + (int)threadIdx.x;
   if (j >= L) return;
-  const long at = (long)((i >> 6) * nI + (j >> 6)) * (LG_MT * LG_MT) + (i & 63) * LG_MT + (j & 63);
-  double acc = 0.0;
-  for (long r = 0; r < n_ranges; ++r) acc += part[r * (nI * nI) * (LG_MT * LG_MT) + at];
+  const double acc = mom::range_sum(part, n_ranges, nI * nI, mom::square_number(i >> 6, j >> 6, nI), i, j);
   c1[(long)i * L + j] = acc / (double)(T - 1);
 }
 
@@ -244,17 +176,16 @@ k_walk_step(const double* __restrict__ dyn, const double* __restrict__ R, const 
 }
 
 struct lag_ws {
-  long n_pairs, n_ranges, keep_bytes, bytes;
-  int nI;
+  long n_pairs, keep_bytes, bytes;
+  mom::tiles lag;
 };
 
 lag_ws lag_layout(long T, long L) {
   lag_ws w;
   w.n_pairs = T - 1;
-  w.n_ranges = (w.n_pairs + LG_RANGE - 1) / LG_RANGE;
-  w.nI = (int)((L + LG_MT - 1) / LG_MT);
   w.keep_bytes = up256(w.n_pairs);
-  w.bytes = w.keep_bytes + w.n_ranges * w.nI * w.nI * (long)(LG_MT * LG_MT) * (long)sizeof(double);
+  w.lag = mom::tile_layout(w.n_pairs, L, true);
+  w.bytes = w.keep_bytes + w.lag.doubles * (long)sizeof(double);
   return w;
 }
 
@@ -296,10 +227,10 @@ int rv_pca_lagcov(const rv_mosaic_desc* d, void* stream) {
   unsigned char* const keep = (unsigned char*)d->ws;
   double* const part = (double*)(keep + w.keep_bytes);
   hipLaunchKernelGGL(k_walk_pairs, dim3(blocks256(w.n_pairs)), dim3(256), 0, st, d->row_start, d->n_rows, w.n_pairs, keep);
-  hipLaunchKernelGGL(k_walk_lag, dim3((unsigned)w.n_ranges, (unsigned)(w.nI * w.nI)), dim3(LG_THREADS), 0, st, d->q, w.n_pairs,
-                     L, d->centre, (const unsigned char*)keep, w.nI, part);
+  hipLaunchKernelGGL(k_walk_lag, dim3((unsigned)w.lag.n_ranges, (unsigned)w.lag.n_tiles), dim3(mom::TILE_THREADS), 0, st, d->q,
+                     w.n_pairs, L, d->centre, (const unsigned char*)keep, w.lag.nI, part);
   hipLaunchKernelGGL(k_walk_lag_sum, dim3((unsigned)((L + 63) / 64), (unsigned)L), dim3(64), 0, st, (const double*)part,
-                     w.n_ranges, w.nI, L, d->T, d->basis);
+                     w.lag.n_ranges, w.lag.nI, L, d->T, d->basis);
   RV_CHECK_LAUNCH();
   return RV_OK;
 }

@@ -263,7 +263,7 @@ def _dims(mu, lv):
     return outs[0]
 
 
-@pytest.mark.parametrize("T", [1, 255, 257, 3 * 256 + 5])
+@pytest.mark.parametrize("T", [1, 255, 257, 3 * 256 + 5, 9 * 256 + 5])   # ten blocks: the total's group of eight, then two
 @pytest.mark.parametrize("L", [1, 8, 100, 256])
 def test_kl_dims_against_the_oracle(T, L):
     from rawaudiovae_kelsey_amd.evaluate import kl_dims
