@@ -918,6 +918,75 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_RECUR_PROFILE 40
 #define RV_RECUR_WORKSPACE 41
 #define RV_RECUR_MIRROR 1
+/* Latent states (csrc/hmm.hip, rawaudiovae_kelsey_amd/states.py): a hidden Markov model with
+ * diagonal Gaussian emissions over the whitened coordinates of "Latent restoration", fitted to a whole corpus by EM.  The
+ * family's conventions: no op syncs or reads a device pointer on the host, each may run under capture, and each returns an
+ * RV_ERR_* whose message names the field before anything is launched: T, S, k, L, stride, n_rows, lam, mode, a null q / centre /
+ * basis / moment / result / state / info / path / score / row_start / ws, ws_bytes too small, ws not 256-byte aligned.  No
+ * atomics, no polling; every output element is written by exactly one thread.  No new member and no new role of the
+ * descriptor: every field is an existing member under its existing name and type, and S, the frame length of the
+ * synthesis ops, counts the states here.  The op code 42 is unassigned like 38 and 39: rv_mosaic answers it as an unknown op.
+ * The fields.  moment = theta, the parameter block.  result = logb [T, S] fp64 (EMIT writes it, FORWARD_BACKWARD and VITERBI
+ * read it); in MSTEP result = the new parameter block.  state = the posteriors, ONE block of T S + n_rows S S + n_rows
+ * doubles: [ gamma (T S) | xi (n_rows S S) | ll (n_rows) ], which FORWARD_BACKWARD writes and MSTEP reads.
+ * The model.  S = the states, 1 <= S <= 64; k = the axes, 1 <= k <= 64; k <= L <= 512; 1 <= T < 2^31; more is RV_ERR_SHAPE
+ * naming the field and its limit.  q = x [T, L] fp32 with a row pitch of stride >= L elements, centre = c [L] and basis = P
+ * [k, L] fp64 (a fitted PCA's or walk's).  y_t = P (x_t - c): y_j = chain fma(P[j, l], (double)x[t, l] - c[l], .) in
+ * ascending l from +0, the device code RV_SMOOTH_FILTER observes with (csrc/sequence.h).  A frame whose x row holds a value
+ * that is not finite is UNOBSERVED.  State s emits N(m_s, diag(v_s)) in these coordinates; pi [S] is the initial law and
+ * A [S, S] the transition matrix (rows sum to 1).  theta, fp64 on the device, 2 S k + 3 S + 2 S^2 doubles:
+ *   [ m (S k) | w = 1 / v (S k) | g (S) | pi (S) | A (S S) | log pi (S) | log A (S S) ]
+ * with g_s = -0.5 (k log(2 pi) + sum_j log v_sj): fl(k * fl64(log(2 pi))), the logarithms added in ascending j from +0, one
+ * add, one product.  Sequence s owns rows [row_start[s], row_start[s+1]), row_start [n_rows + 1] int64 on the device,
+ * 1 <= n_rows < 2^31, under RV_SMOOTH_FILTER's rules (the CALLER checks it on its host copy, the kernels clamp to [0, T]);
+ * an empty sequence is legal and contributes nothing.
+ * RV_HMM_EMIT: q, stride, centre, basis, moment = theta, T, L, k, S -> result = logb [T, S] fp64.  logb[t, s] = g_s - 0.5 q with q one chain
+ *   fma(fl(w_sj d), d, .), d = y_j - m_sj, in ascending j from +0 (the product w_sj d rounded on its own).  An unobserved
+ *   frame gets a row of NaN and changes no other row.  A workgroup takes 64 frames, stages their y in LDS once and writes
+ *   the rows of all S states; one launch over the whole chip.
+ * RV_HMM_FORWARD_BACKWARD: result = logb, row_start, n_rows, moment = theta, T, S, k, ws, ws_bytes -> state = the
+ *   posteriors: gamma [T, S], xi [n_rows, S, S] and ll [n_rows], all fp64.  The scaled recursion, one workgroup per sequence.  A frame is unobserved iff its row of logb
+ *   holds a NaN: then M_t = 0 and b~_t[s] = 1; else M_t = max_s logb[t, s] and b~_t[s] = exp(logb[t, s] - M_t).
+ *   Forward: alpha_0[j] = fl(pi_j b~_0[j]); alpha_t[j] = fl(b~_t[j] * chain_i fma(alpha_{t-1}[i], A[i, j], .)) in ascending i
+ *   from +0; c_t = sum_j alpha_t[j] in ascending j from +0; alpha_t /= c_t; ll = fl(ll + fl(log c_t + M_t)) in ascending t
+ *   from +0.  Backward in descending t from beta = 1: u_j = fl(b~_{t+1}[j] beta_{t+1}[j]) / c_{t+1}, beta_t[i] =
+ *   chain_j fma(A[i, j], u_j, .) in ascending j from +0, gamma_t[i] = fl(alpha_t[i] beta_t[i]).  xi[seq, i, j] = chain over
+ *   the sequence's pairs in descending t from +0 of fma(fl(alpha_t[i] A[i, j]), u_j, .); a sequence of one frame or none
+ *   writes zeros, and ll = 0 for an empty one.  alpha and c live in ws.  A stays in LDS for the whole sequence; wave 0
+ *   runs the recursion with lane j owning state j, alpha and u passing between its lanes through LDS, and all four waves
+ *   accumulate xi in registers, 16 columns of a row per thread.  A sequence's bits depend on its own rows and theta only,
+ *   not on n_rows or on where it lies.
+ * RV_HMM_MSTEP: q, stride, centre, basis, state = the posteriors (ll is not read), row_start, n_rows, moment = the old
+ *   theta, lam = the variance floor (finite, > 0), T, L, k, S, mode = 0 or RV_HMM_MOMENTS, ws, ws_bytes -> result = the new
+ *   theta (a block of its own) and info [S] int32; under RV_HMM_MOMENTS result holds S (1 + 2 k) more doubles behind theta,
+ *   the moments [S, 1 + 2 k]: row s = [N_s | M1[s, .] | M2[s, .]].  Unobserved frames contribute nothing to the
+ *   three moments.  N_s = sum_t gamma[t, s]: blocks of 256 frames, a block in ascending t from +0, the blocks in
+ *   ascending order from +0.  M1 = gamma^T Y and M2 = gamma^T (Y o Y), y^2 one rounded product: ranges of 4096 frames,
+ *   within a range v_mfma_f64_16x16x4_f64 over the frames t0, t0 + 4, .. in ascending order from +0, each instruction
+ *   adding its four frames to the element, 32 frames staged in LDS at a time, the partial tiles to ws, then the ranges in
+ *   ascending order from +0: the tile and the sums of "Latent PCA", in the tile's two-operand form.  Then m = M1 / N,
+ *   v = max(fl(M2 / N - fl(m m)), lam) (NaN gives lam), w = 1 / v, g as above.  A state with N_s < 1 (or NaN) keeps its old
+ *   m, w and g, and info[s] = 1 (else 0).  pi_s = the mean over the non-empty sequences of their first frame's gamma,
+ *   added in ascending sequence order from +0 (no such sequence: the old pi).  A[i, j] = (sum_seq xi[seq, i, j] in ascending
+ *   seq from +0) / (the sum of row i's numerators in ascending j from +0); a row whose sum is not positive keeps its old row.
+ *   log pi and log A with log(0) = -inf.  Four launches; the last is one workgroup.
+ * RV_HMM_VITERBI: result = logb, row_start, n_rows, moment = theta, T, S, k, ws, ws_bytes -> path [T] int32, score [n_rows]
+ *   fp64.  Max-plus in
+ *   fp64 with plain adds: d_0[j] = a_0[j] + log pi_j, d_t[j] = a_t[j] + max_i (d_{t-1}[i] + log A[i, j]), a_t[j] = logb[t, j], or
+ *   0 in an unobserved frame (a NaN in the row).  The max is taken under the total order larger value first, then lower
+ *   i; NaN and -inf never win, and where nothing wins d_t[j] = a_t[j] + (-inf).  score = the best d of the last frame under
+ *   the same order and the path goes back from its state; where no end state wins, score = -inf and the sequence's path
+ *   is -1 throughout.  An empty sequence: score = 0.  Rows outside every sequence are not written.  One wave per
+ *   sequence, log A in LDS, the back-pointers bytes in ws.  Given logb and theta the output is exact.
+ * RV_HMM_WORKSPACE: the bytes of ws for (T, S, k) that serve all three in d->ws_bytes; launches nothing and touches no
+ *   device.  ws is 256-byte aligned.  One EM iteration is EMIT, FORWARD_BACKWARD and MSTEP on one stream and one ws, no
+ *   host sync between them. */
+#define RV_HMM_EMIT 43
+#define RV_HMM_FORWARD_BACKWARD 44
+#define RV_HMM_MSTEP 45
+#define RV_HMM_VITERBI 46
+#define RV_HMM_WORKSPACE 47
+#define RV_HMM_MOMENTS 1
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the
@@ -939,7 +1008,7 @@ typedef struct rv_mosaic_desc {
   void* ws;
   long ws_bytes;
   union { const float* src;      /* GATHER_MEAN */
-          const double* moment; };  /* WALK_FIT, WALK_STEP: the fp64 input matrix the op names */
+          const double* moment; };  /* WALK_FIT, WALK_STEP: the fp64 input matrix the op names; HMM ops: theta */
   long src_len;
   const long long* row_start;
   long stride, n_rows;
@@ -947,11 +1016,11 @@ typedef struct rv_mosaic_desc {
           long fit_radius;       /* GRAIN_FIT, LIVE ops: R */
           long band; };          /* ALIGN ops: r */
   union { float* out;            /* GATHER_MEAN [T, ldo], OLA [n_out] */
-          double* result;        /* WALK_FIT */
+          double* result;        /* WALK_FIT; HMM ops: logb [T, S], HMM_MSTEP: the new theta */
           double* end_costs; };  /* ALIGN_FORWARD (SUBSEQUENCE) [Tb], or NULL */
   long ldo;
   const float* frames;           /* OLA */
-  long F, S, hop;
+  long F, S, hop;                /* S: the frame length; HMM ops: the states */
   const float* window;
   long n_out;
   union { const int* next_of;    /* TRANSITION [N]; LIVE with a fit: [3 N], successors then room */
@@ -976,7 +1045,7 @@ typedef struct rv_mosaic_desc {
   union { double* cost;          /* PATH_BACKTRACK [2]; EVAL_DIMS [L] */
           double* score;         /* GRAIN_FIT, LIVE with a fit */
           double* eigenvalues;   /* PCA ops, WALK_FIT */
-          double* state;         /* WALK_STEP [n_streams, k] */
+          double* state;         /* WALK_STEP [n_streams, k]; HMM ops: the posteriors [gamma | xi | ll] */
           double* path_costs; }; /* ALIGN_BACKTRACK [2] */
   const struct rv_stream_desc* live; /* LIVE ops: weights, block I/O, scale / offset, window, norm, stream workspace */
   long mode;                     /* LIVE: RV_LIVE_GRAINS / RV_LIVE_DECODE; ALIGN_FORWARD: the DP's mode; ALIGN_WARP: the timeline */

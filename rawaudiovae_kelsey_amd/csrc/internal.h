@@ -217,3 +217,11 @@ RV_INTERNAL int rv_smooth_workspace(rv_mosaic_desc* d);
 // launches nothing.
 RV_INTERNAL int rv_recur_profile(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_recur_workspace(rv_mosaic_desc* d);
+// The latent-state ops of rv_mosaic (hmm.hip): RV_HMM_EMIT, RV_HMM_FORWARD_BACKWARD, RV_HMM_MSTEP and RV_HMM_VITERBI on the
+// fields the public header names for them -- checks first, then the launches, no sync and no read of the device -- and
+// RV_HMM_WORKSPACE, which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_hmm_emit(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_hmm_forward_backward(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_hmm_mstep(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_hmm_viterbi(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_hmm_workspace(rv_mosaic_desc* d);

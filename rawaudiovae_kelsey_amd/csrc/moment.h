@@ -3,8 +3,8 @@
 // (eval.hip, the KL sums).  Defined here once, down to the order of every add; no atomics anywhere, so the bits depend
 // on the data and its shape alone.
 //   Second moment.  d[t][c] = (double)x[t][c] - centre[c].  Element (i, j) of the range of RANGE rows from t0 is
-//   sum_t a[t][i] b[t][j], with a = b = d (covariance, t a row) or a[t] = d[t + 1], b[t] = keep[t] d[t] (lag-1, t a
-//   pair): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
+//   sum_t a[t][i] b[t][j], with a = b = d (covariance, t a row), a[t] = d[t + 1], b[t] = keep[t] d[t] (lag-1, t a
+//   pair) or a = gamma, b = y or y o y, two fp64 matrices (the weighted moments of RV_HMM_MSTEP, hmm.hip): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
 //   four rows to the element.  Rows and columns beyond the data stage zeros.  Then the ranges' partials of an element
 //   in ascending range order from +0 (range_sum), and the caller's one division.
 //   Column sum.  Blocks of ROWS rows: a block's terms in ascending t from +0 (colsum_block), then the block sums in
@@ -48,69 +48,97 @@ inline tiles tile_layout(long rows, long L, bool lag) {
   return w;
 }
 
-// The thread's column of both operands at rows t, t + 4, ..: row t + 1 for the left operand and the pair's keep flag
-// when LAG.  A row beyond the range is read from the range's last row (the caller stores a zero in its place).
-template <bool LAG, int PER>
-__device__ __forceinline__ void fetch(const float* __restrict__ xa, const float* __restrict__ xb,
-                                      const unsigned char* __restrict__ keep, long t, long t1, long L, bool diag,
-                                      float (&fa)[PER], float (&fb)[PER], unsigned char (&fk)[PER]) {
+// The operands of a tile as its loop sees them.  A thread carries one column of each operand: `raw` is what it holds of a
+// row between the load and the staging, load() reads row tr of its two columns, left() and right() are the doubles that
+// go into LDS, keeps() whether the right operand of the row counts at all.
+// centred: d = (double)x - centre of one fp32 matrix on both sides (the covariance), or -- LAG -- row t + 1 on the left
+// and keep[t] d[t] on the right (the lag-1 moment).
+template <bool LAG>
+struct centred {
+  const float* __restrict__ xa;
+  const float* __restrict__ xb;
+  const unsigned char* __restrict__ keep;
+  long L;
+  double ma, mb;
+  bool diag;
+  struct raw { float a, b; unsigned char k; };
+  __device__ __forceinline__ void load(long tr, raw& r) const {
+    if constexpr (LAG) {
+      r.a = xa[(tr + 1) * L];
+      r.b = xb[tr * L];
+      r.k = keep[tr];
+    } else {
+      r.a = xa[tr * L];
+      r.b = diag ? 0.f : xb[tr * L];
+    }
+  }
+  __device__ __forceinline__ double left(const raw& r) const { return (double)r.a - ma; }
+  __device__ __forceinline__ double right(const raw& r) const { return (double)r.b - mb; }
+  __device__ __forceinline__ bool keeps(const raw& r) const { return LAG ? r.k != 0 : true; }
+};
+// weighted: two different fp64 matrices, ga [n, lda] on the left as it stands and yb [n, ldb] on the right, or --
+// SQUARE -- its elementwise square, one rounded product formed while staging (the weighted moments of hmm.hip).
+template <bool SQUARE>
+struct weighted {
+  const double* __restrict__ ga;
+  const double* __restrict__ yb;
+  long lda, ldb;
+  struct raw { double a, b; };
+  __device__ __forceinline__ void load(long tr, raw& r) const {
+    r.a = ga[tr * lda];
+    r.b = yb[tr * ldb];
+  }
+  __device__ __forceinline__ double left(const raw& r) const { return r.a; }
+  __device__ __forceinline__ double right(const raw& r) const { return SQUARE ? r.b * r.b : r.b; }
+  __device__ __forceinline__ bool keeps(const raw&) const { return true; }
+};
+
+// The thread's column of both operands at rows t, t + 4, ..  A row beyond the range is read from the range's last row
+// (the caller stores a zero in its place).
+template <class Ops, int PER>
+__device__ __forceinline__ void fetch(const Ops& ops, long t, long t1, typename Ops::raw (&f)[PER]) {
 #pragma unroll
   for (int i = 0; i < PER; ++i) {
     const long tt = t + 4 * i;
-    const long tr = tt < t1 ? tt : t1 - 1;
-    if constexpr (LAG) {
-      fa[i] = xa[(tr + 1) * L];
-      fb[i] = xb[tr * L];
-      fk[i] = keep[tr];
-    } else {
-      fa[i] = xa[tr * L];
-      fb[i] = diag ? 0.f : xb[tr * L];
-    }
+    ops.load(tt < t1 ? tt : t1 - 1, f[i]);
   }
 }
 
-// One range (blockIdx.x) of the n rows (pairs) and the tile (I, J), which is number blockIdx.y of the n_tiles of a
-// range in part.  TILE_THREADS threads; As and Bs are STAGE doubles of LDS each.  Wave w owns the MFMA tiles (w, 0 .. 3) of the tile; on a diagonal
-// tile of the covariance those left of the diagonal are skipped (and not written) and B is read from As.
+// One range (blockIdx.x) of the n rows (pairs) and one 64 x 64 tile of the product, which is number blockIdx.y of the
+// n_tiles of a range in part.  TILE_THREADS threads; As and Bs are STAGE doubles of LDS each.  Thread (cc = lane, ti)
+// stages column cc of both operands (va, vb: whether its column of the left / right operand exists).  Wave w owns the
+// MFMA tiles (w, 0 .. 3) of the tile; on a diagonal tile (`diag`: both operands are the same columns of the same
+// matrix) those left of the diagonal are skipped (and not written) and B is read from As.
 // v_mfma_f64_16x16x4_f64: lane l holds A[i = l & 15][k = l >> 4] and B[k = l >> 4][j = l & 15]; with
 // A[i][k] = a[t + k][i0 + i] and B[k][j] = b[t + k][j0 + j] one instruction adds four rows to the tile.  Its result:
 // column l & 15, row (l >> 4) + 4 reg.
-template <bool LAG>
-__device__ __forceinline__ void moment_tile(double* As, double* Bs, const float* __restrict__ x, long n, int L,
-                                            const double* __restrict__ centre, const unsigned char* __restrict__ keep,
-                                            int I, int J, int n_tiles, double* __restrict__ part) {
-  const bool diag = !LAG && I == J;
+template <class Ops>
+__device__ __forceinline__ void tile_loop(double* As, double* Bs, const Ops& ops, long n, bool va, bool vb, bool diag,
+                                          int n_tiles, double* __restrict__ part) {
   const int lane = threadIdx.x & 63, ti = threadIdx.x >> 6;
   const double* const Bsrc = diag ? As : Bs;
   f64x4 acc[4];
 #pragma unroll
   for (int tj = 0; tj < 4; ++tj) acc[tj] = f64x4{0.0, 0.0, 0.0, 0.0};
   const long t0 = (long)blockIdx.x * RANGE, t1 = t0 + RANGE < n ? t0 + RANGE : n;
-  // Staging: thread (cc = lane, ti) carries column cc of both operands for the rows ti, ti + 4, .. of a chunk.  The
-  // loads of the next chunk are issued before the MFMAs of this one; a row or column beyond the data is read from a
-  // clamped address and replaced by zero on its way into LDS.
+  // Staging: the thread carries its columns for the rows ti, ti + 4, .. of a chunk.  The loads of the next chunk are
+  // issued before the MFMAs of this one; a row or column beyond the data is read from a clamped address and replaced
+  // by zero on its way into LDS.
   constexpr int PER = CHUNK / (TILE_THREADS / MT);   // rows per thread and chunk
   const int cc = lane;
-  const int ca = I * MT + cc, cb = J * MT + cc;
-  const bool va = ca < L, vb = cb < L;
-  const double ma = va ? centre[ca] : 0.0, mb = vb ? centre[cb] : 0.0;
-  const float* const xa = x + (va ? ca : L - 1);
-  const float* const xb = x + (vb ? cb : L - 1);
-  float fa[PER], fb[PER];
-  unsigned char fk[PER];
-  fetch<LAG, PER>(xa, xb, keep, t0 + ti, t1, L, diag, fa, fb, fk);
+  typename Ops::raw f[PER];
+  fetch<Ops, PER>(ops, t0 + ti, t1, f);
   for (long tc = t0; tc < t1; tc += CHUNK) {
     __syncthreads();   // the MFMAs of the chunk before have read LDS
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
       const int r = ti + 4 * i;
       const bool vt = tc + r < t1;
-      As[r * LD + cc] = (vt && va) ? (double)fa[i] - ma : 0.0;
-      if constexpr (LAG) Bs[r * LD + cc] = (vt && vb && fk[i]) ? (double)fb[i] - mb : 0.0;
-      else if (!diag) Bs[r * LD + cc] = (vt && vb) ? (double)fb[i] - mb : 0.0;
+      As[r * LD + cc] = (vt && va) ? ops.left(f[i]) : 0.0;
+      if (!diag) Bs[r * LD + cc] = (vt && vb && ops.keeps(f[i])) ? ops.right(f[i]) : 0.0;
     }
     __syncthreads();
-    if (tc + CHUNK < t1) fetch<LAG, PER>(xa, xb, keep, tc + CHUNK + ti, t1, L, diag, fa, fb, fk);
+    if (tc + CHUNK < t1) fetch<Ops, PER>(ops, tc + CHUNK + ti, t1, f);
 #pragma unroll
     for (int kk = 0; kk < CHUNK; kk += 4) {
       const int row = (kk + (lane >> 4)) * LD + (lane & 15);
@@ -131,6 +159,33 @@ __device__ __forceinline__ void moment_tile(double* As, double* Bs, const float*
     for (int reg = 0; reg < 4; ++reg)
       part_tile[(ti * 16 + (lane >> 4) + 4 * reg) * MT + tj * 16 + (lane & 15)] = acc[tj][reg];
   }
+}
+
+// The tile (I, J) of the second moment of x [n (+ 1 when LAG), L] about centre: the covariance's (J >= I, the diagonal
+// tiles in their half form) or the lag-1 moment's.
+template <bool LAG>
+__device__ __forceinline__ void moment_tile(double* As, double* Bs, const float* __restrict__ x, long n, int L,
+                                            const double* __restrict__ centre, const unsigned char* __restrict__ keep,
+                                            int I, int J, int n_tiles, double* __restrict__ part) {
+  const bool diag = !LAG && I == J;
+  const int cc = threadIdx.x & 63;
+  const int ca = I * MT + cc, cb = J * MT + cc;
+  const bool va = ca < L, vb = cb < L;
+  const centred<LAG> ops{x + (va ? ca : L - 1), x + (vb ? cb : L - 1), keep, L,
+                         va ? centre[ca] : 0.0, vb ? centre[cb] : 0.0, diag};
+  tile_loop(As, Bs, ops, n, va, vb, diag, n_tiles, part);
+}
+
+// The one tile of ga^T yb (SQUARE: ga^T (yb o yb)) for ga [n, na <= 64] and yb [n, nb <= 64], both fp64 and packed:
+// element (i, j) = sum_t ga[t, i] yb[t, j].
+template <bool SQUARE>
+__device__ __forceinline__ void weighted_tile(double* As, double* Bs, const double* __restrict__ ga, int na,
+                                              const double* __restrict__ yb, int nb, long n, int n_tiles,
+                                              double* __restrict__ part) {
+  const int cc = threadIdx.x & 63;
+  const bool va = cc < na, vb = cc < nb;
+  const weighted<SQUARE> ops{ga + (va ? cc : na - 1), yb + (vb ? cc : nb - 1), na, nb};
+  tile_loop(As, Bs, ops, n, va, vb, false, n_tiles, part);
 }
 
 // Element (i, j) of the matrix: its partials in ascending range order from +0.  `tile` is the number of the element's

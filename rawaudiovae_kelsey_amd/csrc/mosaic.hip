@@ -1,5 +1,5 @@
-// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 40 ops (codes 0 .. 37, 40 and
-// 41; 38 and 39 are unassigned and answer as unknown ops).  Each family keeps its kernels, checks and launches in its own
+// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 45 ops (codes 0 .. 37, 40, 41
+// and 43 .. 47; 38, 39 and 42 are unassigned and answer as unknown ops).  Each family keeps its kernels, checks and launches in its own
 // file and hands rv_mosaic one function per op (internal.h):
 //    0, 1, 8, 9   RV_MOSAIC_KNN, _KNN_WORKSPACE, _KNN_SMALL, _KNN_SMALL_WORKSPACE        mosaic_knn.hip
 //    2, 3         RV_MOSAIC_GATHER_MEAN, RV_MOSAIC_OLA                                   this file
@@ -13,6 +13,7 @@
 //   31 .. 33      RV_STRUCT_NOVELTY, _PEAKS, _WORKSPACE                                  structure.hip
 //   34 .. 37      RV_SMOOTH_FILTER, _BACKWARD, _SPLICE, _WORKSPACE                       smooth.hip
 //   40, 41        RV_RECUR_PROFILE, _WORKSPACE                                           recur.hip
+//   43 .. 47      RV_HMM_EMIT, _FORWARD_BACKWARD, _MSTEP, _VITERBI, _WORKSPACE           hmm.hip
 // Here also the two synthesis ops of the offline mosaic (rawaudiovae_kelsey_amd/mosaic.py):
 //   RV_MOSAIC_GATHER_MEAN  out[t] = (1/k) sum_j src[start(idx[t, j]) : + width] (grains or latent rows)
 //   RV_MOSAIC_OLA          offline weighted overlap-add normalised by the window sum
@@ -141,6 +142,11 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
     case RV_SMOOTH_WORKSPACE: return rv_smooth_workspace(d);
     case RV_RECUR_PROFILE: return rv_recur_profile(d, stream);
     case RV_RECUR_WORKSPACE: return rv_recur_workspace(d);
+    case RV_HMM_EMIT: return rv_hmm_emit(d, stream);
+    case RV_HMM_FORWARD_BACKWARD: return rv_hmm_forward_backward(d, stream);
+    case RV_HMM_MSTEP: return rv_hmm_mstep(d, stream);
+    case RV_HMM_VITERBI: return rv_hmm_viterbi(d, stream);
+    case RV_HMM_WORKSPACE: return rv_hmm_workspace(d);
   }
   return rv_fail(RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
 }

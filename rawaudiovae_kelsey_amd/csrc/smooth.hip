@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "internal.h"
+#include "sequence.h"
 
 using namespace rv;
 
@@ -49,13 +50,7 @@ __device__ __forceinline__ double noise_at(const float* __restrict__ weight, flo
   return weight ? (double)lam / (double)weight[t] : (double)lam;
 }
 
-// the sequence's rows, clamped to [0, T]: a row_start the caller did not check reads and writes nothing outside
-__device__ __forceinline__ void rows_of(const long long* __restrict__ row_start, long s, long T, long& t0, long& t1) {
-  t0 = row_start[s];
-  t1 = row_start[s + 1];
-  t0 = t0 < 0 ? 0 : (t0 > T ? T : t0);
-  t1 = t1 < t0 ? t0 : (t1 > T ? T : t1);
-}
+using seq::rows_of;   // the sequence's rows, clamped to [0, T] (sequence.h)
 
 // Qn = B B^T from B^T [k, k]: element (i, j), i <= j, one ascending chain, written to [i, j] and [j, i]
 __global__ void __launch_bounds__(256)
@@ -79,11 +74,7 @@ k_smooth_observe(const float* __restrict__ x, const float* __restrict__ weight, 
   const long t = e / k;
   const int j = (int)(e - t * k);
   double acc = 0.0;
-  if (observed(weight, t)) {
-    const float* const xr = x + t * L;
-    const double* const pr = P + (long)j * L;
-    for (int l = 0; l < L; ++l) acc = __builtin_fma(pr[l], (double)xr[l] - centre[l], acc);
-  }
+  if (observed(weight, t)) acc = seq::whiten_axis(P + (long)j * L, x + t * L, centre, L);
   ys[e] = acc;
 }
 
