@@ -32,7 +32,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from som import _int_flag, load_wav  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, flagged, int_at_least, load_model, load_wav,  # noqa: E402
+                                             model_config, nonneg_real, window_flag)
 
 COMMANDS = ("path", "morph", "find")
 
@@ -53,9 +54,7 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in COMMANDS:
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
-        s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
+        add_model_flags(s)
         s.add_argument("--penalty", default="0", help="cost of a non-diagonal step (default 0)")
         s.add_argument("--out", required=True, help="path: the .npz; morph: the wav; find: the .json")
         if name == "find":
@@ -74,27 +73,19 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: path, morph or find")
-    args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
-    try:
-        pen = float(args.penalty)
-    except ValueError:
-        pen = float("nan")
-    if not 0 <= pen < float("inf"):
-        raise ValueError("--penalty %r: expected a finite number >= 0" % (args.penalty,))
-    args.penalty = pen
+    int_at_least(args, "hop", 1)
+    nonneg_real(args, "penalty")
     if args.command != "find":
-        args.band = None if args.band is None else _int_flag("band", args.band, 0)
+        int_at_least(args, "band", 0)
     if args.command == "morph":
         if (args.alpha is None) == (args.curve is None):
             raise ValueError("--alpha / --curve: expected exactly one of the two")
         if args.timeline not in ("a", "b", "path"):
             raise ValueError("--timeline %r: expected a, b or path" % args.timeline)
-        if args.window not in ("none", "hann"):
-            raise ValueError("--window %r: expected none or hann" % args.window)
-        args.window = None if args.window == "none" else args.window
+        window_flag(args)
         if args.window is not None and args.hop is None:
             raise ValueError("--window %s: needs --hop (without one the frames are concatenated)" % args.window)
-        args.seed = _int_flag("seed", args.seed, 0)
+        int_at_least(args, "seed", 0)
         args.curve_values = parse_alpha(args.alpha) if args.alpha is not None else None
     return args
 
@@ -110,52 +101,31 @@ def load_curve(path):
     return np.ascontiguousarray(c, dtype=np.float64)
 
 
-def _setup(args):
-    from interpolate import read_model_config
-    from rawaudiovae_kelsey_amd.codec import frame_layout
-    cfg = read_model_config(args.config)
-    S = cfg["segment_length"]
-    try:
-        frame_layout(S, S, args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
-    return cfg, S
-
-
-def _flagged(flags, fn):
-    try:
-        return fn()
-    except ValueError as e:
-        raise ValueError("%s: %s" % (flags, e))
-
-
 def run_path(args):
-    from interpolate import load_model
     from rawaudiovae_kelsey_amd.align import LatentAligner
-    cfg, S = _setup(args)
+    cfg, _ = model_config(args)
     a, b = load_wav(args.a, cfg["sampling_rate"]), load_wav(args.b, cfg["sampling_rate"])
     aligner = LatentAligner(load_model(args.checkpoint, cfg))
-    al = _flagged("--a / --b / --band", lambda: aligner.align(a, b, args.hop, args.band, args.penalty))
+    al = flagged("--a / --b / --band", lambda: aligner.align(a, b, args.hop, args.band, args.penalty))
     path = al.path.cpu().numpy()
     with open(args.out, "wb") as f:
         np.savez(f, path=path, cost=al.cost, path_cost=al.path_cost, band=-1 if al.band is None else al.band,
-                 hop=-1 if args.hop is None else args.hop, segment_length=S, frames_a=al.Ta, frames_b=al.Tb)
+                 hop=-1 if args.hop is None else args.hop, segment_length=cfg["segment_length"], frames_a=al.Ta, frames_b=al.Tb)
     print("wrote %s: %d steps through %d x %d frames, cost %.9g, cost per step %.9g, band %s, penalty %g"
           % (args.out, al.P, al.Ta, al.Tb, al.cost, al.normalised_cost, al.band, args.penalty))
     return al
 
 
 def run_morph(args):
-    from interpolate import load_model
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd.align import AlignedInterpolator
     from rawaudiovae_kelsey_amd.mosaic import check_window
-    cfg, S = _setup(args)
-    _flagged("--window %s" % args.window, lambda: check_window(S, S if args.hop is None else args.hop, args.window))
+    cfg, step = model_config(args)
+    flagged("--window %s" % args.window, lambda: check_window(cfg["segment_length"], step, args.window))
     curve = args.curve_values if args.curve is None else load_curve(args.curve)
     a, b = load_wav(args.a, cfg["sampling_rate"]), load_wav(args.b, cfg["sampling_rate"])
     it = AlignedInterpolator(load_model(args.checkpoint, cfg))
-    y = _flagged("--a / --b / --band", lambda: it.curve(a, b, curve, hop=args.hop, window=args.window,
+    y = flagged("--a / --b / --band", lambda: it.curve(a, b, curve, hop=args.hop, window=args.window,
                                                          timeline=args.timeline, band=args.band, penalty=args.penalty,
                                                          seed=args.seed))
     y = y.cpu().numpy()
@@ -167,13 +137,12 @@ def run_morph(args):
 
 
 def run_find(args):
-    from interpolate import load_model
     from rawaudiovae_kelsey_amd.align import LatentAligner
-    cfg, S = _setup(args)
+    cfg, _ = model_config(args)
     sr = cfg["sampling_rate"]
     q, rec = load_wav(args.query, sr), load_wav(args.recording, sr)
     aligner = LatentAligner(load_model(args.checkpoint, cfg))
-    m = _flagged("--query / --in", lambda: aligner.find(q, rec, args.hop, args.penalty))
+    m = flagged("--query / --in", lambda: aligner.find(q, rec, args.hop, args.penalty))
     report = dict(found=m.found, start_frame=m.start_frame, end_frame=m.end_frame, start_sample=m.start_sample,
                   end_sample=m.end_sample, start_seconds=m.start_sample / sr if m.found else None,
                   end_seconds=m.end_sample / sr if m.found else None, cost=m.cost if m.found else None,

@@ -30,18 +30,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-
-def _number(args, flag, kind, ok, what):
-    v = getattr(args, flag.replace("-", "_"))
-    if v is None:
-        return
-    try:
-        x = kind(v)
-    except ValueError:
-        x = None
-    if x is None or not ok(x):
-        raise ValueError("--%s %r: expected %s" % (flag, v, what))
-    setattr(args, flag.replace("-", "_"), x)
+from rawaudiovae_kelsey_amd.frontend import (check_exists, data_files, load_model, load_wav, nonneg_int,  # noqa: E402
+                                             nonneg_real, number_flag, positive_int, read_model_config, window_flag)
 
 
 def parse_args(argv=None):
@@ -90,17 +80,13 @@ def parse_args(argv=None):
             raise ValueError("--seed: only read with --sample")
         if args.config is None:
             args.config = "./default.ini"
-    finite = lambda x: x == x and abs(x) != float("inf")   # noqa: E731
-    _number(args, "segment-length", int, lambda x: x > 0, "a positive integer")
-    _number(args, "hop", int, lambda x: x > 0, "a positive integer")
-    _number(args, "sampling-rate", int, lambda x: x > 0, "a positive integer")
-    _number(args, "seed", int, lambda x: x >= 0, "a non-negative integer")
-    _number(args, "dynamic-range", float, lambda x: 0 < x <= 120, "a number of dB in (0, 120]")
-    _number(args, "kl-beta", float, lambda x: finite(x) and x >= 0, "a finite number >= 0")
-    _number(args, "active-threshold", float, lambda x: finite(x) and x >= 0, "a finite number >= 0")
-    if args.window not in ("none", "hann"):
-        raise ValueError("--window %r: expected none or hann" % args.window)
-    args.window = None if args.window == "none" else args.window
+    for flag in ("segment-length", "hop", "sampling-rate"):
+        positive_int(args, flag)
+    nonneg_int(args, "seed")
+    number_flag(args, "dynamic-range", float, lambda x: 0 < x <= 120, "a number of dB in (0, 120]")
+    nonneg_real(args, "kl-beta")
+    nonneg_real(args, "active-threshold")
+    window_flag(args)
     if args.sample and args.seed is None:
         args.seed = 0
     if args.pair:
@@ -120,18 +106,6 @@ def check_frames(args, segment_length):
     check_args(S, args.hop, args.window, args.dynamic_range, 16384, args.active_threshold)
 
 
-def data_files(path):
-    """The wavs --data names: the file itself, or the folder's *.wav sorted by name."""
-    if os.path.isdir(path):
-        files = sorted(os.path.join(path, f) for f in os.listdir(path) if f.lower().endswith(".wav"))
-        if not files:
-            raise ValueError("--data %r: no .wav files in the folder" % path)
-        return files
-    if not os.path.exists(path):
-        raise ValueError("--data %r: no such file or folder" % path)
-    return [path]
-
-
 def write_per_frame(path, scores, offsets, names):
     from rawaudiovae_kelsey_amd.evaluate import COLUMNS
     np.savez(path, scores=np.asarray(scores, dtype=np.float32), columns=np.array(COLUMNS),
@@ -144,17 +118,15 @@ def main(argv=None):
     from rawaudiovae_kelsey_amd import evaluate as E
     if args.pair:
         for flag in ("ref", "test"):
-            if not os.path.exists(getattr(args, flag)):
-                raise ValueError("--%s %r: no such file" % (flag, getattr(args, flag)))
+            check_exists(flag, getattr(args, flag))
         sr = args.sampling_rate or D.read_wav(args.ref)[1]
-        ref, test = D.load_audio_mono(args.ref, sr), D.load_audio_mono(args.test, sr)
+        ref, test = load_wav(args.ref, sr), load_wav(args.test, sr)
         report, scores = E.compare(ref, test, args.segment_length, args.hop, args.window, args.dynamic_range,
                                    return_scores=True)
         report.update(ref=str(args.ref), test=str(args.test), sampling_rate=int(sr))
         offsets, names = [0, report["frames"]], [str(args.test)]
     else:
         import configparser
-        from interpolate import load_model, read_model_config
         cfg = read_model_config(args.config)
         check_frames(args, cfg["segment_length"])
         files = data_files(args.data)
@@ -166,7 +138,7 @@ def main(argv=None):
         ev = E.Evaluator(model, hop=args.hop, window=args.window, dynamic_range=args.dynamic_range,
                          active_threshold=args.active_threshold)
         for i, f in enumerate(files):
-            ev.add(D.load_audio_mono(f, cfg["sampling_rate"]), os.path.basename(f),
+            ev.add(load_wav(f, cfg["sampling_rate"]), os.path.basename(f),
                    seed=None if not args.sample else args.seed + i)
         report = ev.report(args.kl_beta)
         report.update(checkpoint=str(args.checkpoint), sampling_rate=cfg["sampling_rate"], hop=args.hop,

@@ -29,13 +29,14 @@ import json
 import os
 import sys
 
-import numpy as np
-
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from latent_pca import _positive, check_axes, parse_axis_values  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, check_axes, check_exists, check_fitted, data_files,  # noqa: E402
+                                             encode_wav, load_model, load_wav, model_config, nonneg, nonneg_int,
+                                             number_flag, parse_axis_values, positive, positive_int, read_model_config,
+                                             window_flag)
 
 
 def parse_args(argv=None):
@@ -43,9 +44,7 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in ("fit", "run"):
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
-        s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
+        add_model_flags(s)
         s.add_argument("--out", required=True, help="fit: the .npz; run: the output wav")
         if name == "fit":
             s.add_argument("--data", required=True, help="a wav, or a folder whose *.wav are encoded")
@@ -63,35 +62,17 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: fit or run")
-    _positive(args, "hop")
+    positive_int(args, "hop")
     if args.command == "fit":
-        _positive(args, "keep")
+        positive_int(args, "keep")
         return args
-    _positive(args, "streams")
-    _positive(args, "seed", allow_zero=True)
-    for flag in ("seconds", "temperature"):
-        try:
-            v = float(getattr(args, flag))
-        except ValueError:
-            v = float("nan")
-        if not (v == v and abs(v) != float("inf") and (v > 0 if flag == "seconds" else v >= 0)):
-            raise ValueError("--%s %r: expected a finite %s number" % (
-                flag, getattr(args, flag), "positive" if flag == "seconds" else "non-negative"))
-        setattr(args, flag, v)
-    if args.window not in ("none", "hann"):
-        raise ValueError("--window %r: expected none or hann" % args.window)
-    args.window = None if args.window == "none" else args.window
+    positive_int(args, "streams")
+    nonneg_int(args, "seed")
+    number_flag(args, "seconds", float, positive, "a finite positive number")
+    number_flag(args, "temperature", float, nonneg, "a finite non-negative number")
+    window_flag(args)
     args.pca_shift = {} if args.pca_shift is None else parse_axis_values(args.pca_shift, "pca-shift")
     return args
-
-
-def check_hop(args, meta):
-    """--hop against the hop the walk file was fitted at; ValueError naming both."""
-    from rawaudiovae_kelsey_amd.walk import check_hop as same_hop
-    try:
-        return same_hop(meta["hop"], args.hop, meta["segment_length"])
-    except ValueError as e:
-        raise ValueError("--hop: %s (--walk %r)" % (e, args.walk))
 
 
 def out_paths(out, n_streams):
@@ -103,19 +84,11 @@ def out_paths(out, n_streams):
 
 
 def fit(args):
-    from evaluate import data_files
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import walk as W
-    from rawaudiovae_kelsey_amd.codec import frame_layout
-    cfg = read_model_config(args.config)
-    try:
-        frame_layout(cfg["segment_length"], cfg["segment_length"], args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
+    cfg, _ = model_config(args)
     files = data_files(args.data)
     model = load_model(args.checkpoint, cfg)
-    waves = [D.load_audio_mono(f, cfg["sampling_rate"]) for f in files]
+    waves = [load_wav(f, cfg["sampling_rate"]) for f in files]
     try:
         walk = W.fit_corpus(model, waves, args.hop, args.keep, "diagonal" if args.diagonal else "full")
     except ValueError as e:
@@ -129,21 +102,13 @@ def fit(args):
 
 def start_state(model, walk, path, sampling_rate, hop):
     """The whitened state [1, k] of the last frame of the wav at `path`."""
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd.codec import FrameCodec
-    codec = FrameCodec(model)
-    w = codec.wave(D.load_audio_mono(path, sampling_rate))
-    try:
-        padded, T = codec.pad(w, w.numel(), hop)
-    except ValueError as e:
-        raise ValueError("--start %r: %s" % (path, e))
-    mu, _ = codec.encode(padded, T, hop)
+    _, mu, _, T = encode_wav(FrameCodec(model), load_wav(path, sampling_rate), hop, "start", path)
     return walk.whiten(mu[T - 1:T].contiguous())
 
 
 def run(args):
     import torch
-    from interpolate import load_model, read_model_config
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import walk as W
     from rawaudiovae_kelsey_amd.pca import LatentPCA
@@ -151,14 +116,11 @@ def run(args):
     cfg = read_model_config(args.config)
     S = cfg["segment_length"]
     for flag, path in (("walk", args.walk), ("start", args.start)):
-        if path is not None and not os.path.exists(path):
-            raise ValueError("--%s %r: no such file" % (flag, path))
+        if path is not None:
+            check_exists(flag, path)
     model = load_model(args.checkpoint, cfg)
     walk, meta = W.read_walk(args.walk, model.fc1.weight.device)
-    if meta["segment_length"] != S or meta["latent_dim"] != cfg["latent_dim"]:
-        raise ValueError("--walk %r: fitted for segment_length %d and latent_dim %d, the model has %d and %d" % (
-            args.walk, meta["segment_length"], meta["latent_dim"], S, cfg["latent_dim"]))
-    hop = check_hop(args, meta)
+    hop = check_fitted("walk", args.walk, meta, cfg, args.hop)
     try:
         check_args(S, hop, hop, args.window)
     except ValueError as e:

@@ -18,7 +18,6 @@ checkpoint is a training checkpoint dict (its 'state_dict', as tutorial.ipynb:29
 pickle (best_model.pt / last_model.pt).  Bad flag values raise ValueError naming the flag.
 """
 import argparse
-import configparser
 import os
 import sys
 
@@ -27,6 +26,9 @@ import numpy as np
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
+
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, load_model, load_wav, nonneg_int, number_flag,  # noqa: E402
+                                             positive_int, read_model_config)
 
 
 def parse_alphas(spec):
@@ -70,8 +72,7 @@ def parse_curve(spec):
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Latent interpolation between two sounds (tutorial.ipynb on the GPU)")
-    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    add_model_flags(p, hop_help="AudioDataset hop (default: TestDataset framing)")
     p.add_argument("--a", default=None, help="first sound (wav); or --a-cluster")
     p.add_argument("--b", default=None, help="second sound (wav); or --b-cluster")
     p.add_argument("--som", default=None, help="folder with clusters.json and data-concatenated.json (som.py)")
@@ -82,7 +83,6 @@ def parse_args(argv=None):
     p.add_argument("--mode", default="stepwise", help="stepwise | curve")
     p.add_argument("--alphas", default="0:1.1:0.2", help="stepwise: start:stop:step or a comma list")
     p.add_argument("--curve", default="sin:-500:500:20000", help="curve: sin:lo:hi:n or file.npy")
-    p.add_argument("--hop", default=None, help="AudioDataset hop (default: TestDataset framing)")
     p.add_argument("--match", default="repeat", help="repeat | crop")
     p.add_argument("--seed", default="0", help="seed of the eps draw")
     p.add_argument("--max-rows", default="16384", help="frames per chunk")
@@ -91,66 +91,25 @@ def parse_args(argv=None):
         raise ValueError("--mode %r: expected stepwise or curve" % args.mode)
     if args.match not in ("repeat", "crop"):
         raise ValueError("--match %r: expected repeat or crop" % args.match)
-    for flag in ("hop", "seed", "max_rows"):
-        v = getattr(args, flag)
-        if v is None:
-            continue
-        try:
-            iv = int(v)
-        except ValueError:
-            iv = -1
-        if iv < 0 or (flag != "seed" and iv == 0):
-            raise ValueError("--%s %r: expected a %s integer" % (flag.replace("_", "-"), v,
-                                                                  "non-negative" if flag == "seed" else "positive"))
-        setattr(args, flag, iv)
+    positive_int(args, "hop")
+    nonneg_int(args, "seed")
+    positive_int(args, "max-rows")
     for s in ("a", "b"):
         wav, node = getattr(args, s), getattr(args, s + "_cluster")
         if (wav is None) == (node is None):
             raise ValueError("--%s / --%s-cluster: give exactly one of them" % (s, s))
         if node is not None:
-            try:
-                k = int(node)
-            except ValueError:
-                k = -1
-            if k < 0:
-                raise ValueError("--%s-cluster %r: expected a non-negative node index" % (s, node))
+            number_flag(args, s + "-cluster", int, lambda k: k >= 0, "a non-negative node index")
             if args.som is None or args.audio is None:
                 raise ValueError("--%s-cluster needs --som and --audio" % s)
-            setattr(args, s + "_cluster", k)
     args.alpha_values = parse_alphas(args.alphas) if args.mode == "stepwise" else None
     args.curve_values = parse_curve(args.curve) if args.mode == "curve" else None
     return args
 
 
-def read_model_config(path):
-    config = configparser.ConfigParser(allow_no_value=True)
-    if not config.read(path):
-        raise ValueError("--config %r: file not found" % path)
-    return dict(sampling_rate=config["audio"].getint("sampling_rate"),
-                segment_length=config["audio"].getint("segment_length"),
-                n_units=config["VAE"].getint("n_units"), latent_dim=config["VAE"].getint("latent_dim"))
-
-
-def load_model(path, cfg, device="cuda"):
-    """VAE of the .ini's shape with the checkpoint's parameters."""
-    import torch
-    from rawvae.model import VAE
-    state = torch.load(path, map_location=device, weights_only=False)
-    model = VAE(cfg["segment_length"], cfg["n_units"], cfg["latent_dim"]).to(device)
-    if isinstance(state, dict):
-        sd = state.get("state_dict", state)
-    elif isinstance(state, torch.nn.Module):
-        sd = state.state_dict()
-    else:
-        raise ValueError("--checkpoint %r: neither a checkpoint dict nor a module pickle" % path)
-    model.load_state_dict(sd)
-    return model.eval()
-
-
 def cluster_audio(som_dir, audio_dir, node, sampling_rate, flag):
     """concat_audio_som (tutorial.ipynb:743-756): the node's files in list order, each loaded at sampling_rate, joined
     into one waveform.  A missing or empty node raises ValueError naming `flag`."""
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd.som import cluster_paths, read_som
     clusters, data = read_som(som_dir)
     try:
@@ -159,7 +118,7 @@ def cluster_audio(som_dir, audio_dir, node, sampling_rate, flag):
         raise ValueError("%s %d: no such node in %s" % (flag, node, os.path.join(som_dir, "clusters.json")))
     if not paths:
         raise ValueError("%s %d: the node has no files" % (flag, node))
-    return np.concatenate([D.load_audio_mono(p, sampling_rate) for p in paths], 0)
+    return np.concatenate([load_wav(p, sampling_rate) for p in paths], 0)
 
 
 def main(argv=None):
@@ -169,9 +128,9 @@ def main(argv=None):
     from rawaudiovae_kelsey_amd.interpolate import LatentInterpolator
     model = load_model(args.checkpoint, cfg)
     sr = cfg["sampling_rate"]
-    a = (D.load_audio_mono(args.a, sr) if args.a is not None
+    a = (load_wav(args.a, sr) if args.a is not None
          else cluster_audio(args.som, args.audio, args.a_cluster, sr, "--a-cluster"))
-    b = (D.load_audio_mono(args.b, sr) if args.b is not None
+    b = (load_wav(args.b, sr) if args.b is not None
          else cluster_audio(args.som, args.audio, args.b_cluster, sr, "--b-cluster"))
     it = LatentInterpolator(model, max_rows=args.max_rows)
     if args.mode == "stepwise":

@@ -31,48 +31,9 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-
-def parse_axis_values(text, flag):
-    """{0-based axis: value} of "J:V,J:V,..." with 1-based J; ValueError naming `flag` for anything else, a J < 1, a
-    value that is not finite or an axis given twice."""
-    out = {}
-    for item in str(text).split(","):
-        j, sep, v = item.partition(":")
-        try:
-            if not sep:
-                raise ValueError
-            axis, value = int(j), float(v)
-        except ValueError:
-            raise ValueError("--%s %r: expected J:VALUE,... with J a 1-based axis number, got %r" % (flag, text, item))
-        if axis < 1:
-            raise ValueError("--%s %r: axis %d: axes are numbered from 1" % (flag, text, axis))
-        if value != value or abs(value) == float("inf"):
-            raise ValueError("--%s %r: axis %d: the value must be finite" % (flag, text, axis))
-        if axis - 1 in out:
-            raise ValueError("--%s %r: axis %d is given twice" % (flag, text, axis))
-        out[axis - 1] = value
-    return out
-
-
-def check_axes(values, n_axes, flag):
-    """`values` of parse_axis_values against the number of axes of the .npz; ValueError naming `flag`."""
-    for j in values:
-        if j >= n_axes:
-            raise ValueError("--%s: axis %d: the PCA file holds %d axes" % (flag, j + 1, n_axes))
-    return values
-
-
-def _positive(args, flag, allow_zero=False):
-    v = getattr(args, flag)
-    if v is None:
-        return
-    try:
-        iv = int(v)
-    except ValueError:
-        iv = -1
-    if iv < 0 or (iv == 0 and not allow_zero):
-        raise ValueError("--%s %r: expected a %s integer" % (flag, v, "non-negative" if allow_zero else "positive"))
-    setattr(args, flag, iv)
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, check_axes, check_exists, check_fitted, data_files,  # noqa: E402
+                                             encode_wav, frame_step, load_model, load_wav, nonneg_int,
+                                             parse_axis_values, positive_int, read_model_config, window_flag)
 
 
 def parse_args(argv=None):
@@ -80,9 +41,7 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in ("fit", "edit"):
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
-        s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
+        add_model_flags(s)
         s.add_argument("--out", required=True, help="fit: the .npz; edit: the output wav")
         if name == "fit":
             s.add_argument("--data", required=True, help="a wav, or a folder whose *.wav are encoded")
@@ -96,12 +55,10 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: fit or edit")
-    _positive(args, "hop")
+    positive_int(args, "hop")
     if args.command == "edit":
-        _positive(args, "keep", allow_zero=True)
-        if args.window not in ("none", "hann"):
-            raise ValueError("--window %r: expected none or hann" % args.window)
-        args.window = None if args.window == "none" else args.window
+        nonneg_int(args, "keep")
+        window_flag(args)
         args.gain = {} if args.gain is None else parse_axis_values(args.gain, "gain")
         args.shift = {} if args.shift is None else parse_axis_values(args.shift, "shift")
     return args
@@ -109,17 +66,11 @@ def parse_args(argv=None):
 
 def check_framing(args, segment_length):
     """The framing flags against the model's frame length -> the frame step; ValueError naming the flag."""
-    from rawaudiovae_kelsey_amd.codec import frame_layout
     from rawaudiovae_kelsey_amd.mosaic import check_window
-    S = int(segment_length)
-    try:
-        frame_layout(S, S, args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
-    step = S if args.hop is None else args.hop
+    step = frame_step(args, segment_length)
     if args.command == "edit":
         try:
-            check_window(S, step, args.window)
+            check_window(int(segment_length), step, args.window)
         except ValueError as e:
             raise ValueError("--window %s: %s" % (args.window or "none", e))
     return step
@@ -140,15 +91,12 @@ def controls(args, n_axes):
 
 
 def fit(args):
-    from evaluate import data_files
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import pca as P
     cfg = read_model_config(args.config)
     check_framing(args, cfg["segment_length"])
     files = data_files(args.data)
     model = load_model(args.checkpoint, cfg)
-    waves = [D.load_audio_mono(f, cfg["sampling_rate"]) for f in files]
+    waves = [load_wav(f, cfg["sampling_rate"]) for f in files]
     try:
         pca = P.fit_corpus(model, waves, args.hop)
     except ValueError as e:
@@ -163,7 +111,6 @@ def fit(args):
 
 def edit(args):
     import torch
-    from interpolate import load_model, read_model_config
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import pca as P
     from rawaudiovae_kelsey_amd.codec import FrameCodec
@@ -173,22 +120,14 @@ def edit(args):
     S = cfg["segment_length"]
     step = check_framing(args, S)
     for flag, path in (("pca", args.pca), ("in", args.inp)):
-        if not os.path.exists(path):
-            raise ValueError("--%s %r: no such file" % (flag, path))
+        check_exists(flag, path)
     model = load_model(args.checkpoint, cfg)
     codec = FrameCodec(model)
     pca, meta = P.read_pca(args.pca, codec.device)
-    if meta["segment_length"] != S or meta["latent_dim"] != cfg["latent_dim"]:
-        raise ValueError("--pca %r: fitted for segment_length %d and latent_dim %d, the model has %d and %d" % (
-            args.pca, meta["segment_length"], meta["latent_dim"], S, cfg["latent_dim"]))
+    check_fitted("pca", args.pca, meta, cfg)
     gains, shifts = controls(args, pca.components_.shape[0])
-    w = codec.wave(D.load_audio_mono(args.inp, cfg["sampling_rate"]))
-    try:
-        padded, T = codec.pad(w, w.numel(), args.hop)
-    except ValueError as e:
-        raise ValueError("--in %r: %s" % (args.inp, e))
     with torch.no_grad():
-        mu, _ = codec.encode(padded, T, args.hop)
+        w, mu, _, T = encode_wav(codec, load_wav(args.inp, cfg["sampling_rate"]), args.hop, "in", args.inp)
         frames = codec.decode(pca.edit(mu, gains, shifts))
         win = None if args.window is None else torch.from_numpy(window_values(S, args.window)).to(codec.device)
         y = ola(frames, step, w.numel(), win).cpu().numpy()

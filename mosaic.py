@@ -49,29 +49,16 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-import interpolate as _interp  # noqa: E402  (read_model_config, load_model)
-from som import _int_flag, load_wav  # noqa: E402
-
-
-def _weight_flag(name, value):
-    """A finite float >= 0; ValueError naming the flag otherwise."""
-    try:
-        v = float(value)
-    except (TypeError, ValueError):
-        v = float("nan")
-    if not 0 <= v < float("inf"):
-        raise ValueError("--%s %r: expected a finite number >= 0" % (name, value))
-    return v
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, int_at_least, load_model, load_wav, nonneg_real,  # noqa: E402
+                                             read_model_config, window_flag)
 
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Latent audio mosaicing: resynthesise a target from a corpus's frames")
-    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    add_model_flags(p, hop_help="frame hop (default: segment_length)")
     p.add_argument("--corpus", required=True, help="folder of the corpus's .wav files")
     p.add_argument("--target", required=True, help="the wav to resynthesise")
     p.add_argument("--out", required=True, help="output wav")
-    p.add_argument("--hop", default=None, help="frame hop (default: segment_length)")
     p.add_argument("--k", default="1", help="neighbours per target frame (1..16)")
     p.add_argument("--mode", default="grains", help="grains | decode")
     p.add_argument("--window", default="none", help="none | hann")
@@ -86,30 +73,28 @@ def parse_args(argv=None):
     p.add_argument("--live-fit", default=None, help="--fit for the live path (0..1024; needs --live-block)")
     p.add_argument("--live-gain-max", default=None, help="--gain-max for the live path (needs --live-block)")
     args = p.parse_args(argv)
-    args.live_block = None if args.live_block is None else _int_flag("live-block", args.live_block, 1)
+    int_at_least(args, "live-block", 1)
     if args.streams is not None and args.live_block is None:
         raise ValueError("--streams %s: needs --live-block" % args.streams)
-    args.streams = 1 if args.streams is None else _int_flag("streams", args.streams, 1)
-    args.k = _int_flag("k", args.k, 1)
+    args.streams = int_at_least(args, "streams", 1) or 1
+    int_at_least(args, "k", 1)
     if args.k > 16:
         raise ValueError("--k %d: at most 16" % args.k)
-    args.continuity = _weight_flag("continuity", args.continuity)
+    nonneg_real(args, "continuity")
     if args.lag is not None:
         if args.live_block is None:
             raise ValueError("--lag %s: needs --live-block" % args.lag)
-        args.lag = _int_flag("lag", args.lag, 0)
+        int_at_least(args, "lag", 0)
         if args.lag > 64:
             raise ValueError("--lag %d: at most 64" % args.lag)
         if args.lag > 0 and args.continuity == 0:
             raise ValueError("--lag %d: needs --continuity > 0" % args.lag)
     args.lag = args.lag or 0
-    args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
-    args.max_rows = _int_flag("max-rows", args.max_rows, 1)
+    int_at_least(args, "hop", 1)
+    int_at_least(args, "max-rows", 1)
     if args.mode not in ("grains", "decode"):
         raise ValueError("--mode %r: expected grains or decode" % args.mode)
-    if args.window not in ("none", "hann"):
-        raise ValueError("--window %r: expected none or hann" % args.window)
-    args.window = None if args.window == "none" else args.window
+    window_flag(args)
     for flag, value in (("fit", args.fit), ("gain-max", args.gain_max)):
         if value is None:
             continue
@@ -118,10 +103,10 @@ def parse_args(argv=None):
         if args.mode == "decode":
             raise ValueError("--%s %s: needs --mode grains, --mode decode plays no corpus audio" % (flag, value))
     args.fitted = args.fit is not None or args.gain_max is not None
-    args.fit = 0 if args.fit is None else _int_flag("fit", args.fit, 0)
+    args.fit = int_at_least(args, "fit", 0) or 0
     if args.fit > 1024:
         raise ValueError("--fit %d: at most 1024" % args.fit)
-    args.gain_max = 0.0 if args.gain_max is None else _weight_flag("gain-max", args.gain_max)
+    args.gain_max = nonneg_real(args, "gain-max") or 0.0
     for flag, value in (("live-fit", args.live_fit), ("live-gain-max", args.live_gain_max)):
         if value is None:
             continue
@@ -130,10 +115,10 @@ def parse_args(argv=None):
         if args.mode == "decode":
             raise ValueError("--%s %s: needs --mode grains, --mode decode plays no corpus audio" % (flag, value))
     args.live_fitted = args.live_fit is not None or args.live_gain_max is not None
-    args.live_fit = 0 if args.live_fit is None else _int_flag("live-fit", args.live_fit, 0)
+    args.live_fit = int_at_least(args, "live-fit", 0) or 0
     if args.live_fit > 1024:
         raise ValueError("--live-fit %d: at most 1024" % args.live_fit)
-    args.live_gain_max = 0.0 if args.live_gain_max is None else _weight_flag("live-gain-max", args.live_gain_max)
+    args.live_gain_max = nonneg_real(args, "live-gain-max") or 0.0
     if not os.path.isdir(args.corpus):
         raise ValueError("--corpus %r: not a folder" % args.corpus)
     return args
@@ -185,7 +170,7 @@ def write_matches(path, names_offsets, dist, slot=None, fit=None):
 
 def main(argv=None):
     args = parse_args(argv)
-    cfg = _interp.read_model_config(args.config)
+    cfg = read_model_config(args.config)
     S, sr = cfg["segment_length"], cfg["sampling_rate"]
     hop = check_framing(args, S)
     files = corpus_files(args.corpus)
@@ -205,7 +190,7 @@ def main(argv=None):
     if frame_layout(target.size, S, framing)[0] < 1:
         raise ValueError("--target %r: %d samples make no frame of %d samples at hop %d" % (args.target, target.size,
                                                                                            S, hop))
-    model = _interp.load_model(args.checkpoint, cfg)
+    model = load_model(args.checkpoint, cfg)
     index = LatentIndex(model, hop=framing, max_rows=args.max_rows)
     for f, w in zip(files, waves):
         index.add(w, f)

@@ -18,12 +18,15 @@ alignment"; csrc/align.hip).
 `band` is in frames: cell (i, j) is kept iff |j - floor(i (Tb - 1) / max(Ta - 1, 1))| <= band; None (or 0) is the whole
 matrix.  Nothing here syncs except reading the path length P (Alignment.P and what follows from it).
 """
+import functools
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import RvError, mosaic_call as _call, ptr
 from .codec import FrameCodec
+from .corpus import rows
 from .interpolate import LatentInterpolator
 from .stream import GraphReplay, window_values
 
@@ -84,11 +87,7 @@ def check_penalty(penalty):
     return p
 
 
-def _rows(x, what):
-    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
-        raise ValueError("%s must be a 2-D float32 device tensor, got %s" % (
-            what, "%s %s on %s" % (x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__))
-    return x.contiguous()
+_rows = functools.partial(rows, empty_ok=True)
 
 
 def band_slots(Tb, band):

@@ -57,12 +57,15 @@ encoder, search, gather and decoder step), so the output is bit-identical for an
 decoder are codec.FrameCodec's (`index.codec`); the graphs of the live path are stream.GraphReplay's; every rv_mosaic
 call passes the member names rv_mosaic_desc declares for the op's roles (_lib.mosaic_call).
 """
+import functools
+
 import numpy as np
 import torch
 
 from . import _lib
 from ._lib import mosaic_call as _call, ptr
 from .codec import FrameCodec, frame_layout
+from .corpus import rows
 from .stream import WINDOWS, GraphReplay, StreamingVAE, check_args, each_stream, window_values
 
 MODES = ("grains", "decode")
@@ -79,11 +82,7 @@ def live_fit_table(successors, room):
     return torch.cat([successors, room.reshape(-1)]).contiguous()
 
 
-def _rows(x, what):
-    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
-        raise ValueError("%s must be a 2-D float32 device tensor, got %s" % (
-            what, "%s %s on %s" % (x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__))
-    return x.contiguous()
+_rows = functools.partial(rows, empty_ok=True)
 
 
 def knn_workspace_bytes(T, N, L, k, splits=0, small=False):

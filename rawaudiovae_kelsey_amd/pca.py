@@ -20,21 +20,9 @@ import torch
 
 from . import _lib
 from ._lib import RvError, mosaic_call as _call, ptr
-from .codec import FrameCodec
+from .corpus import encode_corpus, read_fitted, rows as _rows, write_fitted
 
 L_MAX = 512     # csrc/pca.hip
-
-
-def _rows(x, what="x", dtype=torch.float32, cols=None):
-    name = {torch.float32: "float32", torch.float64: "float64"}[dtype]
-    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != dtype or x.device.type != "cuda":
-        raise ValueError("%s must be a 2-D %s device tensor, got %s" % (
-            what, name, "%s %s on %s" % (x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__))
-    if x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("%s is empty: shape %s" % (what, tuple(x.shape)))
-    if cols is not None and x.shape[1] != cols:
-        raise ValueError("%s has %d columns, expected %d" % (what, x.shape[1], cols))
-    return x.contiguous()
 
 
 def _vector(v, what, n, dtype, device):
@@ -246,42 +234,24 @@ class LatentPCA:
 def fit_corpus(model, waves, hop=None, n_components=None, max_rows=16384):
     """LatentPCA fitted on the encoder's mu of every frame of every waveform, framed like TestDataset (hop=None) or
     AudioDataset (hop=int) through codec.FrameCodec."""
-    codec = FrameCodec(model, max_rows=max_rows)
-    waves = list(waves)
-    if not waves:
-        raise ValueError("fit_corpus needs at least one waveform")
-    mus = []
-    for f, w in enumerate(waves):
-        try:
-            w = codec.wave(w)
-            padded, n_frames = codec.pad(w, w.numel(), hop)
-            mus.append(codec.encode(padded, n_frames, hop)[0])
-        except ValueError as e:
-            raise ValueError("waveform %d: %s" % (f, e))
-    return LatentPCA(n_components).fit(torch.cat(mus, 0) if len(mus) > 1 else mus[0])
+    return LatentPCA(n_components).fit(encode_corpus(model, waves, hop, max_rows)[0])
 
 
 def write_pca(path, pca, segment_length, hop=None):
     """One .npz: mean [L], components [k, L], variances [L] (every eigenvalue), all fp64, and segment_length,
     latent_dim, hop (-1: non-overlapping frames), n_frames, sweeps."""
     pca._fitted()
-    with open(path, "wb") as f:
-        np.savez(f, mean=pca.mean_.cpu().numpy(), components=pca.components_.cpu().numpy(),
-                 variances=pca.all_variances_.cpu().numpy(), segment_length=int(segment_length),
-                 latent_dim=int(pca.mean_.numel()), hop=-1 if hop is None else int(hop), n_frames=pca.n_frames_,
-                 sweeps=pca.sweeps_)
+    write_fitted(path, dict(mean=pca.mean_, components=pca.components_, variances=pca.all_variances_),
+                 dict(segment_length=segment_length, latent_dim=pca.mean_.numel(), hop=hop, n_frames=pca.n_frames_,
+                      sweeps=pca.sweeps_))
 
 
 def read_pca(path, device="cuda"):
     """(LatentPCA on `device`, {segment_length, latent_dim, hop (None: non-overlapping), n_frames}) of write_pca's file;
     ValueError when the arrays do not fit one another."""
-    with np.load(path) as z:
-        missing = [n for n in ("mean", "components", "variances", "segment_length", "latent_dim", "hop", "n_frames",
-                               "sweeps") if n not in z.files]
-        if missing:
-            raise ValueError("%s: not a latent-PCA file, it lacks %s" % (path, ", ".join(missing)))
-        mean, comp, lam = (np.ascontiguousarray(z[n], dtype=np.float64) for n in ("mean", "components", "variances"))
-        meta = {n: int(z[n]) for n in ("segment_length", "latent_dim", "hop", "n_frames", "sweeps")}
+    arrays, meta, _ = read_fitted(path, "PCA", ("mean", "components", "variances"),
+                                  ("segment_length", "latent_dim", "hop", "n_frames", "sweeps"))
+    mean, comp, lam = arrays.values()
     L = meta["latent_dim"]
     if mean.shape != (L,) or lam.shape != (L,) or comp.ndim != 2 or comp.shape[1] != L or not 1 <= comp.shape[0] <= L:
         raise ValueError("%s: mean %s, components %s and variances %s do not fit latent_dim %d" % (
@@ -290,5 +260,4 @@ def read_pca(path, device="cuda"):
     pca = LatentPCA(comp.shape[0])._set(torch.from_numpy(mean).to(dev), torch.from_numpy(comp).to(dev),
                                         torch.from_numpy(lam).to(dev), meta["n_frames"], meta.pop("sweeps"),
                                         comp.shape[0])
-    meta["hop"] = None if meta["hop"] < 0 else meta["hop"]
     return pca, meta

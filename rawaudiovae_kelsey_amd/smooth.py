@@ -30,10 +30,10 @@ import torch
 from . import _lib
 from ._lib import mosaic_call as _call, ptr
 from .codec import FrameCodec, frame_layout
+from .corpus import check_hop, check_row_start, rows as _rows
 from .mosaic import check_window, ola
-from .pca import _rows
 from .stream import window_values
-from .walk import LatentWalk, check_hop, check_row_start
+from .walk import LatentWalk
 
 K_DENSE = 64                 # csrc/smooth.hip: the dense mode's axes
 NOISE_MIN, NOISE_MAX = 1e-8, 1e8

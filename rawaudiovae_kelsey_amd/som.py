@@ -11,6 +11,7 @@ The epoch is the batch SOM: every row's best-matching unit (BMU) under the squar
 rows, then w[m] = sum_b h(m, b) sums[b] / sum_b h(m, b) counts[b] with the Gaussian neighbourhood
 h = exp(-|grid(m) - grid(b)|^2 / (2 sigma_t^2)), sigma_t = sigma0 (sigma1 / sigma0)^(t / (E - 1)).
 """
+import functools
 import json
 import os
 
@@ -20,6 +21,7 @@ import torch
 from . import _lib
 from ._lib import lib, ptr, stream_ptr
 from .codec import FrameCodec
+from .corpus import rows
 
 
 def sigma_schedule(sigma0, sigma1, epochs):
@@ -31,13 +33,7 @@ def sigma_schedule(sigma0, sigma1, epochs):
     return float(sigma0) * (float(sigma1) / float(sigma0)) ** (t / (E - 1))
 
 
-def _rows(x, what="x"):
-    if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32 or x.device.type != "cuda":
-        raise ValueError("%s must be an [N, L] float32 device tensor, got %s" % (
-            what, "%s %s on %s" % (x.dtype, tuple(x.shape), x.device) if torch.is_tensor(x) else type(x).__name__))
-    if x.shape[0] < 1 or x.shape[1] < 1:
-        raise ValueError("%s is empty: shape %s" % (what, tuple(x.shape)))
-    return x.contiguous()
+_rows = functools.partial(rows, wording="an [N, L]")
 
 
 def bmu(x, w):

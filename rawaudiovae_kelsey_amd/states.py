@@ -27,7 +27,7 @@ import torch
 
 from . import _lib
 from ._lib import mosaic_call as _call, ptr
-from .codec import FrameCodec
+from .corpus import check_row_start, encode_corpus, read_fitted, write_fitted
 from .pca import LatentPCA
 from .walk import LatentWalk, rank_of
 
@@ -61,22 +61,6 @@ def pack_theta(m, v, pi, A):
     return th
 
 
-def check_sequences(row_start, T):
-    """row_start as a [n + 1] int64 numpy array, checked on the host: from 0 to T and never descending (ValueError)."""
-    if torch.is_tensor(row_start):
-        row_start = row_start.cpu().numpy()
-    rs = np.asarray(row_start)
-    if rs.ndim != 1 or rs.size < 2 or rs.dtype.kind not in "iu":
-        raise ValueError("row_start must be a 1-D integer sequence of n_files + 1 entries, got %s %s" % (rs.dtype, rs.shape))
-    rs = np.array(rs, dtype=np.int64)     # a copy: the caller's array may be read-only
-    if rs[0] != 0 or rs[-1] != int(T):
-        raise ValueError("row_start must run from 0 to T=%d, got %d .. %d" % (int(T), rs[0], rs[-1]))
-    if np.any(np.diff(rs) < 0):
-        f = int(np.argmax(np.diff(rs) < 0))
-        raise ValueError("row_start must not descend: file %d is [%d, %d)" % (f, rs[f], rs[f + 1]))
-    return rs
-
-
 def _count(value, what, hi):
     if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= value <= hi:
         raise ValueError("%s=%r must be an integer in [1, %d]" % (what, value, hi))
@@ -102,7 +86,7 @@ def _f64(t, what, shape, device="cuda"):
 
 
 def _rs_dev(row_start, T, device):
-    rs = check_sequences(row_start, T)
+    rs = check_row_start(row_start, T, empty_files=True)
     return torch.from_numpy(rs).to(device), rs.size - 1
 
 
@@ -301,7 +285,7 @@ class LatentStates:
             raise ValueError("%d frames are fewer than the %d states" % (x.shape[0], S))
         x, _ = _latents(x)
         T, L = x.shape
-        rs = check_sequences(row_start, T)
+        rs = check_row_start(row_start, T, empty_files=True)
         iters = _count(iters, "iters", 1 << 30)
         if not (isinstance(tol, (int, float)) and 0 <= tol < float("inf")):
             raise ValueError("tol=%r must be a finite number >= 0" % (tol,))
@@ -366,25 +350,6 @@ class LatentStates:
         return viterbi(logb, seqs, self.theta_, self.n_states, self.n_components)
 
 
-def encode_corpus(model, waves, hop=None, max_rows=16384):
-    """(mu [T, L] of every frame of every waveform, row_start [n + 1] int64) through codec.FrameCodec, framed like
-    pca.fit_corpus"""
-    codec = FrameCodec(model, max_rows=max_rows)
-    waves = list(waves)
-    if not waves:
-        raise ValueError("fit_corpus needs at least one waveform")
-    mus, starts = [], [0]
-    for f, w in enumerate(waves):
-        try:
-            w = codec.wave(w)
-            padded, n_frames = codec.pad(w, w.numel(), hop)
-            mus.append(codec.encode(padded, n_frames, hop)[0])
-        except ValueError as e:
-            raise ValueError("waveform %d: %s" % (f, e))
-        starts.append(starts[-1] + n_frames)
-    return (torch.cat(mus, 0) if len(mus) > 1 else mus[0]), np.asarray(starts, dtype=np.int64)
-
-
 @torch.no_grad()
 def fit_corpus(model, waves, hop=None, n_states=8, n_components=16, pca=None, iters=50, tol=1e-4, seed=0, var_floor=1e-3,
                max_rows=16384):
@@ -405,24 +370,19 @@ def write_states(path, states, segment_length, hop=None):
     """One .npz: theta, mean [L] and whiten = P [k, L], all fp64, var_floor, ll_history, and segment_length, latent_dim,
     hop (-1: non-overlapping frames), n_frames, n_files, n_states, n_components, n_iter."""
     states._fitted()
-    with open(path, "wb") as f:
-        np.savez(f, theta=states.theta_.cpu().numpy(), mean=states.mean_.cpu().numpy(), whiten=states.P_.cpu().numpy(),
-                 var_floor=float(states.var_floor), ll_history=np.asarray(states.ll_history_, dtype=np.float64),
-                 segment_length=int(segment_length), latent_dim=int(states.mean_.numel()), hop=-1 if hop is None else int(hop),
-                 n_frames=states.n_frames_, n_files=states.n_files_, n_states=states.n_states,
-                 n_components=states.n_components, n_iter=states.n_iter_)
+    write_fitted(path, dict(theta=states.theta_, mean=states.mean_, whiten=states.P_),
+                 dict(segment_length=segment_length, latent_dim=states.mean_.numel(), hop=hop, n_frames=states.n_frames_,
+                      n_files=states.n_files_, n_states=states.n_states, n_components=states.n_components,
+                      n_iter=states.n_iter_),
+                 var_floor=float(states.var_floor), ll_history=np.asarray(states.ll_history_, dtype=np.float64))
 
 
 def read_states(path, device="cuda"):
     """(LatentStates on `device`, {segment_length, latent_dim, hop (None: non-overlapping), n_frames, n_files, n_iter}) of
     write_states' file; ValueError when the arrays do not fit one another."""
-    with np.load(path) as z:
-        missing = [n for n in _ARRAYS + _META + ("var_floor", "ll_history") if n not in z.files]
-        if missing:
-            raise ValueError("%s: not a latent-states file, it lacks %s" % (path, ", ".join(missing)))
-        theta, mean, P = (np.ascontiguousarray(z[n], dtype=np.float64) for n in _ARRAYS)
-        meta = {n: int(z[n]) for n in _META}
-        floor, history = float(z["var_floor"]), np.asarray(z["ll_history"], dtype=np.float64).reshape(-1)
+    arrays, meta, extra = read_fitted(path, "states", _ARRAYS, _META, ("var_floor", "ll_history"))
+    theta, mean, P = arrays.values()
+    floor, history = float(extra["var_floor"]), np.asarray(extra["ll_history"], dtype=np.float64).reshape(-1)
     S, k, L = meta.pop("n_states"), meta.pop("n_components"), meta["latent_dim"]
     if (not 1 <= S <= S_MAX or not 1 <= k <= K_MAX or not k <= L <= L_MAX or theta.shape != (theta_layout(S, k)[1],)
             or mean.shape != (L,) or P.shape != (k, L)):
@@ -431,18 +391,7 @@ def read_states(path, device="cuda"):
     dev = torch.device(device)
     states = LatentStates(S, k, floor)._set(*(torch.from_numpy(a).to(dev) for a in (theta, mean, P)), meta["n_frames"],
                                             meta["n_files"], history)
-    meta["hop"] = None if meta["hop"] < 0 else meta["hop"]
     return states, meta
-
-
-def check_hop(fitted_hop, hop, segment_length):
-    """The hop a recording is framed at against the hop the states were fitted at (None: non-overlapping frames of
-    segment_length); ValueError naming both when they differ."""
-    a = int(segment_length) if fitted_hop is None else int(fitted_hop)
-    b = int(segment_length) if hop is None else int(hop)
-    if a != b:
-        raise ValueError("hop %d: the states were fitted at hop %d; a transition is one frame at that hop" % (b, a))
-    return b
 
 
 def runs(path):

@@ -34,28 +34,12 @@ import torch
 from . import _lib
 from . import pca as P_
 from ._lib import RvError, mosaic_call as _call, ptr
-from .codec import FrameCodec
-from .pca import L_MAX, LatentPCA, _rows, _vector
+from .corpus import check_row_start, encode_corpus, read_fitted, rows as _rows, write_fitted
+from .pca import L_MAX, LatentPCA, _vector
 from .stream import GraphReplay, StreamingVAE, each_stream
 
 MODES = ("full", "diagonal")
 RANK_TOL = 1e-12     # an axis counts while lambda_j > RANK_TOL * lambda_0
-
-
-def check_row_start(row_start, T):
-    """row_start as a [n_files + 1] int64 numpy array, checked on the host: ascending from 0 to T (ValueError)."""
-    if torch.is_tensor(row_start):
-        row_start = row_start.cpu().numpy()
-    rs = np.asarray(row_start)
-    if rs.ndim != 1 or rs.size < 2 or rs.dtype.kind not in "iu":
-        raise ValueError("row_start must be a 1-D integer sequence of n_files + 1 entries, got %s %s" % (rs.dtype, rs.shape))
-    rs = np.ascontiguousarray(rs, dtype=np.int64)
-    if rs[0] != 0 or rs[-1] != int(T):
-        raise ValueError("row_start must run from 0 to T=%d, got %d .. %d" % (int(T), rs[0], rs[-1]))
-    if np.any(np.diff(rs) <= 0):
-        f = int(np.argmax(np.diff(rs) <= 0))
-        raise ValueError("row_start must be ascending: file %d is [%d, %d)" % (f, rs[f], rs[f + 1]))
-    return rs
 
 
 def rank_of(variances):
@@ -184,23 +168,11 @@ def fit_corpus(model, waves, hop=None, n_components=None, mode="full", max_rows=
     """LatentWalk fitted on the encoder's mu of every frame of every waveform, framed like pca.fit_corpus; the files'
     frame counts are kept (row_start_), so no pair of frames spans two files."""
     walk = LatentWalk(n_components, mode)
-    codec = FrameCodec(model, max_rows=max_rows)
-    waves = list(waves)
-    if not waves:
-        raise ValueError("fit_corpus needs at least one waveform")
-    mus, starts = [], [0]
-    for f, w in enumerate(waves):
-        try:
-            w = codec.wave(w)
-            padded, n_frames = codec.pad(w, w.numel(), hop)
-            mus.append(codec.encode(padded, n_frames, hop)[0])
-        except ValueError as e:
-            raise ValueError("waveform %d: %s" % (f, e))
-        starts.append(starts[-1] + n_frames)
+    x, starts = encode_corpus(model, waves, hop, max_rows)
     if starts[-1] < 2:
         raise ValueError("fit_corpus needs at least 2 frames, the waveforms make %d" % starts[-1])
-    walk.fit(torch.cat(mus, 0) if len(mus) > 1 else mus[0], np.asarray(starts, dtype=np.int64))
-    walk.row_start_ = np.asarray(starts, dtype=np.int64)
+    walk.fit(x, starts)
+    walk.row_start_ = starts
     return walk
 
 
@@ -214,21 +186,16 @@ def write_walk(path, walk, segment_length, hop=None):
     n_files, rank, diagonal."""
     walk._fitted()
     arrays = dict(zip(_ARRAYS, (walk.mean_, walk.components_, walk.explained_variance_, walk.dyn_, walk.P_, walk.R_)))
-    with open(path, "wb") as f:
-        np.savez(f, segment_length=int(segment_length), latent_dim=int(walk.mean_.numel()),
-                 hop=-1 if hop is None else int(hop), n_frames=walk.n_frames_, n_files=walk.n_files_, rank=walk.rank_,
-                 diagonal=int(walk.mode == "diagonal"), **{n: t.cpu().numpy() for n, t in arrays.items()})
+    write_fitted(path, arrays,
+                 dict(segment_length=segment_length, latent_dim=walk.mean_.numel(), hop=hop, n_frames=walk.n_frames_,
+                      n_files=walk.n_files_, rank=walk.rank_, diagonal=walk.mode == "diagonal"))
 
 
 def read_walk(path, device="cuda"):
     """(LatentWalk on `device`, {segment_length, latent_dim, hop (None: non-overlapping), n_frames, n_files}) of
     write_walk's file; ValueError when the arrays do not fit one another."""
-    with np.load(path) as z:
-        missing = [n for n in _ARRAYS + _META if n not in z.files]
-        if missing:
-            raise ValueError("%s: not a latent-walk file, it lacks %s" % (path, ", ".join(missing)))
-        arrays = [np.ascontiguousarray(z[n], dtype=np.float64) for n in _ARRAYS]
-        meta = {n: int(z[n]) for n in _META}
+    arrays, meta, _ = read_fitted(path, "walk", _ARRAYS, _META)
+    arrays = list(arrays.values())
     mean, comp, lam, dyn, Pm, R = arrays
     L = meta["latent_dim"]
     k = comp.shape[0] if comp.ndim == 2 else -1
@@ -240,18 +207,7 @@ def read_walk(path, device="cuda"):
     dev = torch.device(device)
     walk = LatentWalk(k, "diagonal" if meta.pop("diagonal") else "full")._set(
         *(torch.from_numpy(a).to(dev) for a in arrays), meta.pop("rank"), meta["n_frames"], meta["n_files"])
-    meta["hop"] = None if meta["hop"] < 0 else meta["hop"]
     return walk, meta
-
-
-def check_hop(fitted_hop, hop, segment_length):
-    """The hop a walk is run at against the hop it was fitted at (None: non-overlapping frames of segment_length);
-    ValueError naming both when they differ."""
-    a = int(segment_length) if fitted_hop is None else int(fitted_hop)
-    b = int(segment_length) if hop is None else int(hop)
-    if a != b:
-        raise ValueError("hop %d: the walk was fitted at hop %d; one step of the walk is one frame at that hop" % (b, a))
-    return b
 
 
 class StreamingWalk(GraphReplay):

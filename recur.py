@@ -34,19 +34,10 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from som import _int_flag, load_wav  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, flagged, int_at_least, load_wav, number_flag,  # noqa: E402
+                                             open_model, positive, window_flag)
 
 COMMANDS = ("motifs", "discords", "loop")
-
-
-def _seconds_flag(name, v):
-    try:
-        fv = float(v)
-    except (TypeError, ValueError):
-        fv = float("nan")
-    if not 0 < fv < float("inf"):
-        raise ValueError("--%s %r: expected a finite number of seconds > 0" % (name, v))
-    return fv
 
 
 def parse_args(argv=None):
@@ -55,10 +46,8 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in COMMANDS:
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+        add_model_flags(s)
         s.add_argument("--in", dest="wav", required=True, help="the wav to search")
-        s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
         s.add_argument("--window-frames", default="16" if name == "loop" else "32", help="the window in frames")
         s.add_argument("--out", required=True, help="motifs, discords: the .json; loop: the wav")
         s.add_argument("--profile", default=None, help="also write the profile as .npy")
@@ -74,45 +63,29 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: motifs, discords or loop")
-    args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
-    args.window_frames = _int_flag("window-frames", args.window_frames, 1)
+    int_at_least(args, "hop", 1)
+    int_at_least(args, "window-frames", 1)
     if args.window_frames > M_MAX:
         raise ValueError("--window-frames %d: at most %d frames" % (args.window_frames, M_MAX))
     if args.command == "loop":
-        args.min_seconds = _seconds_flag("min-seconds", args.min_seconds)
-        args.max_seconds = _seconds_flag("max-seconds", args.max_seconds)
+        for flag in ("min-seconds", "max-seconds"):
+            number_flag(args, flag, float, positive, "a finite number of seconds > 0")
         if args.min_seconds > args.max_seconds:
             raise ValueError("--min-seconds %g: above --max-seconds %g" % (args.min_seconds, args.max_seconds))
-        args.repeats = _int_flag("repeats", args.repeats, 1)
-        if args.window not in ("none", "hann"):
-            raise ValueError("--window %r: expected none or hann" % args.window)
-        args.window = None if args.window == "none" else args.window
+        int_at_least(args, "repeats", 1)
+        window_flag(args)
         if args.window is not None and args.hop is None:
             raise ValueError("--window %s: needs --hop (without one the frames are concatenated)" % args.window)
     else:
-        args.top = _int_flag("top", args.top, 1)
-        args.exclude = None if args.exclude is None else _int_flag("exclude", args.exclude, 0)
+        int_at_least(args, "top", 1)
+        int_at_least(args, "exclude", 0)
     return args
 
 
 def _setup(args):
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd.codec import frame_layout
     from rawaudiovae_kelsey_amd.recur import LatentLooper
-    cfg = read_model_config(args.config)
-    S = cfg["segment_length"]
-    try:
-        frame_layout(S, S, args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
-    return cfg, S if args.hop is None else args.hop, LatentLooper(load_model(args.checkpoint, cfg))
-
-
-def _flagged(flags, fn):
-    try:
-        return fn()
-    except ValueError as e:
-        raise ValueError("%s: %s" % (flags, e))
+    cfg, model, step = open_model(args)
+    return cfg, step, LatentLooper(model)
 
 
 def _save_profile(args, rec):
@@ -125,7 +98,7 @@ def run_picks(args):
     sr, m = cfg["sampling_rate"], args.window_frames
     wave = load_wav(args.wav, sr)
     other = None if args.against is None else load_wav(args.against, sr)
-    rec = _flagged("--in / --against / --window-frames",
+    rec = flagged("--in / --against / --window-frames",
                    lambda: looper.profile(wave, args.hop, m, other, args.exclude, sampling_rate=sr))
     found = rec.motifs(args.top) if args.command == "motifs" else rec.discords(args.top)
     report = dict(command=args.command, windows=rec.T, window_frames=m, hop=step, sampling_rate=sr, exclude=rec.exclude,
@@ -147,7 +120,7 @@ def run_loop(args):
     from rawaudiovae_kelsey_amd.mosaic import check_window
     cfg, step, looper = _setup(args)
     sr, m = cfg["sampling_rate"], args.window_frames
-    _flagged("--window %s" % args.window, lambda: check_window(cfg["segment_length"], step, args.window))
+    flagged("--window %s" % args.window, lambda: check_window(cfg["segment_length"], step, args.window))
     # whole frames inside [min, max] seconds; the 1e-9 keeps a bound that is a whole number of frames on its frame
     lo, hi = int(np.ceil(args.min_seconds * sr / step - 1e-9)), int(np.floor(args.max_seconds * sr / step + 1e-9))
     if lo < m:
@@ -156,7 +129,7 @@ def run_loop(args):
         raise ValueError("--max-seconds %g: no whole number of frames between it and --min-seconds %g"
                          % (args.max_seconds, args.min_seconds))
     wave = load_wav(args.wav, sr)
-    loop = _flagged("--in / --window-frames", lambda: looper.find(wave, args.hop, m, lo, hi, sr))
+    loop = flagged("--in / --window-frames", lambda: looper.find(wave, args.hop, m, lo, hi, sr))
     if loop is None:
         raise ValueError("--in %r: no loop of %g to %g seconds (the recording is too short or holds NaN)"
                          % (args.wav, args.min_seconds, args.max_seconds))

@@ -26,7 +26,6 @@ recording moves as the corpus does) as a .npy and prints the frames above --thre
 """
 import argparse
 import json
-import math
 import os
 import sys
 
@@ -36,20 +35,11 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from latent_pca import _positive  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, check_exists, check_fitted, finite, load_model,  # noqa: E402
+                                             load_wav, nonneg_int, number_flag, positive_int, read_model_config,
+                                             window_flag)
 
 COMMANDS = ("fill", "smooth", "surprise")
-
-
-def _real(args, flag, lo, hi, what):
-    raw = getattr(args, flag)
-    try:
-        v = float(raw)
-    except ValueError:
-        v = float("nan")
-    if not (math.isfinite(v) and lo <= v <= hi):
-        raise ValueError("--%s %r: expected %s" % (flag, raw, what))
-    setattr(args, flag, v)
 
 
 def parse_args(argv=None):
@@ -57,12 +47,10 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in COMMANDS:
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+        add_model_flags(s, hop_help="frame hop: the hop the walk was fitted at")
         s.add_argument("--walk", required=True, help="the .npz written by generate.py fit")
         s.add_argument("--in", dest="wav", required=True, help="the damaged wav")
         s.add_argument("--out", required=True, help="fill, smooth: the output wav; surprise: the .npy")
-        s.add_argument("--hop", default=None, help="frame hop: the hop the walk was fitted at")
         s.add_argument("--noise", default="0.5" if name == "smooth" else "1e-2", help="observation noise, 1e-8 .. 1e8")
         if name != "surprise":
             s.add_argument("--window", default="none", help="none | hann")
@@ -77,25 +65,20 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: fill, smooth or surprise")
-    _positive(args, "hop")
-    _real(args, "noise", 1e-8, 1e8, "a finite number in [1e-8, 1e8]")
+    positive_int(args, "hop")
+    number_flag(args, "noise", float, finite(1e-8, 1e8), "a finite number in [1e-8, 1e8]")
     if args.command != "surprise":
-        if args.window not in ("none", "hann"):
-            raise ValueError("--window %r: expected none or hann" % args.window)
-        args.window = None if args.window == "none" else args.window
+        window_flag(args)
     if args.command == "fill":
         given = [f for f in ("gaps", "gaps_json", "detect_zeros") if getattr(args, f) is not None]
         if len(given) != 1:
             raise ValueError("expected exactly one of --gaps, --gaps-json and --detect-zeros, got %s" % (
                 ", ".join("--" + f.replace("_", "-") for f in given) or "none"))
-        try:
-            _positive(args, "detect_zeros")
-        except ValueError as e:
-            raise ValueError(str(e).replace("--detect_zeros", "--detect-zeros"))
-        _positive(args, "context")
-        _positive(args, "fade", allow_zero=True)
+        positive_int(args, "detect-zeros")
+        positive_int(args, "context")
+        nonneg_int(args, "fade")
     if args.command == "surprise":
-        _real(args, "threshold", 0.0, float("inf"), "a non-negative number")
+        number_flag(args, "threshold", float, finite(0.0, float("inf")), "a non-negative number")
     return args
 
 
@@ -122,25 +105,14 @@ def gap_ranges(args, wave, sampling_rate):
 
 
 def _load(args):
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import walk as W
     cfg = read_model_config(args.config)
     for flag, path in (("walk", args.walk), ("in", args.wav)):
-        if not os.path.exists(path):
-            raise ValueError("--%s %r: no such file" % (flag, path))
+        check_exists(flag, path)
     model = load_model(args.checkpoint, cfg)
     walk, meta = W.read_walk(args.walk, model.fc1.weight.device)
-    S = cfg["segment_length"]
-    if meta["segment_length"] != S or meta["latent_dim"] != cfg["latent_dim"]:
-        raise ValueError("--walk %r: fitted for segment_length %d and latent_dim %d, the model has %d and %d" % (
-            args.walk, meta["segment_length"], meta["latent_dim"], S, cfg["latent_dim"]))
-    try:
-        hop = W.check_hop(meta["hop"], args.hop, S)
-    except ValueError as e:
-        raise ValueError("--hop: %s (--walk %r)" % (e, args.walk))
-    wave = D.load_audio_mono(args.wav, cfg["sampling_rate"])
-    return cfg, model, walk, wave, hop
+    hop = check_fitted("walk", args.walk, meta, cfg, args.hop)
+    return cfg, model, walk, load_wav(args.wav, cfg["sampling_rate"]), hop
 
 
 def fill(args):

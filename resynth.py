@@ -27,14 +27,16 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, check_axes, check_exists, load_model, load_wav,  # noqa: E402
+                                             nonneg_int, number_flag, parse_axis_values, positive_int,
+                                             read_model_config, window_flag)
+
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Block-by-block streaming resynthesis of a wav on the GPU")
-    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    add_model_flags(p, hop_help="frame hop (default: segment_length)")
     p.add_argument("--in", dest="inp", required=True, help="input wav")
     p.add_argument("--out", required=True, help="output wav")
-    p.add_argument("--hop", default=None, help="frame hop (default: segment_length)")
     p.add_argument("--window", default="none", help="none | hann")
     p.add_argument("--block", default=None, help="samples per call (default: segment_length)")
     p.add_argument("--temperature", default="1", help="scale of eps")
@@ -46,26 +48,12 @@ def parse_args(argv=None):
     if (args.pca is None) != (args.pc_shift is None):
         raise ValueError("--%s: --pca and --pc-shift come together" % ("pca" if args.pca is None else "pc-shift"))
     if args.pc_shift is not None:
-        from latent_pca import parse_axis_values
         args.pc_shift = parse_axis_values(args.pc_shift, "pc-shift")
-    for flag in ("hop", "block", "seed"):
-        v = getattr(args, flag)
-        if v is None:
-            continue
-        try:
-            iv = int(v)
-        except ValueError:
-            iv = -1
-        if iv < 0 or (flag != "seed" and iv == 0):
-            raise ValueError("--%s %r: expected a %s integer" % (flag, v, "non-negative" if flag == "seed" else "positive"))
-        setattr(args, flag, iv)
-    try:
-        args.temperature = float(args.temperature)
-    except ValueError:
-        raise ValueError("--temperature %r: expected a number" % args.temperature)
-    if args.window not in ("none", "hann"):
-        raise ValueError("--window %r: expected none or hann" % args.window)
-    args.window = None if args.window == "none" else args.window
+    positive_int(args, "hop")
+    positive_int(args, "block")
+    nonneg_int(args, "seed")
+    number_flag(args, "temperature", float, lambda x: True, "a number")
+    window_flag(args)
     return args
 
 
@@ -104,10 +92,8 @@ def resynthesize(model, audio, hop, block, window=None, temperature=1.0, offset=
 
 def pc_offset(args, cfg, offset, device="cuda"):
     """--offset's values (or None) plus the shift --pca / --pc-shift ask for -> [latent_dim] fp32 numpy array."""
-    from latent_pca import check_axes
     from rawaudiovae_kelsey_amd.pca import read_pca
-    if not os.path.exists(args.pca):
-        raise ValueError("--pca %r: no such file" % args.pca)
+    check_exists("pca", args.pca)
     pca, meta = read_pca(args.pca, device)
     if meta["latent_dim"] != cfg["latent_dim"]:
         raise ValueError("--pca %r: fitted for latent_dim %d, the model has %d" % (args.pca, meta["latent_dim"],
@@ -118,13 +104,11 @@ def pc_offset(args, cfg, offset, device="cuda"):
 
 def main(argv=None):
     args = parse_args(argv)
-    from interpolate import load_model, read_model_config
     cfg = read_model_config(args.config)
     hop, block, _ = check_stream(args, cfg)
     offset = None
     if args.offset is not None:
-        if not os.path.exists(args.offset):
-            raise ValueError("--offset %r: no such file" % args.offset)
+        check_exists("offset", args.offset)
         offset = np.load(args.offset)
         if offset.ndim != 1 or offset.size != cfg["latent_dim"]:
             raise ValueError("--offset %r: expected %d values, got shape %s" % (args.offset, cfg["latent_dim"],
@@ -134,7 +118,7 @@ def main(argv=None):
     from rawaudiovae_kelsey_amd import data as D
     model = load_model(args.checkpoint, cfg)
     sr = cfg["sampling_rate"]
-    a = D.load_audio_mono(args.inp, sr)
+    a = load_wav(args.inp, sr)
     y = resynthesize(model, a, hop, block, args.window, args.temperature, offset, args.seed)
     D.write_wav(args.out, y, sr)
     print("wrote %s: %d samples (%.2f s at %d Hz), hop %d, block %d, window %s"

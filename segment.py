@@ -33,22 +33,10 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from som import _int_flag, load_wav  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, int_at_least, load_model, load_wav, model_config,  # noqa: E402
+                                             nonneg_real, positive_real)
 
 COMMANDS = ("find", "split")
-
-
-def _number(name, v, none_ok=False, positive=False):
-    """A finite float >= 0 (> 0 when `positive`) of flag --name; 'none' -> None where allowed."""
-    if none_ok and str(v).lower() == "none":
-        return None
-    try:
-        fv = float(v)
-    except (TypeError, ValueError):
-        fv = float("nan")
-    if not (0 <= fv < float("inf")) or (positive and fv == 0):
-        raise ValueError("--%s %r: expected a finite number %s" % (name, v, "> 0" if positive else ">= 0"))
-    return fv
 
 
 def parse_args(argv=None):
@@ -56,10 +44,8 @@ def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Latent structure analysis: novelty, boundaries and segments on the GPU")
     sub = p.add_subparsers(dest="command")
     s = sub.add_parser("find")
-    s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-    s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    add_model_flags(s)
     s.add_argument("--in", dest="wav", required=True, help="the wav to segment")
-    s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
     s.add_argument("--kernel", default="32", help="half-width of the kernel in frames (default 32)")
     s.add_argument("--sigma", default="0.5", help="taper width as a fraction of the kernel, or none (default 0.5)")
     s.add_argument("--gap", default="16", help="minimum gap between boundaries in frames (default 16)")
@@ -76,37 +62,32 @@ def parse_args(argv=None):
     if args.command is None:
         raise ValueError("expected a command: find or split")
     if args.command == "find":
-        args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
-        args.kernel = _int_flag("kernel", args.kernel, 1)
+        int_at_least(args, "hop", 1)
+        int_at_least(args, "kernel", 1)
         if args.kernel > R_MAX:
             raise ValueError("--kernel %d: at most %d frames" % (args.kernel, R_MAX))
-        args.gap = _int_flag("gap", args.gap, 0)
-        args.mean_radius = None if args.mean_radius is None else _int_flag("mean-radius", args.mean_radius, 0)
+        int_at_least(args, "gap", 0)
+        int_at_least(args, "mean-radius", 0)
         for name, v in (("gap", args.gap), ("mean-radius", args.mean_radius)):
             if v is not None and v > PEAK_MAX:
                 raise ValueError("--%s %d: at most %d frames" % (name, v, PEAK_MAX))
-        args.sigma = _number("sigma", args.sigma, none_ok=True, positive=True)
-        args.delta = _number("delta", args.delta)
-        args.similar = _number("similar", args.similar)
+        args.sigma = None if args.sigma.lower() == "none" else args.sigma
+        positive_real(args, "sigma")
+        nonneg_real(args, "delta")
+        nonneg_real(args, "similar")
     return args
 
 
 def run_find(args):
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd.codec import frame_layout
     from rawaudiovae_kelsey_amd.structure import LatentSegmenter
-    cfg = read_model_config(args.config)
-    S, sr = cfg["segment_length"], cfg["sampling_rate"]
-    try:
-        frame_layout(S, S, args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
+    cfg, step = model_config(args)
+    sr = cfg["sampling_rate"]
     wave = load_wav(args.wav, sr)
     seg = LatentSegmenter(load_model(args.checkpoint, cfg)).segment(
         wave, args.hop, args.kernel, args.sigma, args.gap, args.mean_radius, args.delta, args.similar, sr)
     frames, samples = seg.boundary_frames, seg.boundary_samples
     report = dict(segments=seg.F, frames=seg.T, samples=int(wave.size), sampling_rate=sr,
-                  hop=S if args.hop is None else args.hop, kernel=args.kernel, band=seg.band,
+                  hop=step, kernel=args.kernel, band=seg.band,
                   boundary_frames=[int(v) for v in frames], boundary_samples=[int(v) for v in samples],
                   boundary_seconds=[float(v) for v in seg.boundary_seconds],
                   sample_offsets=[int(v) for v in seg.sample_offsets], labels=[int(v) for v in seg.labels], form=seg.form)

@@ -23,27 +23,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-import interpolate as _interp  # noqa: E402  (read_model_config, load_model)
-
-
-def _int_flag(name, v, minimum):
-    try:
-        iv = int(v)
-    except (TypeError, ValueError):
-        iv = minimum - 1
-    if iv < minimum:
-        raise ValueError("--%s %r: expected an integer >= %d" % (name, v, minimum))
-    return iv
-
-
-def _float_flag(name, v):
-    try:
-        fv = float(v)
-    except (TypeError, ValueError):
-        fv = float("nan")
-    if not (fv > 0 and fv < float("inf")):
-        raise ValueError("--%s %r: expected a positive number" % (name, v))
-    return fv
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, int_at_least, load_model, load_wav, number_flag,  # noqa: E402
+                                             positive, read_model_config)
 
 
 def parse_grid(spec):
@@ -61,8 +42,7 @@ def parse_grid(spec):
 
 def parse_args(argv=None):
     p = argparse.ArgumentParser(description="Self-organising map of a corpus's latents (writes the tutorial's som/ files)")
-    p.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-    p.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
+    add_model_flags(p, hop_help="AudioDataset hop (default: TestDataset framing)")
     p.add_argument("--audio", required=True, help="folder of the corpus's .wav files")
     p.add_argument("--out", required=True, help="output folder for clusters.json, data-concatenated.json, som.npz")
     p.add_argument("--grid", default="8x8", help="ROWSxCOLS")
@@ -70,16 +50,13 @@ def parse_args(argv=None):
     p.add_argument("--sigma0", default=None, help="initial neighbourhood width (default max(rows, cols) / 2)")
     p.add_argument("--sigma1", default="0.5", help="final neighbourhood width")
     p.add_argument("--seed", default="0")
-    p.add_argument("--hop", default=None, help="AudioDataset hop (default: TestDataset framing)")
     p.add_argument("--max-rows", default="16384", help="frames per encoder chunk")
     args = p.parse_args(argv)
     args.rows, args.cols = parse_grid(args.grid)
-    args.epochs = _int_flag("epochs", args.epochs, 1)
-    args.seed = _int_flag("seed", args.seed, 0)
-    args.max_rows = _int_flag("max-rows", args.max_rows, 1)
-    args.hop = None if args.hop is None else _int_flag("hop", args.hop, 1)
-    args.sigma0 = None if args.sigma0 is None else _float_flag("sigma0", args.sigma0)
-    args.sigma1 = _float_flag("sigma1", args.sigma1)
+    for flag, minimum in (("epochs", 1), ("seed", 0), ("max-rows", 1), ("hop", 1)):
+        int_at_least(args, flag, minimum)
+    for flag in ("sigma0", "sigma1"):
+        number_flag(args, flag, float, positive, "a positive number")
     if not os.path.isdir(args.audio):
         raise ValueError("--audio %r: not a folder" % args.audio)
     return args
@@ -93,25 +70,13 @@ def corpus_files(audio_dir):
     return files
 
 
-def load_wav(path, sr):
-    """data.load_audio_mono with errors that name the file: unreadable or zero-length wavs raise ValueError."""
-    from rawaudiovae_kelsey_amd import data as D
-    try:
-        a = D.load_audio_mono(path, sr)
-    except Exception as e:   # scipy raises ValueError / OSError / struct.error on malformed files
-        raise ValueError("%s: unreadable wav (%s)" % (path, e))
-    if a.size == 0:
-        raise ValueError("%s: zero-length wav" % path)
-    return a
-
-
 def main(argv=None):
     args = parse_args(argv)
-    cfg = _interp.read_model_config(args.config)
+    cfg = read_model_config(args.config)
     files = corpus_files(args.audio)
     waves = [load_wav(os.path.join(args.audio, f), cfg["sampling_rate"]) for f in files]
     from rawaudiovae_kelsey_amd.som import LatentMap, LatentSOM, write_som
-    model = _interp.load_model(args.checkpoint, cfg)
+    model = load_model(args.checkpoint, cfg)
     desc = LatentMap(model, hop=args.hop, max_rows=args.max_rows).describe(waves)
     som = LatentSOM(args.rows, args.cols, sigma0=args.sigma0, sigma1=args.sigma1, epochs=args.epochs,
                     seed=args.seed).fit(desc)

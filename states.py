@@ -36,20 +36,11 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from latent_pca import _positive  # noqa: E402
-from som import load_wav  # noqa: E402
+from rawaudiovae_kelsey_amd.frontend import (add_model_flags, check_exists, check_fitted, data_files, encode_wav,  # noqa: E402
+                                             load_wav, nonneg_int, nonneg_real, open_model, positive_int, positive_real)
 
 COMMANDS = ("fit", "label", "score")
-
-
-def _real(args, flag, positive):
-    try:
-        v = float(getattr(args, flag))
-    except (TypeError, ValueError):
-        v = float("nan")
-    if not (0 <= v < float("inf")) or (positive and v == 0):
-        raise ValueError("--%s %r: expected a finite number %s" % (flag, getattr(args, flag), "> 0" if positive else ">= 0"))
-    setattr(args, flag, v)
+HOP_PHRASES = ("the states were", "a transition is one frame at that hop")
 
 
 def parse_args(argv=None):
@@ -58,9 +49,7 @@ def parse_args(argv=None):
     sub = p.add_subparsers(dest="command")
     for name in COMMANDS:
         s = sub.add_parser(name)
-        s.add_argument("--config", default="./default.ini", help="the training .ini (model shape, sampling_rate)")
-        s.add_argument("--checkpoint", required=True, help="checkpoint dict (ckpt_NNNNN) or whole-module pickle (.pt)")
-        s.add_argument("--hop", default=None, help="frame hop (default: non-overlapping frames)")
+        add_model_flags(s)
         if name == "fit":
             s.add_argument("--data", required=True, help="a wav, or a folder whose *.wav are encoded")
             s.add_argument("--pca", default=None, help="the .npz of latent_pca.py fit or generate.py fit")
@@ -79,63 +68,42 @@ def parse_args(argv=None):
     args = p.parse_args(argv)
     if args.command is None:
         raise ValueError("expected a command: fit, label or score")
-    _positive(args, "hop")
+    positive_int(args, "hop")
     if args.command == "fit":
         for flag, hi in (("states", S_MAX), ("keep", K_MAX)):
-            _positive(args, flag)
-            if getattr(args, flag) > hi:
+            if positive_int(args, flag) > hi:
                 raise ValueError("--%s %d: at most %d" % (flag, getattr(args, flag), hi))
-        _positive(args, "iters")
-        _positive(args, "seed", allow_zero=True)
-        _real(args, "tol", False)
-        _real(args, "floor", True)
+        positive_int(args, "iters")
+        nonneg_int(args, "seed")
+        nonneg_real(args, "tol")
+        positive_real(args, "floor")
     return args
-
-
-def _model(args):
-    from interpolate import load_model, read_model_config
-    from rawaudiovae_kelsey_amd.codec import frame_layout
-    cfg = read_model_config(args.config)
-    try:
-        frame_layout(cfg["segment_length"], cfg["segment_length"], args.hop)
-    except ValueError as e:
-        raise ValueError("--hop %s: %s" % (args.hop, e))
-    return cfg, load_model(args.checkpoint, cfg)
 
 
 def read_axes(path, cfg, hop, device):
     """The fitted axes of --pca: a latent-walk file or a latent-PCA file, at this model's shape and this hop."""
     from rawaudiovae_kelsey_amd import pca as P
-    from rawaudiovae_kelsey_amd import states as ST
     from rawaudiovae_kelsey_amd import walk as W
-    if not os.path.exists(path):
-        raise ValueError("--pca %r: no such file" % path)
+    check_exists("pca", path)
     with np.load(path) as z:
         is_walk = "dynamics" in z.files
     try:
         axes, meta = (W.read_walk if is_walk else P.read_pca)(path, device)
     except ValueError as e:
         raise ValueError("--pca: %s" % e)
-    if meta["segment_length"] != cfg["segment_length"] or meta["latent_dim"] != cfg["latent_dim"]:
-        raise ValueError("--pca %r: fitted for segment_length %d and latent_dim %d, the model has %d and %d" % (
-            path, meta["segment_length"], meta["latent_dim"], cfg["segment_length"], cfg["latent_dim"]))
-    try:
-        ST.check_hop(meta["hop"], hop, meta["segment_length"])
-    except ValueError as e:
-        raise ValueError("--hop: %s (--pca %r)" % (str(e).replace("the states were", "the axes were"), path))
+    check_fitted("pca", path, meta, cfg, hop, "the axes were", HOP_PHRASES[1])
     return axes
 
 
 def fit(args):
-    from evaluate import data_files
-    from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import states as ST
-    cfg, model = _model(args)
+    from rawaudiovae_kelsey_amd.corpus import encode_corpus
+    cfg, model, _ = open_model(args)
     files = data_files(args.data)
     axes = None if args.pca is None else read_axes(args.pca, cfg, args.hop, model.fc1.weight.device)
-    waves = [D.load_audio_mono(f, cfg["sampling_rate"]) for f in files]
+    waves = [load_wav(f, cfg["sampling_rate"]) for f in files]
     try:
-        x, starts = ST.encode_corpus(model, waves, args.hop)
+        x, starts = encode_corpus(model, waves, args.hop)
         st = ST.LatentStates(args.states, args.keep, args.floor)
         st.fit(x, starts, axes, args.iters, args.tol, args.seed)
     except ValueError as e:
@@ -162,29 +130,15 @@ def _encode(args):
     """(states, cfg, the wav, its mu [T, L], row_start, the frame step in samples)"""
     from rawaudiovae_kelsey_amd import states as ST
     from rawaudiovae_kelsey_amd.codec import FrameCodec
-    if not os.path.exists(args.states):
-        raise ValueError("--states %r: no such file" % args.states)
-    cfg, model = _model(args)
+    check_exists("states", args.states)
+    cfg, model, _ = open_model(args)
     try:
         st, meta = ST.read_states(args.states, model.fc1.weight.device)
     except ValueError as e:
         raise ValueError("--states: %s" % e)
-    S = cfg["segment_length"]
-    if meta["segment_length"] != S or meta["latent_dim"] != cfg["latent_dim"]:
-        raise ValueError("--states %r: fitted for segment_length %d and latent_dim %d, the model has %d and %d" % (
-            args.states, meta["segment_length"], meta["latent_dim"], S, cfg["latent_dim"]))
-    try:
-        step = ST.check_hop(meta["hop"], args.hop, S)
-    except ValueError as e:
-        raise ValueError("--hop: %s (--states %r)" % (e, args.states))
+    step = check_fitted("states", args.states, meta, cfg, args.hop, *HOP_PHRASES)
     wave = load_wav(args.wav, cfg["sampling_rate"])
-    codec = FrameCodec(model)
-    w = codec.wave(wave)
-    try:
-        padded, T = codec.pad(w, w.numel(), args.hop)
-    except ValueError as e:
-        raise ValueError("--in %r: %s" % (args.wav, e))
-    mu = codec.encode(padded, T, args.hop)[0]
+    _, mu, _, T = encode_wav(FrameCodec(model), wave, args.hop, "in", args.wav)
     return st, cfg, wave, mu, np.asarray([0, T], dtype=np.int64), step
 
 

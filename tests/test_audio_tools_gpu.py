@@ -1,7 +1,7 @@
 """The host layer the audio tools share, on the GPU: FrameCodec (rawaudiovae_kelsey_amd/codec.py) against the model's
 own exact-fp32 inference, chunked and into a slice, and the graph capture / replay that StreamingVAE and StreamingMosaic
-share (stream.GraphReplay) against the eager calls of a twin.  Everything bit for bit: the same kernels, every row on
-its own."""
+share (stream.GraphReplay) against the eager calls of a twin, and corpus.encode_corpus against the codec file by file.
+Everything bit for bit: the same kernels, every row on its own."""
 import numpy as np
 import pytest
 
@@ -107,3 +107,49 @@ def test_streaming_mosaic_replay_and_drain_replay_equal_the_eager_twin_and_guard
     _raises(graph.replay, REPLACED)
     _raises(graph.drain_replay, REPLACED)
     torch.cuda.synchronize()
+
+
+@pytest.mark.parametrize("hop, starts", [(None, [0, 1, 3, 5]), (S // 4, [0, 1, 6, 8])])
+def test_encode_corpus_is_the_files_encodings_joined_and_the_three_fits_start_from_it(model, hop, starts):
+    """60, 120 and 70 samples: 1, 5 and 2 frames at hop S / 4 (1, 2 and 2 without a hop), every tail zero-padded; with
+    max_rows = 4 the 5 frames cross a chunk edge."""
+    from rawaudiovae_kelsey_amd import pca as P
+    from rawaudiovae_kelsey_amd import states as ST
+    from rawaudiovae_kelsey_amd import walk as W
+    from rawaudiovae_kelsey_amd.codec import FrameCodec
+    from rawaudiovae_kelsey_amd.corpus import encode_corpus
+    waves = [0.5 * _randn(n, seed=10 + i).cpu().numpy() for i, n in enumerate((60, 120, 70))]
+    codec, want = FrameCodec(model, max_rows=4), []
+    for w in waves:
+        w = codec.wave(w)
+        padded, n_frames = codec.pad(w, w.numel(), hop)
+        want.append(codec.encode(padded, n_frames, hop)[0])
+    mu, row_start = encode_corpus(model, waves, hop, max_rows=4)
+    assert row_start.dtype == np.int64 and row_start.tolist() == starts
+    assert mu.shape == (starts[-1], L) and torch.equal(mu, torch.cat(want, 0))
+    one, rs = encode_corpus(model, iter(waves[:1]), hop, max_rows=4)
+    assert rs.tolist() == [0, 1] and torch.equal(one, want[0])
+
+    pca, by_hand = P.fit_corpus(model, waves, hop, 3, max_rows=4), P.LatentPCA(3).fit(mu)
+    for name in ("mean_", "components_", "explained_variance_", "all_variances_"):
+        assert torch.equal(getattr(pca, name), getattr(by_hand, name)), name
+    walk, by_hand = W.fit_corpus(model, waves, hop, 2, max_rows=4), W.LatentWalk(2).fit(mu, row_start)
+    assert walk.row_start_.tolist() == starts and (walk.n_frames_, walk.n_files_) == (starts[-1], 3)
+    for name in ("mean_", "components_", "explained_variance_", "dyn_", "P_", "R_", "lagcov_"):
+        assert torch.equal(getattr(walk, name), getattr(by_hand, name)), name
+    states, by_hand = ST.fit_corpus(model, waves, hop, 2, 2, iters=3, max_rows=4), ST.LatentStates(2, 2)
+    history = by_hand.fit(mu, row_start, None, 3)
+    assert states.row_start_.tolist() == starts and states.ll_history_ == history
+    for name in ("theta_", "mean_", "P_"):
+        assert torch.equal(getattr(states, name), getattr(by_hand, name)), name
+
+    for fit in (encode_corpus, P.fit_corpus, W.fit_corpus, ST.fit_corpus):
+        with pytest.raises(ValueError) as e:
+            fit(model, [], hop)
+        assert str(e.value) == "fit_corpus needs at least one waveform"
+    with pytest.raises(ValueError) as e:
+        W.fit_corpus(model, waves[:1], hop)
+    assert str(e.value) == "fit_corpus needs at least 2 frames, the waveforms make 1"
+    with pytest.raises(ValueError) as e:
+        encode_corpus(model, [waves[0], waves[1][:S // 2]], S // 4)
+    assert str(e.value) == "waveform 1: 32 samples make no frame of 64 samples at hop 16"

@@ -377,7 +377,7 @@ def test_evaluate_py_end_to_end(tmp_path):
     sys.path.insert(0, REPO)
     import evaluate as cli
     import test_train_entry as TE
-    from interpolate import load_model, read_model_config
+    from rawaudiovae_kelsey_amd.frontend import load_model, read_model_config
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd.evaluate import Evaluator
     from rawvae.model import VAE

@@ -12,7 +12,7 @@ import pytest
 from conftest import GOLDEN, REPO
 
 import interpolate as cli  # noqa: E402  (the entry point at the repository root)
-from rawaudiovae_kelsey_amd import _lib  # noqa: E402
+from rawaudiovae_kelsey_amd import _lib, frontend  # noqa: E402
 from rawaudiovae_kelsey_amd import interpolate as I  # noqa: E402
 
 
@@ -119,11 +119,11 @@ def test_cli_flags_are_validated():
         with pytest.raises(ValueError, match=re.escape(name)):
             cli.parse_args(base + flags)
     with pytest.raises(ValueError, match="--config"):
-        cli.read_model_config(os.path.join(REPO, "no_such.ini"))
+        frontend.read_model_config(os.path.join(REPO, "no_such.ini"))
 
 
 def test_model_shape_comes_from_the_ini():
-    cfg = cli.read_model_config(os.path.join(REPO, "default.ini"))
+    cfg = frontend.read_model_config(os.path.join(REPO, "default.ini"))
     assert cfg == dict(sampling_rate=44100, segment_length=1024, n_units=2048, latent_dim=256)
 
 

@@ -283,8 +283,8 @@ def test_cli_writes_the_apis_samples(tmp_path, capsys):
     from rawvae.model import VAE
     from rawaudiovae_kelsey_amd import data as D
     sys.path.insert(0, REPO)
-    import interpolate as interp_cli
     import mosaic as cli
+    from rawaudiovae_kelsey_amd import frontend as interp_cli
     S_, H, L, sr = 64, 128, 8, 8000
     torch.manual_seed(3)
     torch.save({"epoch": 1, "state_dict": VAE(S_, H, L).state_dict(), "optimizer": {}}, tmp_path / "ckpt_00001")
@@ -305,8 +305,8 @@ def test_cli_writes_the_apis_samples(tmp_path, capsys):
     cfg = interp_cli.read_model_config(str(tmp_path / "tiny.ini"))
     index = _M().LatentIndex(interp_cli.load_model(str(tmp_path / "ckpt_00001"), cfg), hop=16)
     for f in sorted(os.listdir(corpus)):
-        index.add(cli.load_wav(str(corpus / f), sr), f)
-    target = cli.load_wav(str(tmp_path / "t.wav"), sr)
+        index.add(interp_cli.load_wav(str(corpus / f), sr), f)
+    target = interp_cli.load_wav(str(tmp_path / "t.wav"), sr)
     ref, _, _, fits = index.mosaic(target, k=3, window="hann", fit=16, gain_max=4.0, return_matches=True, return_fit=True)
     assert np.array_equal(y, ref.cpu().numpy())
     D.write_wav(tmp_path / "ref.wav", ref.cpu().numpy(), sr)

@@ -133,14 +133,15 @@ def test_flag_errors_name_the_flag():
     sys.path.insert(0, REPO)
     import latent_pca as cli
     import resynth
-    assert cli.parse_axis_values("1:2,3:-0.5", "shift") == {0: 2.0, 2: -0.5}
+    from rawaudiovae_kelsey_amd import frontend
+    assert frontend.parse_axis_values("1:2,3:-0.5", "shift") == {0: 2.0, 2: -0.5}
     for text, what in (("2", "expected J:VALUE"), ("a:1", "expected J:VALUE"), ("1:x", "expected J:VALUE"),
                        ("0:1", "numbered from 1"), ("1:nan", "must be finite"), ("1:inf", "must be finite"),
                        ("2:1,2:3", "given twice"), ("", "expected J:VALUE")):
         with pytest.raises(ValueError, match="--shift .*" + what):
-            cli.parse_axis_values(text, "shift")
+            frontend.parse_axis_values(text, "shift")
     with pytest.raises(ValueError, match="--gain: axis 9: the PCA file holds 8 axes"):
-        cli.check_axes({8: 1.0}, 8, "gain")
+        frontend.check_axes({8: 1.0}, 8, "gain")
     base = ["--checkpoint", "c", "--out", "o"]
     edit = ["edit"] + base + ["--pca", "p.npz", "--in", "i.wav"]
     for argv, what in ((["fit"] + base + ["--data", "d", "--hop", "0"], "--hop '0'"),

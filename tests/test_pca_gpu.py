@@ -356,7 +356,7 @@ def test_resynth_py_pc_shift(tmp_path):
     sys.path.insert(0, REPO)
     import latent_pca as cli
     import resynth
-    from interpolate import read_model_config
+    from rawaudiovae_kelsey_amd.frontend import read_model_config
     from rawaudiovae_kelsey_amd import data as D
     from rawaudiovae_kelsey_amd import pca as P
     ini, ck = _files(tmp_path)
@@ -378,7 +378,7 @@ def test_resynth_py_pc_shift(tmp_path):
     assert np.array_equal(resynth.pc_offset(args, cfg, off), off + want)
     np.save(tmp_path / "off.npy", off)
     audio = D.load_audio_mono(tmp_path / "audio" / "0.wav", SR)
-    from interpolate import load_model
+    from rawaudiovae_kelsey_amd.frontend import load_model
     ref = resynth.resynthesize(load_model(str(ck), cfg), audio, 16, S, "hann", 1.0, off + want, 5)
     got = resynth.main(base + ["--out", str(tmp_path / "c.wav"), "--offset", str(tmp_path / "off.npy"), "--pca", str(npz),
                                "--pc-shift", "1:2"])

@@ -16,7 +16,7 @@ from conftest import REPO
 import interpolate as icli  # noqa: E402  (entry points at the repository root)
 import som as scli  # noqa: E402
 import som_oracle as O  # noqa: E402
-from rawaudiovae_kelsey_amd import _lib  # noqa: E402
+from rawaudiovae_kelsey_amd import _lib, frontend  # noqa: E402
 from rawaudiovae_kelsey_amd import som as S  # noqa: E402
 
 torch = pytest.importorskip("torch")
@@ -148,8 +148,8 @@ def test_som_cli_names_bad_wavs(tmp_path):
     assert scli.corpus_files(str(tmp_path)) == ["empty.wav", "junk.wav", "ok.wav"]
     for name in ("empty.wav", "junk.wav"):
         with pytest.raises(ValueError, match=re.escape(name)):
-            scli.load_wav(str(tmp_path / name), 8000)
-    assert scli.load_wav(str(tmp_path / "ok.wav"), 8000).size == 10
+            frontend.load_wav(str(tmp_path / name), 8000)
+    assert frontend.load_wav(str(tmp_path / "ok.wav"), 8000).size == 10
 
 
 def test_interpolate_cluster_flags_are_validated(tmp_path):

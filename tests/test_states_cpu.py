@@ -192,6 +192,7 @@ def test_every_op_names_the_offending_field_before_it_launches():
 
 def test_latent_states_checks_its_arguments():
     from rawaudiovae_kelsey_amd import states as ST
+    from rawaudiovae_kelsey_amd.corpus import check_row_start
     for bad in (0, 65, 2.0, True, None):
         with pytest.raises(ValueError, match="n_states=.* must be an integer in \\[1, 64\\]"):
             ST.LatentStates(bad, 4)
@@ -210,8 +211,8 @@ def test_latent_states_checks_its_arguments():
     for rs, text in (([0, 5, 3, 9], "must not descend: file 1 is \\[5, 3\\)"), ([1, 9], "must run from 0 to T=9"),
                      ([0, 8], "must run from 0 to T=9"), ([0.0, 9.0], "1-D integer sequence"), ([9], "1-D integer sequence")):
         with pytest.raises(ValueError, match=text):
-            ST.check_sequences(rs, 9)
-    assert ST.check_sequences([0, 0, 4, 4, 9], 9).tolist() == [0, 0, 4, 4, 9]       # empty files are legal
+            check_row_start(rs, 9, empty_files=True)
+    assert check_row_start([0, 0, 4, 4, 9], 9, empty_files=True).tolist() == [0, 0, 4, 4, 9]       # empty files are legal
     with pytest.raises(TypeError, match="expected a fitted LatentPCA, a fitted LatentWalk or a \\(centre, P\\) pair"):
         ST.whitening("pca.npz", 2)
     with pytest.raises(ValueError, match="n_components=3: the basis holds P \\(2, 8\\)"):
@@ -230,6 +231,8 @@ def _fitted(S=3, k=2, L=5):
 
 
 def test_npz_round_trip_and_the_hop_check(tmp_path):
+    import states as cli
+    from rawaudiovae_kelsey_amd import corpus as C_
     from rawaudiovae_kelsey_amd import states as ST
     st, th = _fitted()
     p = O.unpack(th, 3, 2)
@@ -245,11 +248,12 @@ def test_npz_round_trip_and_the_hop_check(tmp_path):
         assert a.dtype == torch.float64 and torch.equal(a, b)
     ST.write_states(path, st, 64)
     assert ST.read_states(path, "cpu")[1]["hop"] is None
-    assert ST.check_hop(16, 16, 64) == 16 and ST.check_hop(None, None, 64) == 64 and ST.check_hop(None, 64, 64) == 64
+    check_hop = lambda *a: C_.check_hop(*a, *cli.HOP_PHRASES)     # noqa: E731
+    assert check_hop(16, 16, 64) == 16 and check_hop(None, None, 64) == 64 and check_hop(None, 64, 64) == 64
     with pytest.raises(ValueError, match="hop 32: the states were fitted at hop 16"):
-        ST.check_hop(16, 32, 64)
+        check_hop(16, 32, 64)
     with pytest.raises(ValueError, match="hop 64: the states were fitted at hop 16"):
-        ST.check_hop(16, None, 64)
+        check_hop(16, None, 64)
     with np.load(path) as z:
         arrays = {n: z[n] for n in z.files}
     np.savez(path, **{n: v for n, v in arrays.items() if n != "whiten"})

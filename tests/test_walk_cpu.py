@@ -80,6 +80,7 @@ def test_npz_round_trip_and_a_refused_mismatch(tmp_path, diagonal):
 
 def test_argument_checks_without_a_device():
     from rawaudiovae_kelsey_amd import walk as W
+    from rawaudiovae_kelsey_amd.corpus import check_hop
     assert W.check_row_start([0, 3, 4, 9], 9).dtype == np.int64
     assert np.array_equal(W.check_row_start(torch.tensor([0, 9]), 9), [0, 9])
     for rs, msg in (([0, 3, 3, 9], "ascending: file 1 is \\[3, 3\\)"), ([1, 9], "from 0 to T=9"), ([0, 8], "from 0 to T=9"),
@@ -103,11 +104,11 @@ def test_argument_checks_without_a_device():
         W.StreamingWalk(None, object(), 1, 64)
     with pytest.raises(RuntimeError, match="has not been fitted"):
         W.StreamingWalk(None, W.LatentWalk(2), 1, 64)
-    assert W.check_hop(16, 16, 64) == 16 and W.check_hop(None, 64, 64) == 64 and W.check_hop(None, None, 64) == 64
+    assert check_hop(16, 16, 64) == 16 and check_hop(None, 64, 64) == 64 and check_hop(None, None, 64) == 64
     with pytest.raises(ValueError, match="hop 32: the walk was fitted at hop 16"):
-        W.check_hop(16, 32, 64)
+        check_hop(16, 32, 64)
     with pytest.raises(ValueError, match="hop 64: the walk was fitted at hop 16"):
-        W.check_hop(16, None, 64)
+        check_hop(16, None, 64)
 
 
 def test_op_codes_and_field_roles_follow_the_header():
@@ -153,6 +154,8 @@ def test_generate_py_parser_errors_and_hop_mismatch(tmp_path):
     W.write_walk(tmp_path / "w.npz", walk, 64, 16)
     _, meta = W.read_walk(tmp_path / "w.npz", "cpu")
     args = cli.parse_args(run + ["--seconds", "1", "--hop", "32"])
+    from rawaudiovae_kelsey_amd.frontend import check_fitted
+    cfg = dict(segment_length=64, latent_dim=meta["latent_dim"])
     with pytest.raises(ValueError, match="--hop: hop 32: the walk was fitted at hop 16"):
-        cli.check_hop(args, meta)
-    assert cli.check_hop(cli.parse_args(run + ["--seconds", "1", "--hop", "16"]), meta) == 16
+        check_fitted("walk", args.walk, meta, cfg, args.hop)
+    assert check_fitted("walk", args.walk, meta, cfg, cli.parse_args(run + ["--seconds", "1", "--hop", "16"]).hop) == 16
