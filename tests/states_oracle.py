@@ -398,12 +398,12 @@ def gated_distances(got, S, outlier=False):
 
 
 @functools.lru_cache(maxsize=None)
-def mstep_case(S, k, T=300, lengths=None):
-    """(x [T, k + 6] fp32 with one unobserved frame, c, P, gamma, xi, row_start, theta with zeros in pi and A) for the
-    M-step.  gamma's rows are random laws that favour the early states by up to 1e4, so the late ones hold less than
-    one frame and die; xi is random with zero columns (log A = -inf) and the last state's row all zero (it keeps its old
-    row of A).  Read-only."""
-    L = k + 6
+def mstep_case(S, k, T=300, lengths=None, L=None):
+    """(x [T, L] fp32 with one unobserved frame, L = k + 6 unless given, c, P, gamma, xi, row_start, theta with zeros in
+    pi and A) for the M-step.  gamma's rows are random laws that favour the early states by up to 1e4, so the late ones
+    hold less than one frame and die; xi is random with zero columns (log A = -inf) and the last state's row all zero (it
+    keeps its old row of A).  Read-only."""
+    L = k + 6 if L is None else L
     c, P = basis(k, L)
     x = latents(T, L)
     if T > 2:

@@ -29,7 +29,7 @@ import states_oracle as O  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 STATES = (1, 2, 16, 17, 63, 64)
-EMIT_SHAPES = ((1, 1), (3, 7), (64, 64), (64, 70))
+EMIT_SHAPES = ((1, 1), (3, 7), (64, 64), (64, 70), (64, 512), (1, 257))
 EMIT_FRAMES = (1, 2, 255, 256, 257, O.EMIT_FRAMES + 1)
 VITERBI_LENGTHS = (5, 0, 1, 257, 2, 3, 0)      # the sequence of 3 frames holds a frame every state is -inf at
 
@@ -141,10 +141,10 @@ def test_viterbi_path_and_score_are_exact(S):
     assert S == 1 or len(set(want_path[rs[3]:rs[4]].tolist())) > 1
 
 
-def _mstep(S, k, T, floor=1e-3, lengths=None):
+def _mstep(S, k, T, floor=1e-3, lengths=None, L=None):
     """RV_HMM_MSTEP at O.mstep_case between guards -> (theta', info, moments) as numpy arrays and the oracle's result"""
     from rawaudiovae_kelsey_amd import states as ST
-    x, c, P, gamma, xi, rs, th = O.mstep_case(S, k, T, lengths)
+    x, c, P, gamma, xi, rs, th = O.mstep_case(S, k, T, lengths, L)
     n_theta = O.layout(S, k)["doubles"]
     gt, new = _out((n_theta + S * (1 + 2 * k),))
     gi, info = _out((S,), torch.int32, G.INT_FILL)
@@ -159,8 +159,8 @@ def _mstep(S, k, T, floor=1e-3, lengths=None):
     return _np(new), _np(info), _np(mom), O.mstep(x, c, P, gamma, xi, rs, th, S, k, floor), th
 
 
-def _check_mstep(S, k, T, floor=1e-3, lengths=None):
-    new, info, mom, res, old = _mstep(S, k, T, floor, lengths)
+def _check_mstep(S, k, T, floor=1e-3, lengths=None, L=None):
+    new, info, mom, res, old = _mstep(S, k, T, floor, lengths, L)
     what = "S %d k %d T %d" % (S, k, T)
     _same(mom[:, 0], res["N"], "N " + what)
     _same(mom[:, 1:1 + k], res["M1"], "M1 " + what)
@@ -191,6 +191,11 @@ def test_mstep_moments_at_the_tile_edges(S, k):
     assert dead.any() and not dead.all()
     _same(got["A"][S - 1], was["A"][S - 1], "the row of A without mass")
     assert np.isneginf(got["logA"]).any() and np.isneginf(got["logpi"]).sum() == 0
+
+
+def test_mstep_moments_of_the_widest_latents():
+    got, was, res, dead = _check_mstep(17, 33, 300, L=512)
+    assert dead.any() and not dead.all()
 
 
 def test_mstep_takes_the_variance_floor():
