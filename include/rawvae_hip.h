@@ -987,6 +987,71 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_HMM_VITERBI 46
 #define RV_HMM_WORKSPACE 47
 #define RV_HMM_MOMENTS 1
+/* Latent attributes (csrc/attr.hip, rawaudiovae_kelsey_amd/attributes.py): audio descriptors of every
+ * frame of a waveform, and the linear regression of per-frame targets (those descriptors or the caller's own labels) on the
+ * whitened latents of a corpus, whose coefficients turn "this descriptor by that much" into a latent offset.  The family's
+ * conventions: no op syncs or reads a device pointer on the host, each may run under capture, and each returns an RV_ERR_*
+ * whose message names the field before anything is launched: T, S, hop, k, N, L, stride, lam, dynamic_range, ldo, frames
+ * that overrun n_out, a window without twiddles or with an S that is no power of two in [32, 4096], a null frames / result /
+ * q / centre / basis / moment / info / ws, ws_bytes too small, ws not 256-byte aligned.  No atomics, no polling; every output
+ * element is written by exactly one thread.  No new member and no new role of the descriptor: every field is an existing
+ * member under its existing name and type.  The op code 48 is unassigned like 38, 39 and 42: rv_mosaic answers it as an
+ * unknown op.
+ * RV_ATTR_DESCRIBE: frames, n_out (a padded waveform [n_out]: frame t = frames[t hop, t hop + S), (T - 1) hop + S <= n_out),
+ *   T (1 <= T < 2^31), S, hop (>= 1), window [S] fp32 or NULL, twiddles (RV_EVAL_FRAMES' table, required with a window),
+ *   dynamic_range = R in dB, 0 < R <= 120 -> result = desc [T, ldo] fp64; only columns 0..4 (0..2 without a window) of rows
+ *   0..T-1 are written.  With a window S is a power of two in [32, 4096] and ldo >= 5; without one any S >= 1 and ldo >= 3.
+ *     0  level (dB) = 10 log10(e), e = (1/S) sum_n x[n]^2: the squares and the sum in fp64 in the order of RV_EVAL_FRAMES'
+ *        column 1, one division; silence gives -inf
+ *     1  zcr = #{1 <= n < S : (x[n] < 0) != (x[n-1] < 0)} / (S - 1): the count an exact integer, one division; 0 at S = 1; a
+ *        NaN compares as not negative
+ *     2  crest (dB) = 10 log10(p^2 / e), p = max_n |x[n]| (fp32, exact), p^2 one fp64 product; e == 0 gives NaN
+ *     3  centroid (cycles/sample) = (sum_k k Pa[k]) / (sum_k Pa[k]) / S over k = 0 .. S/2, the terms (double)k * (double)Pa[k];
+ *        a zero denominator gives NaN
+ *     4  flatness (dB) over k = 1 .. S/2: 10 log10(G / A), A = (sum_k Pa[k]) / (S/2), G = exp((sum_k log((double)(Pa[k] + fl)))
+ *        / (S/2)), fl = max_{k >= 0} Pa[k] * fl32(10^(-R/10)) the fp32 product of RV_EVAL_FRAMES, the add Pa[k] + fl rounded
+ *        in fp32; A == 0 gives NaN
+ *   Pa = the power spectrum of a[n] = fl32(window[n] x[n]) by the transform of "Evaluation" (csrc/spectrum.h, which both ops
+ *   call): fp32, every product and sum rounded on its own.  Every sum over n or k is in fp64: thread u of the frame's 256
+ *   takes the terms u, u + 256, .. in ascending order from +0, then the xor butterfly over each wave's lanes and the four
+ *   waves' sums left to right.  Every logarithm is the fp64 library one; each dB is one log10 and one product by 10.
+ *   A sample that is NaN or Inf makes the columns it enters non-finite in that row and touches no other row; a power that is
+ *   not finite makes columns 3 and 4 NaN.  A row's values depend on that row's data, S, R, the window and the table only --
+ *   not on T, hop, ldo or the launch.  One workgroup of 256 threads per frame, one launch; LDS: 2 (S/2) + 1 floats and the
+ *   reductions' scratch.
+ * RV_ATTR_FIT: q = x [T, L] fp32 with a row pitch of stride >= L elements, centre = c [L] and basis = P [k, L] fp64 (rows
+ *   v_j / sqrt(lambda_j) of a fitted PCA), moment = the targets D [T, N] fp64, packed, lam = the ridge (finite, >= 0), ws,
+ *   ws_bytes, T, L, k, N with 1 <= k <= 64, k <= L <= 512, 1 <= N <= 64, 2 <= T < 2^31 -> result (fp64) and info [2] int32.
+ *   A frame is OBSERVED iff its x row and its D row are finite throughout.  y_t = P (x_t - c) by the chain of "Latent states"
+ *   (csrc/sequence.h).  Five launches on one stream:
+ *   1. y, D and the observed flags to ws, a workgroup per 64 frames; an unobserved frame's y and D rows are written as +0.
+ *   2. n = the observed frames and the column sums of y and D over them by the blocked column sum of RV_EVAL_DIMS (blocks of
+ *      256 frames in ascending t from +0, then the blocks in ascending order from +0); then ybar = sum / n, dbar = sum / n,
+ *      one division each (a launch of its own, one workgroup).
+ *   3. Three 64 x 64 tiles per range of 4096 frames: Yc^T Yc, Dc^T Yc and Dc^T Dc of the centred operands u - ubar, with
+ *      an unobserved row staged as zeros on both sides: v_mfma_f64_16x16x4_f64 over the frames t0, t0 + 4, .. in ascending
+ *      order from +0, 32 frames staged in LDS at a time, the partial tiles to ws -- the tile of "Latent PCA" in a third
+ *      operand form (csrc/moment.h).
+ *   4. ONE workgroup closes.  Cyy [k, k], Cdy [N, k], Cdd [N, N] = (the ranges' partials in ascending order from +0) / (n - 1).
+ *      G = Cyy + lam I (one add on the diagonal).  G = R R^T by the left-looking Cholesky, column j = 0 .. k-1:
+ *      s_i = chain fma(-R[i, p], R[j, p], .) from G[i, j] in ascending p < j, for i >= j; R[j, j] = sqrt(s_j), R[i, j] =
+ *      s_i / R[j, j].  The pivot s_j counts as positive iff s_j > 2^-40 G[j, j]: an axis that repeats another leaves a pivot
+ *      of rounding errors of either sign, which is not one.  For every target a, g = Cdy[a, .]: R z = g with z_j = s_j / R[j, j] and then s_i = fma(-R[i, j], z_j,
+ *      s_i) for i > j, in ascending j from s = g; R^T beta = z likewise in descending j.  r2_a = 1 - (Cdd[a, a] - 2 (beta . g)
+ *      + beta^T (Cyy beta)) / Cdd[a, a] with (Cyy beta)_i = chain fma(Cyy[i, j], beta_j, .) in ascending j from +0 and the two
+ *      dot products summed over the axes by the xor butterfly of one wave (absent axes add +0).  A target with Cdd[a, a] == 0
+ *      gets beta = 0 and r2 = 0.
+ *   result = [ n | ybar (k) | dbar (N) | Cdd (N N) | B (N k), row a = beta_a | r2 (N) ], 1 + k + 2 N + N N + N k doubles.
+ *   info = { status, n }: 0 = ok, 1 = fewer than k + 2 observed frames, 2 = a pivot s_j of the Cholesky was not positive (the rule above).
+ *   With a non-zero status B and r2 are written as zeros (n, the means and Cdd by the rules above all the same; fewer
+ *   than two observed frames leave them not finite).  The result is bit-identical from run to run: it depends on the
+ *   data and the shapes only.
+ * RV_ATTR_WORKSPACE: the bytes of ws for (T, k, N) in d->ws_bytes: [ y (T k) | D (T N) | the flags (T bytes) | the block sums
+ *   (ceil(T / 256) (1 + k + N)) | the partial tiles (ceil(T / 4096) 3 64 64) ], doubles unless noted, every part on a
+ *   256-byte boundary; launches nothing and touches no device.  ws is 256-byte aligned. */
+#define RV_ATTR_DESCRIBE 49
+#define RV_ATTR_FIT 50
+#define RV_ATTR_WORKSPACE 51
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the
@@ -1008,7 +1073,7 @@ typedef struct rv_mosaic_desc {
   void* ws;
   long ws_bytes;
   union { const float* src;      /* GATHER_MEAN */
-          const double* moment; };  /* WALK_FIT, WALK_STEP: the fp64 input matrix the op names; HMM ops: theta */
+          const double* moment; };  /* WALK_FIT, WALK_STEP: the fp64 input matrix the op names; HMM ops: theta; ATTR_FIT: the targets D */
   long src_len;
   const long long* row_start;
   long stride, n_rows;
@@ -1016,7 +1081,7 @@ typedef struct rv_mosaic_desc {
           long fit_radius;       /* GRAIN_FIT, LIVE ops: R */
           long band; };          /* ALIGN ops: r */
   union { float* out;            /* GATHER_MEAN [T, ldo], OLA [n_out] */
-          double* result;        /* WALK_FIT; HMM ops: logb [T, S], HMM_MSTEP: the new theta */
+          double* result;        /* WALK_FIT; HMM ops: logb [T, S], HMM_MSTEP: the new theta; ATTR ops: desc [T, ldo] / the fit */
           double* end_costs; };  /* ALIGN_FORWARD (SUBSEQUENCE) [Tb], or NULL */
   long ldo;
   const float* frames;           /* OLA */
@@ -1051,7 +1116,7 @@ typedef struct rv_mosaic_desc {
   long mode;                     /* LIVE: RV_LIVE_GRAINS / RV_LIVE_DECODE; ALIGN_FORWARD: the DP's mode; ALIGN_WARP: the timeline */
   union { const float* weight;   /* LIVE [n_streams] on the device, or NULL: the mean of the k candidates */
           const float* gains;    /* PCA_APPLY (EDIT) [k] */
-          const float* twiddles; };  /* EVAL_FRAMES [S] */
+          const float* twiddles; };  /* EVAL_FRAMES, ATTR_DESCRIBE [S] */
   long which;                    /* LIVE_RESET: the stream, -1 for all */
 } rv_mosaic_desc;
 int rv_mosaic(int op, rv_mosaic_desc* d, void* stream);

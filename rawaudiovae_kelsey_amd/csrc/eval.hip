@@ -12,46 +12,19 @@
 #include "common.h"
 #include "internal.h"
 #include "moment.h"
+#include "spectrum.h"
 
 using namespace rv;
 
 namespace {
 
-constexpr int EV_THREADS = 256;
-constexpr int EV_SMAX = 4096;            // longest frame with spectral columns
-constexpr int EV_SMIN = 32;
-
-__device__ __forceinline__ float block_max_f32(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-}
+constexpr int EV_THREADS = spec::THREADS;
+constexpr int EV_SMAX = spec::SMAX;      // longest frame with spectral columns
+constexpr int EV_SMIN = spec::SMIN;
 
 __device__ __forceinline__ double kl_term(float mu, float lv) {
   const double m = (double)mu, l = (double)lv;
   return -0.5 * (1.0 + l - m * m - exp(l));
-}
-
-// The spectral arithmetic is plain fp32 with every product and sum rounded on its own (no contraction), so that the
-// float32 restatement of tests/eval_oracle.py states it operation for operation.
-struct cpx {
-  float r, i;
-};
-
-__device__ __forceinline__ cpx cmul(float wr, float wi, float zr, float zi) {
-#pragma clang fp contract(off)
-  cpx o;
-  o.r = wr * zr - wi * zi;
-  o.i = wr * zi + wi * zr;
-  return o;
-}
-
-__device__ __forceinline__ float power(float r, float i) {
-#pragma clang fp contract(off)
-  return r * r + i * i;
 }
 
 // One workgroup per row t.  x = xs + t * hop, y = ys + t * stride, S samples each.
@@ -59,16 +32,9 @@ __device__ __forceinline__ float power(float r, float i) {
 // Columns 0 / 1: thread u adds the terms n = u, u + 256, ... in ascending n from +0 in fp64, then block_sum_f64.
 // Column 2 likewise over j < L.
 //
-// Spectral columns (SPEC): N = S / 2, lg = log2 N.  The windowed signal a[n] = fl(w[n] x[n]) is read as N complex
-// points z[m] = a[2m] + i a[2m + 1] and stored bit-reversed, z[m] at ar / ai [rev(m)]; b likewise in br / bi.  lg stages
-// of decimation-in-time butterflies in place, h = 1, 2, .., N / 2: butterfly j < N / 2 has p = j mod h,
-// i0 = 2 h (j div h) + p, i1 = i0 + h, W = tw[p * (N / h)] (tw[q] = exp(-2 pi i q / S), S / 2 entries), t = W z[i1],
-// z[i1] = z[i0] - t, z[i0] = z[i0] + t.  Then the real-transform post-pass on the pairs (k, N - k), k = 0 .. N / 2,
-// with Z[N] = Z[0]: E = (Z[k] + conj Z[N - k]) / 2, O = (Z[k] - conj Z[N - k]) / 2i, T = tw[k] O, and the two powers
-// P[k] = |E + T|^2, P[N - k] = |E - T|^2, written over ar[k], ar[N - k] (ar has N + 1 slots) -- every pair is read and
-// written by one thread.  LDS: 4 N + 2 floats of dynamic shared memory (8 200 bytes at S = 1024, 32 776 at S = 4096).
-// The bit-reversed store of the load sends consecutive lanes N / 64 floats apart (16-way bank conflicts at N = 2048,
-// 4-way at N = 512), once per sample; the stages with h < 32 are 2-way conflicted.
+// Spectral columns (SPEC): a[n] = fl(w[n] x[n]) and b[n] = fl(w[n] y[n]) go through spectrum.h's transform, each signal
+// on its own, into the powers ar[0 .. N] and br[0 .. N], N = S / 2.  LDS: 4 N + 2 floats of dynamic shared memory (8 200
+// bytes at S = 1024, 32 776 at S = 4096).
 template <bool SPEC>
 __global__ void __launch_bounds__(EV_THREADS)
 k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ ys, long stride, int S,
@@ -81,7 +47,7 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
   const float* x = xs + t * hop;
   const float* y = ys + t * stride;
   const int N = S >> 1;
-  const int lg = 31 - __clz(N > 0 ? N : 1);
+  const int lg = spec::stages(N);
   float* const ar = lds;               // N + 1
   float* const ai = ar + N + 1;        // N
   float* const br = ai + N;            // N + 1
@@ -95,14 +61,8 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
     en += (double)xv * (double)xv;
     if constexpr (SPEC) {
       const float w = win[n];
-      const int m = (int)(__brev((unsigned)(n >> 1)) >> (32 - lg));
-      if (n & 1) {
-        ai[m] = w * xv;
-        bi[m] = w * yv;
-      } else {
-        ar[m] = w * xv;
-        br[m] = w * yv;
-      }
+      spec::put(ar, ai, n, lg, w * xv);
+      spec::put(br, bi, n, lg, w * yv);
     }
   }
   sse = block_sum_f64<EV_THREADS / 64>(sse, red);
@@ -114,62 +74,11 @@ k_eval_frames(const float* __restrict__ xs, long hop, const float* __restrict__ 
   }
   float lsd = 0.f, serr = 0.f, sref = 0.f;
   if constexpr (SPEC) {
-    const int half = N >> 1;
-    for (int h = 1, sh = 0; h < N; h <<= 1, ++sh) {
-      __syncthreads();
-      const int tstep = N >> sh;   // N / h
-      for (int j = threadIdx.x; j < half; j += EV_THREADS) {
-        const int p = j & (h - 1);
-        const int i0 = ((j >> sh) << (sh + 1)) + p, i1 = i0 + h;
-        const float wr = tw[2 * p * tstep], wi = tw[2 * p * tstep + 1];
-        {
-          const cpx tt = cmul(wr, wi, ar[i1], ai[i1]);
-          const float ur = ar[i0], ui = ai[i0];
-          ar[i0] = ur + tt.r;
-          ai[i0] = ui + tt.i;
-          ar[i1] = ur - tt.r;
-          ai[i1] = ui - tt.i;
-        }
-        {
-          const cpx tt = cmul(wr, wi, br[i1], bi[i1]);
-          const float ur = br[i0], ui = bi[i0];
-          br[i0] = ur + tt.r;
-          bi[i0] = ui + tt.i;
-          br[i1] = ur - tt.r;
-          bi[i1] = ui - tt.i;
-        }
-      }
-    }
-    __syncthreads();
-    // the post-pass; the pair (k, N - k) belongs to one thread, so the powers may overwrite the points in place
-    float pmax = 0.f;
+    float pmax = 0.f, pmax_b = 0.f;
     bool bad_a = false, bad_b = false;
-    for (int k = threadIdx.x; k <= half; k += EV_THREADS) {
-      const int kn = k == 0 ? 0 : N - k;
-      const float wr = tw[2 * k], wi = tw[2 * k + 1];
-      float p0[2], p1[2];
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        const float* zr = s ? br : ar;
-        const float* zi = s ? bi : ai;
-        const float er = 0.5f * (zr[k] + zr[kn]), ei = 0.5f * (zi[k] - zi[kn]);
-        const float orr = 0.5f * (zi[k] + zi[kn]), oi = -0.5f * (zr[k] - zr[kn]);
-        const cpx tt = cmul(wr, wi, orr, oi);
-        p0[s] = power(er + tt.r, ei + tt.i);
-        p1[s] = power(er - tt.r, ei - tt.i);
-      }
-      ar[k] = p0[0];
-      br[k] = p0[1];
-      if (N - k != k) {
-        ar[N - k] = p1[0];
-        br[N - k] = p1[1];
-      }
-      // a power that is NaN or +inf: fmaxf would drop a NaN, so it is carried on its own
-      bad_a = bad_a || !(p0[0] < INFINITY) || !(p1[0] < INFINITY);
-      bad_b = bad_b || !(p0[1] < INFINITY) || !(p1[1] < INFINITY);
-      pmax = fmaxf(pmax, fmaxf(fmaxf(p0[0], p0[1]), fmaxf(p1[0], p1[1])));
-    }
-    pmax = block_max_f32(pmax, redf);
+    spec::powers(ar, ai, tw, N, pmax, bad_a);
+    spec::powers(br, bi, tw, N, pmax_b, bad_b);
+    pmax = spec::block_max_f32(fmaxf(pmax, pmax_b), redf);
     const int nbad_a = __syncthreads_or(bad_a), nbad_b = __syncthreads_or(bad_b);
     const float fl = pmax * floor_scale;
     double d2 = 0.0, se = 0.0, sr = 0.0;

@@ -27,9 +27,9 @@ namespace {
 constexpr int HM_SMAX = 64;       // states: one wave holds a vector over the states (the header states it)
 constexpr int HM_KMAX = 64;       // axes: one 64 x 64 tile holds a weighted moment
 constexpr int HM_LMAX = 512;
-constexpr int HM_THREADS = 256;
-constexpr int HM_FRAMES = 64;     // frames of one workgroup of k_hmm_emit / k_hmm_observe (the header states it)
-constexpr int HM_PITCH = HM_SMAX + 1;
+constexpr int HM_THREADS = seq::THREADS;
+constexpr int HM_FRAMES = seq::FRAMES;   // frames of one workgroup of k_hmm_emit / k_hmm_observe (the header states it)
+constexpr int HM_PITCH = seq::PITCH;
 constexpr int HM_NONE = 255;      // back-pointer: no predecessor with a score above -inf
 constexpr double LOG_2PI = 1.8378770664093453;   // fl64(log(2 pi))
 
@@ -60,33 +60,6 @@ __host__ __device__ __forceinline__ theta_at theta_layout(long S, long k) {
   return o;
 }
 
-// The frames [t0, t0 + nf) of a workgroup of HM_THREADS threads: sbad[f] != 0 iff row f of x holds a value that is not
-// finite, and sy[f * HM_PITCH + j] = y_j of frame f (+0 for such a frame).  sflag: HM_THREADS bytes of scratch.
-__device__ __forceinline__ void stage_frames(const float* __restrict__ x, long ldx, const double* __restrict__ centre,
-                                             const double* __restrict__ P, long t0, int nf, int L, int k, double* sy,
-                                             unsigned char* sflag, unsigned char* sbad) {
-  const int tid = threadIdx.x;
-  {
-    const int f = tid >> 2, q = tid & 3;
-    bool bad = false;
-    if (f < nf) {
-      const float* const xr = x + (t0 + f) * ldx;
-      for (int l = q; l < L; l += 4) bad |= !(fabsf(xr[l]) <= 3.402823466e38f);
-    }
-    sflag[tid] = bad;
-  }
-  __syncthreads();
-  if (tid < HM_FRAMES) sbad[tid] = sflag[4 * tid] | sflag[4 * tid + 1] | sflag[4 * tid + 2] | sflag[4 * tid + 3];
-  __syncthreads();
-  // a wave shares an axis (P's row is read by all its lanes at once), a lane walks its own frame's row
-  for (int e = tid; e < HM_FRAMES * k; e += HM_THREADS) {
-    const int j = e / HM_FRAMES, f = e - j * HM_FRAMES;
-    if (f >= nf) continue;
-    sy[f * HM_PITCH + j] = sbad[f] ? 0.0 : seq::whiten_axis(P + (long)j * L, x + (t0 + f) * ldx, centre, L);
-  }
-  __syncthreads();
-}
-
 // logb[t, s] = g_s - 0.5 q, q = chain fma(fl(w_sj d), d, .), d = y_j - m_sj, in ascending j from +0; a row of NaN for a
 // frame whose x row is not finite
 __global__ void __launch_bounds__(HM_THREADS)
@@ -96,7 +69,7 @@ k_hmm_emit(const float* __restrict__ x, long ldx, const double* __restrict__ cen
   __shared__ unsigned char sflag[HM_THREADS], sbad[HM_FRAMES];
   const long t0 = (long)blockIdx.x * HM_FRAMES;
   const int nf = T - t0 < HM_FRAMES ? (int)(T - t0) : HM_FRAMES;
-  stage_frames(x, ldx, centre, P, t0, nf, L, k, sy, sflag, sbad);
+  seq::stage_frames(x, ldx, centre, P, t0, nf, L, k, sy, sflag, sbad);
   const theta_at o = theta_layout(S, k);
   for (int e = threadIdx.x; e < nf * S; e += HM_THREADS) {
     const int f = e / S, s = e - f * S;
@@ -124,7 +97,7 @@ k_hmm_observe(const float* __restrict__ x, long ldx, const double* __restrict__ 
   __shared__ unsigned char sflag[HM_THREADS], sbad[HM_FRAMES];
   const long t0 = (long)blockIdx.x * HM_FRAMES;
   const int nf = T - t0 < HM_FRAMES ? (int)(T - t0) : HM_FRAMES;
-  stage_frames(x, ldx, centre, P, t0, nf, L, k, sy, sflag, sbad);
+  seq::stage_frames(x, ldx, centre, P, t0, nf, L, k, sy, sflag, sbad);
   for (int e = threadIdx.x; e < nf * k; e += HM_THREADS) {
     const int f = e / k, j = e - f * k;
     ys[t0 * k + e] = sy[f * HM_PITCH + j];

@@ -225,3 +225,9 @@ RV_INTERNAL int rv_hmm_forward_backward(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_hmm_mstep(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_hmm_viterbi(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_hmm_workspace(rv_mosaic_desc* d);
+// The latent-attribute ops of rv_mosaic (attr.hip): RV_ATTR_DESCRIBE and RV_ATTR_FIT on the fields the public header names
+// for them -- checks first, then the launches, no sync and no read of the device -- and RV_ATTR_WORKSPACE, which writes
+// d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_attr_describe(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_attr_fit(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_attr_workspace(rv_mosaic_desc* d);

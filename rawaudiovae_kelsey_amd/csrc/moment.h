@@ -4,7 +4,8 @@
 // on the data and its shape alone.
 //   Second moment.  d[t][c] = (double)x[t][c] - centre[c].  Element (i, j) of the range of RANGE rows from t0 is
 //   sum_t a[t][i] b[t][j], with a = b = d (covariance, t a row), a[t] = d[t + 1], b[t] = keep[t] d[t] (lag-1, t a
-//   pair) or a = gamma, b = y or y o y, two fp64 matrices (the weighted moments of RV_HMM_MSTEP, hmm.hip): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
+//   pair), a = gamma, b = y or y o y, two fp64 matrices (the weighted moments of RV_HMM_MSTEP, hmm.hip), or a = keep (u - ubar),
+//   b = keep (v - vbar), two fp64 matrices about their column means (RV_ATTR_FIT, attr.hip): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
 //   four rows to the element.  Rows and columns beyond the data stage zeros.  Then the ranges' partials of an element
 //   in ascending range order from +0 (range_sum), and the caller's one division.
 //   Column sum.  Blocks of ROWS rows: a block's terms in ascending t from +0 (colsum_block), then the block sums in
@@ -91,6 +92,25 @@ struct weighted {
   __device__ __forceinline__ double left(const raw& r) const { return r.a; }
   __device__ __forceinline__ double right(const raw& r) const { return SQUARE ? r.b * r.b : r.b; }
   __device__ __forceinline__ bool keeps(const raw&) const { return true; }
+};
+
+// paired: two fp64 matrices a [n, lda] and b [n, ldb], each minus its column's mean, times the row's keep byte: a row whose
+// byte is 0 stages zeros on both sides (the centred moments of RV_ATTR_FIT, attr.hip).
+struct paired {
+  const double* __restrict__ a;
+  const double* __restrict__ b;
+  const unsigned char* __restrict__ keep;
+  long lda, ldb;
+  double ma, mb;
+  struct raw { double a, b; unsigned char k; };
+  __device__ __forceinline__ void load(long tr, raw& r) const {
+    r.a = a[tr * lda];
+    r.b = b[tr * ldb];
+    r.k = keep[tr];
+  }
+  __device__ __forceinline__ double left(const raw& r) const { return r.k ? r.a - ma : 0.0; }
+  __device__ __forceinline__ double right(const raw& r) const { return r.b - mb; }
+  __device__ __forceinline__ bool keeps(const raw& r) const { return r.k != 0; }
 };
 
 // The thread's column of both operands at rows t, t + 4, ..  A row beyond the range is read from the range's last row
@@ -185,6 +205,18 @@ __device__ __forceinline__ void weighted_tile(double* As, double* Bs, const doub
   const int cc = threadIdx.x & 63;
   const bool va = cc < na, vb = cc < nb;
   const weighted<SQUARE> ops{ga + (va ? cc : na - 1), yb + (vb ? cc : nb - 1), na, nb};
+  tile_loop(As, Bs, ops, n, va, vb, false, n_tiles, part);
+}
+
+// The one tile of (a - ma)^T (b - mb) over the kept rows for a [n, na <= 64] and b [n, nb <= 64], both fp64 and packed, ma
+// and mb their column means: element (i, j) = sum_t keep[t] (a[t, i] - ma[i]) (b[t, j] - mb[j]).
+__device__ __forceinline__ void paired_tile(double* As, double* Bs, const double* __restrict__ a, int na,
+                                            const double* __restrict__ ma, const double* __restrict__ b, int nb,
+                                            const double* __restrict__ mb, const unsigned char* __restrict__ keep, long n,
+                                            int n_tiles, double* __restrict__ part) {
+  const int cc = threadIdx.x & 63;
+  const bool va = cc < na, vb = cc < nb;
+  const paired ops{a + (va ? cc : na - 1), b + (vb ? cc : nb - 1), keep, na, nb, va ? ma[cc] : 0.0, vb ? mb[cc] : 0.0};
   tile_loop(As, Bs, ops, n, va, vb, false, n_tiles, part);
 }
 

@@ -1,5 +1,5 @@
-// What the ops over sequences of latent rows share (smooth.hip, hmm.hip): the rows a sequence owns and the whitened
-// coordinate of a frame.  Defined here once, down to the order of every fma.
+// What the ops over sequences of latent rows share (smooth.hip, hmm.hip, attr.hip): the rows a sequence owns, the whitened
+// coordinate of a frame and a workgroup's staging of 64 frames of them.  Defined here once, down to the order of every fma.
 #pragma once
 #include "common.h"
 
@@ -20,6 +20,37 @@ __device__ __forceinline__ double whiten_axis(const double* __restrict__ pr, con
   double acc = 0.0;
   for (int l = 0; l < L; ++l) acc = __builtin_fma(pr[l], (double)xr[l] - centre[l], acc);
   return acc;
+}
+
+constexpr int THREADS = 256;   // the workgroup of stage_frames
+constexpr int FRAMES = 64;     // frames it stages
+constexpr int PITCH = 65;      // doubles between two frames' y in LDS
+
+// The frames [t0, t0 + nf) of a workgroup of THREADS threads: sbad[f] != 0 iff row f of x holds a value that is not
+// finite, and sy[f * PITCH + j] = y_j of frame f (+0 for such a frame).  sflag: THREADS bytes of scratch.
+__device__ __forceinline__ void stage_frames(const float* __restrict__ x, long ldx, const double* __restrict__ centre,
+                                             const double* __restrict__ P, long t0, int nf, int L, int k, double* sy,
+                                             unsigned char* sflag, unsigned char* sbad) {
+  const int tid = threadIdx.x;
+  {
+    const int f = tid >> 2, q = tid & 3;
+    bool bad = false;
+    if (f < nf) {
+      const float* const xr = x + (t0 + f) * ldx;
+      for (int l = q; l < L; l += 4) bad |= !(fabsf(xr[l]) <= 3.402823466e38f);
+    }
+    sflag[tid] = bad;
+  }
+  __syncthreads();
+  if (tid < FRAMES) sbad[tid] = sflag[4 * tid] | sflag[4 * tid + 1] | sflag[4 * tid + 2] | sflag[4 * tid + 3];
+  __syncthreads();
+  // a wave shares an axis (P's row is read by all its lanes at once), a lane walks its own frame's row
+  for (int e = tid; e < FRAMES * k; e += THREADS) {
+    const int j = e / FRAMES, f = e - j * FRAMES;
+    if (f >= nf) continue;
+    sy[f * PITCH + j] = sbad[f] ? 0.0 : whiten_axis(P + (long)j * L, x + (t0 + f) * ldx, centre, L);
+  }
+  __syncthreads();
 }
 
 }  // namespace seq
