@@ -1052,6 +1052,80 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_ATTR_DESCRIBE 49
 #define RV_ATTR_FIT 50
 #define RV_ATTR_WORKSPACE 51
+/* Switching walk (csrc/switch.hip, rawaudiovae_kelsey_amd/switching.py): one linear-Gaussian law per
+ * state of the hidden Markov model of "Latent states", fitted under its posteriors and run block by block like "Latent
+ * walk".  The family's conventions: all arithmetic in fp64, no atomics, no polling, every output element written by exactly
+ * one thread; no op syncs or reads a device pointer on the host, each may run under capture, and each returns an RV_ERR_*
+ * whose message names the field before anything is launched: T, S, k, L, stride, n_rows, mode, ldo, a null q / centre / basis /
+ * moment / state / result / info / eigenvalues / row_start / primed / idx / path / live / ws, ws_bytes too small, a block
+ * that is not 256-byte aligned.  No new member and no new role of the descriptor.  The codes 38, 39, 42 and 48 stay unassigned.
+ * The limits are the HMM's: 1 <= S <= 64, 1 <= k <= 64, k <= L <= 512.
+ * The model.  y_t = P (x_t - c) [k] as in "Latent states"; state s emits N(m_s, diag(v_s)), w = 1 / v.  The standardised
+ * residual of a frame under its posterior gamma_t is r_t = sum_i gamma_t(i) (y_t - m_i) sqrt(w_i); an UNOBSERVED frame (a value
+ * of its x row is not finite) has r_t = +0.  Pair p = frames (p, p + 1), 0 <= p < T - 1; keep[p] = 1 iff both frames lie in
+ * one file (RV_PCA_LAGCOV's rule: p + 1 is none of row_start[0 .. n_rows]) and both are observed.  With ' marking frame p + 1
+ * the moments of state j are N_j = sum keep gamma'(j), C1_j [k, k] = sum (gamma'(j) r') (keep r)^T, D'_j [k] = sum gamma'(j)
+ * keep r'^2 and D_j [k] = sum gamma'(j) keep r^2; A_j[a, b] = C1_j[a, b] / (sqrt(D'_j[a]) sqrt(D_j[b])).  Q_j = I - A_j A_j^T =
+ * U diag(q) U^T; where q_min < 0 the guard sets h = 1 / (1 - q_min), g = sqrt(h), A_j <- g A_j and q_i <- max(1 - h (1 - q_i),
+ * 0), U unchanged; B_j = U diag(sqrt(q)), so A_j A_j^T + B_j B_j^T = I for every state.
+ * RV_SWITCH_RESIDUAL: q = x [T, L] fp32 with a row pitch of stride >= L, centre, basis = P [k, L], moment = theta (the HMM's
+ *   block; m and w are read), state = gamma [T, S] fp64, T (1 <= T < 2^31), L, k, S -> result = the residual block, 256-byte
+ *   aligned: [ r (T k) fp64 | observed (T) bytes at byte offset 8 T k rounded up to 256 ].  y by csrc/sequence.h's chain;
+ *   r[t, j] = ONE chain acc = fma(gamma[t, i], fl(fl(y_j - m_ij) * sqrt(w_ij)), acc) in ascending i from +0; observed[t] = 1
+ *   iff the x row is finite.  A workgroup takes 64 frames; one launch over the whole chip.
+ * RV_SWITCH_MOMENTS: moment = the residual block, state = gamma [T, S], row_start [n_rows + 1] int64 on the device (the CALLER
+ *   checks it on its host copy), n_rows, T (2 <= T < 2^31), S, k, ws, ws_bytes -> result = fp64 [ N (S) | D' (S k) | D (S k) |
+ *   C1 (S k k) ].  Four launches.  keep as above.  N_j: the terms keep[p] ? gamma[p + 1, j] : 0 of the pairs in blocks of 256, a
+ *   block in ascending p from +0, the blocks in ascending order from +0 (RV_EVAL_DIMS's blocked column sum).  The other three
+ *   on the tile of "Latent PCA" under a fourth operand form, `gated` (csrc/moment.h): the T - 1 pairs in ranges of 4096; a
+ *   workgroup owns one range and one of its S + 2 tiles, stages 32 pairs at a time in LDS and adds them, four pairs per
+ *   v_mfma_f64_16x16x4_f64, in ascending p from +0.  Tile j < S is C1_j: left = fl(gamma[p + 1, j] r[p + 1, a]) (one rounded
+ *   product formed while staging), right = keep[p] ? r[p, b] : 0.  Tile S is D': left = gamma[p + 1, i], right = keep[p] ?
+ *   fl(r[p + 1, b]^2) : 0.  Tile S + 1 is D: left = gamma[p + 1, i], right = keep[p] ? fl(r[p, b]^2) : 0.  Only the right
+ *   operand is gated.  The partial tiles go to ws; the last launch adds every element's partials in ascending range order
+ *   from +0.  No division.  The bits depend on the inputs and the shapes only.
+ * RV_SWITCH_FIT, 1 <= S <= 64, 1 <= k <= 64:
+ *   mode RV_SWITCH_DYNAMICS: moment = the moments block of RV_SWITCH_MOMENTS -> result = fp64 [ A (S k k) | Q (S k k) ] (a block of
+ *     its own) and info [S] int32.  A_j[a, b] = fl(fl(C1_j[a, b] / sqrt(D'_j[a])) / sqrt(D_j[b])); 0 where D'_j[a] or D_j[b] is not
+ *     positive and finite; the whole A_j = 0 and info[j] = 1 (else 0) where N_j < 2 (or NaN).  Q_j[i, l] for i <= l =
+ *     (i == l ? 1 : 0) - chain_m fma(A_j[i, m], A_j[l, m], .) in ascending m from +0, written to [i, l] and [l, i]: bitwise
+ *     symmetric, RV_WALK_FIT's rule.  Two launches.  The caller then runs RV_PCA_EIG on every Q_j in place.
+ *   mode RV_SWITCH_NOISE: basis = A [S, k, k], moment = the eigenvectors of every Q_j as RV_PCA_EIG leaves them (row i the i-th)
+ *     [S, k, k], eigenvalues = q [S, k] -> result = fp64 [ dyn (S 2 k k) | g (S) ], dyn_j = [A_j^T | B_j^T] in RV_WALK_STEP's
+ *     layout.  q_min = the least q_i (ties and order do not matter).  q_min < 0: h = 1 / fl(1 - q_min), g = sqrt(h), A^T[b, a] =
+ *     fl(g A[a, b]), q_i' = fl(1 - fl(h fl(1 - q_i))); otherwise g = 1, A as it stands, q' = q.  B^T[i, a] = fl(sqrt(max(q_i',
+ *     0)) u_i[a]).  One launch.
+ * RV_SWITCH_STEP: one block of every stream of *live generated, enqueued without a sync: the step launch, then
+ *   rv_stream_process's fc3, fc4 and overlap-add launches (four in all); live as in RV_WALK_STEP, eps_in [n_streams * F, k].
+ *   L = live->L, k <= L <= 512; centre [L], basis = R [k, L] (the un-whitening rows), moment = phi fp64 =
+ *     [ m (S k) | sd (S k) | pi (S) | A_hmm (S S) | dyn (S 2 k k) ],
+ *   state = u [n_streams, k] fp64 (the standardised state), primed [n_streams] int32 and idx = the current state of every
+ *   stream [n_streams] int32, all three read and written; next_of = the forced states [n_streams * F] int32 or NULL; weight = fp32
+ *   uniforms [n_streams * F] or NULL; path = the states out [n_streams * F] int32; out [n_streams * F, ldo >= L] or NULL.
+ *   One workgroup per stream steps the F = block / hop frames in order.  For stream s and absolute frame f:
+ *   1. The state.  A forced state in [0, S) is taken as given.  Otherwise (no next_of, -1 or >= S) v = the caller's uniform of
+ *      the frame or, without weight, min((float(word) + 0.5f) 2^-32, 0.99999994f) of the FIRST word of Philox(seed) at counter
+ *      (lo = f, hi = 2^32 + s); the noise below uses hi = s < 2^31, so the two never collide.  The law is pi when the stream is
+ *      not primed (or idx is outside [0, S)), else row idx of A_hmm.  cum_j = the law's plain sums in ascending j from +0;
+ *      s' = the first j with (double)v < cum_j, or, if none, the highest j of positive probability (none: 0).
+ *   2. The noise.  e_j = (double)temperature[s] * (double)eps as in RV_WALK_STEP: eps_in, or Philox(seed) at index f k + j,
+ *      offset s.
+ *   3. The standardised state.  Not primed: u = e and the flag is set.  Otherwise u'_i is ONE chain acc = fma(A_s'[i, j], u_j, acc)
+ *      over ascending j from +0 continued by fma(B_s'[i, j], e_j, acc) over ascending j.
+ *   4. The latent row.  y_j = fma(sd[s', j], u_j, m[s', j]); z_l = (float)(centre_l + (double)offset[s, l] + chain_j fma(y_j,
+ *      R[j, l], .)) in ascending j from +0, to the stream workspace's latent row s F + frame and, when out is not NULL, to out.
+ *   5. The record.  path[s F + frame] = s'; after the block idx[s] = the last s'.
+ *   A stream's bits depend on its own state, controls and draws only, not on n_streams or on the block length.
+ * RV_SWITCH_WORKSPACE: the bytes of ws of RV_SWITCH_MOMENTS for (T >= 2, S, k) in d->ws_bytes: [ keep (T - 1) bytes | the block
+ *   sums (ceil((T - 1) / 256) S) | the partial tiles (ceil((T - 1) / 4096) (S + 2) 64 64) ], doubles unless noted, every part on
+ *   a 256-byte boundary; launches nothing and touches no device.  ws is 256-byte aligned. */
+#define RV_SWITCH_RESIDUAL 52
+#define RV_SWITCH_MOMENTS 53
+#define RV_SWITCH_FIT 54
+#define RV_SWITCH_STEP 55
+#define RV_SWITCH_WORKSPACE 56
+#define RV_SWITCH_DYNAMICS 0
+#define RV_SWITCH_NOISE 1
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the

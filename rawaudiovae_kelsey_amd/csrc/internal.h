@@ -231,3 +231,11 @@ RV_INTERNAL int rv_hmm_workspace(rv_mosaic_desc* d);
 RV_INTERNAL int rv_attr_describe(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_attr_fit(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_attr_workspace(rv_mosaic_desc* d);
+// The switching-walk ops of rv_mosaic (switch.hip): RV_SWITCH_RESIDUAL, RV_SWITCH_MOMENTS, RV_SWITCH_FIT and RV_SWITCH_STEP
+// on the fields the public header names for them -- checks first, then the launches, no sync and no read of the device --
+// and RV_SWITCH_WORKSPACE, which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_switch_residual(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_switch_moments(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_switch_fit(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_switch_step(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_switch_workspace(rv_mosaic_desc* d);

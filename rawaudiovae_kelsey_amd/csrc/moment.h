@@ -5,7 +5,9 @@
 //   Second moment.  d[t][c] = (double)x[t][c] - centre[c].  Element (i, j) of the range of RANGE rows from t0 is
 //   sum_t a[t][i] b[t][j], with a = b = d (covariance, t a row), a[t] = d[t + 1], b[t] = keep[t] d[t] (lag-1, t a
 //   pair), a = gamma, b = y or y o y, two fp64 matrices (the weighted moments of RV_HMM_MSTEP, hmm.hip), or a = keep (u - ubar),
-//   b = keep (v - vbar), two fp64 matrices about their column means (RV_ATTR_FIT, attr.hip): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
+//   b = keep (v - vbar), two fp64 matrices about their column means (RV_ATTR_FIT, attr.hip), or a[p] = fl(g[p + 1] r[p + 1])
+//   (or g[p + 1]), b[p] = keep[p] r[p] (or its square, or that of r[p + 1]), the gated moments of a pair of rows under the
+//   weights of its second row (RV_SWITCH_MOMENTS, switch.hip): v_mfma_f64_16x16x4_f64 over the rows t0, t0 + 4, .. in ascending order from +0, each instruction adding its
 //   four rows to the element.  Rows and columns beyond the data stage zeros.  Then the ranges' partials of an element
 //   in ascending range order from +0 (range_sum), and the caller's one division.
 //   Column sum.  Blocks of ROWS rows: a block's terms in ascending t from +0 (colsum_block), then the block sums in
@@ -113,6 +115,32 @@ struct paired {
   __device__ __forceinline__ bool keeps(const raw& r) const { return r.k != 0; }
 };
 
+// gated: the moments of a pair (p, p + 1) of rows of one fp64 matrix r [n + 1, ldr] under the weights g [n + 1, ldg] of the
+// pair's SECOND row and the pair's keep byte, which gates the right operand only (RV_SWITCH_MOMENTS, switch.hip).
+//   GATED_CROSS    left = fl(g[p + 1, col] r[p + 1, a]), one rounded product formed while staging, `col` one fixed column of
+//                  g; right = keep[p] ? r[p, b] : 0
+//   GATED_NEXT_SQ  left = g[p + 1, a]; right = keep[p] ? fl(r[p + 1, b]^2) : 0
+//   GATED_THIS_SQ  left = g[p + 1, a]; right = keep[p] ? fl(r[p, b]^2) : 0
+enum { GATED_CROSS = 0, GATED_NEXT_SQ = 1, GATED_THIS_SQ = 2 };
+template <int FORM>
+struct gated {
+  const double* __restrict__ g;    // row 0 of the thread's column of g
+  const double* __restrict__ ra;   // ... of r on the left (GATED_CROSS)
+  const double* __restrict__ rb;   // ... of r on the right
+  const unsigned char* __restrict__ keep;
+  long ldg, ldr;
+  struct raw { double g, a, b; unsigned char k; };
+  __device__ __forceinline__ void load(long tr, raw& r) const {
+    r.g = g[(tr + 1) * ldg];
+    r.a = FORM == GATED_CROSS ? ra[(tr + 1) * ldr] : 1.0;
+    r.b = rb[(FORM == GATED_NEXT_SQ ? tr + 1 : tr) * ldr];
+    r.k = keep[tr];
+  }
+  __device__ __forceinline__ double left(const raw& r) const { return FORM == GATED_CROSS ? r.g * r.a : r.g; }
+  __device__ __forceinline__ double right(const raw& r) const { return FORM == GATED_CROSS ? r.b : r.b * r.b; }
+  __device__ __forceinline__ bool keeps(const raw& r) const { return r.k != 0; }
+};
+
 // The thread's column of both operands at rows t, t + 4, ..  A row beyond the range is read from the range's last row
 // (the caller stores a zero in its place).
 template <class Ops, int PER>
@@ -217,6 +245,20 @@ __device__ __forceinline__ void paired_tile(double* As, double* Bs, const double
   const int cc = threadIdx.x & 63;
   const bool va = cc < na, vb = cc < nb;
   const paired ops{a + (va ? cc : na - 1), b + (vb ? cc : nb - 1), keep, na, nb, va ? ma[cc] : 0.0, vb ? mb[cc] : 0.0};
+  tile_loop(As, Bs, ops, n, va, vb, false, n_tiles, part);
+}
+
+// The one tile of a gated moment over the n pairs of r [n + 1, nr <= 64] under g [n + 1, ng <= 64], both fp64 and packed:
+// GATED_CROSS, element (a, b) = sum_p fl(g[p + 1, col] r[p + 1, a]) keep[p] r[p, b]; the two squares, element (i, b) =
+// sum_p g[p + 1, i] keep[p] fl(r[p + 1 or p, b]^2).
+template <int FORM>
+__device__ __forceinline__ void gated_tile(double* As, double* Bs, const double* __restrict__ g, int ng, int col,
+                                           const double* __restrict__ r, int nr, const unsigned char* __restrict__ keep, long n,
+                                           int n_tiles, double* __restrict__ part) {
+  const int cc = threadIdx.x & 63;
+  const bool va = cc < (FORM == GATED_CROSS ? nr : ng), vb = cc < nr;
+  const int cr = vb ? cc : nr - 1;
+  const gated<FORM> ops{g + (FORM == GATED_CROSS ? col : (va ? cc : ng - 1)), r + cr, r + cr, keep, ng, nr};
   tile_loop(As, Bs, ops, n, va, vb, false, n_tiles, part);
 }
 

@@ -1,5 +1,6 @@
-// What the ops over sequences of latent rows share (smooth.hip, hmm.hip, attr.hip): the rows a sequence owns, the whitened
-// coordinate of a frame and a workgroup's staging of 64 frames of them.  Defined here once, down to the order of every fma.
+// What the ops over sequences of latent rows share (smooth.hip, hmm.hip, attr.hip, walk.hip, switch.hip): the rows a
+// sequence owns, which pairs of rows lie in one file, the whitened coordinate of a frame, a workgroup's staging of 64 frames
+// of them, and the roundings of a generated frame.  Defined here once, down to the order of every fma.
 #pragma once
 #include "common.h"
 
@@ -12,6 +13,29 @@ __device__ __forceinline__ void rows_of(const long long* __restrict__ row_start,
   t1 = row_start[s + 1];
   t0 = t0 < 0 ? 0 : (t0 > T ? T : t0);
   t1 = t1 < t0 ? t0 : (t1 > T ? T : t1);
+}
+
+// whether the pair of rows (p, p + 1) spans two files: p + 1 is one of row_start[0 .. n_files] (ascending; the first entry
+// >= p + 1 by bisection).  RV_PCA_LAGCOV's and RV_SWITCH_MOMENTS' rule.
+__device__ __forceinline__ bool pair_spans_files(const long long* __restrict__ row_start, long n_files, long p) {
+  long lo = 0, hi = n_files + 1;
+  while (lo < hi) {
+    const long mid = (lo + hi) >> 1;
+    if (row_start[mid] < p + 1) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo <= n_files && row_start[lo] == p + 1;
+}
+
+// The two roundings of a generated frame that RV_WALK_STEP and RV_SWITCH_STEP share, never contracted into an fma: the
+// noise temperature * eps, and the latent (float)(c + (double)offset + acc).
+__device__ __forceinline__ double noise_of(double temp, float e) {
+#pragma clang fp contract(off)
+  return temp * (double)e;
+}
+__device__ __forceinline__ float latent_of(double c, float off, double acc) {
+#pragma clang fp contract(off)
+  return (float)(c + (double)off + acc);
 }
 
 // y_j = sum_l P[j, l] ((double)x[l] - c[l]) in ascending l from +0: pr = row j of P, xr = the frame's latent row

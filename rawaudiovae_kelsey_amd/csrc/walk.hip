@@ -15,6 +15,7 @@
 #include "philox.h"
 #include "internal.h"
 #include "moment.h"
+#include "sequence.h"
 
 using namespace rv;
 
@@ -28,13 +29,7 @@ __global__ void __launch_bounds__(256)
 k_walk_pairs(const long long* __restrict__ row_start, long n_files, long n_pairs, unsigned char* __restrict__ keep) {
   const long p = (long)blockIdx.x * 256 + threadIdx.x;
   if (p >= n_pairs) return;
-  long lo = 0, hi = n_files + 1;   // the first entry >= p + 1
-  while (lo < hi) {
-    const long mid = (lo + hi) >> 1;
-    if (row_start[mid] < p + 1) lo = mid + 1;
-    else hi = mid;
-  }
-  keep[p] = (lo <= n_files && row_start[lo] == p + 1) ? 0 : 1;
+  keep[p] = seq::pair_spans_files(row_start, n_files, p) ? 0 : 1;
 }
 
 // Grid (ranges of pairs, nI * nI tiles): moment.h's tile in its lag-1 form, A[i][k] = d[p + k + 1][i0 + i] and
@@ -116,15 +111,8 @@ k_walk_diagonal(const double* __restrict__ a, int k, double* __restrict__ dyn) {
   dyn[(long)k * k + e] = bv;
 }
 
-__device__ __forceinline__ double noise_of(double temp, float e) {
-#pragma clang fp contract(off)
-  return temp * (double)e;
-}
-
-__device__ __forceinline__ float latent_of(double c, float off, double acc) {
-#pragma clang fp contract(off)
-  return (float)(c + (double)off + acc);
-}
+using seq::latent_of;
+using seq::noise_of;
 
 // One workgroup per stream; the F frames of the call one after the other.  LDS: the state w, the frame's noise e and
 // the new state.  Thread i owns coordinate i of the state (A^T and B^T are read along their rows: consecutive lanes,
