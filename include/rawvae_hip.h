@@ -1126,6 +1126,51 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_SWITCH_WORKSPACE 56
 #define RV_SWITCH_DYNAMICS 0
 #define RV_SWITCH_NOISE 1
+/* ---- Latent transport (csrc/transport.hip; rawaudiovae_kelsey_amd/transport.py) ----
+ * Entropic optimal transport between two clouds of whitened latent rows: the Sinkhorn half-step and the barycentric map,
+ * fp64 attention that never stores its N x M matrix.  The family's conventions: all arithmetic in fp64, no atomics, no polling,
+ * every output element written by exactly one thread; no op syncs or reads a device pointer on the host, each may run under
+ * capture, and each returns an RV_ERR_* whose message names the field before anything is launched.  No new member and no new
+ * role of the descriptor.  The codes 38, 39, 42, 48 and 57 stay unassigned.  Limits: 1 <= k <= 64, k <= L <= 512, T and N in
+ * [1, 2^31).  The slots: fp64 pointers basis, moment, result, centre, state; fp32 pointers a, out (one slot with result: an op
+ * uses one of the two), weight; int pointer info; lam = epsilon (fp32, widened once to fp64); the longs T, N, L, k, stride, ldo,
+ * ws_bytes; live and ws.
+ * Definitions.  For a row a_i and a column b_j [k]: c_ij = max(fma(-2, a_i . b_j, |a_i|^2 + |b_j|^2), 0), the norms chains
+ * fma(v, v, .) in ascending d from +0 and the product the sum of v_mfma_f64_16x16x4_f64 in ascending d.  This Gram form carries
+ * a rounding of about u (|a|^2 + |b|^2); nothing here pins its bits against a summation order.  s_ij = fma(h_j - c_ij, 1 / eps,
+ * lw_j), and -inf where lw_j is -inf: such a column contributes an exact 0.  The N columns are cut into slabs of
+ * max(256, ceil(N / 8) rounded up to 64) columns, a rule of N alone.  Within a slab a row takes the columns in tiles of 16: m' =
+ * max(m, the tile's maximum), every running sum times exp(m - m') (skipped when m' = m), then w_ij = exp(s_ij - m') added.  A row's
+ * slabs are merged in ascending slab order: M = max_s m_s, e_s = exp(m_s - M), Z = sum_s fl(sw_s e_s) from +0.  The running
+ * maximum is always subtracted: nothing overflows for a row 10^3 standard deviations out.  No element depends on another row of
+ * the call: a row's bits are the same whatever T is and whichever rows stand beside it, and two runs are bit-equal.
+ * RV_OT_WHITEN: a = x [T, L] fp32 with a row pitch of stride >= L, basis = [ centre (L) | P (k L) ] -> result = y [T, k] fp64 by
+ *   csrc/sequence.h's chain (the bits RV_HMM_EMIT observes with) and info [T] int32, 1 for an observed row; a row of x that holds
+ *   a value that is not finite gives y = +0 and info 0.  One launch, a workgroup per 64 frames.
+ * RV_OT_SOFTMIN, one Sinkhorn half-step: basis = A [T, k], moment = B [N, k], centre = [ h (N) | lw (N) ] (the other side's
+ *   potential and its log-weights), lam = eps > 0, ws, ws_bytes -> result [T] fp64 = -eps (M_i + log Z_i); +inf for a row with no
+ *   column of finite weight.  Two launches.  ws holds the slabs' partials [T, n_slabs, 2].
+ * RV_OT_MAP, the barycentric map: a = x [T, L] with pitch stride, basis = [ centre (L) | P (k L) | W (L k) ] (W the un-whitening,
+ *   columns v_d sqrt(lambda_d)), moment = V [N, k], centre = [ g | lw ], lam = eps, weight = alpha [1] fp32 on the device or NULL
+ *   (1), ws, ws_bytes -> out [T, ldo >= L] fp32 and state [T, 3 + k] fp64.  Three launches: y = RV_OT_WHITEN's of x into ws, the
+ *   scan, the merge.  T_i = sum_j w_ij V_j / Z_i (the second MFMA, then the slabs in ascending order by fma, then one division);
+ *   x'_il = (float)((double)x_il + fl(alpha sum_d W[l, d] (T_id - y_id))), the sum one fma chain in ascending d from +0; where
+ *   that product is 0 the output is the input's bits.  Only the kept subspace moves.  state row i = [ f_i, support_i, cbar_i, T_i0 ..
+ *   T_i,k-1 ]: f_i as RV_OT_SOFTMIN, support_i = Z^2 / sum w^2 (1: the row was mosaiced; N: it got the target's mean), cbar_i =
+ *   sum w c / Z.  A row of x that is not finite passes through unchanged, its state row NaN, 0, NaN, NaN ..; a finite row with no
+ *   column of finite weight passes through as well, its state row +inf, 0, NaN, NaN ...  out may be x itself.
+ * RV_OT_LIVE, one block of the streaming engine: live = the rv_stream_desc; rv_stream_encode (q = mu * scale + offset),
+ *   RV_OT_MAP's launches on the n_streams * F latent rows (L = live->L; weight = alpha [n_streams] on the device, row r takes
+ *   alpha[r / F]; state [n_streams * F, 3 + k]), then fc3, fc4 and the overlap-add.  No host sync inside; it may be captured.
+ *   ws = [ q (n_streams F L) fp32 | RV_OT_MAP's ws ].  A block's rows equal RV_OT_MAP's of the same latent rows bit for bit.
+ * RV_OT_WORKSPACE: the bytes of ws in d->ws_bytes, for (T, N, k) the larger of RV_OT_SOFTMIN's and RV_OT_MAP's ([ y (T k) |
+ *   observed (T) int32 | partials (T n_slabs (4 + k)) ], doubles unless noted, every part on a 256-byte boundary); with live set,
+ *   RV_OT_LIVE's for (live, N, k).  Launches nothing and touches no device.  ws is 256-byte aligned. */
+#define RV_OT_WHITEN 58
+#define RV_OT_SOFTMIN 59
+#define RV_OT_MAP 60
+#define RV_OT_LIVE 61
+#define RV_OT_WORKSPACE 62
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the

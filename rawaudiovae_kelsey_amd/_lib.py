@@ -117,10 +117,11 @@ HMM_MOMENTS = 1   # RV_HMM_MSTEP's mode
 ATTR_DESCRIBE, ATTR_FIT, ATTR_WORKSPACE = 49, 50, 51   # RV_ATTR_* (rv_mosaic); 48 is unassigned
 SWITCH_RESIDUAL, SWITCH_MOMENTS, SWITCH_FIT, SWITCH_STEP, SWITCH_WORKSPACE = 52, 53, 54, 55, 56   # RV_SWITCH_* (rv_mosaic)
 SWITCH_DYNAMICS, SWITCH_NOISE = 0, 1   # RV_SWITCH_FIT's mode
+OT_WHITEN, OT_SOFTMIN, OT_MAP, OT_LIVE, OT_WORKSPACE = 58, 59, 60, 61, 62   # RV_OT_* (rv_mosaic); 57 is unassigned
 
 _HOST_ONLY_OPS = frozenset((MOSAIC_KNN_WORKSPACE, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_PATH_WORKSPACE, MOSAIC_LIVE_WORKSPACE,
                             PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE, STRUCT_WORKSPACE, SMOOTH_WORKSPACE,
-                            RECUR_WORKSPACE, HMM_WORKSPACE, ATTR_WORKSPACE, SWITCH_WORKSPACE))   # mosaic_call: they launch nothing
+                            RECUR_WORKSPACE, HMM_WORKSPACE, ATTR_WORKSPACE, SWITCH_WORKSPACE, OT_WORKSPACE))   # mosaic_call: they launch nothing
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

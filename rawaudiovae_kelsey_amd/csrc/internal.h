@@ -239,3 +239,11 @@ RV_INTERNAL int rv_switch_moments(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_switch_fit(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_switch_step(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_switch_workspace(rv_mosaic_desc* d);
+// The latent-transport ops of rv_mosaic (transport.hip): RV_OT_WHITEN, RV_OT_SOFTMIN, RV_OT_MAP and RV_OT_LIVE on the fields the
+// public header names for them -- checks first, then the launches, no sync and no read of the device -- and RV_OT_WORKSPACE,
+// which writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_ot_whiten(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_ot_softmin(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_ot_map(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_ot_live(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_ot_workspace(rv_mosaic_desc* d);
