@@ -1171,6 +1171,52 @@ int rv_som_update(const double* sums, const long long* counts, const float* w_ol
 #define RV_OT_MAP 60
 #define RV_OT_LIVE 61
 #define RV_OT_WORKSPACE 62
+/* Latent beats (csrc/beat.hip, rawaudiovae_kelsey_amd/beats.py): the pulse of a latent trajectory.
+ * The novelty curve of "Latent structure" under a small kernel is an onset-strength curve at the frame rate; these ops
+ * condition it, find the period it prefers and place the beats (the dynamic programme of Ellis 2007).  The family's
+ * conventions: all arithmetic in fp64, every product rounded before it is added (nothing is contracted into an fma), fixed
+ * summation orders, no atomics, no polling, every output element written by exactly one thread; no op syncs or reads a
+ * device pointer on the host, each may run under capture, and each returns an RV_ERR_* whose message names the field before
+ * anything is launched: T, width, hop, lag, N, ldo, n_out, a null moment / basis / result / centre / path / idx / info /
+ * summary / cost / ws, ws_bytes too small, ws not 256-byte aligned.  No new member and no new role of the descriptor.
+ * RV_BEAT_ONSET: T >= 1, moment = nov [T] fp64 (what RV_STRUCT_NOVELTY writes), ws / ws_bytes -> result = o [T] fp64,
+ *   summary [4] int32, cost [2] fp64.  h[t] = nov[t] where it is finite and > 0, +0 otherwise.  q = sum of fl64(h[t] * h[t]) in
+ *   RV_EVAL_DIMS's order: blocks of 256 frames added in ascending t from +0, the block sums added in ascending order from +0.
+ *   s = sqrt(q / (double)T), o[t] = h[t] / s when s > 0 and +0 otherwise: one IEEE division, one IEEE square root and one
+ *   IEEE division per frame.  summary = {the entries that are finite and > 0, the finite entries, 0, 0}, cost = {s, +0}.
+ *   Three launches.  result may not be moment.
+ * RV_BEAT_TEMPOGRAM: T >= 1, moment = o [T] fp64, width = Wn, the window in frames, 1 <= Wn <= 8192, hop = Hw >= 1, the frames
+ *   between two windows, lag = lo and N = hi, the lags, 1 <= lo <= hi <= 1024, basis = [ win (Wn) | prior (hi - lo + 1) ] fp64
+ *   -> result = A [nW, ldo] fp64 with nW = ceil(T / Hw) <= 2^22 and ldo >= hi - lo + 1 (the column of lag tau is tau - lo; the columns
+ *   beyond are not written), centre = G [hi - lo + 1] fp64, path = period [nW] int32, info [4] int32, cost [2] fp64.
+ *   A[n, tau] = the sum over i in [0, Wn), with a = n Hw + i, of fl64(win[i] * fl64(o[a] * o[a + tau])); a term with
+ *   a + tau >= T is skipped, by index.  The sum goes in tiles of 64 values of i: each tile a chain from +0 in ascending i,
+ *   the tile sums added in ascending order from +0.  G[tau] = sum_n A[n, tau] in ascending n from +0; score[tau] =
+ *   fl64(prior[tau - lo] * G[tau]); P = the tau of the largest score that is finite and > 0, ties to the smaller tau, 0 when
+ *   there is none (silence); period[n] by the same rule on fl64(prior[tau - lo] * A[n, tau]).  info = {P, nW, 0, 0},
+ *   cost = {score[P], G[P]}, and {+0, +0} when P = 0.  A workgroup takes one window and 256 lags, a thread per lag, and
+ *   stages o[n Hw, n Hw + Wn + hi) and win once in LDS ((2 Wn + hi) doubles, at most 136 KiB); then a workgroup per window
+ *   picks its period and one workgroup adds G and picks P.  Three launches; the bits depend on the operands only, not on the
+ *   launch.
+ * RV_BEAT_TRACK: T >= 1, moment = o [T] fp64, lag = dlo and width = dhi, the nearest and the furthest predecessor in frames,
+ *   1 <= dlo <= dhi <= 2048, N = P, the end window, 1 <= P <= 2048, basis = pen [dhi - dlo + 1] fp64, the transition scores
+ *   (pen[delta - dlo] for a step of delta frames) -> result = C [T] fp64, idx = back [T] int32, path = beats [n_out] int32
+ *   with n_out >= (T - 1) / dlo + 1, summary [4] int32, cost [2] fp64.  h[t] = o[t] where it is finite, +0 otherwise.  The
+ *   candidates of frame t are p = t - delta, delta in [dlo, dhi], p >= 0, with v = fl64(C[p] + pen[delta - dlo]); a NaN is
+ *   skipped; best = the largest v > -inf, ties to the nearer p.  With no such v, C[t] = h[t] and back[t] = -1; otherwise
+ *   C[t] = fl64(h[t] + best) and back[t] = p.  t* = the frame of the largest C over [max(0, T - P), T), ties to the earlier
+ *   frame.  beats = t* followed back to -1, written in ascending order, n of them; the rest of path is -1.  summary =
+ *   {n, t*, 0, 0}, cost = {C[t*], the sum of h at the beats in ascending order from +0}.  Every entry of every output is
+ *   written.  ONE workgroup, one launch: the frames [b dlo, (b + 1) dlo) read only C[p] with p < b dlo, so a block of dlo
+ *   frames is taken at once, every frame's window spread over the lanes that are left (a power of two, at most a wave); the
+ *   last dhi + dlo values of C live in LDS.  The maximum and the single rounded add make the bits independent of how the
+ *   window is split.
+ * RV_BEAT_WORKSPACE: the bytes of ws of RV_BEAT_ONSET for T in d->ws_bytes; launches nothing and touches no device.
+ *   ws is 256-byte aligned. */
+#define RV_BEAT_ONSET 63
+#define RV_BEAT_TEMPOGRAM 64
+#define RV_BEAT_TRACK 65
+#define RV_BEAT_WORKSPACE 66
 struct rv_stream_desc;
 typedef struct rv_mosaic_desc {
   /* A slot that ops read under more than one name is an anonymous union of its roles: same address, the type of the

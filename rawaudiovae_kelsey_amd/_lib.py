@@ -118,10 +118,11 @@ ATTR_DESCRIBE, ATTR_FIT, ATTR_WORKSPACE = 49, 50, 51   # RV_ATTR_* (rv_mosaic); 
 SWITCH_RESIDUAL, SWITCH_MOMENTS, SWITCH_FIT, SWITCH_STEP, SWITCH_WORKSPACE = 52, 53, 54, 55, 56   # RV_SWITCH_* (rv_mosaic)
 SWITCH_DYNAMICS, SWITCH_NOISE = 0, 1   # RV_SWITCH_FIT's mode
 OT_WHITEN, OT_SOFTMIN, OT_MAP, OT_LIVE, OT_WORKSPACE = 58, 59, 60, 61, 62   # RV_OT_* (rv_mosaic); 57 is unassigned
+BEAT_ONSET, BEAT_TEMPOGRAM, BEAT_TRACK, BEAT_WORKSPACE = 63, 64, 65, 66   # RV_BEAT_* (rv_mosaic)
 
 _HOST_ONLY_OPS = frozenset((MOSAIC_KNN_WORKSPACE, MOSAIC_KNN_SMALL_WORKSPACE, MOSAIC_PATH_WORKSPACE, MOSAIC_LIVE_WORKSPACE,
                             PCA_WORKSPACE, WALK_WORKSPACE, ALIGN_WORKSPACE, STRUCT_WORKSPACE, SMOOTH_WORKSPACE,
-                            RECUR_WORKSPACE, HMM_WORKSPACE, ATTR_WORKSPACE, SWITCH_WORKSPACE, OT_WORKSPACE))   # mosaic_call: they launch nothing
+                            RECUR_WORKSPACE, HMM_WORKSPACE, ATTR_WORKSPACE, SWITCH_WORKSPACE, OT_WORKSPACE, BEAT_WORKSPACE))   # mosaic_call: they launch nothing
 
 # name -> (restype, argtypes); every int-returning entry is error-checked by _wrap.
 _SIGS = {

@@ -247,3 +247,10 @@ RV_INTERNAL int rv_ot_softmin(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_ot_map(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_ot_live(const rv_mosaic_desc* d, void* stream);
 RV_INTERNAL int rv_ot_workspace(rv_mosaic_desc* d);
+// The beat ops of rv_mosaic (beat.hip): RV_BEAT_ONSET, RV_BEAT_TEMPOGRAM and RV_BEAT_TRACK on the fields the public header
+// names for them -- checks first, then the launches, no sync and no read of the device -- and RV_BEAT_WORKSPACE, which
+// writes d->ws_bytes and launches nothing.
+RV_INTERNAL int rv_beat_onset(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_beat_tempogram(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_beat_track(const rv_mosaic_desc* d, void* stream);
+RV_INTERNAL int rv_beat_workspace(rv_mosaic_desc* d);

@@ -1,5 +1,5 @@
-// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 58 ops (codes 0 .. 37, 40, 41,
-// 43 .. 47, 49 .. 56 and 58 .. 62; 38, 39, 42, 48 and 57 are unassigned and answer as unknown ops).  Each family keeps its kernels, checks and launches in its own
+// rv_mosaic(op, desc, stream): the one entry point of the audio tools, a dispatch table over 62 ops (codes 0 .. 37, 40, 41,
+// 43 .. 47, 49 .. 56 and 58 .. 66; 38, 39, 42, 48 and 57 are unassigned and answer as unknown ops).  Each family keeps its kernels, checks and launches in its own
 // file and hands rv_mosaic one function per op (internal.h):
 //    0, 1, 8, 9   RV_MOSAIC_KNN, _KNN_WORKSPACE, _KNN_SMALL, _KNN_SMALL_WORKSPACE        mosaic_knn.hip
 //    2, 3         RV_MOSAIC_GATHER_MEAN, RV_MOSAIC_OLA                                   this file
@@ -17,6 +17,7 @@
 //   49 .. 51      RV_ATTR_DESCRIBE, _FIT, _WORKSPACE                                     attr.hip
 //   52 .. 56      RV_SWITCH_RESIDUAL, _MOMENTS, _FIT, _STEP, _WORKSPACE                  switch.hip
 //   58 .. 62      RV_OT_WHITEN, _SOFTMIN, _MAP, _LIVE, _WORKSPACE                        transport.hip
+//   63 .. 66      RV_BEAT_ONSET, _TEMPOGRAM, _TRACK, _WORKSPACE                          beat.hip
 // Here also the two synthesis ops of the offline mosaic (rawaudiovae_kelsey_amd/mosaic.py):
 //   RV_MOSAIC_GATHER_MEAN  out[t] = (1/k) sum_j src[start(idx[t, j]) : + width] (grains or latent rows)
 //   RV_MOSAIC_OLA          offline weighted overlap-add normalised by the window sum
@@ -163,6 +164,10 @@ extern "C" int rv_mosaic(int op, rv_mosaic_desc* d, void* stream) {
     case RV_OT_MAP: return rv_ot_map(d, stream);
     case RV_OT_LIVE: return rv_ot_live(d, stream);
     case RV_OT_WORKSPACE: return rv_ot_workspace(d);
+    case RV_BEAT_ONSET: return rv_beat_onset(d, stream);
+    case RV_BEAT_TEMPOGRAM: return rv_beat_tempogram(d, stream);
+    case RV_BEAT_TRACK: return rv_beat_track(d, stream);
+    case RV_BEAT_WORKSPACE: return rv_beat_workspace(d);
   }
   return rv_fail(RV_ERR_UNSUPPORTED, "rv_mosaic: unknown op %d", op);
 }
